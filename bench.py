@@ -2,6 +2,12 @@
 """bench.py -- headline benchmark of the MI355X Genome-on-Diet hot path (contract: see the task statement).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --dump-outputs DIR                 (+ the records of the last timed step as DIR/*.npy: dump_outputs)
+    python bench.py ... --full                             (+ every pass beyond the headline figure, see below)
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, p50 latency, stage times, the
+roofline of the timed DP launches).  --full adds, after the timed steps and outside the timed region: config.with_upload,
+roofline.kernel_ms_alone + config.self_check (one more synchronous launch), latency_mode, cpu_baseline + config.parity_at_scale.
 
 Workload = BASELINE.json configs[3], the configuration the metric is quoted on:
     GDiet-LongReads `-ax map-hifi -Z 10 -W 2 -i 0.2 -k 19 -w 19 -N 1 -r 1000 --vt_dis=650 --vt_nb_loc=5 --vt_df1=0.0106
@@ -39,6 +45,7 @@ import subprocess
 import sys
 import tempfile
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -60,7 +67,17 @@ def synth_reference(total_mbp, seed=2):
     rng = np.random.default_rng(seed)
     scale = total_mbp * 1e6 / sum(GRCH38)
     lens = [max(20000, int(l * scale)) for l in GRCH38]
-    contigs = [BASES[rng.integers(0, 4, size=l, dtype=np.uint8)] for l in lens]
+    # contigs[i] = BASES[codes of contig i]: the codes are drawn in contig order on this thread while worker threads look up the
+    # bases of the contigs drawn before (numpy releases the GIL in both) -- the same draws in the same order, in about half the time
+    contigs, looked_up = [], []
+    with ThreadPoolExecutor(4) as pool:
+        for l in lens:
+            codes, c = rng.integers(0, 4, size=l, dtype=np.uint8), np.empty(l, np.uint8)
+            cuts = [l * k // 4 for k in range(5)]
+            looked_up += [pool.submit(np.take, BASES, codes[a:b], out=c[a:b], mode="clip") for a, b in zip(cuts, cuts[1:])]
+            contigs.append(c)
+        for f in looked_up:
+            f.result()
     total = sum(lens)
     fams = [BASES[rng.integers(0, 4, size=int(rng.integers(300, 6000)), dtype=np.uint8)] for _ in range(2000)]
     p = np.array(lens, np.float64) / total
@@ -88,13 +105,16 @@ def synth_reference(total_mbp, seed=2):
 def synth_hifi_reads(rng, contigs, n, only_contig=None, first=0):
     """SURVEY 8d HiFi reads: length N(15000, 2000) clipped to [5000, 25000], sub 0.2 % / ins 0.1 % / del 0.1 %, half of them
     reverse-complemented.  Error positions are drawn as counts (binomial) + positions, not as one uniform per base: 40 batches
-    of 5120 reads have to be made before the timed region."""
+    of 5120 reads have to be made before the timed region.  The draws are those of np.clip / rng.choice(p=) / np.delete / np.insert
+    (numpy's own algorithms, restated without their per-call argument handling: same generator calls, same reads)."""
     lens = np.array([len(c) for c in contigs], np.float64)
     pc = lens / lens.sum()
+    cdf = pc.cumsum()  # rng.choice(len(contigs), p=pc): one rng.random() looked up in the normalised cumulative sum
+    cdf /= cdf[-1]
     out = []
     for i in range(n):
-        ln = int(np.clip(rng.normal(15000, 2000), 5000, 25000))
-        c = only_contig if only_contig is not None else int(rng.choice(len(contigs), p=pc))
+        ln = int(min(max(rng.normal(15000, 2000), 5000), 25000))
+        c = only_contig if only_contig is not None else int(cdf.searchsorted(rng.random(), side="right"))
         ln = min(ln, len(contigs[c]) - 2)
         st = int(rng.integers(0, len(contigs[c]) - ln))
         s = contigs[c][st:st + ln].copy()
@@ -103,11 +123,21 @@ def synth_hifi_reads(rng, contigs, n, only_contig=None, first=0):
         if len(m):
             s[m] = BASES[(np.searchsorted(BASES, s[m]) + rng.integers(1, 4, size=len(m))) & 3]
         d = rng.integers(0, ln, size=rng.binomial(ln, 0.001))
-        if len(d):
-            s = np.delete(s, d)
+        if len(d):  # np.delete(s, d)
+            keep = np.ones(len(s), bool)
+            keep[d] = False
+            s = s[keep]
         ip = rng.integers(0, len(s), size=rng.binomial(len(s), 0.001))
-        if len(ip):
-            s = np.insert(s, ip, BASES[rng.integers(0, 4, size=len(ip))])
+        if len(ip):  # np.insert(s, ip, new bases): the k-th inserted base (in stable order of ip) lands at ip + k
+            ins = BASES[rng.integers(0, 4, size=len(ip))]
+            at = ip.copy()
+            at[ip.argsort(kind="mergesort")] += np.arange(len(ip))
+            old = np.ones(len(s) + len(ip), bool)
+            old[at] = False
+            t = np.empty(len(s) + len(ip), np.uint8)
+            t[at] = ins
+            t[old] = s
+            s = t
         if rng.random() < 0.5:
             s = COMP[s[::-1]]
         out.append(("r%d_c%d_%d" % (first + i, c + 1, st), s.tobytes()))
@@ -319,6 +349,38 @@ def self_check(res, res_again, reads):
     return {"reads": n, "mapped": mapped, "pipelined_equals_synchronous": bool(same), "cigar_spans_consistent": cig_ok, "primary_at_true_origin": placed}
 
 
+def dump_outputs(d, res, cap_bytes=64 << 20):
+    """--dump-outputs: what gdiet_hip_map_wait handed back for the batch of the last timed step, as float64 arrays (every value is a
+    32-bit integer: exact).  Two builds given the same arguments map the same reads, so their files compare element for element.
+        read_index.npy (R,)     the reads of the batch written below (all of them unless that would exceed cap_bytes: then a fixed
+                                sample, seed 0, in batch order)
+        n_regs.npy     (R,)     records per read
+        regs.npy       (M, 19)  the records of those reads in order, the scalar fields of gdiet_reg_t in declaration order
+                                (id cnt rid score qs qe rs re parent subsc mlen blen mapq rev sam_pri dp_score dp_max n_ambi n_cigar)
+        cigar.npy      (C,)     the records' CIGAR words (len << 4 | op) back to back, in record order
+    Returns the file names and sizes."""
+    reg_t = res.regs._type_._type_
+    cols = [name for name, _ in reg_t._fields_ if name != "cigar"]
+    n_regs = np.frombuffer(res.n_regs, dtype=np.int32, count=res.n).copy()
+    recs = []  # per read: (fields (nr, 19) int64, CIGAR words)
+    for i in range(res.n):
+        rs = [res.regs[i][j] for j in range(n_regs[i])]
+        recs.append((np.array([[getattr(r, c) for c in cols] for r in rs], np.int64).reshape(-1, len(cols)),
+                     np.concatenate([np.ctypeslib.as_array(r.cigar, shape=(r.n_cigar,)) for r in rs if r.n_cigar] or [np.zeros(0, np.uint32)])))
+    size = [8 * (2 + f.size + len(c)) for f, c in recs]
+    pick = np.arange(res.n)
+    if sum(size) > cap_bytes:
+        order = np.random.default_rng(0).permutation(res.n)
+        pick = np.sort(order[:int(np.searchsorted(np.cumsum(np.array(size)[order]), cap_bytes, side="right"))])
+    out = {"read_index": pick, "n_regs": n_regs[pick],
+           "regs": np.concatenate([recs[i][0] for i in pick] or [np.zeros((0, len(cols)), np.int64)]),
+           "cigar": np.concatenate([recs[i][1] for i in pick] or [np.zeros(0, np.uint32)])}
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float64))
+    return {name + ".npy": int(a.size * 8) for name, a in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -338,6 +400,12 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = every rank maps its own --batch reads per step (the contract's default); strong = ONE read set, each "
                          "batch cut into contiguous ranges of equal DP cost (read_ranges_by_cost), one per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every pass beyond the headline figure: the PCIe-inclusive pass (config.with_upload), the "
+                         "last launch alone (roofline.kernel_ms_alone) and the self-checks (config.self_check), the latency modes, the CPU baseline and "
+                         "the parity at scale (cpu_baseline, config.parity_at_scale); --no-* below leave single ones out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records the last timed step returned (rank 0) as DIR/*.npy, float64 (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-ref", default="whole", choices=["whole", "largest", "smallest"],
                     help="what the reference binary indexes for the CPU baseline (whole: the GPU leg's reference and reads; falls back to largest if that fails)")
@@ -378,28 +446,36 @@ def main():
     # the same reference on every rank (replicated index): synthesised once per node
     names, contigs, t_ref, ref_how = shared_reference(args.ref_mbp, local_rank, local_world, (lambda: dist.barrier()) if world > 1 else (lambda: None),
                                                       os.environ.get("MASTER_PORT", "0"))
-    t1 = time.time()
-    mapper = pkg.Mapper(ctx, names, contigs, preset="hifi", n_threads=cores)
-    host_threads = args.host_threads or cores
-    mapper.set_host_threads(host_threads)  # N ranks on one node share its cores
-    t_index = time.time() - t1
-    # ---- the read set: distinct batches, uploaded before the timed region (value = inputs resident in HBM)
+    # ---- the read set: distinct batches, uploaded before the timed region (value = inputs resident in HBM).  The reads are drawn on a
+    # worker thread (numpy only, no GPU call) while this thread builds the index (gdiet_hip_index_build releases the GIL)
     n_distinct = max(1, min(args.steps, -(-args.total_reads // args.batch)))
+
+    def draw_reads():
+        t = time.time()
+        sets = []  # reads [(name, bytes)] per batch
+        if args.scaling == "strong" and world > 1:
+            rng = np.random.default_rng(5)  # ONE read set, identical on every rank; each rank keeps its cost-balanced contiguous share
+            for b in range(n_distinct):
+                allr = synth_hifi_reads(rng, contigs, args.batch, first=b * args.batch)
+                bounds = pkg.read_ranges_by_cost([len(s) for _, s in allr], world, band=W_HIFI)
+                sets.append(allr[bounds[rank]:bounds[rank + 1]])
+        else:
+            rng = np.random.default_rng(pkg.rank_seed(5, rank))  # HiFi reads seed 5 (+rank: read-sharded weak scaling)
+            for b in range(n_distinct):
+                sets.append(synth_hifi_reads(rng, contigs, args.batch, first=b * args.batch))
+        return sets, time.time() - t
+
+    with ThreadPoolExecutor(1) as pool:
+        drawn = pool.submit(draw_reads)
+        t1 = time.time()
+        mapper = pkg.Mapper(ctx, names, contigs, preset="hifi", n_threads=cores)
+        host_threads = args.host_threads or cores
+        mapper.set_host_threads(host_threads)  # N ranks on one node share its cores
+        t_index = time.time() - t1
+        read_sets, t_draw = drawn.result()
     t2 = time.time()
-    batches = []  # (device batch, reads [(name, bytes)], read_lens)
-    if args.scaling == "strong" and world > 1:
-        rng = np.random.default_rng(5)  # ONE read set, identical on every rank; each rank keeps its cost-balanced contiguous share
-        for b in range(n_distinct):
-            allr = synth_hifi_reads(rng, contigs, args.batch, first=b * args.batch)
-            bounds = pkg.read_ranges_by_cost([len(s) for _, s in allr], world, band=W_HIFI)
-            mine = allr[bounds[rank]:bounds[rank + 1]]
-            batches.append((mapper.upload([s for _, s in mine]), mine, np.array([len(s) for _, s in mine])))
-    else:
-        rng = np.random.default_rng(pkg.rank_seed(5, rank))  # HiFi reads seed 5 (+rank: read-sharded weak scaling)
-        for b in range(n_distinct):
-            reads = synth_hifi_reads(rng, contigs, args.batch, first=b * args.batch)
-            batches.append((mapper.upload([s for _, s in reads]), reads, np.array([len(s) for _, s in reads])))
-    t_reads = time.time() - t2
+    batches = [(mapper.upload([s for _, s in reads]), reads, np.array([len(s) for _, s in reads])) for reads in read_sets]  # (device batch, reads, read_lens)
+    t_reads = t_draw + time.time() - t2
 
     clock = pkg.JobClock(dist if world > 1 else None, dev, lambda: torch.cuda.synchronize(dev))
     mapper.set_lanes(args.lanes)
@@ -469,9 +545,11 @@ def main():
     rec = {k: [] for k in ("stages", "kern", "work", "mapped_bases", "mapped_reads", "latency", "aligns")}
     res, res_bi = run_steps(args.steps, rec)  # every record of all K batches is on the host when this returns
     elapsed = clock.stop()  # synchronize + barrier
+    dumped = dump_outputs(args.dump_outputs, res) if args.dump_outputs and rank == 0 else None
+    # everything below up to the result line runs with --full only: passes of their own, outside the timed region
+    with_upload, dp_alone, check, lat_modes = None, None, None, None
     # the PCIe-inclusive figure (never `value`): the same kind of steps with the reads handed over as host buffers
-    with_upload = None
-    if not args.no_upload_pass:
+    if args.full and not args.no_upload_pass:
         k2 = min(args.steps, 10)
         rec2 = {k: [] for k in rec}
         t3 = time.perf_counter()
@@ -480,19 +558,19 @@ def main():
         dt2 = time.perf_counter() - t3
         with_upload = {"steps": k2, "ms_per_step": 1e3 * dt2 / k2, "bases_per_s_this_rank": sum(rec2["mapped_bases"]) / dt2,
                        "note": "gdiet_hip_batch_upload (host threads encode, one H2D copy) of the next batch while the lanes work, then submit; outside the timed region"}
-    # for reference: the last launch once more with nothing else on the GPU (outside the timed region)
-    mapper.set_lanes(1)
-    res1 = mapper.map_uploaded(batches[res_bi][0])
-    dp_alone = ctx.last_kernel_ms()[0]
-    all_cells[0] += ctx.last_dp_work()[0]
-    all_cells[1] += 1
-    # size-independent self-checks at full size (outside the timed region): the pipelined steps and this synchronous pass give the
-    # same records (idempotence); every CIGAR consumes exactly its query and reference interval; the primary record of a mapped
-    # read lies where the read was drawn from (the read names carry contig and start)
-    check = self_check(res, res1, batches[res_bi][1])
-    del res1
-    lat_modes = None
-    if rank == 0 and world == 1 and not args.no_latency_modes:  # (one rank only: the other ranks of a multi-GPU run would wait in the final reduction meanwhile)
+    if args.full:
+        # for reference: the last launch once more with nothing else on the GPU (outside the timed region)
+        mapper.set_lanes(1)
+        res1 = mapper.map_uploaded(batches[res_bi][0])
+        dp_alone = ctx.last_kernel_ms()[0]
+        all_cells[0] += ctx.last_dp_work()[0]
+        all_cells[1] += 1
+        # size-independent self-checks at full size (outside the timed region): the pipelined steps and this synchronous pass give the
+        # same records (idempotence); every CIGAR consumes exactly its query and reference interval; the primary record of a mapped
+        # read lies where the read was drawn from (the read names carry contig and start)
+        check = self_check(res, res1, batches[res_bi][1])
+        del res1
+    if args.full and rank == 0 and world == 1 and not args.no_latency_modes:  # (one rank only: the other ranks of a multi-GPU run would wait in the final reduction meanwhile)
         # the same pipelined steps with fewer batches in flight: a batch then waits for fewer DP kernels ahead of it (p50 ~ depth x step)
         lat_modes = []
         # (gdiet_hip_set_dp_waves(4) -- a fifth of every SIMD's registers left to the next batch's seeding / voting kernels -- was measured
@@ -597,7 +675,8 @@ def main():
                                                 % (1e3 * float(np.percentile(rec["latency"], 10)), 1e3 * float(np.percentile(rec["latency"], 90))),
                        "batches_in_flight": args.inflight, "self_check": check, "with_upload": with_upload,
                        "parallelism": "reads sharded over %d GPU(s), index replicated, no collective" % world, "host_threads": host_threads,
-                       "cpus_usable_on_node": pkg_cpus, "pipeline_lanes": args.lanes, "gpu_waits": os.environ.get("GDIET_SYNC", "spin")},
+                       "cpus_usable_on_node": pkg_cpus, "pipeline_lanes": args.lanes, "gpu_waits": os.environ.get("GDIET_SYNC", "spin"),
+                       "full": args.full, "dumped_outputs": dumped},
             "roofline": dict({"bound": "hbm", "kernel": "ksw_extd2_wave_kernel<64, 0, true>", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                               "algorithmic_bytes_per_launch": float(alg.mean()), "dp_cells_per_launch": cells_launch,
@@ -614,7 +693,7 @@ def main():
         if st[2] + st[4] > 0.8 * dp * 1e-3:
             out["config"]["host_bound_warning"] = ("host stages %.1f ms per step with %d threads against a %.1f ms DP kernel: this rank is host-bound"
                                                    % (1e3 * (st[2] + st[4]), host_threads, dp))
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed on rank 0 at N = 1 only
             port_reads = [np.searchsorted(BASES, np.frombuffer(s, np.uint8)).clip(0, 3).astype(np.uint8) for _, s in batches[0][1][:64]]
             try:  # the reference binary itself where it travelled with the repo (and runs on this host's CPU) ...
                 if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "gdiet_lr_avx")):

@@ -3,12 +3,12 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/fin3; mkdir -p $O
 export TMPDIR=/tmp
 if [ "$1" = a ]; then
-cd $R && python bench.py > $O/bench.json 2> $O/bench.err || exit 1
+cd $R && python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 echo "bench done"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --no-cpu-baseline --no-upload-pass --no-latency-modes > $O/bench_under_rocprof.json 2> $O/kt.err || exit 2
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --full --no-cpu-baseline --no-upload-pass --no-latency-modes > $O/bench_under_rocprof.json 2> $O/kt.err || exit 2
 echo "kernel trace done"
-B="python3 $R/bench.py --steps 2 --warmup 0 --inflight 1 --no-cpu-baseline --no-upload-pass --no-latency-modes"
+B="python3 $R/bench.py --full --steps 2 --warmup 0 --inflight 1 --no-cpu-baseline --no-upload-pass --no-latency-modes"
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $O/pmc1 -- $B > $O/pmc1.json 2> $O/pmc1.err || exit 3
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d $O/pmc2 -- $B > $O/pmc2.json 2> $O/pmc2.err || exit 4
 echo "pmc valu done"
