@@ -767,13 +767,14 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 	// (GDIET_DIAG_SHORTCUT=0: every short alignment goes through the DP and is walked back, also those the pre-filter could answer from the
 	// main diagonal's score -- see ksw_exact_match_kernel)
 	static const bool diag_shortcut = !(getenv("GDIET_DIAG_SHORTCUT") && atoi(getenv("GDIET_DIAG_SHORTCUT")) == 0);
+	const int score_bias = (int)(K.q + K.e) - (sc->q + sc->e); // 0 unless the caller passed the larger gap model first: ksw_score_bias_kernel
 	int32_t *d_diag = nullptr;
 	if (diag_shortcut && !ids[GD_KIND_WAVE16].empty()) {
 		if ((rc = gd_grow(ctx, ctx->diag, sizeof(int32_t) * (size_t)n))) return rc;
 		d_diag = (int32_t *)ctx->diag.p;
 	}
 	hipLaunchKernelGGL(ksw_exact_match_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_tasks, n, d_qseq, d_tseq,
-	                   d_status, d_score, d_n_cigar, d_cigar, d_diag, (int)K.sc_mch, (int)K.sc_mis, d_diag && K.sc_mis <= K.sc_mch && K.q + K.e > 0 ? (int)(K.sc_mch + 2 * (K.q + K.e)) + 1 : 0);
+	                   d_status, d_score, d_n_cigar, d_cigar, d_diag, (int)K.sc_mch, (int)K.sc_mis, d_diag && K.sc_mis <= K.sc_mch && K.q + K.e > 0 ? (int)(K.sc_mch + 2 * (K.q + K.e)) + 1 : 0, score_bias);
 	// Head / tail split of a big 64-lane launch.  The grid is sorted longest-first, so the first `wave_slots` alignments start at
 	// once and the rest fill in as slots free up -- it is the latter that finish last.  Launched as two kernels (head on the
 	// caller's stream, tail on a second one), the head's backtrack runs while the tail is still in the DP, and only the tail's
@@ -850,6 +851,7 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 		backtrack(d_ids + id_off[GD_KIND_WAVE64] + n64, (int)(ctx->h_ids.size() - id_off[GD_KIND_WAVE64] - n64), stream);
 		GD_HIP(hipStreamWaitEvent(stream, ctx->ev2[2], 0)); // join: later work on the caller's stream sees the tail's results too
 	} else backtrack(d_ids, (int)ctx->h_ids.size(), stream);
+	if (score_bias) hipLaunchKernelGGL(ksw_score_bias_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, n, d_tasks, d_status, d_score, score_bias);
 	GD_HIP(hipEventRecord(ctx->ev[2], stream));
 	GD_HIP(hipGetLastError());
 	plan_mark("launch");
@@ -958,18 +960,35 @@ extern "C" int gdiet_hip_ksw_extd2_batch(gdiet_ctx *ctx, int n, const uint8_t *q
 }
 
 // ---- K3: single-affine form ----------------------------------------------------------------------------------
+static int gd_extz2_literal(gdiet_ctx *ctx, int n, const uint8_t *qseq, const int64_t *qoff, const uint8_t *tseq, const int64_t *toff,
+                            const int32_t *w, const gdiet_ksw_score_t *sc, int32_t flag, int32_t zdrop, int32_t end_bonus,
+                            gdiet_ksw_extz_t *ez, int32_t *n_cigar, uint32_t *cigar, const int64_t *cigar_off);
+
 extern "C" int gdiet_hip_ksw_extz2_batch(gdiet_ctx *ctx, int n, const uint8_t *qseq, const int64_t *qoff, const uint8_t *tseq,
                                          const int64_t *toff, const int32_t *w, const gdiet_ksw_score_t *sc, int32_t *score,
                                          int32_t *n_cigar, uint32_t *cigar, const int64_t *cigar_off)
 {
 	if (!ctx) return GDIET_E_PARAM;
+	if (n <= 0) return GDIET_OK;
 	if (!sc) { ctx->err = "scoring is NULL"; return GDIET_E_PARAM; }
 	gdiet_ksw_score_t s2 = *sc;
-	s2.q2 = sc->q, s2.e2 = sc->e; // ksw_extz2(q,e) == ksw_extd2(q,e,q,e) cell for cell in APPROX_MAX mode (see include/gdiet_hip.h)
-	ctx->single_affine = true;     // the 16- and 64-lane kernels then run their single-affine form (no X2 / Y2 half)
-	const int rc = gdiet_hip_ksw_extd2_batch(ctx, n, qseq, qoff, tseq, toff, w, nullptr, &s2, score, n_cigar, cigar, cigar_off);
-	ctx->single_affine = false;
-	return rc;
+	s2.q2 = sc->q, s2.e2 = sc->e;
+	KswConst K;
+	int rc = gd_consts(ctx, &s2, K); // (the same parameter checks at every scoring, whichever form runs)
+	if (rc) return rc;
+	if (gd_wave_scoring_ok(K)) {
+		// ksw_extz2(q,e) == ksw_extd2(q,e,q,e) cell for cell at every scoring the register-resident kernels take (see include/gdiet_hip.h)
+		ctx->single_affine = true; // the 16- and 64-lane kernels then run their single-affine form (no X2 / Y2 half)
+		rc = gdiet_hip_ksw_extd2_batch(ctx, n, qseq, qoff, tseq, toff, w, nullptr, &s2, score, n_cigar, cigar, cigar_off);
+		ctx->single_affine = false;
+		return rc;
+	}
+	// elsewhere the two can differ: ksw_extz2_sse's own recurrence, APPROX_MAX branch (ksw_extz2_exact.hip.h)
+	if (!score) { ctx->err = "NULL argument"; return GDIET_E_PARAM; }
+	std::vector<gdiet_ksw_extz_t> ez((size_t)n);
+	if ((rc = gd_extz2_literal(ctx, n, qseq, qoff, tseq, toff, w, sc, GD_EZ_APPROX_MAX, -1, 0, ez.data(), n_cigar, cigar, cigar_off))) return rc;
+	for (int i = 0; i < n; ++i) score[i] = ez[i].score;
+	return GDIET_OK;
 }
 
 // exact-max mode of ksw_extz2 (flag without APPROX_MAX): ksw_extz2_exact.hip.h
@@ -979,18 +998,26 @@ extern "C" int gdiet_hip_ksw_extz2_batch_ex(gdiet_ctx *ctx, int n, const uint8_t
 {
 	if (!ctx) return GDIET_E_PARAM;
 	if (n <= 0) return GDIET_OK;
-	if (!qseq || !qoff || !tseq || !toff || !w || !sc || !ez || !n_cigar || !cigar || !cigar_off) { ctx->err = "NULL argument"; return GDIET_E_PARAM; }
-	if (sc->flag & ~GD_EZ_EXTZ_ONLY) {
+	if (sc && (sc->flag & ~GD_EZ_EXTZ_ONLY)) {
 		ctx->err = "gdiet_hip_ksw_extz2_batch_ex takes flag 0 or KSW_EZ_EXTZ_ONLY (exact maximum); APPROX_MAX: gdiet_hip_ksw_extz2_batch";
 		return GDIET_E_PARAM;
 	}
+	return gd_extz2_literal(ctx, n, qseq, qoff, tseq, toff, w, sc, sc ? sc->flag : 0, zdrop, end_bonus, ez, n_cigar, cigar, cigar_off);
+}
+
+// ksw_extz2_sse with ksw_backtrack, literally: flag 0 / KSW_EZ_EXTZ_ONLY (exact maximum) or KSW_EZ_APPROX_MAX (sc->flag is not read)
+static int gd_extz2_literal(gdiet_ctx *ctx, int n, const uint8_t *qseq, const int64_t *qoff, const uint8_t *tseq, const int64_t *toff,
+                            const int32_t *w, const gdiet_ksw_score_t *sc, int32_t flag, int32_t zdrop, int32_t end_bonus,
+                            gdiet_ksw_extz_t *ez, int32_t *n_cigar, uint32_t *cigar, const int64_t *cigar_off)
+{
+	if (!qseq || !qoff || !tseq || !toff || !w || !sc || !ez || !n_cigar || !cigar || !cigar_off) { ctx->err = "NULL argument"; return GDIET_E_PARAM; }
 	static_assert(sizeof(gdiet_ksw_extz_t) == sizeof(GdExtzOut), "public and kernel record differ");
 	if (gd_tickets_open(ctx)) return GDIET_E_PARAM;
 	(void)hipSetDevice(ctx->device);
 	hipStream_t s = ctx->stream;
 	KswzConst K;
 	K.q = sc->q, K.e = sc->e, K.sc_mch = sc->match, K.sc_mis = sc->mismatch, K.sc_N = sc->sc_ambi == 0 ? -sc->e : sc->sc_ambi;
-	K.zdrop = zdrop, K.end_bonus = end_bonus, K.flag = sc->flag;
+	K.zdrop = zdrop, K.end_bonus = end_bonus, K.flag = flag;
 	{ // :88-90: the reference returns without aligning
 		const int min_sc = std::min<int>(std::min<int>(sc->mismatch, sc->match), std::min<int>(sc->sc_ambi, 0));
 		if (-min_sc > 2 * (K.q + K.e)) { ctx->err = "-min_sc > 2*(q+e): the reference returns without aligning"; return GDIET_E_PARAM; }
@@ -1011,8 +1038,8 @@ extern "C" int gdiet_hip_ksw_extz2_batch_ex(gdiet_ctx *ctx, int n, const uint8_t
 		bt += gd_align256((size_t)(T.qlen + T.tlen - 1) * (size_t)T.row_bytes + 64);
 		max_cap = std::max(max_cap, gd_generic_cap(T.qlen, T.tlen, T.w));
 	}
-	const size_t lds = (size_t)max_cap * 9;
-	if (lds > 160 * 1024 - 1024) { ctx->err = "band wider than the LDS window of the exact-maximum kernel"; return GDIET_E_PARAM; }
+	const size_t lds = (size_t)max_cap * (flag & GD_EZ_APPROX_MAX ? 5 : 9); // u v x y s, and the int32 H ring of the exact maximum
+	if (lds > 160 * 1024 - 1024) { ctx->err = "band wider than the LDS window of the literal ksw_extz2 kernel"; return GDIET_E_PARAM; }
 	const size_t qb = (size_t)qoff[n], tb = (size_t)toff[n], cb = (size_t)cigar_off[n];
 	if ((rc = gd_grow(ctx, ctx->arena, bt))) return rc;
 	if ((rc = gd_grow(ctx, ctx->tasks, sizeof(KswTask) * n))) return rc;

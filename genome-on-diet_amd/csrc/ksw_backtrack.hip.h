@@ -48,7 +48,7 @@ __global__ __launch_bounds__(64) void ksw_exact_match_kernel(const KswTask *__re
                                                              const uint8_t *__restrict__ tseq,
                                                              int32_t *__restrict__ status, int32_t *__restrict__ score,
                                                              int32_t *__restrict__ n_cigar, uint32_t *__restrict__ cigar,
-                                                             int32_t *__restrict__ diag, int sc_mch, int sc_mis, int gap_thr)
+                                                             int32_t *__restrict__ diag, int sc_mch, int sc_mis, int gap_thr, int score_bias = 0)
 {
 	const int tid = blockIdx.x * blockDim.x + threadIdx.x;
 	if (tid >= n) return;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(64) void ksw_exact_match_kernel(const KswTask *__re
 			dg = (T.qlen - n_mis) * sc_mch + n_mis * sc_mis;
 			if (st == GD_ST_PENDING && n_mis * (sc_mch - sc_mis) < gap_thr) { // (1): no other path can reach the diagonal's score
 				st = GD_ST_EXACT;
-				score[tid] = dg;
+				score[tid] = dg + score_bias; // (see ksw_score_bias_kernel)
 				n_cigar[tid] = 1;
 				if (T.cig_cap >= 1) cigar[T.cig_off] = (uint32_t)T.qlen << 4;
 			}
@@ -88,6 +88,18 @@ __global__ __launch_bounds__(64) void ksw_exact_match_kernel(const KswTask *__re
 	}
 	status[tid] = st;
 	if (diag) diag[tid] = dg;
+}
+
+// The reference sets qe = q + e from the caller's FIRST gap model before it swaps the two (SR/ksw2_extd2_sse.c:68,78) and starts the
+// score walk with it (:379): passed the larger model first, every score it reports from the DP is off by score_bias = (the smaller q+e) -
+// (the caller's q+e).  Added once the walks are done (ksw_backtrack_kernel compares the unbiased score with the diagonal's); the pre-filter's
+// exact-match answers are the caller's exact_score and stay as they are.  Launched only where the bias is not 0.
+__global__ __launch_bounds__(64) void ksw_score_bias_kernel(int n, const KswTask *__restrict__ tasks, const int32_t *__restrict__ status,
+                                                            int32_t *__restrict__ score, int score_bias)
+{
+	const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+	if (tid >= n || tasks[tid].qlen <= 0 || tasks[tid].tlen <= 0) return;
+	if (status[tid] != GD_ST_EXACT && score[tid] != GD_NEG_INF) score[tid] += score_bias;
 }
 
 // ksw_backtrack (SR/ksw2.h:131-163) of one alignment by ONE THREAD, from cell (i, j): the body of ksw_backtrack_kernel, and the tail of

@@ -1,8 +1,9 @@
-// K3, exact-max mode (flag without KSW_EZ_APPROX_MAX): ksw_extz2_sse with the per-cell H array (SR/ksw2_extz2_sse.c:31-312,
-// exact branch :226-268), one 64-lane wavefront per alignment, DP state and H in an LDS sliding window.  The APPROX_MAX mode --
-// the only one GDiet's live path passes -- runs on the register-resident kernels (ksw_wave.hip.h); this kernel exists for
-// BASELINE config 2 ("flags KSW_EZ_APPROX_MAX and 0") and returns everything ksw_extz_t carries: max / max_q / max_t (z-drop
-// bookkeeping, SR/ksw2.h:172-188), mqe / mqe_t, mte / mte_q, score, zdropped, reach_end.
+// K3, literal form: ksw_extz2_sse (SR/ksw2_extz2_sse.c:31-312), one 64-lane wavefront per alignment, DP state in an LDS sliding
+// window.  Exact-max mode (flag without KSW_EZ_APPROX_MAX): the per-cell H array (exact branch :226-268); this is BASELINE config 2
+// ("flags KSW_EZ_APPROX_MAX and 0") and returns everything ksw_extz_t carries: max / max_q / max_t (z-drop bookkeeping,
+// SR/ksw2.h:172-188), mqe / mqe_t, mte / mte_q, score, zdropped, reach_end.  APPROX_MAX mode (:278-294, no APPROX_DROP): the score
+// walked along the running maximum; gdiet_hip_ksw_extz2_batch runs it at the scorings where ksw_extz2(q,e) is not ksw_extd2(q,e,q,e)
+// (every scoring the register-resident kernels refuse, see include/gdiet_hip.h).
 //
 // Literal semantics: the unsigned-biased recurrence (z = s + 2(q+e), signed compares for the direction, unsigned max / min for
 // the value, :38-56,185-203), 16-aligned computed window with stale s[], boundary x1 = v1 = 0 / q rule (:126-131), H[en0] from
@@ -21,6 +22,7 @@ struct KswzConst {
 	int32_t q, e, sc_mch, sc_mis, sc_N, zdrop, end_bonus, flag;
 };
 #define GD_EZ_EXTZ_ONLY 0x40
+#define GD_EZ_APPROX_MAX 0x08
 
 // start[2*tid], start[2*tid+1]: the cell (i0, j0) the backtrack starts from (SR/ksw2_extz2_sse.c:296-305); status DONE = walk,
 // ZDROPPED = no CIGAR
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(64) void ksw_extz2_exact_kernel(const KswTask *__re
 	const KswTask T = tasks[tid];
 	const int mask = cap - 1;
 	uint8_t *u = gdz_lds, *v = u + cap, *x = v + cap, *y = x + cap, *s = y + cap;
-	int32_t *H = (int32_t *)(s + cap);
+	int32_t *H = (int32_t *)(s + cap); // (exact-maximum mode only: APPROX_MAX launches allocate no H ring and never touch it)
 	const uint8_t *query = qseq + T.qoff, *target = tseq + T.toff;
 	const int qlen = T.qlen, tlen = T.tlen;
 	const int w = T.w < 0 ? (tlen > qlen ? tlen : qlen) : T.w;
@@ -48,6 +50,7 @@ __global__ __launch_bounds__(64) void ksw_extz2_exact_kernel(const KswTask *__re
 	const int8_t sc_mch = (int8_t)K.sc_mch, sc_mis = (int8_t)K.sc_mis, sc_N = (int8_t)K.sc_N;
 
 	int hi_init = -1, last_st = -1, last_en = -1;
+	int32_t H0 = 0, last_H0_t = 0; // APPROX_MAX (lane 0 only)
 	// ez (every lane keeps the same copy)
 	int32_t ez_max = 0, ez_max_q = -1, ez_max_t = -1, ez_mqe = GD_NEG_INF, ez_mqe_t = -1, ez_mte = GD_NEG_INF, ez_mte_q = -1, ez_score = GD_NEG_INF;
 	int zdropped = 0;
@@ -67,7 +70,7 @@ __global__ __launch_bounds__(64) void ksw_extz2_exact_kernel(const KswTask *__re
 		for (int t = hi_init + 1 + lane; t <= hi; t += 64) { // the reference's kcalloc'd state (:96-103) and H = KSW_NEG_INF (:106)
 			const int c = t & mask;
 			u[c] = v[c] = x[c] = y[c] = s[c] = 0;
-			H[c] = GD_NEG_INF;
+			if (!(K.flag & GD_EZ_APPROX_MAX)) H[c] = GD_NEG_INF;
 		}
 		if (hi > hi_init) hi_init = hi;
 		__syncthreads();
@@ -114,6 +117,22 @@ __global__ __launch_bounds__(64) void ksw_extz2_exact_kernel(const KswTask *__re
 				pr[t - st] = (uint8_t)d;
 			}
 			__syncthreads();
+		}
+		if (K.flag & GD_EZ_APPROX_MAX) { // ---- approximate maximum (:278-294): the score walked along the running maximum, lane 0 ----
+			if (lane == 0) {
+				if (r > 0) {
+					if (last_H0_t >= st0 && last_H0_t <= en0 && last_H0_t + 1 >= st0 && last_H0_t + 1 <= en0) {
+						const int32_t d0 = (int32_t)v[last_H0_t & mask] - qe, d1 = (int32_t)u[(last_H0_t + 1) & mask] - qe;
+						if (d0 > d1) H0 += d0;
+						else H0 += d1, ++last_H0_t;
+					} else if (last_H0_t >= st0 && last_H0_t <= en0) H0 += (int32_t)v[last_H0_t & mask] - qe;
+					else ++last_H0_t, H0 += (int32_t)u[last_H0_t & mask] - qe;
+				} else H0 = (int32_t)v[0] - qe - qe, last_H0_t = 0;
+				if (r == qlen + tlen - 2 && en0 == tlen - 1) ez_score = H0;
+			}
+			last_st = st, last_en = en;
+			__syncthreads();
+			continue;
 		}
 		// ---- exact maximum of the row (:226-268) ----
 		int32_t max_H, max_t;

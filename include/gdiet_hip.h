@@ -104,11 +104,14 @@ int gdiet_hip_ksw_extd2_batch_dev(gdiet_ctx *ctx, int n,
  * mapping path).  Same batch layout and outputs as gdiet_hip_ksw_extd2_batch; sc->q / sc->e are the gap costs, sc->q2 / sc->e2
  * are ignored, sc->flag must be GDIET_EZ_APPROX_MAX (the only mode GDiet ever passes; the exact-maximum mode is
  * gdiet_hip_ksw_extz2_batch_ex below); sequence bytes must be 0..4 (the one
- * out-of-alphabet byte GDiet produces, 7 for a reverse-complemented N, only ever reaches ksw_extd2).  Implementation note: in
- * that mode ksw_extz2(q,e) and ksw_extd2(q,e,q,e) visit identical cells with identical values (the unsigned bias of extz2 is a
- * re-labelling, and a second gap model equal to the first can never win the priority chain), so the register-resident kernels
- * run their single-affine form -- the dual-affine recurrence with the X2 / Y2 half dropped -- and the generic LDS kernel runs
- * with both gap models equal; tests pin this against ksw_extz2_sse's own outputs (tests/golden/ksw2_extz2.npz). */
+ * out-of-alphabet byte GDiet produces, 7 for a reverse-complemented N, only ever reaches ksw_extd2).  Implementation note: at the
+ * scorings the register-resident kernels take (gd_wave_scoring_ok: a + 3(q+e) + max(b,|N|) <= 120 and q+e small enough for the
+ * byte-wide S keys) ksw_extz2(q,e) and ksw_extd2(q,e,q,e) visit identical cells with identical values -- the unsigned bias of extz2
+ * is then a re-labelling that never crosses 127, and a second gap model equal to the first never wins the priority chain -- so
+ * those kernels run their single-affine form.  Elsewhere the identity does not hold (the biased bytes leave the signed range, e.g.
+ * a + 2(q+e) >= 128 wraps, and smaller scorings such as (a,b,q,e) = (2,32,40,2) differ in CIGARs through the band-edge padding
+ * cells), and the call runs ksw_extz2_sse's own recurrence (ksw_extz2_exact.hip.h, APPROX_MAX branch; last_kernel_mask 2).  Tests
+ * pin both against ksw_extz2_sse's outputs (tests/golden/ksw2_extz2.npz, ksw2_scoring.npz). */
 int gdiet_hip_ksw_extz2_batch(gdiet_ctx *ctx, int n,
                               const uint8_t *qseq, const int64_t *qoff,
                               const uint8_t *tseq, const int64_t *toff,

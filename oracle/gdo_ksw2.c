@@ -152,7 +152,7 @@ void gdo_ksw_extd2(int qlen, const uint8_t *query, int tlen, const uint8_t *targ
                    gdo_extz_t *ez)
 {
 	int r, t, i, qe = q + e, n_col_, *off = 0, *off_end = 0, tlen_, qlen_, last_st, last_en, max_sc, min_sc;
-	int long_thres, long_diff;
+	int long_thres, long_diff, h0_qe;
 	int with_cigar = !(flag & GDO_EZ_SCORE_ONLY), approx_max = !!(flag & GDO_EZ_APPROX_MAX);
 	int32_t *H = 0, H0 = 0, last_H0_t = 0;
 	u8t *mem, *qr, *sf, *p = 0;
@@ -161,6 +161,9 @@ void gdo_ksw_extd2(int qlen, const uint8_t *query, int tlen, const uint8_t *targ
 
 	reset_extz(ez);
 	if (m <= 1 || qlen <= 0 || tlen <= 0) return;
+	/* :68,78: qe is set from the caller's FIRST gap model before the swap, and the reference keeps using it where H[0] / H0 start
+	 * (:358,379) -- passed the larger model first, every score it reports is off by (the caller's q+e) - (the smaller q+e) */
+	h0_qe = qe;
 	if (q2 + e2 < q + e) t = q, q = q2, q2 = t, t = e, e = e2, e2 = t; /* :78 */
 	qe = q + e;
 	sc_mch = mat[0], sc_mis = mat[1];
@@ -279,7 +282,7 @@ void gdo_ksw_extd2(int qlen, const uint8_t *query, int tlen, const uint8_t *targ
 					H[t] += (int32_t)v[t];
 					if (H[t] > max_H) max_H = H[t], max_t = t;
 				}
-			} else H[0] = v[0] - qe, max_H = H[0], max_t = 0;
+			} else H[0] = v[0] - h0_qe, max_H = H[0], max_t = 0;
 			if (en0 == tlen - 1 && H[en0] > ez->mte) ez->mte = H[en0], ez->mte_q = r - en;
 			if (r - st0 == qlen - 1 && H[st0] > ez->mqe) ez->mqe = H[st0], ez->mqe_t = st0;
 			if (apply_zdrop(ez, max_H, r, max_t, zdrop, e2)) break;
@@ -295,7 +298,7 @@ void gdo_ksw_extd2(int qlen, const uint8_t *query, int tlen, const uint8_t *targ
 				} else {
 					++last_H0_t, H0 += u[last_H0_t];
 				}
-			} else H0 = v[0] - qe, last_H0_t = 0;
+			} else H0 = v[0] - h0_qe, last_H0_t = 0;
 			if ((flag & GDO_EZ_APPROX_DROP) && apply_zdrop(ez, H0, r, last_H0_t, zdrop, e2)) break;
 			if (r == qlen + tlen - 2 && en0 == tlen - 1) ez->score = H0;
 		}

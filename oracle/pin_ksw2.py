@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Pin the ksw2 oracle (oracle/gdo_ksw2.c) against the reference itself and (re)generate the committed golden
-vectors tests/golden/ksw2_extd2.npz, ksw2_extz2.npz, exact_match.npz.
+vectors tests/golden/ksw2_extd2.npz, ksw2_extz2.npz, exact_match.npz and, over gdo.SCORINGS, ksw2_scoring.npz.
 
 Runs only where oracle/_ref has been built from /root/reference (this container).  The golden vectors hold
 inputs + the REFERENCE's outputs (ksw_extd2_sse / ksw_extz2_sse / exact_match_sse called through ctypes), so the
@@ -84,8 +84,144 @@ def cases(rng, n, heavy=True):
         yield ("k%d" % kind, q, t, preset, w, zdrop, end_bonus, flag)
 
 
+WIDE_AT = ("sr", "ont", "bound120_last", "skey_corner", "a16", "wrap_2_8_60_3", "k3_2_32_40_2")
+SC_CLASSES = ("sr", "group", "lane64", "wide", "misc", "k3")
+
+
+def scoring_cases(rng, name):
+    """yield (class, query, target, w) for one scoring of gdo.SCORINGS: the shapes each kernel form takes -- short-read 150 x 150
+    (one exact copy among them), the grouped widths (targets around 128 / 160 / 256), 64-lane lengths, for a few scorings the wide
+    ONT band, and band-edge / N stress"""
+    for i in range(4):
+        q, t = gdo.make_pair(rng, 150, 0.02, 0.003, 0.003, n_frac=0.01 if i == 2 else 0.0)
+        n = min(len(q), len(t))
+        q, t = (t[:150].copy(), t[:150]) if i == 0 else (q[:n], t[:n])
+        yield "sr", q, t, 150
+    for tl in (120, 155, 250):
+        q, t = gdo.make_pair(rng, tl, 0.03, 0.006, 0.006)
+        yield "group", q, t, 150
+    for _ in range(2):
+        tl = int(rng.integers(300, 3000))
+        q, t = gdo.make_pair(rng, tl, 0.01, 0.003, 0.003)
+        yield "lane64", q, t, int(rng.integers(100, 500))
+    if name in WIDE_AT:
+        q, t = gdo.make_pair(rng, int(rng.integers(1500, 2500)), 0.03, 0.02, 0.02)
+        yield "wide", q, t, 1300
+    tl = int(rng.integers(300, 900))
+    w = int(rng.integers(40, 200))
+    q, t = gdo.make_pair(rng, tl, 0.01, 0.002, 0.002, big_indel=int(w * rng.uniform(0.4, 0.62)) * (1 if rng.random() < 0.5 else -1))
+    yield "misc", q, t, w
+    q, t = gdo.make_pair(rng, int(rng.integers(60, 600)), 0.05, 0.02, 0.02, n_frac=0.03)
+    yield "misc", q, t, int(rng.integers(10, 300))
+
+
+SC_KEYS = ("score", "zdropped", "max", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "reach_end")
+
+
+def k3_cases(ref, rng, name, want=3, tries=3000):
+    """yield ("k3", query, target, w): divergent pairs in narrow bands at one of the table's k3_* scorings on which the reference's own
+    ksw_extz2_sse and ksw_extd2_sse(q,e,q,e) differ (they differ in a few pairs in a hundred, so a fixed shape set would miss them)"""
+    a, b, go, ge, _, _, amb = gdo.SCORINGS[name]
+    mat = gdo.score_matrix(a, b, sc_ambi=amb)
+    n = 0
+    for _ in range(tries):
+        tl, w = int(rng.integers(30, 400)), int(rng.integers(10, 200))
+        q, t = gdo.make_pair(rng, tl, 0.05, 0.03, 0.03)
+        if not gdo.same(gdo.ref_extz2(ref, q, t, mat, go, ge, w), gdo.ref_extd2(ref, q, t, mat, go, ge, go, ge, w)):
+            yield "k3", q, t, w
+            n += 1
+            if n == want:
+                return
+
+
+def pin_scorings(ora, ref, seed):
+    """every scoring of gdo.SCORINGS: the reference's ksw_extd2_sse, ksw_extd2_avx512 (byte-7 queries), ksw_extz2_sse in APPROX_MAX and in
+    exact mode against the oracle; returns (mismatches, golden records, pairs where ksw_extz2 != ksw_extd2(q,e,q,e))"""
+    rng = np.random.default_rng(seed + 2000)
+    n_bad = n_k3 = n_avx_k3 = 0
+    gold = []
+    for si, (name, (a, b, go, ge, go2, ge2, amb)) in enumerate(gdo.SCORINGS.items()):
+        mat = gdo.score_matrix(a, b, sc_ambi=amb)
+        shapes = list(scoring_cases(rng, name))
+        if name.startswith("k3_"):
+            k3 = list(k3_cases(ref, rng, name))
+            if not k3:
+                n_bad += 1
+                print("NO PAIR where ksw_extz2 != ksw_extd2(q,e,q,e) found at", name)
+            shapes += k3
+        for ci, (cls, q, t, w) in enumerate(shapes):
+            r = gdo.ref_extd2(ref, q, t, mat, go, ge, go2, ge2, w)
+            o = gdo.oracle_extd2(ora, q, t, mat, go, ge, go2, ge2, w)
+            q7 = q.copy()
+            if ci % 2 and len(q7) > 4 and cls != "k3":  # (k3 pairs: no byte-7 queries, see DESIGN.md "Scorings")
+                q7[rng.integers(0, len(q7), size=max(1, len(q7) // 100))] = 7
+            v = gdo.ref_extd2(ref, q7, t, mat, go, ge, go2, ge2, w, fn="ksw_extd2_avx512")
+            o7 = gdo.oracle_extd2(ora, q7, t, mat, go, ge, go2, ge2, w, flag=gdo.EZ_APPROX_MAX | gdo.EZ_AVX512_SC)
+            rz = gdo.ref_extz2(ref, q, t, mat, go, ge, w)
+            oz = gdo.oracle_extz2(ora, q, t, mat, go, ge, w)
+            flag_x, zdrop_x, eb_x = (0, gdo.EZ_EXTZ_ONLY)[ci % 2], (-1, 100, 400)[ci % 3], (0, 5)[ci % 2]
+            rx = gdo.ref_extz2(ref, q, t, mat, go, ge, w, zdrop_x, eb_x, flag_x)
+            ox = gdo.oracle_extz2(ora, q, t, mat, go, ge, w, zdrop_x, eb_x, flag_x)
+            for what, x, y in (("extd2", o, r), ("extd2_avx512", o7, v), ("extz2", oz, rz), ("extz2_exact", ox, rx)):
+                if what == "extd2_avx512" and cls == "k3":
+                    # the pairs picked because the band-edge padding cells decide them: there ksw_extd2_avx512, whose windows are
+                    # 64-cell aligned, can differ from ksw_extd2_sse (16-cell), and the oracle models the SSE windows only
+                    n_avx_k3 += not gdo.same(x, y, SC_KEYS)
+                    continue
+                if not gdo.same(x, y, SC_KEYS):
+                    n_bad += 1
+                    if n_bad <= 5:
+                        print("MISMATCH scoring", name, what, cls, len(q), len(t), w, {k: (x[k], y[k]) for k in SC_KEYS if x[k] != y[k]})
+            n_k3 += not gdo.same(rz, gdo.ref_extd2(ref, q, t, mat, go, ge, go, ge, w))
+            gold.append((si, cls, q, q7, t, w, flag_x, zdrop_x, eb_x, r, v, rz, rx))
+    print("k3 pairs where ksw_extd2_avx512 differs from the oracle (SSE windows): %d" % n_avx_k3)
+    return n_bad, gold, n_k3
+
+
+def write_scoring_golden(path, gold):
+    def pack(seqs, dt=np.uint8):
+        offs = np.zeros(len(seqs) + 1, np.int64)
+        offs[1:] = np.cumsum([len(x) for x in seqs])
+        return (np.concatenate(seqs).astype(dt) if seqs else np.zeros(0, dt)), offs
+    out = {}
+    out["q"], out["qo"] = pack([g[2] for g in gold])
+    out["q7"], _ = pack([g[3] for g in gold])
+    out["t"], out["to"] = pack([g[4] for g in gold])
+    out["params"] = np.array([[g[0], SC_CLASSES.index(g[1]), g[5], g[6], g[7], g[8]] for g in gold], np.int32)
+    out["scorings"] = np.array(list(gdo.SCORINGS.values()), np.int32)
+    out["scoring_names"] = np.array(list(gdo.SCORINGS.keys()))
+    for key, k in (("extd2", 9), ("extd2_avx512", 10), ("extz2", 11), ("extz2_exact", 12)):
+        out[key + "_cigar"], out[key + "_cigar_off"] = pack([g[k]["cigar"].view(np.uint8) for g in gold])
+        out[key + "_scalars"] = np.array([[g[k][f] for f in SC_KEYS] for g in gold], np.int64)
+    np.savez_compressed(path, **out)
+
+
+def identity_sweep(ref, pairs=24, seed=11):
+    """ksw_extz2_sse(q,e) against ksw_extd2_sse(q,e,q,e) on `pairs` pairs at every single-affine scoring with a <= 16, b <= 40,
+    q <= 40, e <= 20 that gd_consts accepts, split by gdo.wave_scoring_ok: (scorings taken, of them differing), (refused, differing)"""
+    rng = np.random.default_rng(seed)
+    ps = []
+    for i in range(pairs):
+        q, t = gdo.make_pair(rng, int(rng.integers(30, 400)), 0.05, 0.03, 0.03, n_frac=0.01 if i % 5 == 0 else 0)
+        ps.append((q, t, int(rng.integers(10, 200)) if i % 4 else -1))
+    cnt = {True: [0, 0], False: [0, 0]}
+    for a in range(1, 17):
+        for b in range(1, 41):
+            for go in range(0, 41):
+                for ge in range(1, 21):
+                    if 2 * (go + ge) > 127 or b > 2 * (go + ge):
+                        continue
+                    ok = gdo.wave_scoring_ok(a, b, go, ge, go, ge)
+                    mat = gdo.score_matrix(a, b)
+                    bad = any(not gdo.same(gdo.ref_extz2(ref, q, t, mat, go, ge, w), gdo.ref_extd2(ref, q, t, mat, go, ge, go, ge, w)) for q, t, w in ps)
+                    cnt[ok][0] += 1
+                    cnt[ok][1] += bad
+    return cnt[True], cnt[False]
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--identity-sweep", action="store_true", help="only the ksw_extz2 / ksw_extd2(q,e,q,e) sweep (minutes)")
     ap.add_argument("--fuzz", type=int, default=1200)
     ap.add_argument("--seed", type=int, default=4)
     ap.add_argument("--write-golden", action="store_true")
@@ -94,6 +230,11 @@ def main():
     gdo.build_oracle()
     ora = gdo.load_oracle()
     ref = gdo.load_ref("lr_avx")
+    if args.identity_sweep:
+        (n_ok, bad_ok), (n_no, bad_no) = identity_sweep(ref)
+        print("single-affine scorings the wave forms take: %d, ksw_extz2 != ksw_extd2(q,e,q,e) at %d; refused: %d, differing at %d"
+              % (n_ok, bad_ok, n_no, bad_no))
+        return 1 if bad_ok else 0
     rng = np.random.default_rng(args.seed)
 
     n_bad_sse = n_bad_avx = n_sse_vs_avx = 0
@@ -190,6 +331,10 @@ def main():
         if i < 300:
             gold_exact.append((q, t, preset, w, zdrop, end_bonus, flag, rz))
     n_bad_sse += n_bad_exact
+    n_bad_sc, gold_sc, n_k3 = pin_scorings(ora, ref, args.seed)
+    n_bad_sse += n_bad_sc
+    print("scoring table: %d scorings, %d pairs, oracle_vs_reference_mismatch=%d (ksw_extz2 != ksw_extd2(q,e,q,e) in %d pairs)"
+          % (len(gdo.SCORINGS), len(gold_sc), n_bad_sc, n_k3))
     print("extz2 exact-maximum mode: pairs=%d oracle_vs_sse_mismatch=%d (z-dropped in %d of the %d golden pairs)"
           % (1200 if args.fuzz >= 1000 else 300, n_bad_exact, sum(1 for g in gold_exact if g[7]["zdropped"]), len(gold_exact)))
     print("pairs=%d oracle_vs_sse_mismatch=%d oracle_vs_avx512_mismatch=%d sse_vs_avx512_differ_on_byte7_inputs=%d exact_match_mismatch=%d"
@@ -232,6 +377,7 @@ def main():
         et, eto = pack([e[1] for e in em])
         np.savez_compressed(os.path.join(GOLDEN, "exact_match.npz"), q=eq, qo=eqo, t=et, to=eto,
                             expect=np.array([e[2] for e in em], np.int32))
+        write_scoring_golden(os.path.join(GOLDEN, "ksw2_scoring.npz"), gold_sc)
         print("golden vectors written to", GOLDEN)
     return 1 if (n_bad_sse or n_bad_em) else 0
 

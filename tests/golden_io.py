@@ -58,3 +58,27 @@ def load_lchain():
         b = np.stack([z["bx"][z["bo"][i]:z["bo"][i + 1]], z["by"][z["bo"][i]:z["bo"][i + 1]]], axis=1).astype(np.uint64)
         out.append(dict(a=a, par=par, u=u, b=b))
     return out
+
+
+SCORING_CLASSES = ("sr", "group", "lane64", "wide", "misc", "k3")
+SCORING_OUTPUTS = ("extd2", "extd2_avx512", "extz2", "extz2_exact")
+
+
+def load_scoring():
+    """tests/golden/ksw2_scoring.npz (oracle/pin_ksw2.py): per case the scoring of gdo.SCORINGS it was run at (name and
+    (a, b, q, e, q2, e2, sc_ambi)), its shape class, the inputs (q7: the query with byte-7 Ns the AVX-512 output was computed on) and
+    the reference's ksw_extd2_sse / ksw_extd2_avx512 / ksw_extz2_sse (APPROX_MAX) / ksw_extz2_sse (exact mode: flag, zdrop, end_bonus)
+    outputs"""
+    z = np.load(os.path.join(GOLDEN, "ksw2_scoring.npz"))
+    names = [str(s) for s in z["scoring_names"]]
+    out = []
+    for i in range(len(z["params"])):
+        si, cls, w, flag_x, zdrop_x, eb_x = [int(v) for v in z["params"][i]]
+        c = dict(scoring=names[si], sc=tuple(int(v) for v in z["scorings"][si]), cls=SCORING_CLASSES[cls], w=w,
+                 flag_x=flag_x, zdrop_x=zdrop_x, end_bonus_x=eb_x,
+                 q=z["q"][z["qo"][i]:z["qo"][i + 1]], q7=z["q7"][z["qo"][i]:z["qo"][i + 1]], t=z["t"][z["to"][i]:z["to"][i + 1]])
+        for k in SCORING_OUTPUTS:
+            off = z[k + "_cigar_off"]
+            c[k] = dict(zip(SCALARS, [int(v) for v in z[k + "_scalars"][i]]), cigar=z[k + "_cigar"][off[i]:off[i + 1]].view(np.uint32))
+        out.append(c)
+    return out

@@ -1,7 +1,7 @@
 """CPU: the oracle (oracle/gdo_ksw2.c) reproduces the reference's outputs stored in tests/golden/."""
 import numpy as np
 
-from golden_io import SCALARS, load_exact, load_ksw
+from golden_io import SCALARS, SCORING_OUTPUTS, load_exact, load_ksw, load_scoring
 
 
 def test_extd2_oracle_matches_reference_golden(oracle):
@@ -132,23 +132,81 @@ def test_few_mismatches_mean_the_main_diagonal(oracle):
     """what the library's widened pre-filter rests on (ksw_exact_match_kernel, csrc/ksw_backtrack.hip.h): an N-free pair of equal length
     with m substitutions and m (a + b) <= a + 2 (q + e) aligns along its main diagonal -- score (n - m) a - m b, CIGAR "<n>M" -- because any
     other corner-to-corner path pays two gap opens and scores one pair less (at equality a gapped path may tie; the backtrack's priority
-    order still walks the diagonal).  Checked on the oracle for the three presets, wide and
-    narrow bands, and on the reference's own ksw_extd2_sse where oracle/_ref is built"""
+    order still walks the diagonal).  Checked on the oracle for every scoring of gdo.SCORINGS the short-alignment kernels take (the
+    pre-filter only answers for those), wide and narrow bands, and on the reference's own ksw_extd2_sse where oracle/_ref is built.
+    (Passed the larger gap model first, the reference reports every DP score shifted by the difference of the two q+e: ksw_score_bias_kernel.)"""
     gdo, lib = oracle
     ref = gdo.load_ref() if gdo.have_ref() else None
     rng = np.random.default_rng(2025)
     n = 0
-    for name, (a, b, go, ge, go2, ge2) in gdo.PRESETS.items():
-        if go2 + ge2 < go + ge:
-            go, ge, go2, ge2 = go2, ge2, go, ge
-        mat = gdo.score_matrix(a, b)
-        for q, t, mm in _diag_cases(rng, 700, a, b, a + 2 * (go + ge)):
+    for name, (a, b, go, ge, go2, ge2, amb) in gdo.SCORINGS.items():
+        if not gdo.wave_scoring_ok(a, b, go, ge, go2, ge2, amb):
+            continue
+        bias = min(go + ge, go2 + ge2) - (go + ge)
+        mat = gdo.score_matrix(a, b, sc_ambi=amb)
+        for q, t, mm in _diag_cases(rng, 700 if name in gdo.PRESETS else 150, a, b, a + 2 * min(go + ge, go2 + ge2)):
             ln = len(q)
             for w in (ln, ln // 3 + 20):
                 o = gdo.oracle_extd2(lib, q, t, mat, go, ge, go2, ge2, w)
-                assert o["score"] == (ln - mm) * a - mm * b and list(o["cigar"]) == [ln << 4], (name, ln, mm, w)
+                assert o["score"] == (ln - mm) * a - mm * b + bias and list(o["cigar"]) == [ln << 4], (name, ln, mm, w)
                 if ref is not None and n % 5 == 0:
                     r = gdo.ref_extd2(ref, q, t, mat, go, ge, go2, ge2, w)
                     assert r["score"] == o["score"] and np.array_equal(r["cigar"], o["cigar"]), (name, ln, mm, w)
                 n += 1
     assert n > 3000
+
+
+def test_oracle_matches_reference_golden_at_every_table_scoring(oracle):
+    """tests/golden/ksw2_scoring.npz: at every scoring of gdo.SCORINGS (presets, both sides of the wave forms' limits, single affine,
+    the gap models swapped, large match scores, the mismatch limit, a score for N, scorings where the 8-bit recurrence wraps, those where
+    ksw_extz2 != ksw_extd2(q,e,q,e)) the oracle reproduces ksw_extd2_sse, ksw_extd2_avx512, and ksw_extz2_sse in both modes"""
+    gdo, lib = oracle
+    cases = load_scoring()
+    assert {c["scoring"] for c in cases} == set(gdo.SCORINGS) and len(cases) >= 200
+    assert {c["scoring"]: c["sc"] for c in cases} == dict(gdo.SCORINGS)
+    for c in cases:
+        a, b, q, e, q2, e2, amb = c["sc"]
+        mat = gdo.score_matrix(a, b, sc_ambi=amb)
+        got = dict(extd2=gdo.oracle_extd2(lib, c["q"], c["t"], mat, q, e, q2, e2, c["w"]),
+                   extd2_avx512=gdo.oracle_extd2(lib, c["q7"], c["t"], mat, q, e, q2, e2, c["w"], flag=gdo.EZ_APPROX_MAX | gdo.EZ_AVX512_SC),
+                   extz2=gdo.oracle_extz2(lib, c["q"], c["t"], mat, q, e, c["w"]),
+                   extz2_exact=gdo.oracle_extz2(lib, c["q"], c["t"], mat, q, e, c["w"], c["zdrop_x"], c["end_bonus_x"], c["flag_x"]))
+        for k in SCORING_OUTPUTS:
+            if k == "extd2_avx512" and c["cls"] == "k3":
+                continue  # (decided by the band-edge padding cells, whose width differs in the AVX-512 build: DESIGN.md, K3)
+            for f in SCALARS:
+                assert got[k][f] == c[k][f], (c["scoring"], c["cls"], k, f, got[k][f], c[k][f])
+            assert np.array_equal(got[k]["cigar"], c[k]["cigar"]), (c["scoring"], c["cls"], k)
+
+
+def test_extz2_is_extd2_where_the_wave_forms_run_and_not_everywhere(oracle):
+    """gdiet_hip_ksw_extz2_batch runs ksw_extz2(q,e) as ksw_extd2(q,e,q,e) only at scorings the register-resident kernels take
+    (gdo.wave_scoring_ok); there the two agree on every golden pair and on a sweep of single-affine scorings.  At the table's K3 scorings
+    they do not -- which is why the library runs ksw_extz2's own recurrence there"""
+    gdo, lib = oracle
+    cases = load_scoring()
+    differ = set()
+    for c in cases:
+        a, b, q, e, _, _, amb = c["sc"]
+        mat = gdo.score_matrix(a, b, sc_ambi=amb)
+        d = gdo.oracle_extd2(lib, c["q"], c["t"], mat, q, e, q, e, c["w"])
+        if gdo.wave_scoring_ok(a, b, q, e, q, e, amb):
+            assert gdo.same(d, c["extz2"]), (c["scoring"], c["cls"])
+        elif not gdo.same(d, c["extz2"]):
+            differ.add(c["scoring"])
+    assert {"wrap_2_8_60_3", "wrap_10_20_40_20"} | {k for k in gdo.SCORINGS if k.startswith("k3_")} <= differ, differ
+    assert all(not gdo.wave_scoring_ok(*gdo.SCORINGS[k]) for k in differ)
+    rng = np.random.default_rng(99)
+    pairs = [gdo.make_pair(rng, int(rng.integers(30, 300)), 0.05, 0.03, 0.03) + (int(rng.integers(10, 150)),) for _ in range(6)]
+    n = 0
+    for a in (1, 2, 4):
+        for q in range(0, 15, 2):
+            for e in (1, 2, 3):
+                for b in range(2, 2 * (q + e) + 1, 3):
+                    if not gdo.wave_scoring_ok(a, b, q, e, q, e):
+                        continue
+                    mat = gdo.score_matrix(a, b)
+                    for qs, ts, w in pairs:
+                        assert gdo.same(gdo.oracle_extz2(lib, qs, ts, mat, q, e, w), gdo.oracle_extd2(lib, qs, ts, mat, q, e, q, e, w)), (a, b, q, e)
+                        n += 1
+    assert n > 1000
