@@ -45,18 +45,13 @@ struct gdiet_ctx {
 	DevBuf pipes, pipe_runs, pipe_dst; // PipeWave / PipeRun records of the batch and the compacted id lists of its runs (ksw_pipe.hip.h)
 	DevBuf qseq, tseq, score, ncig, cigar; // host-API staging
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-	// head / tail split of a big DP launch (see gdiet_hip_ksw_extd2_batch_dev)
-	hipStream_t stream2 = nullptr;
-	hipStream_t stream_dp = nullptr;   // stream of the DP stage in an async lane (GDIET_DP_PRIORITY=1 raises its priority)
-	hipEvent_t ev2[3] = {nullptr, nullptr, nullptr}; // go, DP of the tail done, tail done
-	int dp_split = 1, wave_slots = 5120, last_split = 0;
-	int dp_waves = 5;                  // wavefronts per SIMD the 64-lane DP kernel is launched for (gdiet_hip_set_dp_waves / GDIET_DP_WAVES: 5 or 4)
+	hipStream_t stream_dp = nullptr;   // stream of the DP stage in an async lane
+	int wave_slots = 5120;
+	int dp_waves = 5;                  // wavefronts per SIMD the 64-lane DP kernel is launched for (gdiet_hip_set_dp_waves: 5 or 4)
 	int wide_ckpt = -1;                // GDIET_WIDE_CKPT: 1 / 0 force / forbid the checkpointed wide-band kernel, default by batch size
 	int wide_two_waves = -1;           // GDIET_WIDE_TWO_WAVES: 1 / 0 force the two-wavefront / two-blocks-per-lane kernel for wide bands, default by count
 	int vote_wave = 1;                 // GDIET_VOTE_WAVE=0: the sequential vote kernel for long reads too
 	int index_on_device = 1;           // GDIET_INDEX_BUILD=host: gdiet_hip_index_build sketches and sorts on host threads instead
-	int post_on_device = 1;            // GDIET_POST=host: mm_fix_cigar / mm_update_extra on host threads instead of map_post_kernel
-	int fuse_bt = 1;                   // GDIET_FUSE_BT=0: the 64-lane kernel leaves the backtrack to the separate kernel
 	bool single_affine = false;        // set for the duration of a gdiet_hip_ksw_extz2_batch call: single-affine kernel variants
 	std::vector<int32_t> h_ids;
 	std::vector<PipeWave> h_pipes;
@@ -94,11 +89,8 @@ struct gdiet_ctx {
 	bool last_was_async = false;       // gdiet_hip_last_kernel_ms then reports the lane's events, copied at gdiet_hip_map_wait
 	float async_dp_ms = 0, async_bt_ms = 0;
 	int map_lanes = 1;                 // software-pipeline depth of gdiet_hip_map_uploaded
-	int slices_per_lane = 1;           // GDIET_SLICES_PER_LANE
 	std::vector<gdiet_ctx *> children; // the lanes (child contexts on the same device)
 	int seed_thread_kernel = 0;
-	int bt_wave = 1;                   // GDIET_BT_WAVE=0: always the one-walk-per-thread backtrack kernel
-	int spread = 1;                    // the serial vote kernel runs one read per wavefront (GDIET_SPREAD=0: one per thread)
 	double stage_s[6] = {0, 0, 0, 0, 0, 0};
 	uint64_t last_cells = 0, last_alg_bytes = 0; // of the most recent DP launch
 	// reads the most recent map call gave up on (a DP box outside its read / contig: undefined behaviour in the reference); they come back
@@ -207,13 +199,9 @@ extern "C" int gdiet_hip_init(gdiet_ctx **out, int device)
 	{
 		int lo = 0, hi = 0; // numerically lower = higher priority
 		(void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-		const char *pe = getenv("GDIET_DP_PRIORITY");
-		const bool prio = pe && atoi(pe) != 0; // measured: no gain from a raised priority, the separate stream is what matters
-		if (hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio ? hi : lo) != hipSuccess) { delete ctx; return GDIET_E_HIP; }
-		if (hipStreamCreateWithPriority(&ctx->stream_dp, hipStreamNonBlocking, prio ? hi : lo) != hipSuccess) { delete ctx; return GDIET_E_HIP; }
+		// the least priority: a raised one measured no gain, the separate stream is what matters
+		if (hipStreamCreateWithPriority(&ctx->stream_dp, hipStreamNonBlocking, lo) != hipSuccess) { delete ctx; return GDIET_E_HIP; }
 	}
-	for (int i = 0; i < 3; ++i)
-		if (hipEventCreate(&ctx->ev2[i]) != hipSuccess) { delete ctx; return GDIET_E_HIP; }
 	if (hipEventCreateWithFlags(&ctx->wait_ev, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { delete ctx; return GDIET_E_HIP; }
 	{ const char *sy = getenv("GDIET_SYNC"); if (sy) ctx->blocking_wait = strcmp(sy, "block") == 0; }
 	if (hipEventCreateWithFlags(&ctx->arena_ev, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->gather_ev, hipEventDisableTiming) != hipSuccess) { delete ctx; return GDIET_E_HIP; }
@@ -222,10 +210,6 @@ extern "C" int gdiet_hip_init(gdiet_ctx **out, int device)
 	{
 		const char *e = getenv("GDIET_SEED_KERNEL");
 		ctx->seed_thread_kernel = e && !strcmp(e, "thread") ? 1 : e && !strcmp(e, "wave") ? 2 : 0; // 0: by read length
-		const char *sl = getenv("GDIET_SLICES_PER_LANE");
-		if (sl && atoi(sl) > 0) ctx->slices_per_lane = atoi(sl);
-		const char *bw = getenv("GDIET_BT_WAVE");
-		if (bw) ctx->bt_wave = atoi(bw) != 0;
 		const char *tw = getenv("GDIET_WIDE_TWO_WAVES");
 		if (tw) ctx->wide_two_waves = atoi(tw) != 0;
 		const char *wc = getenv("GDIET_WIDE_CKPT");
@@ -234,18 +218,8 @@ extern "C" int gdiet_hip_init(gdiet_ctx **out, int device)
 		if (vw) ctx->vote_wave = atoi(vw) != 0;
 		const char *ib = getenv("GDIET_INDEX_BUILD");
 		if (ib) ctx->index_on_device = strcmp(ib, "host") != 0;
-		const char *po = getenv("GDIET_POST");
-		if (po) ctx->post_on_device = strcmp(po, "host") != 0;
-		const char *dw = getenv("GDIET_DP_WAVES");
-		if (dw && atoi(dw) == 4) ctx->dp_waves = 4;
 		const char *sb = getenv("GDIET_SR_BOXES");
 		if (sb) ctx->sr_boxes_on_device = strcmp(sb, "host") != 0;
-		const char *fb = getenv("GDIET_FUSE_BT");
-		if (fb) ctx->fuse_bt = atoi(fb) != 0;
-		const char *ds = getenv("GDIET_DP_SPLIT");
-		if (ds) ctx->dp_split = atoi(ds) != 0;
-		const char *sp = getenv("GDIET_SPREAD");
-		if (sp) ctx->spread = atoi(sp) != 0;
 	}
 	*out = ctx;
 	return GDIET_OK;
@@ -276,12 +250,9 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 	for (DevBuf *b : hosts) free(b->p);
 	for (int i = 0; i < 4; ++i)
 		if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-	for (int i = 0; i < 3; ++i)
-		if (ctx->ev2[i]) (void)hipEventDestroy(ctx->ev2[i]);
 	if (ctx->arena_ev) (void)hipEventDestroy(ctx->arena_ev);
 	if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
 	if (ctx->gather_ev) (void)hipEventDestroy(ctx->gather_ev);
-	if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
 	if (ctx->stream_dp) (void)hipStreamDestroy(ctx->stream_dp);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -339,14 +310,6 @@ extern "C" int gdiet_hip_set_dp_waves(gdiet_ctx *ctx, int waves_per_simd)
 {
 	if (!ctx || (waves_per_simd != 4 && waves_per_simd != 5)) return GDIET_E_PARAM;
 	ctx->dp_waves = waves_per_simd;
-	return GDIET_OK;
-}
-
-extern "C" int gdiet_hip_set_dp_split(gdiet_ctx *ctx, int on)
-{
-	if (!ctx) return GDIET_E_PARAM;
-	ctx->dp_split = on != 0;
-	for (int i = 0; i < GD_MAX_INFLIGHT; ++i) if (ctx->async_lane[i]) ctx->async_lane[i]->dp_split = ctx->dp_split;
 	return GDIET_OK;
 }
 
@@ -577,7 +540,7 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 	}
 	plan_mark("fields");
 	bool wide_ck = false;
-	if (!ids[GD_KIND_WAVE128].empty() && ctx->fuse_bt && !(ctx->single_affine && K.q == K.q2 && K.e == K.e2)) {
+	if (!ids[GD_KIND_WAVE128].empty() && !(ctx->single_affine && K.q == K.q2 && K.e == K.e2)) {
 		size_t full = 0;
 		for (int32_t id : ids[GD_KIND_WAVE128]) full += (size_t)(h_tasks[id].qlen + h_tasks[id].tlen - 1) * (size_t)h_tasks[id].row_bytes;
 		wide_ck = ctx->wide_ckpt == 1 || (ctx->wide_ckpt < 0 && ((int)ids[GD_KIND_WAVE128].size() >= ctx->wave_slots / 5 || full > ((size_t)100 << 30)));
@@ -626,26 +589,23 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 	}
 	plan_mark("order");
 	// checkpointed wide-band alignments whose band fits a 96-block ring (w = 1300: 83 blocks) go to the form with one block + one half
-	// block per lane; the rest (wider bands) keep two blocks per lane.  Both lists stay longest-first.  GDIET_WIDE_RING=128 forces the latter.
+	// block per lane; the rest (wider bands) keep two blocks per lane.  Both lists stay longest-first.
 	size_t n_ring96 = 0;
 	if (wide_ck) {
-		static const bool ring128_only = getenv("GDIET_WIDE_RING") && atoi(getenv("GDIET_WIDE_RING")) == 128;
 		std::vector<int32_t> &v = ids[GD_KIND_WAVE128];
-		if (!ring128_only)
-			n_ring96 = (size_t)(std::stable_partition(v.begin(), v.end(), [&](int32_t id) {
-				const KswTask &A = h_tasks[id];
-				return gd_wave_supported(A.qlen, A.tlen, A.w, 96);
-			}) - v.begin());
+		n_ring96 = (size_t)(std::stable_partition(v.begin(), v.end(), [&](int32_t id) {
+			const KswTask &A = h_tasks[id];
+			return gd_wave_supported(A.qlen, A.tlen, A.w, 96);
+		}) - v.begin());
 	}
 	// the short-alignment kernels run 4 / 6 / 8 alignments of identical (qlen, tlen, w) per wavefront (groups of 16 / 10 / 8 lanes):
 	// cut the sorted list into such groups, one list per group width (-1 pads an incomplete group)
 	std::vector<int32_t> groups[3]; // [0]: 16 lanes, [1]: 10, [2]: 8
 	// Full matrices (a short-read batch: w >= both lengths) of one geometry, enough of them to keep every group of a wavefront busy for a
 	// few alignments, run as skewed pipelines instead (ksw_pipe.hip.h): a wavefront takes np alignments per group, sized so that the
-	// run fills the GPU's wavefront slots once.  GDIET_SR_PIPE=0 keeps the grouped kernels; GDIET_PIPE_NP forces np.
+	// run fills the GPU's wavefront slots once.  GDIET_SR_PIPE=0 keeps the grouped kernels.
 	const bool use_pipe = gd_use_pipe;
-	static const int pipe_np_forced = getenv("GDIET_PIPE_NP") ? atoi(getenv("GDIET_PIPE_NP")) : 0;
-	static const int pipe_np_min = getenv("GDIET_PIPE_NP_MIN") ? std::max(1, atoi(getenv("GDIET_PIPE_NP_MIN"))) : 8; // see pipe_compact_kernel
+	const size_t pipe_np_min = 8; // see pipe_compact_kernel
 	std::vector<int32_t> pipe_ids;
 	ctx->h_pipes.clear(), ctx->h_pipe_runs.clear();
 	{
@@ -667,14 +627,13 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 					// pipes lose less to filling and draining (26.4 -> 28.7 M reads/s with eight batches in flight) -- but never fewer than 256 wavefronts.
 					const size_t all_slots = (size_t)(ctx->wave_slots / 5 * 4), groups = (m + geo.NG - 1) / geo.NG;
 					size_t np;
-					if (pipe_np_forced > 0) np = (size_t)pipe_np_forced;
-					else if (!ctx->parent) np = std::max<size_t>(1, (groups + all_slots * 7 / 10 - 1) / (all_slots * 7 / 10));
+					if (!ctx->parent) np = std::max<size_t>(1, (groups + all_slots * 7 / 10 - 1) / (all_slots * 7 / 10));
 					else np = std::min(std::max<size_t>(8, (groups + all_slots / 2 - 1) / (all_slots / 2)), std::max<size_t>(1, groups / 256));
 					np = std::min(np, groups);
 					const size_t n_waves = (m + geo.NG * np - 1) / (geo.NG * np);
 					PipeRun R;
 					memset(&R, 0, sizeof(R));
-					R.src_off = (int32_t)pipe_ids.size(), R.dst_off = R.src_off, R.m = (int32_t)m, R.wave_off = (int32_t)ctx->h_pipes.size(), R.n_waves = (int32_t)n_waves, R.ng = geo.NG, R.np_min = (int32_t)std::max<size_t>(1, std::min<size_t>(np, (size_t)pipe_np_min));
+					R.src_off = (int32_t)pipe_ids.size(), R.dst_off = R.src_off, R.m = (int32_t)m, R.wave_off = (int32_t)ctx->h_pipes.size(), R.n_waves = (int32_t)n_waves, R.ng = geo.NG, R.np_min = (int32_t)std::max<size_t>(1, std::min(np, pipe_np_min));
 					for (size_t k = i; k < j; ++k) pipe_ids.push_back(v[k]);
 					PipeWave W; // (id_off, cnt, np: pipe_compact_kernel, once the pre-filter has answered)
 					memset(&W, 0, sizeof(W));
@@ -775,45 +734,20 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 	}
 	hipLaunchKernelGGL(ksw_exact_match_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_tasks, n, d_qseq, d_tseq,
 	                   d_status, d_score, d_n_cigar, d_cigar, d_diag, (int)K.sc_mch, (int)K.sc_mis, d_diag && K.sc_mis <= K.sc_mch && K.q + K.e > 0 ? (int)(K.sc_mch + 2 * (K.q + K.e)) + 1 : 0, score_bias);
-	// Head / tail split of a big 64-lane launch.  The grid is sorted longest-first, so the first `wave_slots` alignments start at
-	// once and the rest fill in as slots free up -- it is the latter that finish last.  Launched as two kernels (head on the
-	// caller's stream, tail on a second one), the head's backtrack runs while the tail is still in the DP, and only the tail's
-	// (shorter, fewer) walks remain after the last DP wavefront.  Same kernels, same work, same results.
+	// The 64-lane, two-wavefront and two-blocks-per-lane kernels walk their own alignments back (status TRACED: the backtrack below skips them).
 	const int n64 = (int)ids[GD_KIND_WAVE64].size();
 	const bool single = ctx->single_affine && K.q == K.q2 && K.e == K.e2;
-	const bool fuse = ctx->fuse_bt != 0; // the 64-lane kernel walks its own alignments back (status TRACED: the kernels below skip them)
-	const bool split = !single && !fuse && ctx->dp_split && n64 > ctx->wave_slots + ctx->wave_slots / 8;
-	const int n_head = split ? ctx->wave_slots : n64;
-	const bool bt_wave = ctx->bt_wave && cells_sum / (uint64_t)n > 200000; // long walks: one wavefront each; short reads: one walk per thread
-	auto backtrack = [&](const int32_t *list, int cnt, hipStream_t st) {
-		if (cnt <= 0) return;
-		if (bt_wave) hipLaunchKernelGGL(ksw_backtrack_wave_kernel, dim3((cnt + 3) / 4), dim3(256), 0, st, d_tasks, cnt, d_bt, d_status, d_score, d_n_cigar, d_cigar, list);
-		else hipLaunchKernelGGL(ksw_backtrack_kernel, dim3((cnt + 63) / 64), dim3(64), 0, st, d_tasks, cnt, d_bt, d_status, d_score, d_n_cigar, d_cigar, 0, list,
-		                        (const int32_t *)nullptr, (const int32_t *)d_diag);
-	};
-	ctx->last_split = split;
-	if (split) {
-		GD_HIP(hipEventRecord(ctx->ev2[0], stream)); // the tail may start once the pre-filter has answered
-		GD_HIP(hipStreamWaitEvent(ctx->stream2, ctx->ev2[0], 0));
-	}
 	if (n64 > 0)
-		gd_launch_wave64(d_tasks, d_ids + id_off[GD_KIND_WAVE64], n_head, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, split ? 1 : 0, single,
-		                 fuse ? d_n_cigar : nullptr, fuse ? d_cigar : nullptr, ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves);
-	if (split) {
-		gd_launch_wave64(d_tasks, d_ids + id_off[GD_KIND_WAVE64] + n_head, n64 - n_head, d_qseq, d_tseq, d_bt, d_status, d_score, K, ctx->stream2, 2, false,
-		                 fuse ? d_n_cigar : nullptr, fuse ? d_cigar : nullptr);
-		GD_HIP(hipEventRecord(ctx->ev2[1], ctx->stream2));
-		backtrack(d_ids + id_off[GD_KIND_WAVE64] + n_head, n64 - n_head, ctx->stream2);
-		GD_HIP(hipEventRecord(ctx->ev2[2], ctx->stream2));
-	}
+		gd_launch_wave64(d_tasks, d_ids + id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
+		                 ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves);
 	if (!ids[GD_KIND_WAVE16].empty()) {
 		// The short-alignment kernels CAN walk their own alignments back (every group's first lane, gd_bt_thread_walk), but it does not pay:
 		// a wavefront then holds its slot for a few hundred dependent steps of six lanes -- DP kernel 7.6 -> 10.8 ms per 262 144 short reads
 		// against 1.65 ms of the separate backtrack kernel it saves (17.9 -> 15.1 M reads/s whole path; K3 alone 35.5 -> 26.6 M pairs/s).
 		// GDIET_FUSE_BT_GROUPS=1 switches it on (same results: the GPU suite passes either way).
 		static const bool fuse_groups = getenv("GDIET_FUSE_BT_GROUPS") && atoi(getenv("GDIET_FUSE_BT_GROUPS")) != 0;
-		int32_t *g_nc = fuse && fuse_groups ? d_n_cigar : nullptr;
-		uint32_t *g_cg = fuse && fuse_groups ? d_cigar : nullptr;
+		int32_t *g_nc = fuse_groups ? d_n_cigar : nullptr;
+		uint32_t *g_cg = fuse_groups ? d_cigar : nullptr;
 		gd_launch_wave_groups<16>(d_tasks, d_ids + group_off[0], (int)(groups[0].size() / 4), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
 		gd_launch_wave_groups<10>(d_tasks, d_ids + group_off[1], (int)(groups[1].size() / 6), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
 		gd_launch_wave_groups<8>(d_tasks, d_ids + group_off[2], (int)(groups[2].size() / 8), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
@@ -832,11 +766,9 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 			if ((size_t)n128 > n_ring96)
 				gd_launch_wave128(d_tasks, d_ids + id_off[GD_KIND_WAVE128] + n_ring96, n128 - (int)n_ring96, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar, true);
 		} else if (two)
-			gd_launch_wave2x64(d_tasks, d_ids + id_off[GD_KIND_WAVE128], n128, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream,
-			                   fuse ? d_n_cigar : nullptr, fuse ? d_cigar : nullptr);
+			gd_launch_wave2x64(d_tasks, d_ids + id_off[GD_KIND_WAVE128], n128, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar);
 		else
-			gd_launch_wave128(d_tasks, d_ids + id_off[GD_KIND_WAVE128], n128, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream,
-			                  fuse ? d_n_cigar : nullptr, fuse ? d_cigar : nullptr);
+			gd_launch_wave128(d_tasks, d_ids + id_off[GD_KIND_WAVE128], n128, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar);
 	}
 	if (!ids[GD_KIND_GENERIC].empty()) {
 		const size_t lds = (size_t)max_cap * 7;
@@ -846,11 +778,15 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 		                   d_tasks, d_ids + id_off[GD_KIND_GENERIC], d_qseq, d_tseq, d_bt, d_status, d_score, K, max_cap);
 	}
 	GD_HIP(hipEventRecord(ctx->ev[1], stream));
-	if (split) { // everything but the tail: the lists of the four kinds sit back to back in d_ids, the tail is the end of the 64-lane list
-		backtrack(d_ids, (int)id_off[GD_KIND_WAVE64] + n_head, stream);
-		backtrack(d_ids + id_off[GD_KIND_WAVE64] + n64, (int)(ctx->h_ids.size() - id_off[GD_KIND_WAVE64] - n64), stream);
-		GD_HIP(hipStreamWaitEvent(stream, ctx->ev2[2], 0)); // join: later work on the caller's stream sees the tail's results too
-	} else backtrack(d_ids, (int)ctx->h_ids.size(), stream);
+	// the walks the DP kernels left, over the lists of the four kinds (back to back in d_ids)
+	const int n_ids = (int)ctx->h_ids.size();
+	if (n_ids > 0) {
+		if (cells_sum / (uint64_t)n > 200000) // long walks: one wavefront each; short reads: one walk per thread
+			hipLaunchKernelGGL(ksw_backtrack_wave_kernel, dim3((n_ids + 3) / 4), dim3(256), 0, stream, d_tasks, n_ids, d_bt, d_status, d_score, d_n_cigar, d_cigar, d_ids);
+		else
+			hipLaunchKernelGGL(ksw_backtrack_kernel, dim3((n_ids + 63) / 64), dim3(64), 0, stream, d_tasks, n_ids, d_bt, d_status, d_score, d_n_cigar, d_cigar, d_ids,
+			                   (const int32_t *)nullptr, (const int32_t *)d_diag);
+	}
 	if (score_bias) hipLaunchKernelGGL(ksw_score_bias_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, n, d_tasks, d_status, d_score, score_bias);
 	GD_HIP(hipEventRecord(ctx->ev[2], stream));
 	GD_HIP(hipGetLastError());
@@ -888,11 +824,6 @@ extern "C" int gdiet_hip_last_kernel_ms(gdiet_ctx *ctx, float *dp_ms, float *bt_
 	}
 	float a = 0, b = 0;
 	GD_HIP(hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
-	if (ctx->last_split) { // the DP phase ends with the later of the two launches
-		float a2 = 0;
-		GD_HIP(hipEventElapsedTime(&a2, ctx->ev[0], ctx->ev2[1]));
-		a = std::max(a, a2);
-	}
 	GD_HIP(hipEventElapsedTime(&b, ctx->ev[0], ctx->ev[2]));
 	b -= a; // what remains after the last DP wavefront
 	if (dp_ms) *dp_ms = a;
@@ -1055,13 +986,13 @@ static int gd_extz2_literal(gdiet_ctx *ctx, int n, const uint8_t *qseq, const in
 	GD_HIP(hipMemcpyAsync(ctx->tseq.p, tseq, tb, hipMemcpyHostToDevice, s));
 	GD_HIP(hipMemcpyAsync(ctx->tasks.p, h_tasks, sizeof(KswTask) * n, hipMemcpyHostToDevice, s));
 	if (lds > 64 * 1024) GD_HIP(hipFuncSetAttribute((const void *)ksw_extz2_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	ctx->last_mask = 2, ctx->last_was_async = false, ctx->last_split = 0;
+	ctx->last_mask = 2, ctx->last_was_async = false;
 	GD_HIP(hipEventRecord(ctx->ev[0], s));
 	hipLaunchKernelGGL(ksw_extz2_exact_kernel, dim3(n), dim3(64), lds, s, (const KswTask *)ctx->tasks.p, n, (const uint8_t *)ctx->qseq.p, (const uint8_t *)ctx->tseq.p,
 	                   (uint8_t *)ctx->arena.p, (int32_t *)ctx->status.p, d_score, d_ez, d_start, K, max_cap);
 	GD_HIP(hipEventRecord(ctx->ev[1], s));
 	hipLaunchKernelGGL(ksw_backtrack_kernel, dim3((n + 63) / 64), dim3(64), 0, s, (const KswTask *)ctx->tasks.p, n, (const uint8_t *)ctx->arena.p,
-	                   (const int32_t *)ctx->status.p, d_score, (int32_t *)ctx->ncig.p, (uint32_t *)ctx->cigar.p, 0, (const int32_t *)nullptr, (const int32_t *)d_start);
+	                   (const int32_t *)ctx->status.p, d_score, (int32_t *)ctx->ncig.p, (uint32_t *)ctx->cigar.p, (const int32_t *)nullptr, (const int32_t *)d_start);
 	GD_HIP(hipEventRecord(ctx->ev[2], s));
 	GD_HIP(hipMemcpyAsync(ez, d_ez, sizeof(GdExtzOut) * n, hipMemcpyDeviceToHost, s));
 	GD_HIP(hipMemcpyAsync(n_cigar, ctx->ncig.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
@@ -1132,7 +1063,7 @@ extern "C" int gdiet_hip_ksw_exts2_batch(gdiet_ctx *ctx, int n, const uint8_t *q
 	if (junc) GD_HIP(hipMemcpyAsync(d_junc, junc, tb, hipMemcpyHostToDevice, s));
 	GD_HIP(hipMemcpyAsync(ctx->tasks.p, h_tasks, sizeof(KswTask) * n, hipMemcpyHostToDevice, s));
 	if (lds > 64 * 1024) GD_HIP(hipFuncSetAttribute((const void *)ksw_exts2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	ctx->last_mask = 2, ctx->last_was_async = false, ctx->last_split = 0;
+	ctx->last_mask = 2, ctx->last_was_async = false;
 	GD_HIP(hipEventRecord(ctx->ev[0], s));
 	hipLaunchKernelGGL(ksw_exts2_kernel, dim3(n), dim3(64), lds, s, (const KswTask *)ctx->tasks.p, n, (const uint8_t *)ctx->qseq.p, (const uint8_t *)ctx->tseq.p,
 	                   (const uint8_t *)d_junc, (uint8_t *)ctx->arena.p, (GdExtzOut *)ctx->score.p, (int32_t *)ctx->ncig.p, (uint32_t *)ctx->cigar.p, K, max_cap);
@@ -1185,7 +1116,7 @@ extern "C" int gdiet_hip_lchain_dp_batch(gdiet_ctx *ctx, int n_reads, const uint
 	int32_t *h_f = (int32_t *)ctx->h_res.p, *h_p = h_f + tot, *h_v = h_p + tot;
 	GD_HIP(hipMemcpyAsync(ctx->qseq.p, a, sizeof(uint64_t) * 2 * (size_t)tot, hipMemcpyHostToDevice, s));
 	GD_HIP(hipMemcpyAsync(ctx->tasks.p, aoff, sizeof(int64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, s));
-	ctx->last_mask = 0, ctx->last_was_async = false, ctx->last_split = 0;
+	ctx->last_mask = 0, ctx->last_was_async = false;
 	GD_HIP(hipEventRecord(ctx->ev[0], s));
 	hipLaunchKernelGGL(lchain_fill_kernel, dim3(n_reads), dim3(64), 0, s, n_reads, (const uint64_t *)ctx->qseq.p, (const int64_t *)ctx->tasks.p, O, d_f, d_p, d_v, d_t);
 	GD_HIP(hipEventRecord(ctx->ev[1], s));

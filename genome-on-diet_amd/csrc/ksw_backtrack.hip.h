@@ -183,17 +183,11 @@ __global__ __launch_bounds__(64) void ksw_backtrack_kernel(const KswTask *__rest
                                                            const uint8_t *__restrict__ bt,
                                                            const int32_t *__restrict__ status,
                                                            int32_t *__restrict__ score, int32_t *__restrict__ n_cigar,
-                                                           uint32_t *__restrict__ cigar, int spread, const int32_t *__restrict__ task_ids,
+                                                           uint32_t *__restrict__ cigar, const int32_t *__restrict__ task_ids,
                                                            const int32_t *__restrict__ start = nullptr /* (i0, j0) per task; default: the last cell */,
                                                            const int32_t *__restrict__ diag = nullptr /* ksw_exact_match_kernel's diagonal scores */)
 {
-	// spread = 1: one alignment per WAVEFRONT (lane 0 walks, the other lanes idle).  Kept for experiments only: it measured 2x
-	// SLOWER than one walk per thread, whose 64 x 16 prefetched loads per wavefront hide the latency better.
 	int tid = blockIdx.x * blockDim.x + threadIdx.x;
-	if (spread) {
-		if (threadIdx.x & 63) return;
-		tid >>= 6;
-	}
 	if (tid >= n) return;
 	if (task_ids) { tid = task_ids[tid]; if (tid < 0) return; } // a sub-list of the batch (-1: padding of a 16-lane quartet)
 	const int st = status[tid];

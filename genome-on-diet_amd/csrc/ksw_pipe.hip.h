@@ -261,11 +261,6 @@ static inline void gd_launch_pipe(const KswTask *tasks, const int32_t *all_ids, 
 	WaveK K;
 	gdw_make_consts(C, K);
 	const dim3 grid((n_pipes + GDP_BLOCK_WAVES - 1) / GDP_BLOCK_WAVES), block(64 * GDP_BLOCK_WAVES);
-	// GDIET_PIPE_WAVES = 3 / 2: at most that many wavefronts of this kernel per SIMD (a workgroup puts one on each SIMD of its CU; an unused
-	// dynamic LDS allocation caps the workgroups per CU), the registers of the fourth stay free for the other kernels of the batches in flight
-	static const int cap_waves = getenv("GDIET_PIPE_WAVES") ? atoi(getenv("GDIET_PIPE_WAVES")) : 4;
-	size_t lds = 0;
-	if (cap_waves == 2 || cap_waves == 3) lds = (size_t)(160 * 1024) / (cap_waves + 1) + 1024 - (size_t)GDP_BLOCK_WAVES * 2 * GDP_BUF_BYTES;
-	if (single) hipLaunchKernelGGL((ksw_extd2_pipe_kernel<false>), grid, block, lds, s, tasks, ids, pipes, n_pipes, q, t, bt, status, score, K);
-	else hipLaunchKernelGGL((ksw_extd2_pipe_kernel<true>), grid, block, lds, s, tasks, ids, pipes, n_pipes, q, t, bt, status, score, K);
+	if (single) hipLaunchKernelGGL((ksw_extd2_pipe_kernel<false>), grid, block, 0, s, tasks, ids, pipes, n_pipes, q, t, bt, status, score, K);
+	else hipLaunchKernelGGL((ksw_extd2_pipe_kernel<true>), grid, block, 0, s, tasks, ids, pipes, n_pipes, q, t, bt, status, score, K);
 }

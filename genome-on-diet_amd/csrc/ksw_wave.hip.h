@@ -76,8 +76,8 @@ static inline bool gd_wave_supported(int qlen, int tlen, int w, int lanes)
 //              16-cell block of such an alignment has a lane of its own for the whole run, so a group needs no ring and can be any
 //              run of consecutive lanes.  A 150 x 150 alignment uses 10 of the 16 lanes of a DPP row; six groups of ten fill 60 of
 //              the 64 lanes (lanes 60-63 shadow group 0 without storing).
-// TAG only names the launch (0: a whole batch; 1 / 2: the head / tail launch of a split batch, see gdiet_hip.hip) so that a
-// profile lists them apart.
+// TAG is always 0.  It stays a template parameter so that the 64-lane kernel keeps its symbol, ksw_extd2_wave_kernel<64, 0, true>
+// (_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E): bench.py's roofline record and the register budgets in build.py name it.
 // DUAL = false is the single-affine (ksw_extz2) form of the same kernel: see gdw_compute.
 // Every wavefront of the 64-lane kernel stamps s_memtime (the shader clock) and s_memrealtime (the constant 100 MHz reference) around its
 // DP rows -- four scalar stores per wavefront, nothing kept in registers in between -- so that the clock the kernel really sustained can be
@@ -290,29 +290,18 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 	}
 }
 
-static inline int gd_wave64_block()
-{
-	static int bs = 0;
-	if (!bs) { const char *e = getenv("GDIET_WAVE64_BLOCK"); bs = e ? atoi(e) : 64; if (bs != 64 && bs != 128 && bs != 256) bs = 64; }
-	return bs;
-}
-
 static inline void gd_launch_wave64(const KswTask *tasks, const int32_t *ids, int n, const uint8_t *q, const uint8_t *t,
-                                    uint8_t *bt, int32_t *status, int32_t *score, KswConst C, hipStream_t s, int tag = 0, bool single = false,
-                                    int32_t *n_cigar = nullptr, uint32_t *cigar = nullptr /* both given: fused backtrack */,
-                                    int waves_per_simd = 5 /* 4: see gdiet_hip_set_dp_waves */)
+                                    uint8_t *bt, int32_t *status, int32_t *score, KswConst C, hipStream_t s, bool single,
+                                    int32_t *n_cigar, uint32_t *cigar /* fused backtrack */, int waves_per_simd /* 4: see gdiet_hip_set_dp_waves */)
 {
 	WaveK K;
 	gdw_make_consts(C, K);
 	// one wavefront per workgroup: a finished wavefront frees its slot at once instead of waiting for its three block mates
-	const int bs = gd_wave64_block();
-	const dim3 grid((n + bs / 64 - 1) / (bs / 64)), block(bs);
+	const dim3 grid(n), block(64);
 	// Four wavefronts per SIMD instead of five: the kernel uses no LDS, so an (unused) dynamic allocation of a sixteenth of the CU's 160 KB
 	// per wavefront caps the CU at 16 of them; the fifth wavefront's 96 registers per SIMD then stay free for other kernels.
-	const size_t lds = waves_per_simd == 4 ? (size_t)(160 * 1024 / 16) * (bs / 64) : 0;
+	const size_t lds = waves_per_simd == 4 ? (size_t)(160 * 1024 / 16) : 0;
 	if (single) hipLaunchKernelGGL((ksw_extd2_wave_kernel<64, 0, false>), grid, block, lds, s, tasks, ids, n, q, t, bt, status, score, K, n_cigar, cigar);
-	else if (tag == 1) hipLaunchKernelGGL((ksw_extd2_wave_kernel<64, 1>), grid, block, lds, s, tasks, ids, n, q, t, bt, status, score, K, n_cigar, cigar);
-	else if (tag == 2) hipLaunchKernelGGL((ksw_extd2_wave_kernel<64, 2>), grid, block, lds, s, tasks, ids, n, q, t, bt, status, score, K, n_cigar, cigar);
 	else hipLaunchKernelGGL((ksw_extd2_wave_kernel<64, 0>), grid, block, lds, s, tasks, ids, n, q, t, bt, status, score, K, n_cigar, cigar);
 }
 // ids: 64 / G task ids per wavefront (identical geometry; -1 pads an incomplete group), n_groups wavefronts; G = 16, 10 or 8

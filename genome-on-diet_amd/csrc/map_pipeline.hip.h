@@ -372,20 +372,6 @@ struct GdBatchView {
 	const int64_t *d_roff; // device copy of roff (already offset to the slice)
 };
 
-// LDS capacities of the wave seed / vote kernels (entries; the launch sizes its dynamic LDS from them): upper bounds, lowered for A/B
-// measurements with GDIET_SEED_SORT_CAP / GDIET_VOTE_CAP -- less LDS per wavefront = more wavefronts per CU, longer lists go through the
-// kernels' global-memory paths (every path is exact)
-static int gd_sort_cap_max()
-{
-	static const int v = [] { const char *e = getenv("GDIET_SEED_SORT_CAP"); int c = e ? atoi(e) : MAP_SORT_CAP_MAX; int p = MAP_SORT_CAP; while (p < c && p < MAP_SORT_CAP_MAX) p <<= 1; return p; }();
-	return v;
-}
-static unsigned gd_vote_cap_max()
-{
-	static const unsigned v = [] { const char *e = getenv("GDIET_VOTE_CAP"); unsigned c = e ? (unsigned)atoi(e) : MAP_VOTE_CAP, p = 256; while (p < c && p < MAP_VOTE_CAP) p <<= 1; return p; }();
-	return v;
-}
-
 // B4 (gdiet_hip_seed_batch): what the seeding stage leaves, copied out right behind the seed kernel instead of going on
 struct GdSeedExport {
 	std::vector<MapSeedOut> out;   // per read: shift, tmp_extracted_len, n_mv, n_seeds, n_a
@@ -453,14 +439,14 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 	// the default priority they get the issue slots those leave, hold their scarce slots for a long time, and the batch is ready only when
 	// that DP kernel ends -- with two batches in flight the next DP kernel then starts ~5 ms late (834 Mbases/s).  At s_setprio(2) they are
 	// through in ~60 ms, the DP kernels follow each other back to back with TWO batches in flight (875-881 Mbases/s) and a batch spends two
-	// step times in the pipeline instead of three (p50 174 instead of 261 ms).  GDIET_SIDE_PRIO=0..3 for A/B runs.
-	{ static const int side_prio = getenv("GDIET_SIDE_PRIO") ? atoi(getenv("GDIET_SIDE_PRIO")) : 2; D.prio = side_prio; }
+	// step times in the pipeline instead of three (p50 174 instead of 261 ms).
+	D.prio = 2;
 	{ // LDS sort capacity of the wave seed kernel: ~1.25 x the minimizers expected of the longest read (2 / (w + 1) of its sparsified bases)
 		int64_t max_len = 0;
 		for (int i = 0; i < n; ++i) max_len = std::max<int64_t>(max_len, B.roff[i + 1] - B.roff[i]);
 		const double est = 1.25 * 2.0 / (O.w + 1) * gd_diet_len(O.pat, (unsigned)max_len, 0);
 		int cap = MAP_SORT_CAP;
-		while (cap < gd_sort_cap_max() && cap < est) cap <<= 1;
+		while (cap < MAP_SORT_CAP_MAX && cap < est) cap <<= 1;
 		D.sort_cap = cap;
 	}
 	// Reads of very different lengths (ONT: log-normal up to 150 kbp): one launch per capacity class, each read in the class its own
@@ -475,7 +461,7 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 		for (int i = 0; i < n; ++i) {
 			const double est = 1.25 * 2.0 / (O.w + 1) * gd_diet_len(O.pat, (unsigned)(B.roff[i + 1] - B.roff[i]), 0);
 			int cap = MAP_SORT_CAP, c = 0;
-			while (cap < gd_sort_cap_max() && cap < est) cap <<= 1, ++c;
+			while (cap < MAP_SORT_CAP_MAX && cap < est) cap <<= 1, ++c;
 			cap_of[i] = c, ++n_cls[c];
 		}
 		int used = 0;
@@ -555,13 +541,13 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 	GD_HIP(hipMemcpyAsync(ctx->m_hitoff.p, hoff.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
 	// ---- S6, S7, V1, V3, G1a -----------------------------------------------------------------------------------------
 	// long reads: one read per wavefront (parallel expansion + LDS sort); short reads (a handful of hits each): one read per thread
-	const int spread = ctx->spread && (B.roff[n] - B.roff[0]) / n >= 1024;
+	const int spread = (B.roff[n] - B.roff[0]) / n >= 1024;
 	if (spread == 1 && ctx->vote_wave) {
 		// LDS sort buffer of the batch: the largest hit count of a read bounds either strand (see the kernel)
 		int64_t max_hits = 0;
 		for (int i = 0; i < n; ++i) max_hits = std::max(max_hits, hoff[i + 1] - hoff[i]);
 		unsigned vote_cap = 256;
-		while (vote_cap < gd_vote_cap_max() && (int64_t)vote_cap < max_hits) vote_cap <<= 1;
+		while (vote_cap < MAP_VOTE_CAP && (int64_t)vote_cap < max_hits) vote_cap <<= 1;
 		// the kernel also holds static LDS (its candidate list): with the full sort buffer the total passes 64 KB, which a launch is
 		// only granted after the attribute has been raised
 		if (sizeof(GdLoc) * (size_t)vote_cap + sizeof(GdVt) * GDM_MAX_VT + 64 > 64 * 1024)
@@ -794,10 +780,8 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 	nbp = ((size_t)std::max(nb, 1) + 63) & ~(size_t)63;
 	if ((rc = gd_host_grow(ctx, ctx->h_res, sizeof(int32_t) * 2 * nbp))) return rc;
 	int32_t *h_score = (int32_t *)ctx->h_res.p, *h_ncig = h_score + nbp;
-	const bool post_dev = ctx->post_on_device != 0;
-	if (post_dev && (rc = gd_host_grow(ctx, ctx->h_post, sizeof(GdPostOut) * (size_t)std::max(nb, 1)))) return rc;
+	if ((rc = gd_host_grow(ctx, ctx->h_post, sizeof(GdPostOut) * (size_t)std::max(nb, 1)))) return rc;
 	const GdPostOut *h_post = (const GdPostOut *)ctx->h_post.p;
-	static const bool no_export = getenv("GDIET_POST_EXPORT") && atoi(getenv("GDIET_POST_EXPORT")) == 0;
 	uint32_t *h_cig = nullptr;
 	bool exported = false; // the DP results came to the host with map_post_kernel's own stores
 	std::vector<int64_t> poff(1, 0);
@@ -842,7 +826,7 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 			if (!ctx->own_arena) GD_HIP(hipEventRecord(ctx->parent->arena_ev, sd)); // the backtrack is done by then: the CIGARs sit in this lane's own buffer
 			if (dp_lock.owns_lock()) dp_lock.unlock();
 		}
-		if (post_dev) { // P1 on the device, behind the backtrack of this stage (reads this lane's own windows and CIGAR slots, not the arena)
+		{ // P1 on the device, behind the backtrack of this stage (reads this lane's own windows and CIGAR slots, not the arena)
 			if ((rc = gd_grow(ctx, ctx->m_post, sizeof(GdPostOut) * (size_t)nb))) { (void)hipStreamSynchronize(sd); return rc; }
 			MapPostOpt PO;
 			const int g_ = O.a, bb_ = O.b < 0 ? O.b : -O.b;
@@ -856,7 +840,7 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 			// batch); short reads keep one alignment per thread (hundreds of thousands of 150-base walks).  GDIET_POST_WAVE=0 / 1 forces one.
 			static const char *pw_env = getenv("GDIET_POST_WAVE");
 			const bool post_wave = pw_env ? atoi(pw_env) != 0 : coff[nb] / std::max(nb, 1) >= 2000;
-			const bool xport = (ctx->last_mask & 8) != 0 && !no_export;
+			const bool xport = (ctx->last_mask & 8) != 0;
 			if (xport) {
 				const size_t need = sizeof(GdPostOut) * (size_t)nb + sizeof(int32_t) * 2 * nbp + 256;
 				if (need > ctx->h_pin.cap) {
@@ -866,34 +850,27 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 					else ctx->h_pin.cap = need + need / 2;
 				}
 			}
-			if (xport && ctx->h_pin.p) {
-				int32_t *x_score = (int32_t *)ctx->h_pin.p, *x_ncig = x_score + nbp;
-				GdPostOut *x_post = (GdPostOut *)(x_ncig + nbp);
-				if (post_wave) {
-					hipLaunchKernelGGL(map_fix_cigar_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-					                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, x_post);
-					hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-					                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, PO, x_post, x_score, x_ncig);
-				}
-				else hipLaunchKernelGGL(map_post_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-				                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, PO, x_post, x_score, x_ncig);
-				h_score = x_score, h_ncig = x_ncig, h_post = x_post;
-				exported = true;
-			} else {
-				if (post_wave) {
-					hipLaunchKernelGGL(map_fix_cigar_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-					                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, (GdPostOut *)ctx->m_post.p);
-					hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-					                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, PO, (GdPostOut *)ctx->m_post.p,
-					                   (int32_t *)nullptr, (int32_t *)nullptr);
-				}
-				else hipLaunchKernelGGL(map_post_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-				                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, PO, (GdPostOut *)ctx->m_post.p,
-				                   (int32_t *)nullptr, (int32_t *)nullptr);
-				GD_HIP(hipMemcpyAsync(ctx->h_post.p, ctx->m_post.p, sizeof(GdPostOut) * (size_t)nb, hipMemcpyDeviceToHost, sd));
+			exported = xport && ctx->h_pin.p;
+			// outputs: the page-locked export buffer, else m_post (copied to h_post below, with the scores and CIGAR lengths)
+			GdPostOut *o_post = (GdPostOut *)ctx->m_post.p;
+			int32_t *o_score = nullptr, *o_ncig = nullptr;
+			if (exported) {
+				o_score = (int32_t *)ctx->h_pin.p, o_ncig = o_score + nbp, o_post = (GdPostOut *)(o_ncig + nbp);
+				h_score = o_score, h_ncig = o_ncig, h_post = o_post;
 			}
+			if (post_wave) {
+				hipLaunchKernelGGL(map_fix_cigar_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
+				                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, o_post);
+				hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
+				                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, PO, o_post, o_score, o_ncig);
+			}
+			else hipLaunchKernelGGL(map_post_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
+			                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, PO, o_post, o_score, o_ncig);
 		}
-		if (!exported) GD_HIP(hipMemcpyAsync(h_score, d_score, sizeof(int32_t) * 2 * nbp, hipMemcpyDeviceToHost, sd));
+		if (!exported) {
+			GD_HIP(hipMemcpyAsync(ctx->h_post.p, ctx->m_post.p, sizeof(GdPostOut) * (size_t)nb, hipMemcpyDeviceToHost, sd));
+			GD_HIP(hipMemcpyAsync(h_score, d_score, sizeof(int32_t) * 2 * nbp, hipMemcpyDeviceToHost, sd));
+		}
 		GD_HIP(gd_stream_wait(ctx, sd));
 	mark("d:wait");
 		// CIGARs are short compared with their capacity (qlen+tlen): pack them on the device, then one copy
@@ -945,9 +922,9 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 			for (size_t j = 0; j < nc; ++j) gd_cand_unbox(cflat[(size_t)cfirst[i] + j], C[j]);
 			const uint32_t rl = (uint32_t)(B.roff[i + 1] - B.roff[i]);
 			const uint8_t *enc = B.enc + B.roff[i];
-			// the reverse-complemented read: for P1 on the host, else only where a reverse-strand candidate may be concatenated (P2)
+			// the reverse-complemented read: only where a reverse-strand candidate may be concatenated (P2)
 			bool need_rev = false;
-			for (auto &c : C) need_rev |= c.v.str != 0 && (!post_dev || c.next >= 0);
+			for (auto &c : C) need_rev |= c.v.str != 0 && c.next >= 0;
 			if (need_rev) { rev.resize(rl); for (uint32_t j = 0; j < rl; ++j) rev[rl - 1 - j] = enc[j] ^ 3; }
 			dp.resize(nc);
 			for (size_t j = 0; j < nc; ++j) {
@@ -955,7 +932,7 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 				dp[j].score = h_score[b], dp[j].n_cigar = h_ncig[b], dp[j].cigar = h_cig + poff[b];
 			}
 			out.clear();
-			const GdPostOut *pre = post_dev ? h_post + box_first[i] : nullptr;
+			const GdPostOut *pre = h_post + box_first[i];
 			if (is_sr) gd_sr_finish(C, dp, O, R, rl, enc, need_rev ? rev.data() : enc, out, pre);
 			else gd_lr_finish(C, dp, O, R, rl, enc, need_rev ? rev.data() : enc, out, nullptr, pre);
 			if (out.empty()) continue;
@@ -972,6 +949,13 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 	return GDIET_OK;
 }
 
+
+// the dispatch choices a lane (pipeline child or async lane) takes over from the context that drives it
+static void gd_copy_lane_opts(gdiet_ctx *c, const gdiet_ctx *ctx)
+{
+	c->kernel_mode = ctx->kernel_mode, c->seed_thread_kernel = ctx->seed_thread_kernel, c->vote_wave = ctx->vote_wave;
+	c->wide_two_waves = ctx->wide_two_waves, c->wide_ckpt = ctx->wide_ckpt;
+}
 
 extern "C" int gdiet_hip_set_map_lanes(gdiet_ctx *ctx, int n)
 {
@@ -1016,10 +1000,10 @@ extern "C" int gdiet_hip_map_uploaded(gdiet_ctx *ctx, const gdiet_index *ix, con
 		gdiet_ctx *c = nullptr;
 		int rc = gdiet_hip_init(&c, ctx->device);
 		if (rc) { ctx->err = "cannot create a pipeline lane"; return rc; }
-		c->kernel_mode = ctx->kernel_mode, c->seed_thread_kernel = ctx->seed_thread_kernel, c->spread = ctx->spread, c->bt_wave = ctx->bt_wave, c->dp_split = ctx->dp_split, c->fuse_bt = ctx->fuse_bt, c->vote_wave = ctx->vote_wave, c->wide_two_waves = ctx->wide_two_waves, c->wide_ckpt = ctx->wide_ckpt, c->post_on_device = ctx->post_on_device;
+		gd_copy_lane_opts(c, ctx);
 		ctx->children.push_back(c);
 	}
-	const int n_slices = std::min(n, lanes * ctx->slices_per_lane);
+	const int n_slices = std::min(n, lanes);
 	std::atomic<int> next(0);
 	std::vector<int> rcs(lanes, 0);
 	std::vector<std::thread> th;
@@ -1115,7 +1099,7 @@ extern "C" int gdiet_hip_map_submit(gdiet_ctx *ctx, const gdiet_index *ix, const
 		ctx->async_lane[l] = c;
 	}
 	gdiet_ctx *c = ctx->async_lane[l];
-	c->kernel_mode = ctx->kernel_mode, c->seed_thread_kernel = ctx->seed_thread_kernel, c->spread = ctx->spread, c->bt_wave = ctx->bt_wave, c->dp_split = ctx->dp_split, c->fuse_bt = ctx->fuse_bt, c->vote_wave = ctx->vote_wave, c->wide_two_waves = ctx->wide_two_waves, c->wide_ckpt = ctx->wide_ckpt, c->post_on_device = ctx->post_on_device;
+	gd_copy_lane_opts(c, ctx);
 	c->lane_threads = c->host_threads = ctx->host_threads; // all lanes draw from the parent's pool
 	ctx->async_busy[l] = true, ctx->async_next++;
 	t->lane = l;

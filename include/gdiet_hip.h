@@ -172,10 +172,6 @@ size_t gdiet_hip_ksw_workspace_bytes(int n, const int64_t *qoff, const int64_t *
 /* restrict dispatch: 0 = automatic (default), 1 = force the generic LDS kernel, 2 = wave kernel only (fails
  * with GDIET_E_PARAM for alignments it cannot take).  For tests and A/B measurements. */
 int gdiet_hip_set_kernel_mode(gdiet_ctx *ctx, int mode);
-/* 1 (default): a 64-lane DP launch with more alignments than the GPU holds at once is issued as a head launch (the longest
- * alignments, one per resident wavefront slot) and a tail launch on a second stream, so that the head's backtrack overlaps the
- * tail's DP.  0: one launch, one backtrack (what bench.py uses for its roofline passes: one kernel, one duration). */
-int gdiet_hip_set_dp_split(gdiet_ctx *ctx, int on);
 /* Wavefronts per SIMD the 64-lane DP kernel (long reads) is launched for: 5 (default: 96 VGPRs, the best throughput of a full pipeline)
  * or 4 (a fifth of every SIMD's registers stays free, so the seeding / voting kernels of the NEXT batch run beside the
  * DP kernel instead of trickling through as its wavefronts retire -- two batches in flight then keep the DP kernels back to back, at
