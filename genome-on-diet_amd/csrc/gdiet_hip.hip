@@ -25,10 +25,27 @@
 #include "ksw_pipe.hip.h"
 #include "ksw_extz2_exact.hip.h"
 #include "ksw_exts2.hip.h"
+#include "ksw_plan.h"
 
+// A buffer a context keeps between batches.  It remembers which allocator made it (gd_grow: device memory, gd_host_grow: posix_memalign,
+// the page-locked h_pin of map_pipeline.hip.h) and releases itself with the context that declares it.
 struct DevBuf {
+	enum Kind { DEVICE, PINNED, HOST };
 	void *p = nullptr;
 	size_t cap = 0;
+	Kind kind = DEVICE;
+	DevBuf() = default;
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	~DevBuf() { (void)release(); }
+	hipError_t release()
+	{
+		hipError_t e = hipSuccess;
+		if (p && kind == HOST) free(p);
+		else if (p) e = kind == PINNED ? hipHostFree(p) : hipFree(p);
+		p = nullptr, cap = 0;
+		return e;
+	}
 };
 
 #define GD_MAX_INFLIGHT 8 // batches in flight per context (gdiet_hip_set_inflight)
@@ -53,9 +70,7 @@ struct gdiet_ctx {
 	int vote_wave = 1;                 // GDIET_VOTE_WAVE=0: the sequential vote kernel for long reads too
 	int index_on_device = 1;           // GDIET_INDEX_BUILD=host: gdiet_hip_index_build sketches and sorts on host threads instead
 	bool single_affine = false;        // set for the duration of a gdiet_hip_ksw_extz2_batch call: single-affine kernel variants
-	std::vector<int32_t> h_ids;
-	std::vector<PipeWave> h_pipes;
-	std::vector<PipeRun> h_pipe_runs;
+	GdPlan plan;                       // of the most recent DP batch (ksw_plan.h); its vectors are reused from batch to batch
 	// per-read mapping path (map_pipeline.hip.h)
 	DevBuf m_sc, m_mv, m_u64, m_seed, m_seedout, m_voteout, m_hitoff, m_hits, m_boxes, m_q, m_t, m_aux, m_cig, m_pack, m_post, m_seedids;
 	DevBuf m_srbox, m_srtab, m_srscan, m_srcand; // device-side box stage of the ShortReads variant (map_pipeline.hip.h)
@@ -125,8 +140,8 @@ static int gd_grow(gdiet_ctx *ctx, DevBuf &b, size_t bytes)
 	if (bytes <= b.cap) return GDIET_OK;
 	// growth is rare (first batches); it synchronises the stream because older work may still read the buffer
 	GD_HIP(hipStreamSynchronize(ctx->stream));
-	if (b.p) GD_HIP(hipFree(b.p));
-	b.p = nullptr, b.cap = 0;
+	GD_HIP(b.release());
+	b.kind = DevBuf::DEVICE;
 	size_t want = bytes + (bytes >> 3) + 4096;
 	hipError_t e = hipMalloc(&b.p, want);
 	if (e != hipSuccess) {
@@ -240,22 +255,13 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 		if (ctx->async_lane[i]) gdiet_hip_destroy(ctx->async_lane[i]), ctx->async_lane[i] = nullptr;
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-	DevBuf *bufs[] = {&ctx->arena, &ctx->tasks, &ctx->ids, &ctx->status, &ctx->qseq, &ctx->tseq, &ctx->score, &ctx->ncig, &ctx->cigar,
-	                  &ctx->m_sc, &ctx->m_mv, &ctx->m_u64, &ctx->m_seed, &ctx->m_seedout, &ctx->m_voteout, &ctx->m_hitoff, &ctx->m_hits,
-	                  &ctx->m_boxes, &ctx->m_q, &ctx->m_t, &ctx->m_aux, &ctx->m_cig, &ctx->m_pack, &ctx->m_post, &ctx->m_seedids, &ctx->pipes, &ctx->pipe_runs, &ctx->pipe_dst, &ctx->diag};
-	for (DevBuf *b : bufs)
-		if (b->p) (void)hipFree(b->p);
-	if (ctx->h_pin.p) (void)hipHostFree(ctx->h_pin.p);
-	DevBuf *hosts[] = {&ctx->h_boxes, &ctx->h_cand, &ctx->h_tasks, &ctx->h_seedout, &ctx->h_res, &ctx->h_cig, &ctx->h_post};
-	for (DevBuf *b : hosts) free(b->p);
-	for (int i = 0; i < 4; ++i)
-		if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-	if (ctx->arena_ev) (void)hipEventDestroy(ctx->arena_ev);
-	if (ctx->wait_ev) (void)hipEventDestroy(ctx->wait_ev);
-	if (ctx->gather_ev) (void)hipEventDestroy(ctx->gather_ev);
-	if (ctx->stream_dp) (void)hipStreamDestroy(ctx->stream_dp);
-	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-	delete ctx;
+	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev};
+	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream};
+	delete ctx; // every DevBuf of the context releases itself here: before the streams and events go
+	for (hipEvent_t e : events)
+		if (e) (void)hipEventDestroy(e);
+	for (hipStream_t s : streams)
+		if (s) (void)hipStreamDestroy(s);
 }
 
 #ifdef GD_CLOCK_STAMP
@@ -322,50 +328,21 @@ extern "C" int gdiet_hip_reserve(gdiet_ctx *ctx, size_t bytes)
 
 // ---- planning ----------------------------------------------------------------------------------------------
 
-// number of cells the generic kernel's LDS ring must hold for this geometry (see ksw_generic.hip.h)
-static int gd_generic_cap(int qlen, int tlen, int w)
-{
-	if (w < 0) w = tlen > qlen ? tlen : qlen;
-	int n = std::min(std::min(qlen, tlen), w + 1);
-	int need = n + 64, cap = 256;
-	while (cap < need) cap <<= 1;
-	return cap;
-}
-
-static inline size_t gd_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
+// what the planner (ksw_plan.h) takes from the environment
 static const int gd_group_lanes = getenv("GDIET_GROUP_LANES") ? atoi(getenv("GDIET_GROUP_LANES")) : 0; // 16: always four alignments per wavefront
 // GDIET_SR_PIPE=0: no skewed pipelines (ksw_pipe.hip.h), short alignments on the grouped kernels only
 static const bool gd_use_pipe = !(getenv("GDIET_SR_PIPE") && atoi(getenv("GDIET_SR_PIPE")) == 0);
 
-// decide kernel + backtrace geometry of one alignment
-static void gd_plan_one(int mode, bool wave_scoring_ok, int qlen, int tlen, int w, int32_t &kind, int32_t &row_bytes)
-{
-	const int ncol = gd_ncol16(qlen, tlen, w);
-	kind = GD_KIND_GENERIC, row_bytes = ncol * 16;
-	if (mode == 1 || !wave_scoring_ok) return;
-	if (gd_wave_supported(qlen, tlen, w, 64)) {
-		if (gd_wave_supported(qlen, tlen, w, 16)) {
-			// short alignments: several per wavefront.  Targets of <= 128 / 160 bases keep every block in a lane of its own: groups of
-			// 8 / 10 lanes (8 / 6 alignments per wavefront) instead of one DPP row of 16 each
-			// (the reference's n_col_ counts one block more -- the spill of the score row above the window -- but beyond the target's
-			// last block that spill is never read)
-			const int g = gd_group_lanes == 16 ? 16 : tlen <= 128 ? 8 : tlen <= 160 ? 10 : 16;
-			kind = GD_KIND_WAVE16, row_bytes = g * 16;
-		}
-		else if (gd_use_pipe && gd_pipe_geometry_ok(qlen, tlen, w)) kind = GD_KIND_WAVE16, row_bytes = 16 * 16; // 241..256 bases, full matrix: one block more than the 16-lane groups hold -- the pipelines take it (every run, however short)
-		else kind = GD_KIND_WAVE64, row_bytes = 64 * 16;
-	} else if (gd_wave_supported(qlen, tlen, w, 128)) kind = GD_KIND_WAVE128; // row_bytes stays n_col_*16
-}
-
 extern "C" size_t gdiet_hip_ksw_workspace_bytes(int n, const int64_t *qoff, const int64_t *toff, const int32_t *w)
 {
 	size_t tot = 0;
+	GdPlanOpt plan_opt;
+	plan_opt.group_lanes = gd_group_lanes, plan_opt.use_pipe = gd_use_pipe;
 	for (int i = 0; i < n; ++i) {
 		const int qlen = (int)(qoff[i + 1] - qoff[i]), tlen = (int)(toff[i + 1] - toff[i]);
 		if (qlen <= 0 || tlen <= 0) continue;
 		int32_t kind, rb;
-		gd_plan_one(0, true, qlen, tlen, w[i], kind, rb);
+		gd_plan_one(plan_opt, qlen, tlen, w[i], kind, rb);
 		const size_t a = (size_t)(qlen + tlen - 1) * (size_t)rb;
 		const size_t b = (size_t)(qlen + tlen - 1) * (size_t)gd_ncol16(qlen, tlen, w[i]) * 16; // forced-generic worst case
 		tot += gd_align256(std::max(a, b) + 64);
@@ -403,8 +380,8 @@ static int gd_consts(gdiet_ctx *ctx, const gdiet_ksw_score_t *sc, KswConst &K)
 static int gd_host_grow(gdiet_ctx *ctx, DevBuf &b, size_t bytes)
 {
 	if (bytes <= b.cap) return GDIET_OK;
-	free(b.p);
-	b.p = nullptr, b.cap = 0;
+	(void)b.release();
+	b.kind = DevBuf::HOST;
 	const size_t want = bytes + (bytes >> 2) + 4096;
 	if (posix_memalign(&b.p, 256, want)) b.p = nullptr; // (256-byte aligned: the runtime's copy kernels pick their form by the alignment of both ends)
 	if (!b.p) { ctx->err = "out of host memory (" + std::to_string(want) + " bytes)"; return GDIET_E_NOMEM; }
@@ -413,6 +390,111 @@ static int gd_host_grow(gdiet_ctx *ctx, DevBuf &b, size_t bytes)
 }
 
 // ---- device-pointer entry point ----------------------------------------------------------------------------
+
+static double gd_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// GDIET_TRACE_STAGES=1: wall time of the host-side steps of a call to stderr (development aid).  trace("name") closes a step; the
+// caller prints `s` behind a head of its own, one line per call.
+static bool gd_trace_stages() { static const bool on = getenv("GDIET_TRACE_STAGES") != nullptr; return on; }
+struct GdStageTrace {
+	const bool on = gd_trace_stages();
+	const double t0 = on ? gd_now() : 0;
+	double t = t0;
+	std::string s;
+	GdStageTrace() = default;
+	GdStageTrace(const GdStageTrace &) = delete; // (the steps of a call add up in ONE trace: pass it by reference)
+	void operator()(const char *what)
+	{
+		if (!on) return;
+		const double now = gd_now();
+		char b[64];
+		snprintf(b, sizeof b, " %s %.2f", what, 1e3 * (now - t));
+		s += b, t = now;
+	}
+};
+
+// The launches of a planned batch on `stream`, its descriptors uploaded: the exact-match pre-filter, the DP kernels of the four kinds over
+// their id lists, the walks they left, the score bias; ctx->ev[0..2] before the first, after the DP and after the last.
+static int gd_dp_launch(gdiet_ctx *ctx, const GdPlan &P, int n, const KswConst &K, const gdiet_ksw_score_t *sc, const uint8_t *d_qseq, const uint8_t *d_tseq,
+                        uint8_t *d_bt, int32_t *d_score, int32_t *d_n_cigar, uint32_t *d_cigar, hipStream_t stream, hipEvent_t arena_free)
+{
+	int rc;
+	const KswTask *d_tasks = (const KswTask *)ctx->tasks.p;
+	const int32_t *d_ids = (const int32_t *)ctx->ids.p;
+	int32_t *d_status = (int32_t *)ctx->status.p;
+
+	if (arena_free) GD_HIP(hipStreamWaitEvent(stream, arena_free, 0)); // descriptors are across; only the kernels queue behind the arena's last user
+	GD_HIP(hipEventRecord(ctx->ev[0], stream));
+	// (GDIET_DIAG_SHORTCUT=0: every short alignment goes through the DP and is walked back, also those the pre-filter could answer from the
+	// main diagonal's score -- see ksw_exact_match_kernel)
+	static const bool diag_shortcut = !(getenv("GDIET_DIAG_SHORTCUT") && atoi(getenv("GDIET_DIAG_SHORTCUT")) == 0);
+	const int score_bias = (int)(K.q + K.e) - (sc->q + sc->e); // 0 unless the caller passed the larger gap model first: ksw_score_bias_kernel
+	int32_t *d_diag = nullptr;
+	if (diag_shortcut && P.n_kind[GD_KIND_WAVE16]) {
+		if ((rc = gd_grow(ctx, ctx->diag, sizeof(int32_t) * (size_t)n))) return rc;
+		d_diag = (int32_t *)ctx->diag.p;
+	}
+	hipLaunchKernelGGL(ksw_exact_match_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_tasks, n, d_qseq, d_tseq,
+	                   d_status, d_score, d_n_cigar, d_cigar, d_diag, (int)K.sc_mch, (int)K.sc_mis, d_diag && K.sc_mis <= K.sc_mch && K.q + K.e > 0 ? (int)(K.sc_mch + 2 * (K.q + K.e)) + 1 : 0, score_bias);
+	// The 64-lane, two-wavefront and two-blocks-per-lane kernels walk their own alignments back (status TRACED: the backtrack below skips them).
+	const int n64 = (int)P.n_kind[GD_KIND_WAVE64];
+	const bool single = ctx->single_affine && K.q == K.q2 && K.e == K.e2;
+	if (n64 > 0)
+		gd_launch_wave64(d_tasks, d_ids + P.id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
+		                 ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves);
+	if (P.n_kind[GD_KIND_WAVE16]) {
+		// The short-alignment kernels CAN walk their own alignments back (every group's first lane, gd_bt_thread_walk), but it does not pay:
+		// a wavefront then holds its slot for a few hundred dependent steps of six lanes -- DP kernel 7.6 -> 10.8 ms per 262 144 short reads
+		// against 1.65 ms of the separate backtrack kernel it saves (17.9 -> 15.1 M reads/s whole path; K3 alone 35.5 -> 26.6 M pairs/s).
+		// GDIET_FUSE_BT_GROUPS=1 switches it on (same results: the GPU suite passes either way).
+		static const bool fuse_groups = getenv("GDIET_FUSE_BT_GROUPS") && atoi(getenv("GDIET_FUSE_BT_GROUPS")) != 0;
+		int32_t *g_nc = fuse_groups ? d_n_cigar : nullptr;
+		uint32_t *g_cg = fuse_groups ? d_cigar : nullptr;
+		gd_launch_wave_groups<16>(d_tasks, d_ids + P.group_off[0], (int)(P.n_group[0] / 4), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
+		gd_launch_wave_groups<10>(d_tasks, d_ids + P.group_off[1], (int)(P.n_group[1] / 6), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
+		gd_launch_wave_groups<8>(d_tasks, d_ids + P.group_off[2], (int)(P.n_group[2] / 8), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
+		int max_run = 0;
+		for (const PipeRun &R : P.pipe_runs) max_run = std::max(max_run, (int)R.m);
+		gd_launch_pipe(d_tasks, d_ids, (PipeRun *)ctx->pipe_runs.p, (int)P.pipe_runs.size(), max_run, (int32_t *)ctx->pipe_dst.p, (PipeWave *)ctx->pipes.p,
+		               (int)P.pipes.size(), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single);
+	}
+	if (P.n_kind[GD_KIND_WAVE128]) {
+		// few wide-band alignments (the arena bounds how many 50 kbp ONT alignments fit): two wavefronts share one, halving the
+		// serial chain; plenty of them: one wavefront each, two blocks per lane, no barrier
+		const int n128 = (int)P.n_kind[GD_KIND_WAVE128];
+		const int32_t *d_ids128 = d_ids + P.id_off[GD_KIND_WAVE128];
+		const bool two = !P.wide_ck && (ctx->wide_two_waves == 1 || (ctx->wide_two_waves < 0 && n128 < ctx->wave_slots / 2));
+		if (P.wide_ck) {
+			if (P.n_ring96) gd_launch_wave96c(d_tasks, d_ids128, (int)P.n_ring96, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar);
+			if ((size_t)n128 > P.n_ring96)
+				gd_launch_wave128(d_tasks, d_ids128 + P.n_ring96, n128 - (int)P.n_ring96, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar, true);
+		} else if (two)
+			gd_launch_wave2x64(d_tasks, d_ids128, n128, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar);
+		else
+			gd_launch_wave128(d_tasks, d_ids128, n128, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar);
+	}
+	if (P.n_kind[GD_KIND_GENERIC]) {
+		const size_t lds = (size_t)P.max_cap * 7;
+		if (lds > 64 * 1024)
+			GD_HIP(hipFuncSetAttribute((const void *)ksw_extd2_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+		hipLaunchKernelGGL(ksw_extd2_generic_kernel, dim3((unsigned)P.n_kind[GD_KIND_GENERIC]), dim3(64), lds, stream,
+		                   d_tasks, d_ids + P.id_off[GD_KIND_GENERIC], d_qseq, d_tseq, d_bt, d_status, d_score, K, P.max_cap);
+	}
+	GD_HIP(hipEventRecord(ctx->ev[1], stream));
+	// the walks the DP kernels left, over the lists of the four kinds (back to back in d_ids)
+	const int n_ids = (int)P.ids.size();
+	if (n_ids > 0) {
+		if (P.cells / (uint64_t)n > 200000) // long walks: one wavefront each; short reads: one walk per thread
+			hipLaunchKernelGGL(ksw_backtrack_wave_kernel, dim3((n_ids + 3) / 4), dim3(256), 0, stream, d_tasks, n_ids, d_bt, d_status, d_score, d_n_cigar, d_cigar, d_ids);
+		else
+			hipLaunchKernelGGL(ksw_backtrack_kernel, dim3((n_ids + 63) / 64), dim3(64), 0, stream, d_tasks, n_ids, d_bt, d_status, d_score, d_n_cigar, d_cigar, d_ids,
+			                   (const int32_t *)nullptr, (const int32_t *)d_diag);
+	}
+	if (score_bias) hipLaunchKernelGGL(ksw_score_bias_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, n, d_tasks, d_status, d_score, score_bias);
+	GD_HIP(hipEventRecord(ctx->ev[2], stream));
+	GD_HIP(hipGetLastError());
+	return GDIET_OK;
+}
 
 // The work of gdiet_hip_ksw_extd2_batch_dev.  h_cigar_off / h_exact_score: host copies of the two small device arrays the
 // planner needs; a caller that has them (the mapping pipeline) passes them and the call then never waits for the stream --
@@ -447,227 +529,22 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 		GD_HIP(hipStreamSynchronize(stream));
 		h_cigar_off = h_cig_own.data(), h_exact_score = d_exact_score ? h_ex_own.data() : nullptr;
 	}
-	const int64_t *h_cig = h_cigar_off;
-	const int32_t *h_ex = h_exact_score;
 
-	// GDIET_TRACE_STAGES: where the planner's time goes (one line per call on stderr)
-	static const bool plan_trace = getenv("GDIET_TRACE_STAGES") != nullptr;
-	std::string plan_s;
-	double plan_t = plan_trace ? std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0.0;
-	auto plan_mark = [&](const char *what) {
-		if (!plan_trace) return;
-		const double t = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-		char b[64];
-		snprintf(b, sizeof b, " %s %.2f", what, 1e3 * (t - plan_t));
-		plan_s += b, plan_t = t;
-	};
+	GdStageTrace mark; // where the planner's time goes
 	if ((rc = gd_host_grow(ctx, ctx->h_tasks, sizeof(KswTask) * (size_t)n))) return rc;
 	KswTask *h_tasks = (KswTask *)ctx->h_tasks.p;
-	const bool wave_scoring_ok = gd_wave_scoring_ok(K);
-	size_t bt = 0;
-	uint64_t cells_sum = 0, alg_sum = 0;
-	std::vector<int32_t> ids[4];
-	int max_cap = 0;
-	ctx->last_mask = 0;
-	// kernel + backtrace geometry of every alignment first, on the host threads: the admission test of the wave kernels walks the blocks
-	// of the band (~1 000 steps for a 15 kbp alignment: 4-5 ms for the 9 400 alignments of a HiFi batch on one thread -- time that sat
-	// between the gather kernel and the DP kernel whenever a batch was not ready early).  Slices with a memo each: a short-read
-	// batch repeats a few geometries.
-	// (the same pass fills every other field of the descriptor, checks it, adds up the roofline accounting and lists the alignments by
-	// kind -- per slice, joined in slice order afterwards: done by one thread this was 3-5 ms per 262 144 short alignments, most of a
-	// short-read batch's planning)
-	struct PlanSlice { uint64_t cells = 0, alg = 0; int max_cap = 0, err = 0; uint32_t mask = 0; std::vector<int32_t> ids[4]; };
-	const int n_sl = std::max(1, std::min(64, n / 256));
-	std::vector<PlanSlice> slices((size_t)n_sl);
-	{
-		gd_parallel_for(ctx, ctx->lane_threads, n_sl, [&](int sl) {
-			struct { int qlen = -1, tlen = -1, w = 0; int32_t kind = 0, row_bytes = 0; } memo;
-			PlanSlice &S = slices[sl];
-			const int i0 = (int)((int64_t)n * sl / n_sl), i1 = (int)((int64_t)n * (sl + 1) / n_sl);
-			for (int k = 0; k < 4; ++k) S.ids[k].reserve((size_t)(i1 - i0));
-			for (int i = i0; i < i1; ++i) {
-				KswTask &T = h_tasks[i];
-				T.qlen = (int)(h_qoff[i + 1] - h_qoff[i]), T.tlen = (int)(h_toff[i + 1] - h_toff[i]), T.w = h_w[i];
-				T.kind = GD_KIND_GENERIC, T.row_bytes = 0;
-				T.qoff = h_qoff[i], T.toff = h_toff[i];
-				T.cig_off = h_cig[i], T.cig_cap = (int32_t)std::min<int64_t>(h_cig[i + 1] - h_cig[i], 0x7fffffff);
-				T.exact_score = d_exact_score ? h_ex[i] : GD_NEG_INF;
-				T.pad = 0, T.bt_off = 0;
-				if (T.qlen <= 0 || T.tlen <= 0) { S.err |= 1; continue; } // (refused below)
-				if (T.qlen == memo.qlen && T.tlen == memo.tlen && T.w == memo.w) T.kind = memo.kind, T.row_bytes = memo.row_bytes;
-				else {
-					gd_plan_one(ctx->kernel_mode, wave_scoring_ok, T.qlen, T.tlen, T.w, T.kind, T.row_bytes);
-					memo.qlen = T.qlen, memo.tlen = T.tlen, memo.w = T.w, memo.kind = T.kind, memo.row_bytes = T.row_bytes;
-				}
-				if (ctx->kernel_mode == 2 && T.kind == GD_KIND_GENERIC) S.err |= 2;
-				if (T.kind == GD_KIND_GENERIC) {
-					const int cap = gd_generic_cap(T.qlen, T.tlen, T.w);
-					if (cap * 7 > 160 * 1024 - 1024) S.err |= 4;
-					S.max_cap = std::max(S.max_cap, cap);
-				}
-				{ // accounting for the roofline: SURVEY.md 8d's per-alignment figure
-					const uint64_t wb = (uint64_t)(T.w < 0 ? std::max(T.qlen, T.tlen) : T.w) + 1;
-					const uint64_t band = std::min<uint64_t>(wb, (uint64_t)std::min(T.qlen, T.tlen));
-					const uint64_t cells = (uint64_t)(T.qlen + T.tlen - 1) * band;
-					S.cells += cells;
-					S.alg += cells + (uint64_t)(T.qlen + T.tlen) + (uint64_t)T.qlen + (uint64_t)(T.tlen + 1) / 2;
-				}
-				S.ids[T.kind].push_back(i);
-				S.mask |= T.kind == GD_KIND_GENERIC ? 2 : T.kind == GD_KIND_WAVE16 ? 4 : T.kind == GD_KIND_WAVE128 ? 8 : 1;
-			}
-		});
-	}
-	plan_mark("kinds");
-	{
-		int err = 0;
-		size_t cnt[4] = {0, 0, 0, 0};
-		for (const PlanSlice &S : slices) {
-			err |= S.err, cells_sum += S.cells, alg_sum += S.alg, max_cap = std::max(max_cap, S.max_cap), ctx->last_mask |= (int)S.mask;
-			for (int k = 0; k < 4; ++k) cnt[k] += S.ids[k].size();
-		}
-		// (the first failure in the order the sequential form reported them)
-		if (err & 1) { ctx->err = "empty sequence in batch (the reference returns without aligning)"; return GDIET_E_PARAM; }
-		if (err & 2) { ctx->err = "alignment does not fit the wave kernel"; return GDIET_E_PARAM; }
-		if (err & 4) { ctx->err = "band wider than the LDS window of the generic kernel"; return GDIET_E_PARAM; }
-		for (int k = 0; k < 4; ++k) {
-			ids[k].resize(cnt[k]);
-			size_t at = 0;
-			for (const PlanSlice &S : slices) {
-				if (!S.ids[k].empty()) memcpy(ids[k].data() + at, S.ids[k].data(), S.ids[k].size() * sizeof(int32_t));
-				at += S.ids[k].size();
-			}
-		}
-	}
-	plan_mark("fields");
-	bool wide_ck = false;
-	if (!ids[GD_KIND_WAVE128].empty() && !(ctx->single_affine && K.q == K.q2 && K.e == K.e2)) {
-		size_t full = 0;
-		for (int32_t id : ids[GD_KIND_WAVE128]) full += (size_t)(h_tasks[id].qlen + h_tasks[id].tlen - 1) * (size_t)h_tasks[id].row_bytes;
-		wide_ck = ctx->wide_ckpt == 1 || (ctx->wide_ckpt < 0 && ((int)ids[GD_KIND_WAVE128].size() >= ctx->wave_slots / 5 || full > ((size_t)100 << 30)));
-	}
-	for (int i = 0; i < n; ++i) {
-		KswTask &T = h_tasks[i];
-		T.bt_off = (int64_t)bt;
-		if (wide_ck && T.kind == GD_KIND_WAVE128) bt += gd_align256(gd_ck_bytes(T.qlen, T.tlen, T.row_bytes) + 64);
-		else bt += gd_align256((size_t)(T.qlen + T.tlen - 1) * (size_t)T.row_bytes + 64);
-	}
-	plan_mark("bt_off");
-	// longest alignments first inside each class: the tail of the grid is then made of short jobs (a class whose members all have
-	// one geometry -- a short-read batch -- is in order already)
-	for (int k = 0; k < 4; ++k) {
-		bool uniform = true;
-		for (size_t j = 1; j < ids[k].size() && uniform; ++j) {
-			const KswTask &A = h_tasks[ids[k][0]], &B = h_tasks[ids[k][j]];
-			uniform = A.qlen == B.qlen && A.tlen == B.tlen && A.w == B.w;
-		}
-		if (uniform) continue;
-		// (a stable sort by geometry, done by grouping: a short-read batch has 400 k alignments but a few dozen geometries)
-		struct Geo { int qlen, tlen, w; std::vector<int32_t> members; };
-		std::vector<Geo> geos;
-		std::unordered_map<uint64_t, std::vector<int>> slot_of; // hash of the geometry -> geos[] entries with that hash
-		int g_prev = -1;
-		for (int32_t id : ids[k]) {
-			const KswTask &A = h_tasks[id];
-			if (g_prev >= 0 && geos[g_prev].qlen == A.qlen && geos[g_prev].tlen == A.tlen && geos[g_prev].w == A.w) { geos[g_prev].members.push_back(id); continue; }
-			const uint64_t h = ((uint64_t)(uint32_t)A.qlen * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(uint32_t)A.tlen * 0xC2B2AE3D27D4EB4Full) ^ (uint64_t)(uint32_t)A.w;
-			std::vector<int> &cand = slot_of[h];
-			int g = -1;
-			for (int c : cand) if (geos[c].qlen == A.qlen && geos[c].tlen == A.tlen && geos[c].w == A.w) { g = c; break; }
-			if (g < 0) { g = (int)geos.size(); geos.push_back(Geo{A.qlen, A.tlen, A.w, {}}); cand.push_back(g); }
-			geos[g].members.push_back(id), g_prev = g;
-		}
-		std::vector<int> order(geos.size());
-		for (size_t g = 0; g < geos.size(); ++g) order[g] = (int)g;
-		std::sort(order.begin(), order.end(), [&](int a, int b) {
-			const Geo &A = geos[a], &B = geos[b];
-			if ((int64_t)A.qlen + A.tlen != (int64_t)B.qlen + B.tlen) return (int64_t)A.qlen + A.tlen > (int64_t)B.qlen + B.tlen;
-			if (A.qlen != B.qlen) return A.qlen > B.qlen; // equal geometries are neighbours (16-lane quartets below)
-			return A.w > B.w;
-		});
-		size_t at = 0;
-		for (int g : order) for (int32_t id : geos[g].members) ids[k][at++] = id;
-	}
-	plan_mark("order");
-	// checkpointed wide-band alignments whose band fits a 96-block ring (w = 1300: 83 blocks) go to the form with one block + one half
-	// block per lane; the rest (wider bands) keep two blocks per lane.  Both lists stay longest-first.
-	size_t n_ring96 = 0;
-	if (wide_ck) {
-		std::vector<int32_t> &v = ids[GD_KIND_WAVE128];
-		n_ring96 = (size_t)(std::stable_partition(v.begin(), v.end(), [&](int32_t id) {
-			const KswTask &A = h_tasks[id];
-			return gd_wave_supported(A.qlen, A.tlen, A.w, 96);
-		}) - v.begin());
-	}
-	// the short-alignment kernels run 4 / 6 / 8 alignments of identical (qlen, tlen, w) per wavefront (groups of 16 / 10 / 8 lanes):
-	// cut the sorted list into such groups, one list per group width (-1 pads an incomplete group)
-	std::vector<int32_t> groups[3]; // [0]: 16 lanes, [1]: 10, [2]: 8
-	// Full matrices (a short-read batch: w >= both lengths) of one geometry, enough of them to keep every group of a wavefront busy for a
-	// few alignments, run as skewed pipelines instead (ksw_pipe.hip.h): a wavefront takes np alignments per group, sized so that the
-	// run fills the GPU's wavefront slots once.  GDIET_SR_PIPE=0 keeps the grouped kernels.
-	const bool use_pipe = gd_use_pipe;
-	const size_t pipe_np_min = 8; // see pipe_compact_kernel
-	std::vector<int32_t> pipe_ids;
-	ctx->h_pipes.clear(), ctx->h_pipe_runs.clear();
-	{
-		const std::vector<int32_t> &v = ids[GD_KIND_WAVE16];
-		size_t i = 0;
-		while (i < v.size()) {
-			const KswTask &A = h_tasks[v[i]];
-			if (use_pipe && gd_pipe_geometry_ok(A.qlen, A.tlen, A.w)) {
-				size_t j = i + 1;
-				while (j < v.size() && h_tasks[v[j]].qlen == A.qlen && h_tasks[v[j]].tlen == A.tlen && h_tasks[v[j]].row_bytes == A.row_bytes &&
-				       gd_pipe_geometry_ok(A.qlen, A.tlen, h_tasks[v[j]].w)) ++j;
-				const PipeGeo geo = gd_pipe_geo(A.qlen, A.tlen);
-				const size_t m = j - i;
-				if (m >= (size_t)(2 * geo.NG) || !gd_wave_supported(A.qlen, A.tlen, A.w, 16)) { // (the second: nothing else takes it, see gd_plan_one)
-					// Alignments per group of a wavefront.  The kernel has 4 wavefront slots per SIMD.  A batch on its own (synchronous call): one
-					// round of wavefronts over 70 % of the slots (100 000 pairs: np 6 -> 2.18 ms, 8 -> 2.48; 12 000 pairs: np 1 -> 0.30 ms,
-					// 8 -> 0.84 -- a short run wants many short pipes, filling and draining is cheaper than an empty GPU).  A lane of a context
-					// with batches in flight: half of the slots and at least 8 per group -- two batches' kernels share the GPU, and the longer
-					// pipes lose less to filling and draining (26.4 -> 28.7 M reads/s with eight batches in flight) -- but never fewer than 256 wavefronts.
-					const size_t all_slots = (size_t)(ctx->wave_slots / 5 * 4), groups = (m + geo.NG - 1) / geo.NG;
-					size_t np;
-					if (!ctx->parent) np = std::max<size_t>(1, (groups + all_slots * 7 / 10 - 1) / (all_slots * 7 / 10));
-					else np = std::min(std::max<size_t>(8, (groups + all_slots / 2 - 1) / (all_slots / 2)), std::max<size_t>(1, groups / 256));
-					np = std::min(np, groups);
-					const size_t n_waves = (m + geo.NG * np - 1) / (geo.NG * np);
-					PipeRun R;
-					memset(&R, 0, sizeof(R));
-					R.src_off = (int32_t)pipe_ids.size(), R.dst_off = R.src_off, R.m = (int32_t)m, R.wave_off = (int32_t)ctx->h_pipes.size(), R.n_waves = (int32_t)n_waves, R.ng = geo.NG, R.np_min = (int32_t)std::max<size_t>(1, std::min(np, pipe_np_min));
-					for (size_t k = i; k < j; ++k) pipe_ids.push_back(v[k]);
-					PipeWave W; // (id_off, cnt, np: pipe_compact_kernel, once the pre-filter has answered)
-					memset(&W, 0, sizeof(W));
-					W.qlen = A.qlen, W.tlen = A.tlen, W.row_bytes = A.row_bytes;
-					ctx->h_pipes.insert(ctx->h_pipes.end(), n_waves, W);
-					ctx->h_pipe_runs.push_back(R);
-					i = j;
-					continue;
-				}
-			}
-			const int gl = A.row_bytes >> 4, per = 64 / gl, which = gl == 16 ? 0 : gl == 10 ? 1 : 2;
-			size_t j = i + 1;
-			while (j < v.size() && j < i + per) {
-				const KswTask &B = h_tasks[v[j]];
-				if (B.qlen != A.qlen || B.tlen != A.tlen || B.w != A.w) break;
-				++j;
-			}
-			for (size_t k = i; k < i + per; ++k) groups[which].push_back(k < j ? v[k] : -1);
-			i = j;
-		}
-	}
-	plan_mark("groups");
-	ctx->h_ids.clear();
-	size_t id_off[4], group_off[3] = {0, 0, 0};
-	for (int k = 0; k < 4; ++k) {
-		id_off[k] = ctx->h_ids.size();
-		if (k == GD_KIND_WAVE16) {
-			for (int g = 0; g < 3; ++g) group_off[g] = ctx->h_ids.size(), ctx->h_ids.insert(ctx->h_ids.end(), groups[g].begin(), groups[g].end());
-			for (PipeRun &R : ctx->h_pipe_runs) R.src_off += (int32_t)ctx->h_ids.size(); // (relative to the batch's whole id list from here on)
-			ctx->h_ids.insert(ctx->h_ids.end(), pipe_ids.begin(), pipe_ids.end());
-			if (!ctx->h_pipes.empty()) ctx->last_mask |= 16;
-		} else ctx->h_ids.insert(ctx->h_ids.end(), ids[k].begin(), ids[k].end());
-	}
-	ctx->last_cells = cells_sum, ctx->last_alg_bytes = alg_sum;
+	GdPlanOpt O;
+	O.kernel_mode = ctx->kernel_mode, O.wave_scoring_ok = gd_wave_scoring_ok(K), O.single_affine = ctx->single_affine && K.q == K.q2 && K.e == K.e2;
+	O.wide_ckpt = ctx->wide_ckpt, O.wave_slots = ctx->wave_slots, O.lane = ctx->parent != nullptr, O.group_lanes = gd_group_lanes, O.use_pipe = gd_use_pipe;
+	GdPlan &P = ctx->plan;
+	gd_plan_batch(P, O, n, h_qoff, h_toff, h_w, h_cigar_off, d_exact_score ? h_exact_score : nullptr, h_tasks,
+	              [&](int n_sl, auto f) { gd_parallel_for(ctx, ctx->lane_threads, n_sl, f); }, mark);
+	ctx->last_mask = P.mask;
+	if (P.err == 1) { ctx->err = "empty sequence in batch (the reference returns without aligning)"; return GDIET_E_PARAM; }
+	if (P.err == 2) { ctx->err = "alignment does not fit the wave kernel"; return GDIET_E_PARAM; }
+	if (P.err == 4) { ctx->err = "band wider than the LDS window of the generic kernel"; return GDIET_E_PARAM; }
+	ctx->last_cells = P.cells, ctx->last_alg_bytes = P.alg_bytes;
+	const size_t bt = P.bt;
 	// An async lane works in its parent's arena, taking turns behind parent->arena_ev -- unless the batch's backtrace is small
 	// enough for every lane in flight to hold one of its own (long-read batches of few reads: their DP kernels then overlap, which
 	// fills the GPU while one batch's longest alignments are still running).
@@ -680,7 +557,7 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 		const size_t want = std::min(ctx->parent->lane_arena_cap, std::max<size_t>(bt + (bt >> 2), (size_t)1 << 30));
 		if (gd_grow(ctx, ctx->arena, std::max(bt, want - (want >> 3) - 4096)) && gd_grow(ctx, ctx->arena, bt)) own = false, ctx->err.clear(); // no room: take turns in the shared one
 	}
-	if (ctx->parent && !own && ctx->arena.p) { (void)hipFree(ctx->arena.p); ctx->arena.p = nullptr, ctx->arena.cap = 0; }
+	if (ctx->parent && !own && ctx->arena.p) (void)ctx->arena.release();
 	ctx->own_arena = own;
 	if (own) arena_free = nullptr, arena_turn = nullptr;
 	DevBuf &arena = ctx->parent && !own ? ctx->parent->arena : ctx->arena;
@@ -695,103 +572,29 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 			std::lock_guard<std::mutex> guard(owner->async_mu); // async_busy[] belongs to submit / wait
 			for (int i = 0; i < GD_MAX_INFLIGHT; ++i) {
 				gdiet_ctx *c = owner->async_lane[i];
-				if (c && c != ctx && !owner->async_busy[i] && c->arena.p) { (void)hipFree(c->arena.p); c->arena.p = nullptr, c->arena.cap = 0, freed = true; }
+				if (c && c != ctx && !owner->async_busy[i] && c->arena.p) (void)c->arena.release(), freed = true;
 			}
 		}
 		if (!freed || (rc = gd_grow(ctx, arena, bt))) return rc;
 		ctx->err.clear();
 	}
-	plan_mark("arena");
+	mark("arena");
 	if ((rc = gd_grow(ctx, ctx->tasks, sizeof(KswTask) * n))) return rc;
-	if ((rc = gd_grow(ctx, ctx->ids, sizeof(int32_t) * ctx->h_ids.size()))) return rc;
+	if ((rc = gd_grow(ctx, ctx->ids, sizeof(int32_t) * P.ids.size()))) return rc;
 	if ((rc = gd_grow(ctx, ctx->status, sizeof(int32_t) * n))) return rc;
 	GD_HIP(hipMemcpyAsync(ctx->tasks.p, h_tasks, sizeof(KswTask) * n, hipMemcpyHostToDevice, stream));
-	GD_HIP(hipMemcpyAsync(ctx->ids.p, ctx->h_ids.data(), sizeof(int32_t) * ctx->h_ids.size(), hipMemcpyHostToDevice, stream));
-	if (!ctx->h_pipes.empty()) {
-		if ((rc = gd_grow(ctx, ctx->pipes, sizeof(PipeWave) * ctx->h_pipes.size()))) return rc;
-		if ((rc = gd_grow(ctx, ctx->pipe_runs, sizeof(PipeRun) * ctx->h_pipe_runs.size()))) return rc;
-		if ((rc = gd_grow(ctx, ctx->pipe_dst, sizeof(int32_t) * pipe_ids.size()))) return rc;
-		GD_HIP(hipMemcpyAsync(ctx->pipes.p, ctx->h_pipes.data(), sizeof(PipeWave) * ctx->h_pipes.size(), hipMemcpyHostToDevice, stream));
-		GD_HIP(hipMemcpyAsync(ctx->pipe_runs.p, ctx->h_pipe_runs.data(), sizeof(PipeRun) * ctx->h_pipe_runs.size(), hipMemcpyHostToDevice, stream));
+	GD_HIP(hipMemcpyAsync(ctx->ids.p, P.ids.data(), sizeof(int32_t) * P.ids.size(), hipMemcpyHostToDevice, stream));
+	if (!P.pipes.empty()) {
+		if ((rc = gd_grow(ctx, ctx->pipes, sizeof(PipeWave) * P.pipes.size()))) return rc;
+		if ((rc = gd_grow(ctx, ctx->pipe_runs, sizeof(PipeRun) * P.pipe_runs.size()))) return rc;
+		if ((rc = gd_grow(ctx, ctx->pipe_dst, sizeof(int32_t) * P.n_pipe_ids))) return rc;
+		GD_HIP(hipMemcpyAsync(ctx->pipes.p, P.pipes.data(), sizeof(PipeWave) * P.pipes.size(), hipMemcpyHostToDevice, stream));
+		GD_HIP(hipMemcpyAsync(ctx->pipe_runs.p, P.pipe_runs.data(), sizeof(PipeRun) * P.pipe_runs.size(), hipMemcpyHostToDevice, stream));
 	}
-
-	plan_mark("upload");
-	const KswTask *d_tasks = (const KswTask *)ctx->tasks.p;
-	const int32_t *d_ids = (const int32_t *)ctx->ids.p;
-	int32_t *d_status = (int32_t *)ctx->status.p;
-	uint8_t *d_bt = (uint8_t *)arena.p;
-
-	if (arena_free) GD_HIP(hipStreamWaitEvent(stream, arena_free, 0)); // descriptors are across; only the kernels queue behind the arena's last user
-	GD_HIP(hipEventRecord(ctx->ev[0], stream));
-	// (GDIET_DIAG_SHORTCUT=0: every short alignment goes through the DP and is walked back, also those the pre-filter could answer from the
-	// main diagonal's score -- see ksw_exact_match_kernel)
-	static const bool diag_shortcut = !(getenv("GDIET_DIAG_SHORTCUT") && atoi(getenv("GDIET_DIAG_SHORTCUT")) == 0);
-	const int score_bias = (int)(K.q + K.e) - (sc->q + sc->e); // 0 unless the caller passed the larger gap model first: ksw_score_bias_kernel
-	int32_t *d_diag = nullptr;
-	if (diag_shortcut && !ids[GD_KIND_WAVE16].empty()) {
-		if ((rc = gd_grow(ctx, ctx->diag, sizeof(int32_t) * (size_t)n))) return rc;
-		d_diag = (int32_t *)ctx->diag.p;
-	}
-	hipLaunchKernelGGL(ksw_exact_match_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_tasks, n, d_qseq, d_tseq,
-	                   d_status, d_score, d_n_cigar, d_cigar, d_diag, (int)K.sc_mch, (int)K.sc_mis, d_diag && K.sc_mis <= K.sc_mch && K.q + K.e > 0 ? (int)(K.sc_mch + 2 * (K.q + K.e)) + 1 : 0, score_bias);
-	// The 64-lane, two-wavefront and two-blocks-per-lane kernels walk their own alignments back (status TRACED: the backtrack below skips them).
-	const int n64 = (int)ids[GD_KIND_WAVE64].size();
-	const bool single = ctx->single_affine && K.q == K.q2 && K.e == K.e2;
-	if (n64 > 0)
-		gd_launch_wave64(d_tasks, d_ids + id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
-		                 ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves);
-	if (!ids[GD_KIND_WAVE16].empty()) {
-		// The short-alignment kernels CAN walk their own alignments back (every group's first lane, gd_bt_thread_walk), but it does not pay:
-		// a wavefront then holds its slot for a few hundred dependent steps of six lanes -- DP kernel 7.6 -> 10.8 ms per 262 144 short reads
-		// against 1.65 ms of the separate backtrack kernel it saves (17.9 -> 15.1 M reads/s whole path; K3 alone 35.5 -> 26.6 M pairs/s).
-		// GDIET_FUSE_BT_GROUPS=1 switches it on (same results: the GPU suite passes either way).
-		static const bool fuse_groups = getenv("GDIET_FUSE_BT_GROUPS") && atoi(getenv("GDIET_FUSE_BT_GROUPS")) != 0;
-		int32_t *g_nc = fuse_groups ? d_n_cigar : nullptr;
-		uint32_t *g_cg = fuse_groups ? d_cigar : nullptr;
-		gd_launch_wave_groups<16>(d_tasks, d_ids + group_off[0], (int)(groups[0].size() / 4), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
-		gd_launch_wave_groups<10>(d_tasks, d_ids + group_off[1], (int)(groups[1].size() / 6), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
-		gd_launch_wave_groups<8>(d_tasks, d_ids + group_off[2], (int)(groups[2].size() / 8), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, g_nc, g_cg);
-		int max_run = 0;
-		for (const PipeRun &R : ctx->h_pipe_runs) max_run = std::max(max_run, (int)R.m);
-		gd_launch_pipe(d_tasks, d_ids, (PipeRun *)ctx->pipe_runs.p, (int)ctx->h_pipe_runs.size(), max_run, (int32_t *)ctx->pipe_dst.p, (PipeWave *)ctx->pipes.p,
-		               (int)ctx->h_pipes.size(), d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single);
-	}
-	if (!ids[GD_KIND_WAVE128].empty()) {
-		// few wide-band alignments (the arena bounds how many 50 kbp ONT alignments fit): two wavefronts share one, halving the
-		// serial chain; plenty of them: one wavefront each, two blocks per lane, no barrier
-		const int n128 = (int)ids[GD_KIND_WAVE128].size();
-		const bool two = !wide_ck && (ctx->wide_two_waves == 1 || (ctx->wide_two_waves < 0 && n128 < ctx->wave_slots / 2));
-		if (wide_ck) {
-			if (n_ring96) gd_launch_wave96c(d_tasks, d_ids + id_off[GD_KIND_WAVE128], (int)n_ring96, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar);
-			if ((size_t)n128 > n_ring96)
-				gd_launch_wave128(d_tasks, d_ids + id_off[GD_KIND_WAVE128] + n_ring96, n128 - (int)n_ring96, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar, true);
-		} else if (two)
-			gd_launch_wave2x64(d_tasks, d_ids + id_off[GD_KIND_WAVE128], n128, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar);
-		else
-			gd_launch_wave128(d_tasks, d_ids + id_off[GD_KIND_WAVE128], n128, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, d_n_cigar, d_cigar);
-	}
-	if (!ids[GD_KIND_GENERIC].empty()) {
-		const size_t lds = (size_t)max_cap * 7;
-		if (lds > 64 * 1024)
-			GD_HIP(hipFuncSetAttribute((const void *)ksw_extd2_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		hipLaunchKernelGGL(ksw_extd2_generic_kernel, dim3((unsigned)ids[GD_KIND_GENERIC].size()), dim3(64), lds, stream,
-		                   d_tasks, d_ids + id_off[GD_KIND_GENERIC], d_qseq, d_tseq, d_bt, d_status, d_score, K, max_cap);
-	}
-	GD_HIP(hipEventRecord(ctx->ev[1], stream));
-	// the walks the DP kernels left, over the lists of the four kinds (back to back in d_ids)
-	const int n_ids = (int)ctx->h_ids.size();
-	if (n_ids > 0) {
-		if (cells_sum / (uint64_t)n > 200000) // long walks: one wavefront each; short reads: one walk per thread
-			hipLaunchKernelGGL(ksw_backtrack_wave_kernel, dim3((n_ids + 3) / 4), dim3(256), 0, stream, d_tasks, n_ids, d_bt, d_status, d_score, d_n_cigar, d_cigar, d_ids);
-		else
-			hipLaunchKernelGGL(ksw_backtrack_kernel, dim3((n_ids + 63) / 64), dim3(64), 0, stream, d_tasks, n_ids, d_bt, d_status, d_score, d_n_cigar, d_cigar, d_ids,
-			                   (const int32_t *)nullptr, (const int32_t *)d_diag);
-	}
-	if (score_bias) hipLaunchKernelGGL(ksw_score_bias_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, n, d_tasks, d_status, d_score, score_bias);
-	GD_HIP(hipEventRecord(ctx->ev[2], stream));
-	GD_HIP(hipGetLastError());
-	plan_mark("launch");
-	if (plan_trace) fprintf(stderr, "[gdiet dp planner, ms] n=%d%s\n", n, plan_s.c_str());
+	mark("upload");
+	if ((rc = gd_dp_launch(ctx, P, n, K, sc, d_qseq, d_tseq, (uint8_t *)arena.p, d_score, d_n_cigar, d_cigar, stream, arena_free))) return rc;
+	mark("launch");
+	if (mark.on) fprintf(stderr, "[gdiet dp planner, ms] n=%d%s\n", n, mark.s.c_str());
 	return GDIET_OK;
 }
 
@@ -844,6 +647,41 @@ static bool gd_tickets_open(gdiet_ctx *ctx)
 	return false;
 }
 
+// after the results of a kernel-level batch are back on the host: does every CIGAR fit its slot?
+static int gd_check_cigar_caps(gdiet_ctx *ctx, int n, const int32_t *n_cigar, const int64_t *cigar_off)
+{
+	for (int i = 0; i < n; ++i)
+		if (n_cigar[i] > cigar_off[i + 1] - cigar_off[i]) {
+			ctx->err = "CIGAR of alignment " + std::to_string(i) + " needs " + std::to_string(n_cigar[i]) + " ops";
+			return GDIET_E_CIGAR_CAP;
+		}
+	return GDIET_OK;
+}
+
+// The descriptors of a batch whose alignments all go to one LDS-resident kernel (ksw_extz2_exact.hip.h, ksw_exts2.hip.h), in ctx->h_tasks:
+// band w[i] (w == nullptr: -1, no band), rows of the reference's n_col_ blocks, the backtrace matrices back to back (with_bt == false:
+// none, every bt_off 0).  bt: bytes of arena; max_cap: the largest gd_generic_cap.
+static int gd_literal_tasks(gdiet_ctx *ctx, int n, const int64_t *qoff, const int64_t *toff, const int32_t *w, const int64_t *cigar_off, bool with_bt,
+                            size_t &bt, int &max_cap)
+{
+	const int rc = gd_host_grow(ctx, ctx->h_tasks, sizeof(KswTask) * (size_t)n);
+	if (rc) return rc;
+	KswTask *h_tasks = (KswTask *)ctx->h_tasks.p;
+	bt = 0, max_cap = 0;
+	for (int i = 0; i < n; ++i) {
+		KswTask &T = h_tasks[i];
+		T.qoff = qoff[i], T.toff = toff[i], T.qlen = (int)(qoff[i + 1] - qoff[i]), T.tlen = (int)(toff[i + 1] - toff[i]), T.w = w ? w[i] : -1;
+		if (T.qlen <= 0 || T.tlen <= 0) { ctx->err = "empty sequence in batch (the reference returns without aligning)"; return GDIET_E_PARAM; }
+		T.cig_off = cigar_off[i], T.cig_cap = (int32_t)std::min<int64_t>(cigar_off[i + 1] - cigar_off[i], 0x7fffffff);
+		T.exact_score = GD_NEG_INF, T.kind = GD_KIND_GENERIC, T.pad = 0;
+		T.row_bytes = gd_ncol16(T.qlen, T.tlen, T.w) * 16; // (w < 0: (min(qlen, tlen) + 15) / 16 + 1 blocks, n_col_ of ksw_exts2, :80)
+		T.bt_off = (int64_t)bt;
+		if (with_bt) bt += gd_align256((size_t)(T.qlen + T.tlen - 1) * (size_t)T.row_bytes + 64);
+		max_cap = std::max(max_cap, gd_generic_cap(T.qlen, T.tlen, T.w));
+	}
+	return GDIET_OK;
+}
+
 extern "C" int gdiet_hip_ksw_extd2_batch(gdiet_ctx *ctx, int n, const uint8_t *qseq, const int64_t *qoff,
                                          const uint8_t *tseq, const int64_t *toff, const int32_t *w,
                                          const int32_t *exact_score, const gdiet_ksw_score_t *sc, int32_t *score,
@@ -882,12 +720,7 @@ extern "C" int gdiet_hip_ksw_extd2_batch(gdiet_ctx *ctx, int n, const uint8_t *q
 	GD_HIP(hipMemcpyAsync(n_cigar, ctx->ncig.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
 	GD_HIP(hipMemcpyAsync(cigar, ctx->cigar.p, sizeof(uint32_t) * cb, hipMemcpyDeviceToHost, s));
 	GD_HIP(hipStreamSynchronize(s));
-	for (int i = 0; i < n; ++i)
-		if (n_cigar[i] > cigar_off[i + 1] - cigar_off[i]) {
-			ctx->err = "CIGAR of alignment " + std::to_string(i) + " needs " + std::to_string(n_cigar[i]) + " ops";
-			return GDIET_E_CIGAR_CAP;
-		}
-	return GDIET_OK;
+	return gd_check_cigar_caps(ctx, n, n_cigar, cigar_off);
 }
 
 // ---- K3: single-affine form ----------------------------------------------------------------------------------
@@ -953,22 +786,9 @@ static int gd_extz2_literal(gdiet_ctx *ctx, int n, const uint8_t *qseq, const in
 		const int min_sc = std::min<int>(std::min<int>(sc->mismatch, sc->match), std::min<int>(sc->sc_ambi, 0));
 		if (-min_sc > 2 * (K.q + K.e)) { ctx->err = "-min_sc > 2*(q+e): the reference returns without aligning"; return GDIET_E_PARAM; }
 	}
-	int rc;
-	if ((rc = gd_host_grow(ctx, ctx->h_tasks, sizeof(KswTask) * (size_t)n))) return rc;
-	KswTask *h_tasks = (KswTask *)ctx->h_tasks.p;
-	size_t bt = 0;
-	int max_cap = 0;
-	for (int i = 0; i < n; ++i) {
-		KswTask &T = h_tasks[i];
-		T.qoff = qoff[i], T.toff = toff[i], T.qlen = (int)(qoff[i + 1] - qoff[i]), T.tlen = (int)(toff[i + 1] - toff[i]), T.w = w[i];
-		if (T.qlen <= 0 || T.tlen <= 0) { ctx->err = "empty sequence in batch (the reference returns without aligning)"; return GDIET_E_PARAM; }
-		T.cig_off = cigar_off[i], T.cig_cap = (int32_t)std::min<int64_t>(cigar_off[i + 1] - cigar_off[i], 0x7fffffff);
-		T.exact_score = GD_NEG_INF, T.kind = GD_KIND_GENERIC, T.pad = 0;
-		T.row_bytes = gd_ncol16(T.qlen, T.tlen, T.w) * 16;
-		T.bt_off = (int64_t)bt;
-		bt += gd_align256((size_t)(T.qlen + T.tlen - 1) * (size_t)T.row_bytes + 64);
-		max_cap = std::max(max_cap, gd_generic_cap(T.qlen, T.tlen, T.w));
-	}
+	int rc, max_cap;
+	size_t bt;
+	if ((rc = gd_literal_tasks(ctx, n, qoff, toff, w, cigar_off, true, bt, max_cap))) return rc;
 	const size_t lds = (size_t)max_cap * (flag & GD_EZ_APPROX_MAX ? 5 : 9); // u v x y s, and the int32 H ring of the exact maximum
 	if (lds > 160 * 1024 - 1024) { ctx->err = "band wider than the LDS window of the literal ksw_extz2 kernel"; return GDIET_E_PARAM; }
 	const size_t qb = (size_t)qoff[n], tb = (size_t)toff[n], cb = (size_t)cigar_off[n];
@@ -984,7 +804,7 @@ static int gd_extz2_literal(gdiet_ctx *ctx, int n, const uint8_t *qseq, const in
 	GdExtzOut *d_ez = (GdExtzOut *)(d_start + 2 * (size_t)n);
 	GD_HIP(hipMemcpyAsync(ctx->qseq.p, qseq, qb, hipMemcpyHostToDevice, s));
 	GD_HIP(hipMemcpyAsync(ctx->tseq.p, tseq, tb, hipMemcpyHostToDevice, s));
-	GD_HIP(hipMemcpyAsync(ctx->tasks.p, h_tasks, sizeof(KswTask) * n, hipMemcpyHostToDevice, s));
+	GD_HIP(hipMemcpyAsync(ctx->tasks.p, ctx->h_tasks.p, sizeof(KswTask) * n, hipMemcpyHostToDevice, s));
 	if (lds > 64 * 1024) GD_HIP(hipFuncSetAttribute((const void *)ksw_extz2_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	ctx->last_mask = 2, ctx->last_was_async = false;
 	GD_HIP(hipEventRecord(ctx->ev[0], s));
@@ -999,9 +819,7 @@ static int gd_extz2_literal(gdiet_ctx *ctx, int n, const uint8_t *qseq, const in
 	GD_HIP(hipMemcpyAsync(cigar, ctx->cigar.p, sizeof(uint32_t) * cb, hipMemcpyDeviceToHost, s));
 	GD_HIP(hipStreamSynchronize(s));
 	GD_HIP(hipGetLastError());
-	for (int i = 0; i < n; ++i)
-		if (n_cigar[i] > cigar_off[i + 1] - cigar_off[i]) { ctx->err = "CIGAR of alignment " + std::to_string(i) + " needs " + std::to_string(n_cigar[i]) + " ops"; return GDIET_E_CIGAR_CAP; }
-	return GDIET_OK;
+	return gd_check_cigar_caps(ctx, n, n_cigar, cigar_off);
 }
 
 // ksw_exts2 (splice-aware extension; not called by GDiet): ksw_exts2.hip.h
@@ -1031,22 +849,9 @@ extern "C" int gdiet_hip_ksw_exts2_batch(gdiet_ctx *ctx, int n, const uint8_t *q
 	K.long_thres = (q2 - q) / e - 1; // :92-95
 	if (q2 > q + e + K.long_thres * e) ++K.long_thres;
 	K.long_diff = K.long_thres * e - (q2 - q);
-	int rc;
-	if ((rc = gd_host_grow(ctx, ctx->h_tasks, sizeof(KswTask) * (size_t)n))) return rc;
-	KswTask *h_tasks = (KswTask *)ctx->h_tasks.p;
-	size_t bt = 0;
-	int max_cap = 0;
-	for (int i = 0; i < n; ++i) {
-		KswTask &T = h_tasks[i];
-		T.qoff = qoff[i], T.toff = toff[i], T.qlen = (int)(qoff[i + 1] - qoff[i]), T.tlen = (int)(toff[i + 1] - toff[i]), T.w = -1;
-		if (T.qlen <= 0 || T.tlen <= 0) { ctx->err = "empty sequence in batch (the reference returns without aligning)"; return GDIET_E_PARAM; }
-		T.cig_off = cigar_off[i], T.cig_cap = (int32_t)std::min<int64_t>(cigar_off[i + 1] - cigar_off[i], 0x7fffffff);
-		T.exact_score = GD_NEG_INF, T.kind = GD_KIND_GENERIC, T.pad = 0;
-		T.row_bytes = (((T.qlen < T.tlen ? T.qlen : T.tlen) + 15) / 16 + 1) * 16; // n_col_ * 16, :80
-		T.bt_off = (int64_t)bt;
-		if (!(flag & GD_EZ_SCORE_ONLY)) bt += gd_align256((size_t)(T.qlen + T.tlen - 1) * (size_t)T.row_bytes + 64);
-		max_cap = std::max(max_cap, gd_generic_cap(T.qlen, T.tlen, -1));
-	}
+	int rc, max_cap;
+	size_t bt;
+	if ((rc = gd_literal_tasks(ctx, n, qoff, toff, nullptr, cigar_off, !(flag & GD_EZ_SCORE_ONLY), bt, max_cap))) return rc;
 	const size_t lds = (size_t)max_cap * 10 + 16;
 	if (lds > 160 * 1024 - 1024) { ctx->err = "alignment longer than the LDS window of the ksw_exts2 kernel (min(qlen, tlen) <= ~8000)"; return GDIET_E_PARAM; }
 	const size_t qb = (size_t)qoff[n], tb = (size_t)toff[n], cb = (size_t)cigar_off[n];
@@ -1061,7 +866,7 @@ extern "C" int gdiet_hip_ksw_exts2_batch(gdiet_ctx *ctx, int n, const uint8_t *q
 	GD_HIP(hipMemcpyAsync(ctx->qseq.p, qseq, qb, hipMemcpyHostToDevice, s));
 	GD_HIP(hipMemcpyAsync(ctx->tseq.p, tseq, tb, hipMemcpyHostToDevice, s));
 	if (junc) GD_HIP(hipMemcpyAsync(d_junc, junc, tb, hipMemcpyHostToDevice, s));
-	GD_HIP(hipMemcpyAsync(ctx->tasks.p, h_tasks, sizeof(KswTask) * n, hipMemcpyHostToDevice, s));
+	GD_HIP(hipMemcpyAsync(ctx->tasks.p, ctx->h_tasks.p, sizeof(KswTask) * n, hipMemcpyHostToDevice, s));
 	if (lds > 64 * 1024) GD_HIP(hipFuncSetAttribute((const void *)ksw_exts2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	ctx->last_mask = 2, ctx->last_was_async = false;
 	GD_HIP(hipEventRecord(ctx->ev[0], s));
@@ -1074,9 +879,7 @@ extern "C" int gdiet_hip_ksw_exts2_batch(gdiet_ctx *ctx, int n, const uint8_t *q
 	GD_HIP(hipMemcpyAsync(cigar, ctx->cigar.p, sizeof(uint32_t) * cb, hipMemcpyDeviceToHost, s));
 	GD_HIP(hipStreamSynchronize(s));
 	GD_HIP(hipGetLastError());
-	for (int i = 0; i < n; ++i)
-		if (n_cigar[i] > cigar_off[i + 1] - cigar_off[i]) { ctx->err = "CIGAR of alignment " + std::to_string(i) + " needs " + std::to_string(n_cigar[i]) + " ops"; return GDIET_E_CIGAR_CAP; }
-	return GDIET_OK;
+	return gd_check_cigar_caps(ctx, n, n_cigar, cigar_off);
 }
 
 #include "map_pipeline.hip.h"

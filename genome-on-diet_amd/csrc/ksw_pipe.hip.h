@@ -13,14 +13,6 @@
 #include "ksw_wave.hip.h"
 #include "ksw_pipe_core.h"
 
-// one wavefront's work: cnt alignments of geometry qlen x tlen, np = ceil(cnt / NG) per group, alignment n of group g = ids[id_off + n * NG + g]
-struct PipeWave { int32_t id_off, qlen, tlen, np, row_bytes, cnt, pad[2]; };
-// A run of alignments of one geometry = n_waves consecutive PipeWave records.  The planner (host) knows which alignments the run has, not
-// which of them the exact-match pre-filter will answer (22 % of a 1 %-error short-read batch): pipe_compact_kernel, between the
-// pre-filter and the DP, keeps the ids that are still pending and deals them out to the run's wavefronts in equal shares -- a slot of a
-// pipe that holds an answered alignment would cost its qlen + 15 steps all the same.
-struct PipeRun { int32_t src_off, m, dst_off, wave_off, n_waves, ng, count, done, np_min, pad[3]; }; // count / done: zero when uploaded, the kernel's counters
-
 // Blocks of GDP_COMPACT_THREADS x GDP_COMPACT_ITEMS ids each, grid (chunks of the longest run, runs).  The order of a run's alignments
 // does not matter (every alignment is computed on its own), so a wavefront reserves room for its pending ids with one atomic add on the
 // run's counter; the block that finishes last deals the run out to its wavefronts.

@@ -55,6 +55,14 @@ static inline __host__ __device__ PipeGeo gd_pipe_geo(int qlen, int tlen)
 	return g;
 }
 
+// one wavefront's work: cnt alignments of geometry qlen x tlen, np = ceil(cnt / NG) per group, alignment n of group g = ids[id_off + n * NG + g]
+struct PipeWave { int32_t id_off, qlen, tlen, np, row_bytes, cnt, pad[2]; };
+// A run of alignments of one geometry = n_waves consecutive PipeWave records.  The planner (host) knows which alignments the run has, not
+// which of them the exact-match pre-filter will answer (22 % of a 1 %-error short-read batch): pipe_compact_kernel, between the
+// pre-filter and the DP, keeps the ids that are still pending and deals them out to the run's wavefronts in equal shares -- a slot of a
+// pipe that holds an answered alignment would cost its qlen + 15 steps all the same.
+struct PipeRun { int32_t src_off, m, dst_off, wave_off, n_waves, ng, count, done, np_min, pad[3]; }; // count / done: zero when uploaded, the kernel's counters
+
 // rows of block `sub` that hold cells of the matrix: r in [16 sub, min(16 sub + 15, tlen - 1) + qlen - 1]
 GDW_HD int gdp_valid_rows(const PipeGeo &g, int sub)
 {

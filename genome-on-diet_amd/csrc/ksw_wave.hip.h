@@ -53,20 +53,6 @@ __device__ __forceinline__ const uint8_t *gdw_uniform_ptr(const uint8_t *p, int 
 	return (const uint8_t *)((uintptr_t)hi << 32 | lo);
 }
 
-static inline bool gd_wave_scoring_ok(const KswConst &C)
-{
-	WaveK K;
-	if (!gdw_make_consts(C, K)) return false;
-	// no 8-bit wrap-around anywhere in the reference recurrence for these magnitudes (see ksw_wave_core.h)
-	const int mis = C.sc_mis < 0 ? -C.sc_mis : C.sc_mis, n = C.sc_N < 0 ? -C.sc_N : C.sc_N;
-	return C.sc_mch > 0 && C.sc_mch + 2 * (C.q2 + C.e2) + (mis > n ? mis : n) + (C.q + C.e) <= 120;
-}
-
-static inline bool gd_wave_supported(int qlen, int tlen, int w, int lanes)
-{
-	return qlen + tlen < (1 << 21) && gd_wave_geometry_ok(qlen, tlen, w, lanes); // (a row's offset into the backtrace is a 32-bit quantity)
-}
-
 // LANES == 64: one alignment per wavefront (task_ids[slot]).
 // LANES == 16: four alignments OF IDENTICAL GEOMETRY (qlen, tlen, w) per wavefront, one per DPP row of 16 lanes
 //              (task_ids[4*slot + row]; -1 = empty row, which shadows row 0 without storing).  Identical geometry keeps every
@@ -449,14 +435,7 @@ __global__ __launch_bounds__(128) void ksw_extd2_wave128_kernel(const KswTask *_
 // end: restore the snapshot of the chunk, recompute its rows (the cone of the walk only, below) into a GD_CK_ROWS-row buffer (1 MB), let the walk consume them, go
 // on with the chunk below.  ~1.85x the arithmetic (the first pass drops the flag / direction bytes), 4.9 MB instead of 134 MB per
 // alignment: thousands in flight.  Rows, scores and CIGARs are those of the kernel above (same row function, same walk).
-#define GD_CK_ROWS 480  // the cells a walk can visit inside one chunk, and all they depend on, span at most 62 HALF blocks (gdw_cone_row_half; <= 31 blocks for gdw_cone_row)
-#define GD_CK_REGS 136 // dwords per lane per snapshot: 2 x (48 state + 16 Sb/Tb/Qc/SEL + tn, blk, R) + Rf + pad
-static inline __host__ __device__ size_t gd_ck_bytes(int qlen, int tlen, int /*row_bytes*/)
-{
-	const size_t rows = (size_t)qlen + tlen - 1, n_ck = (rows + GD_CK_ROWS - 1) / GD_CK_ROWS;
-	return n_ck * (size_t)GD_CK_REGS * 64 * 4 + (size_t)GD_CK_ROWS * 1024; // snapshots + one chunk of 64-block rows
-}
-
+// (GD_CK_ROWS, GD_CK_REGS and gd_ck_bytes, which the planner needs too: ksw_wave_core.h)
 __device__ __forceinline__ void gdw_lane_save(const WaveLane &L, u32 *d) // d: this lane's column of the snapshot, stride 64 dwords
 {
 #pragma unroll

@@ -29,6 +29,7 @@
 // the reference's H0 (each unit square between two such paths contributes u+v'=v+u' identically, because both
 // u(r,t) and v(r,t) are z minus the stored neighbours).  Each lane tracks 8*H at its cell 0; see gdw_track_*.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "ksw_common.h"
 
@@ -488,6 +489,29 @@ static inline bool gd_wave_geometry_ok(int qlen, int tlen, int w, int lanes)
 		if (e0 != tlen - 1 || s0 > 16 * mlast) return false;
 	}
 	return true;
+}
+
+static inline bool gd_wave_scoring_ok(const KswConst &C)
+{
+	WaveK K;
+	if (!gdw_make_consts(C, K)) return false;
+	// no 8-bit wrap-around anywhere in the reference recurrence for these magnitudes (see ksw_wave_core.h)
+	const int mis = C.sc_mis < 0 ? -C.sc_mis : C.sc_mis, n = C.sc_N < 0 ? -C.sc_N : C.sc_N;
+	return C.sc_mch > 0 && C.sc_mch + 2 * (C.q2 + C.e2) + (mis > n ? mis : n) + (C.q + C.e) <= 120;
+}
+
+static inline bool gd_wave_supported(int qlen, int tlen, int w, int lanes)
+{
+	return qlen + tlen < (1 << 21) && gd_wave_geometry_ok(qlen, tlen, w, lanes); // (a row's offset into the backtrace is a 32-bit quantity)
+}
+
+// the checkpointed backtrace of the wide-band kernels (ksw_wave.hip.h, "the same with a CHECKPOINTED backtrace")
+#define GD_CK_ROWS 480  // the cells a walk can visit inside one chunk, and all they depend on, span at most 62 HALF blocks (gdw_cone_row_half; <= 31 blocks for gdw_cone_row)
+#define GD_CK_REGS 136 // dwords per lane per snapshot: 2 x (48 state + 16 Sb/Tb/Qc/SEL + tn, blk, R) + Rf + pad
+static inline __host__ __device__ size_t gd_ck_bytes(int qlen, int tlen, int /*row_bytes*/)
+{
+	const size_t rows = (size_t)qlen + tlen - 1, n_ck = (rows + GD_CK_ROWS - 1) / GD_CK_ROWS;
+	return n_ck * (size_t)GD_CK_REGS * 64 * 4 + (size_t)GD_CK_ROWS * 1024; // snapshots + one chunk of 64-block rows
 }
 
 // ---- half blocks (wide bands on a 96-block ring: ksw_extd2_wave96c_kernel) -------------------------------------------------------

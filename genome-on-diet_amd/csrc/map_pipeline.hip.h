@@ -51,7 +51,6 @@ static GdPool *gd_pool(gdiet_ctx *ctx)
 
 template <class F> static void gd_parallel_for(gdiet_ctx *ctx, int n_threads, int n, F f) { gd_pool(ctx)->run(n_threads, n, f); }
 
-static double gd_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static int gd_index_upload(gdiet_ctx *ctx, gdiet_index *ix)
 {
@@ -213,7 +212,7 @@ extern "C" int gdiet_hip_batch_upload(gdiet_ctx *ctx, gdiet_read_batch **out, in
 {
 	if (!ctx || !out || n < 0 || (n && (!seqs || !lens))) return GDIET_E_PARAM;
 	(void)hipSetDevice(ctx->device);
-	static const bool trace = getenv("GDIET_TRACE_STAGES") != nullptr;
+	const bool trace = gd_trace_stages();
 	double t_[5] = {gd_now(), 0, 0, 0, 0};
 	gdiet_read_batch *b = new gdiet_read_batch();
 	b->n = n;
@@ -381,18 +380,7 @@ struct GdSeedExport {
 // the whole per-read path for one slice, on ctx's own stream and buffers (ctx is a lane: the parent context or one of its children)
 static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O, const GdBatchView &B, int32_t *n_regs, gdiet_reg_t **regs, GdSeedExport *sx = nullptr)
 {
-	// GDIET_TRACE_STAGES=1: wall time of the host-side sub-steps of this call to stderr (development aid)
-	static const bool trace = getenv("GDIET_TRACE_STAGES") != nullptr;
-	double tr_t = trace ? gd_now() : 0;
-	const double tr_t0 = tr_t;
-	std::string tr_s;
-	auto mark = [&](const char *what) {
-		if (!trace) return;
-		const double now = gd_now();
-		char b[64];
-		snprintf(b, sizeof b, " %s %.2f", what, 1e3 * (now - tr_t));
-		tr_s += b, tr_t = now;
-	};
+	GdStageTrace mark; // wall time of the host-side sub-steps of this call
 
 	(void)hipSetDevice(ctx->device);
 	const int n = B.n;
@@ -844,8 +832,8 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 			if (xport) {
 				const size_t need = sizeof(GdPostOut) * (size_t)nb + sizeof(int32_t) * 2 * nbp + 256;
 				if (need > ctx->h_pin.cap) {
-					if (ctx->h_pin.p) (void)hipHostFree(ctx->h_pin.p);
-					ctx->h_pin.p = nullptr, ctx->h_pin.cap = 0;
+					(void)ctx->h_pin.release();
+					ctx->h_pin.kind = DevBuf::PINNED;
 					if (hipHostMalloc(&ctx->h_pin.p, need + need / 2, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->h_pin.p = nullptr; }
 					else ctx->h_pin.cap = need + need / 2;
 				}
@@ -945,7 +933,7 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 	if (no_mem.load()) { gdiet_hip_free_regs(n, n_regs, regs); ctx->err = "out of host memory for the records"; return GDIET_E_NOMEM; }
 	ctx->stage_s[4] += gd_now() - t0;
 	mark("post");
-	if (trace) fprintf(stderr, "[gdiet stages, ms] lane=%p start=%.2f end=%.2f n=%d%s\n", (void *)ctx, 1e3 * fmod(tr_t0, 1000.0), 1e3 * fmod(gd_now(), 1000.0), n, tr_s.c_str());
+	if (mark.on) fprintf(stderr, "[gdiet stages, ms] lane=%p start=%.2f end=%.2f n=%d%s\n", (void *)ctx, 1e3 * fmod(mark.t0, 1000.0), 1e3 * fmod(gd_now(), 1000.0), n, mark.s.c_str());
 	return GDIET_OK;
 }
 
@@ -993,8 +981,7 @@ extern "C" int gdiet_hip_map_uploaded(gdiet_ctx *ctx, const gdiet_index *ix, con
 	// host stages of one slice overlap with the DP kernel of the others.  No result depends on the slicing.
 	if (ctx->arena.p) { // ... and the parent's whole-batch arena is not needed while the lanes hold their own
 		(void)hipStreamSynchronize(ctx->stream);
-		(void)hipFree(ctx->arena.p);
-		ctx->arena.p = nullptr, ctx->arena.cap = 0;
+		(void)ctx->arena.release();
 	}
 	while ((int)ctx->children.size() < lanes) {
 		gdiet_ctx *c = nullptr;

@@ -232,7 +232,7 @@ def abi_consts(a, b, q, e, q2, e2, sc_ambi=0):
 
 
 def wave_scoring_ok(a, b, q, e, q2, e2, sc_ambi=0):
-    """gd_wave_scoring_ok (ksw_wave.hip.h) with gdw_make_consts (ksw_wave_core.h): the scorings the register-resident kernels take"""
+    """gd_wave_scoring_ok with gdw_make_consts (ksw_wave_core.h): the scorings the register-resident kernels take"""
     mch, mis, n, q, e, q2, e2 = abi_consts(a, b, q, e, q2, e2, sc_ambi)
     qe = q + e
     if qe < 1:
