@@ -31,13 +31,7 @@ __device__ __forceinline__ void map_set_prio(int p)
 	else if (p >= 3) __builtin_amdgcn_s_setprio(3);
 }
 
-struct MapReadScratch { // per-read slices of the batch scratch arena (element offsets)
-	uint64_t mv_off;     // GdMini[mv_cap]
-	uint64_t u64_off;    // uint64[2*mv_cap]
-	uint64_t seed_off;   // GdSeed[mv_cap]
-	uint32_t mv_cap;
-	uint32_t pad;
-};
+// (MapReadScratch, MapVoteOut, MapBox and the sort capacities MAP_SORT_CAP / _MAX live in map_stages.h: the host-only planner map_plan.h reads them)
 
 struct MapSeedOut {
 	int32_t n_seeds;  // kept seeds (< 0: scratch overflow)
@@ -106,11 +100,6 @@ __global__ __launch_bounds__(64) void map_seed_kernel(int n_reads, const uint8_t
 	o.n_seeds = gd_collect_matches2(I, mv, n_mv, len, O.mid_occ, O.max_max_occ, O.occ_dist, seed_arena + S.seed_off, &o.n_a);
 	out[rid] = o;
 }
-
-struct MapVoteOut {
-	uint32_t n_cand, pad;
-	GdVt cand[GDM_MAX_VT];
-};
 
 __global__ __launch_bounds__(64) void map_vote_kernel(int n_reads, const int64_t *__restrict__ roff, GdIdxView I, MapDevOpt O,
                                                       const MapReadScratch *__restrict__ sc, const GdSeed *__restrict__ seed_arena,
@@ -318,16 +307,7 @@ __global__ __launch_bounds__(64) void map_vote_wave_kernel(int n_reads, const in
 	for (unsigned i = lane; i < s_ncand; i += 64) o.cand[i] = s_cand[i];
 }
 
-// one DP box: where its query / target windows come from and where they go in the packed ksw batch buffers
 #define GD_NEG_INF_SCORE_DEV (-0x40000000)
-struct MapBox {
-	int64_t read_off;   // offset of the read in the nt4 read buffer
-	int64_t q_dst, t_dst; // destination offsets in the packed query / target buffers
-	uint64_t t_src;     // absolute base offset in S (contig offset + target_start)
-	uint32_t read_len, qseq_off, qlen, tlen, t_avail; // t_avail: bases that exist (window clipped at the contig end)
-	uint32_t rev;       // query window taken from the reverse-complemented read
-};
-
 __global__ __launch_bounds__(64) void map_gather_kernel(int n_box, const MapBox *__restrict__ boxes, const uint8_t *__restrict__ reads,
                                                         const uint32_t *__restrict__ S, uint8_t *__restrict__ qbuf, uint8_t *__restrict__ tbuf)
 {
@@ -372,7 +352,7 @@ __global__ __launch_bounds__(64) void map_sr_box_kernel(int n_reads, const int64
 		const GdVt v = vo[rid].cand[j];
 		GdCandBox b;
 		if (!gd_sr_box_core(v, k, a, rl, v.chrom_id < n_seq ? (int32_t)seq_len[v.chrom_id] : 0, b)) continue;
-		bad |= b.qlen == 0 || b.tlen == 0 || b.qlen > rl || b.qseq_off + b.qlen > rl || b.tlen > 8u * rl + 100000u;
+		bad |= gd_box_degenerate(b, rl);
 		out[m++] = b, sl += b.qlen;
 	}
 	if (bad) { m = 0, sl = 0; atomicAdd(&tot->n_failed, 1), atomicMax(&tot->last_failed, rid); }
@@ -402,15 +382,7 @@ __global__ __launch_bounds__(64) void map_sr_fill_kernel(int n_reads, const int6
 	for (int j = 0; j < m; ++j) {
 		const GdCandBox c = sbox[(size_t)rid * slots + j];
 		const int b = box_first[rid] + j;
-		MapBox M;
-		M.read_off = roff[rid], M.read_len = rl, M.qseq_off = c.qseq_off, M.qlen = c.qlen, M.tlen = c.tlen, M.rev = c.v.str;
-		uint32_t avail = 0;
-		uint64_t src = 0;
-		if (c.target_id < n_seq && c.target_start < seq_len[c.target_id]) { // (a window hanging off its contig: the missing part is zero-filled)
-			const uint32_t left = seq_len[c.target_id] - c.target_start;
-			avail = c.tlen < left ? c.tlen : left, src = seq_off[c.target_id] + c.target_start;
-		}
-		M.t_avail = avail, M.t_src = src, M.q_dst = off, M.t_dst = off;
+		const MapBox M = gd_map_box(c, roff[rid], rl, c.target_id < n_seq ? seq_len + c.target_id : nullptr, seq_off + c.target_id, off, off);
 		O.boxes[b] = M, O.cand[b] = c, O.qoff[b] = off, O.coff[b] = 2 * off, O.bw[b] = bw, O.ex[b] = c.exact_score;
 		off += c.qlen;
 	}
@@ -606,8 +578,6 @@ __global__ __launch_bounds__(64) void map_post_wave_kernel(int nb, const MapBox 
 // The winnowing automaton is sequential, but exact slices of it can be produced independently (gd_sketch_slice), so the 64
 // lanes sketch 64 slices of the read, compact their minimizers in read order with a wavefront prefix sum, probe the index
 // in parallel, and leave only the short sequential parts (query-occurrence filter, high-occurrence seed selection) to lane 0.
-#define MAP_SORT_CAP 2048      // hashes of one read the seed kernel sorts in LDS: at least (16 KB) ...
-#define MAP_SORT_CAP_MAX 16384 // ... and at most (128 KB: ONT reads of up to ~180 kbp), chosen per batch from its longest read
 
 #ifdef GD_SEED_PROF
 __device__ unsigned long long gd_seed_prof[8];

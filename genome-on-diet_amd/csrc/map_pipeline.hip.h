@@ -1,6 +1,9 @@
 // B1: batch driver of the per-read mapping path.  Included at the end of gdiet_hip.hip (needs gdiet_ctx, GD_HIP, gd_grow).
 //   host threads : encode reads, candidate linking + DP boxes (gd_lr_link_and_boxes), post-processing (gd_lr_finish)
 //   device       : map_seed_kernel -> map_vote_kernel -> map_gather_kernel -> ksw batch (exact-match, DP, backtrack)
+// gd_map_range is a sequence of stages (gd_stage_setup, _seed, _vote, _boxes_device / _boxes_host, gd_upload_boxes, gd_stage_dp, _pack,
+// _records) over one GdMapCall; their host arithmetic -- capacity classes, scratch layout, box tables, failed reads -- is map_plan.h,
+// which has no HIP in it and is tested on the CPU (tests/test_map_plan.py).
 #pragma once
 #include <atomic>
 #include <memory>
@@ -9,6 +12,7 @@
 #include <thread>
 #include <mutex>
 #include "map_host.h"
+#include "map_plan.h"
 #include "map_index.h"
 #include "map_kernels.hip.h"
 
@@ -322,6 +326,14 @@ static void gd_regs_fill(const std::vector<GdReg> &v, void *at, bool head, int32
 	*regs = r;
 }
 
+// the inverse: a record of the C interface as the formatters' GdReg
+static void gd_reg_from_c(const gdiet_reg_t &r, GdReg &g)
+{
+	g.id = r.id, g.cnt = r.cnt, g.rid = r.rid, g.score = r.score, g.qs = r.qs, g.qe = r.qe, g.rs = r.rs, g.re = r.re, g.parent = r.parent, g.subsc = r.subsc;
+	g.mlen = r.mlen, g.blen = r.blen, g.mapq = r.mapq, g.rev = r.rev, g.sam_pri = r.sam_pri, g.dp_score = r.dp_score, g.dp_max = r.dp_max, g.n_ambi = r.n_ambi;
+	g.has_p = true, g.cigar.assign(r.cigar, r.cigar + r.n_cigar);
+}
+
 extern "C" void gdiet_hip_free_regs(int n, int32_t *n_regs, gdiet_reg_t **regs)
 {
 	if (!n_regs || !regs) return;
@@ -377,124 +389,129 @@ struct GdSeedExport {
 	std::vector<GdSeed> seeds;     // the kept seeds of all reads, back to back
 };
 
-// the whole per-read path for one slice, on ctx's own stream and buffers (ctx is a lane: the parent context or one of its children)
-static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O, const GdBatchView &B, int32_t *n_regs, gdiet_reg_t **regs, GdSeedExport *sx = nullptr)
+// GDIET_FAULT_BOX=<read index> (fault injection for the tests): the boxes of that read of every batch count as degenerate; -1: none
+static int gd_fault_box()
 {
-	GdStageTrace mark; // wall time of the host-side sub-steps of this call
+	static const char *fault_env = getenv("GDIET_FAULT_BOX");
+	return fault_env ? atoi(fault_env) : -1;
+}
 
-	(void)hipSetDevice(ctx->device);
-	const int n = B.n;
-	for (int i = 0; i < 6; ++i) ctx->stage_s[i] = 0;
-	if (n == 0) return GDIET_OK;
-	if (!sx) for (int i = 0; i < n; ++i) n_regs[i] = 0, regs[i] = nullptr; // whatever happens below, gdiet_hip_free_regs on these arrays is safe
-	hipStream_t s = ctx->stream;
+// The state of one gd_map_range call: what its stages hand to each other.  Lives on that function's stack.
+struct GdMapCall {
+	gdiet_ctx *ctx; // the lane: the parent context or one of its children
+	const gdiet_index *ix;
+	const GdMapOpt &O;
+	const GdBatchView &B;
+	int32_t *n_regs;
+	gdiet_reg_t **regs;
+	GdStageTrace mark; // wall time of the host-side sub-steps of this call
+	double t0 = 0;     // start of the step that ctx->stage_s[] is charged for next (gd_lap)
+	MapDevOpt D;
+	bool is_sr = false, sr_dev = false; // ShortReads variant; its box stage on the device
+	std::vector<MapReadScratch> sc;     // scratch layout
+	GdSeedClasses cls;                  // capacity classes of the seed kernel
+	MapSeedOut *so = nullptr;           // host copy of the seed records (ctx->h_seedout)
+	std::vector<int64_t> hoff;          // hit offsets, n + 1
+	GdBoxTables T;
+	// pointers into m_aux: d_coff | d_ex | d_score | d_ncig in one buffer, the last three 256-byte aligned as their host copies
+	size_t nbp = 64;
+	int64_t *d_coff = nullptr;
+	int32_t *d_ex = nullptr, *d_score = nullptr, *d_ncig = nullptr;
+	// results of the DP and pack stages on the host
+	int32_t *h_score = nullptr, *h_ncig = nullptr;
+	const GdPostOut *h_post = nullptr;
+	uint32_t *h_cig = nullptr;
+	std::vector<int64_t> poff{0};
+};
+
+static void gd_lap(GdMapCall &c, int stage) { c.ctx->stage_s[stage] += gd_now() - c.t0, c.t0 = gd_now(); }
+
+static int gd_scratch_grow(GdMapCall &c, bool full)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const int n = c.B.n;
+	const uint64_t tot = gd_scratch_layout(n, c.B.roff, c.O.w, full, c.sc.data());
 	int rc;
-	double t0 = gd_now();
-	// ---- scratch layout -------------------------------------------------------------------------------------------
-	// minimizer lists: len/3 + 512 entries per read cover every density the presets produce; a read that overflows its list
-	// (tiny windows, homopolymer reads) makes the whole batch retry once with the hard bound
-	std::vector<MapReadScratch> sc(n);
-	uint64_t tot = 0;
-	auto layout = [&](bool full) -> int {
-		tot = 0;
-		for (int i = 0; i < n; ++i) {
-			const uint32_t len = (uint32_t)(B.roff[i + 1] - B.roff[i]);
-			// hard bound: one minimizer per base, plus the per-lane staging lists of the wavefront sketch (64 lists of ceil(len/64) + w + 2)
-			sc[i].mv_cap = full ? len + 64 * (uint32_t)(O.w + 4) : len / 3 + 512, sc[i].mv_off = tot, sc[i].u64_off = 2 * tot, sc[i].seed_off = tot, sc[i].pad = 0;
-			tot += sc[i].mv_cap;
-		}
-		int rc2;
-		if ((rc2 = gd_grow(ctx, ctx->m_sc, sizeof(MapReadScratch) * n))) return rc2;
-		if ((rc2 = gd_grow(ctx, ctx->m_mv, sizeof(GdMini) * tot))) return rc2;
-		if ((rc2 = gd_grow(ctx, ctx->m_u64, sizeof(uint64_t) * 2 * tot))) return rc2;
-		if ((rc2 = gd_grow(ctx, ctx->m_seed, sizeof(GdSeed) * tot))) return rc2;
-		GD_HIP(hipMemcpyAsync(ctx->m_sc.p, sc.data(), sizeof(MapReadScratch) * n, hipMemcpyHostToDevice, s));
-		return GDIET_OK;
-	};
-	if ((rc = layout(false))) return rc;
+	if ((rc = gd_grow(ctx, ctx->m_sc, sizeof(MapReadScratch) * n))) return rc;
+	if ((rc = gd_grow(ctx, ctx->m_mv, sizeof(GdMini) * tot))) return rc;
+	if ((rc = gd_grow(ctx, ctx->m_u64, sizeof(uint64_t) * 2 * tot))) return rc;
+	if ((rc = gd_grow(ctx, ctx->m_seed, sizeof(GdSeed) * tot))) return rc;
+	GD_HIP(hipMemcpyAsync(ctx->m_sc.p, c.sc.data(), sizeof(MapReadScratch) * n, hipMemcpyHostToDevice, ctx->stream));
+	return GDIET_OK;
+}
+
+// scratch layout, MapDevOpt from GdMapOpt, capacity classes of the seed kernel
+static int gd_stage_setup(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const GdMapOpt &O = c.O;
+	const int n = c.B.n;
+	int rc;
+	c.sc.resize(n);
+	if ((rc = gd_scratch_grow(c, false))) return rc;
 	if ((rc = gd_grow(ctx, ctx->m_seedout, sizeof(MapSeedOut) * n))) return rc;
 	if ((rc = gd_grow(ctx, ctx->m_voteout, sizeof(MapVoteOut) * n))) return rc;
 	if ((rc = gd_grow(ctx, ctx->m_hitoff, sizeof(int64_t) * (n + 1)))) return rc;
-	MapDevOpt D;
+	MapDevOpt &D = c.D;
 	D.k = O.k, D.w = O.w, D.max_seeds = O.max_seeds, D.q_occ_frac = O.q_occ_frac, D.mid_occ = O.mid_occ, D.max_max_occ = O.max_max_occ, D.occ_dist = O.occ_dist;
 	D.max_nb_seeds = (O.flag & GD_F_FRAG_MODE) ? (O.max_frag_len == 0 ? 800u : (uint32_t)O.max_frag_len) : UINT32_MAX;
 	D.flag = O.flag, D.pat = O.pat;
 	D.vote.vt_dis = O.vt_dis, D.vote.vt_nb_loc = O.vt_nb_loc, D.vote.bw = O.bw, D.vote.vt_cov = O.vt_cov, D.vote.vt_f = O.vt_f;
 	D.vote.vt_df1 = O.vt_df1, D.vote.vt_df2 = O.vt_df2, D.vote.k = O.k;
-	const bool is_sr = (O.flag & GD_F_SR) != 0;
-	D.is_sr = is_sr;
+	c.is_sr = (O.flag & GD_F_SR) != 0;
+	D.is_sr = c.is_sr;
 	// The seeding / voting wavefronts of a batch run beside the DP wavefronts of the batch before it (five per SIMD, VALU-bound, older): at
 	// the default priority they get the issue slots those leave, hold their scarce slots for a long time, and the batch is ready only when
 	// that DP kernel ends -- with two batches in flight the next DP kernel then starts ~5 ms late (834 Mbases/s).  At s_setprio(2) they are
 	// through in ~60 ms, the DP kernels follow each other back to back with TWO batches in flight (875-881 Mbases/s) and a batch spends two
 	// step times in the pipeline instead of three (p50 174 instead of 261 ms).
 	D.prio = 2;
-	{ // LDS sort capacity of the wave seed kernel: ~1.25 x the minimizers expected of the longest read (2 / (w + 1) of its sparsified bases)
-		int64_t max_len = 0;
-		for (int i = 0; i < n; ++i) max_len = std::max<int64_t>(max_len, B.roff[i + 1] - B.roff[i]);
-		const double est = 1.25 * 2.0 / (O.w + 1) * gd_diet_len(O.pat, (unsigned)max_len, 0);
-		int cap = MAP_SORT_CAP;
-		while (cap < MAP_SORT_CAP_MAX && cap < est) cap <<= 1;
-		D.sort_cap = cap;
-	}
-	// Reads of very different lengths (ONT: log-normal up to 150 kbp): one launch per capacity class, each read in the class its own
-	// length asks for, so that a 30 kbp read does not hold the 128 KB of LDS the longest read of the batch needs -- 128 KB is one
-	// wavefront per CU, and never beside a DP kernel that keeps 48 KB of it.  (A read is treated exactly as if it were the longest read
-	// of its batch: every path of the kernel is exact, the capacity only selects between them.)
-	std::vector<int32_t> seed_ids;
-	std::vector<std::pair<int, int>> seed_classes; // (capacity, reads), longest class first; empty: one launch over all reads
-	if (D.sort_cap > MAP_SORT_CAP && n > 1) {
-		std::vector<int> cap_of(n);
-		int n_cls[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-		for (int i = 0; i < n; ++i) {
-			const double est = 1.25 * 2.0 / (O.w + 1) * gd_diet_len(O.pat, (unsigned)(B.roff[i + 1] - B.roff[i]), 0);
-			int cap = MAP_SORT_CAP, c = 0;
-			while (cap < MAP_SORT_CAP_MAX && cap < est) cap <<= 1, ++c;
-			cap_of[i] = c, ++n_cls[c];
-		}
-		int used = 0;
-		for (int c = 0; c < 8; ++c) used += n_cls[c] > 0;
-		if (used > 1) {
-			seed_ids.reserve(n);
-			for (int c = 7; c >= 0; --c) {
-				if (!n_cls[c]) continue;
-				seed_classes.push_back({MAP_SORT_CAP << c, n_cls[c]});
-				for (int i = 0; i < n; ++i) if (cap_of[i] == c) seed_ids.push_back(i);
-			}
-		}
-	}
+	gd_seed_classes(O.pat, O.w, n, c.B.roff, c.cls); // (map_plan.h)
+	D.sort_cap = c.cls.sort_cap;
 	D.sr.min_cnt = O.min_cnt, D.sr.rec_threshold_frac = O.rec_threshold_frac, D.sr.bw_frac = O.bw_frac, D.sr.bw_min = O.bw_min, D.sr.bw_max = O.bw_max;
 	D.sr.af_max_loc = O.af_max_loc, D.sr.max_nb_seeds = D.max_nb_seeds, D.sr.frag_mode = (O.flag & GD_F_FRAG_MODE) != 0;
-	const uint8_t *d_reads = (const uint8_t *)B.d_reads;
-	const int64_t *d_roff = (const int64_t *)B.d_roff;
-	ctx->stage_s[5] += gd_now() - t0, t0 = gd_now();
-	// ---- S1-S5 ----------------------------------------------------------------------------------------------------
+	// ShortReads: the box stage on the device (map_sr_box_kernel / map_sr_fill_kernel).  GDIET_SR_BOXES=host keeps the host stages.
+	c.sr_dev = c.is_sr && ctx->sr_boxes_on_device && (int64_t)n * std::min<int64_t>(O.af_max_loc, GDM_MAX_VT) < ((int64_t)1 << 28);
+	return GDIET_OK;
+}
+
+// S1-S5: the seed kernel in one of its three launch forms; a scratch overflow makes the batch retry once with the hard bound
+static int gd_stage_seed(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const gdiet_index *ix = c.ix;
+	const GdMapOpt &O = c.O;
+	const GdBatchView &B = c.B;
+	MapDevOpt &D = c.D;
+	const int n = B.n;
+	hipStream_t s = ctx->stream;
+	int rc;
 	if ((rc = gd_host_grow(ctx, ctx->h_seedout, sizeof(MapSeedOut) * (size_t)n))) return rc;
-	MapSeedOut *so = (MapSeedOut *)ctx->h_seedout.p;
-	const size_t seed_lds = std::max<size_t>((size_t)O.w * 64 * sizeof(GdMini), (size_t)D.sort_cap * sizeof(uint64_t));
+	MapSeedOut *so = c.so = (MapSeedOut *)ctx->h_seedout.p;
+	const size_t seed_lds = gd_seed_lds_bytes(O.w, D.sort_cap);
 	D.seed_lds = (uint32_t)seed_lds;
 	if (seed_lds > 64 * 1024) GD_HIP(hipFuncSetAttribute((const void *)map_seed_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)seed_lds));
 	for (int attempt = 0; attempt < 2; ++attempt) {
 		// one read per thread (the plain sequential form) for short reads -- a 150 bp read has ~75 sparsified bases, far too few to
 		// split over 64 lanes (measured 18x faster at 150 bp) -- and on request (GDIET_SEED_KERNEL=thread) for A/B checks
 		if (ctx->seed_thread_kernel == 1 || (ctx->seed_thread_kernel == 0 && (B.roff[n] - B.roff[0]) / n < 1024))
-			hipLaunchKernelGGL(map_seed_kernel, dim3((n + 63) / 64), dim3(64), (size_t)O.w * 64 * sizeof(GdMini), s, n, d_reads, d_roff, ix->dview, D, (const MapReadScratch *)ctx->m_sc.p,
+			hipLaunchKernelGGL(map_seed_kernel, dim3((n + 63) / 64), dim3(64), (size_t)O.w * 64 * sizeof(GdMini), s, n, B.d_reads, B.d_roff, ix->dview, D, (const MapReadScratch *)ctx->m_sc.p,
 			                   (GdMini *)ctx->m_mv.p, (uint64_t *)ctx->m_u64.p, (GdSeed *)ctx->m_seed.p, (MapSeedOut *)ctx->m_seedout.p);
-		else if (!seed_classes.empty()) { // one read per wavefront, one launch per LDS capacity class
+		else if (!c.cls.classes.empty()) { // one read per wavefront, one launch per LDS capacity class
 			if ((rc = gd_grow(ctx, ctx->m_seedids, sizeof(int32_t) * (size_t)n))) return rc;
-			GD_HIP(hipMemcpyAsync(ctx->m_seedids.p, seed_ids.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+			GD_HIP(hipMemcpyAsync(ctx->m_seedids.p, c.cls.ids.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
 			int at = 0;
-			for (const auto &cls : seed_classes) {
+			for (const auto &cls : c.cls.classes) {
 				MapDevOpt Dc = D;
 				Dc.sort_cap = cls.first;
-				const size_t lds_c = std::max<size_t>((size_t)O.w * 64 * sizeof(GdMini), (size_t)cls.first * sizeof(uint64_t));
+				const size_t lds_c = gd_seed_lds_bytes(O.w, cls.first);
 				Dc.seed_lds = (uint32_t)lds_c;
-				hipLaunchKernelGGL(map_seed_wave_kernel, dim3(cls.second), dim3(64), lds_c, s, cls.second, d_reads, d_roff, ix->dview, Dc, (const MapReadScratch *)ctx->m_sc.p,
+				hipLaunchKernelGGL(map_seed_wave_kernel, dim3(cls.second), dim3(64), lds_c, s, cls.second, B.d_reads, B.d_roff, ix->dview, Dc, (const MapReadScratch *)ctx->m_sc.p,
 				                   (GdMini *)ctx->m_mv.p, (uint64_t *)ctx->m_u64.p, (GdSeed *)ctx->m_seed.p, (MapSeedOut *)ctx->m_seedout.p, (const int32_t *)ctx->m_seedids.p + at);
 				at += cls.second;
 			}
 		} else // one read per wavefront: 64 exact slices of the winnowing automaton + parallel index probes
-			hipLaunchKernelGGL(map_seed_wave_kernel, dim3(n), dim3(64), seed_lds, s, n, d_reads, d_roff, ix->dview, D, (const MapReadScratch *)ctx->m_sc.p,
+			hipLaunchKernelGGL(map_seed_wave_kernel, dim3(n), dim3(64), seed_lds, s, n, B.d_reads, B.d_roff, ix->dview, D, (const MapReadScratch *)ctx->m_sc.p,
 			                   (GdMini *)ctx->m_mv.p, (uint64_t *)ctx->m_u64.p, (GdSeed *)ctx->m_seed.p, (MapSeedOut *)ctx->m_seedout.p, (const int32_t *)nullptr);
 		GD_HIP(hipGetLastError()); // a refused launch (LDS size, grid) must not pass for stale seed records
 		GD_HIP(hipMemcpyAsync(so, ctx->m_seedout.p, sizeof(MapSeedOut) * n, hipMemcpyDeviceToHost, s));
@@ -503,31 +520,48 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 		for (int i = 0; i < n; ++i) overflow |= so[i].n_seeds < 0;
 		if (!overflow) break;
 		if (attempt == 1) { ctx->err = "minimizer scratch overflow even with one entry per base"; return GDIET_E_NOMEM; }
-		if ((rc = layout(true))) return rc;
+		if ((rc = gd_scratch_grow(c, true))) return rc;
 	}
-	ctx->stage_s[0] += gd_now() - t0, t0 = gd_now();
-	mark("seed");
-	if (sx) { // B4: the seeds themselves are the result
-		sx->out.assign(so, so + n);
-		int64_t tot_seeds = 0;
-		for (int i = 0; i < n; ++i) tot_seeds += so[i].n_seeds > 0 ? so[i].n_seeds : 0;
-		sx->seeds.resize((size_t)tot_seeds);
-		int64_t at = 0;
-		for (int i = 0; i < n; ++i)
-			if (so[i].n_seeds > 0) {
-				GD_HIP(hipMemcpyAsync(sx->seeds.data() + at, (const GdSeed *)ctx->m_seed.p + sc[i].seed_off, sizeof(GdSeed) * (size_t)so[i].n_seeds, hipMemcpyDeviceToHost, s));
-				at += so[i].n_seeds;
-			}
-		GD_HIP(gd_stream_wait(ctx, s));
-		return GDIET_OK;
-	}
-	std::vector<int64_t> hoff(n + 1, 0);
+	return GDIET_OK;
+}
+
+// B4: the seeds themselves are the result
+static int gd_seed_export(GdMapCall &c, GdSeedExport &sx)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const int n = c.B.n;
+	const MapSeedOut *so = c.so;
+	hipStream_t s = ctx->stream;
+	sx.out.assign(so, so + n);
+	int64_t tot_seeds = 0;
+	for (int i = 0; i < n; ++i) tot_seeds += so[i].n_seeds > 0 ? so[i].n_seeds : 0;
+	sx.seeds.resize((size_t)tot_seeds);
+	int64_t at = 0;
+	for (int i = 0; i < n; ++i)
+		if (so[i].n_seeds > 0) {
+			GD_HIP(hipMemcpyAsync(sx.seeds.data() + at, (const GdSeed *)ctx->m_seed.p + c.sc[i].seed_off, sizeof(GdSeed) * (size_t)so[i].n_seeds, hipMemcpyDeviceToHost, s));
+			at += so[i].n_seeds;
+		}
+	GD_HIP(gd_stream_wait(ctx, s));
+	return GDIET_OK;
+}
+
+// S6, S7, V1, V3, G1a: hit offsets, then the vote kernel in one of its two launch forms
+static int gd_stage_vote(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const gdiet_index *ix = c.ix;
+	const GdBatchView &B = c.B;
+	const int n = B.n;
+	hipStream_t s = ctx->stream;
+	std::vector<int64_t> &hoff = c.hoff;
+	int rc;
+	hoff.assign(n + 1, 0);
 	for (int i = 0; i < n; ++i) {
-		hoff[i + 1] = hoff[i] + (so[i].n_seeds > 0 ? so[i].n_a : 0);
+		hoff[i + 1] = hoff[i] + (c.so[i].n_seeds > 0 ? c.so[i].n_a : 0);
 	}
 	if ((rc = gd_grow(ctx, ctx->m_hits, sizeof(GdLoc) * 3 * (size_t)(hoff[n] + 1)))) return rc;
 	GD_HIP(hipMemcpyAsync(ctx->m_hitoff.p, hoff.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
-	// ---- S6, S7, V1, V3, G1a -----------------------------------------------------------------------------------------
 	// long reads: one read per wavefront (parallel expansion + LDS sort); short reads (a handful of hits each): one read per thread
 	const int spread = (B.roff[n] - B.roff[0]) / n >= 1024;
 	if (spread == 1 && ctx->vote_wave) {
@@ -540,347 +574,339 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 		// only granted after the attribute has been raised
 		if (sizeof(GdLoc) * (size_t)vote_cap + sizeof(GdVt) * GDM_MAX_VT + 64 > 64 * 1024)
 			GD_HIP(hipFuncSetAttribute((const void *)map_vote_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(GdLoc) * (size_t)vote_cap)));
-		hipLaunchKernelGGL(map_vote_wave_kernel, dim3(n), dim3(64), sizeof(GdLoc) * (size_t)vote_cap, s, n, d_roff, ix->dview, D, (const MapReadScratch *)ctx->m_sc.p,
+		hipLaunchKernelGGL(map_vote_wave_kernel, dim3(n), dim3(64), sizeof(GdLoc) * (size_t)vote_cap, s, n, B.d_roff, ix->dview, c.D, (const MapReadScratch *)ctx->m_sc.p,
 		                   (const GdSeed *)ctx->m_seed.p, (const MapSeedOut *)ctx->m_seedout.p, (const int64_t *)ctx->m_hitoff.p, (GdLoc *)ctx->m_hits.p,
 		                   (MapVoteOut *)ctx->m_voteout.p, vote_cap);
 	} else
-		hipLaunchKernelGGL(map_vote_kernel, dim3(spread ? n : (n + 63) / 64), dim3(64), 0, s, n, d_roff, ix->dview, D, (const MapReadScratch *)ctx->m_sc.p,
+		hipLaunchKernelGGL(map_vote_kernel, dim3(spread ? n : (n + 63) / 64), dim3(64), 0, s, n, B.d_roff, ix->dview, c.D, (const MapReadScratch *)ctx->m_sc.p,
 		                   (const GdSeed *)ctx->m_seed.p, (const MapSeedOut *)ctx->m_seedout.p, (const int64_t *)ctx->m_hitoff.p, (GdLoc *)ctx->m_hits.p,
 		                   (MapVoteOut *)ctx->m_voteout.p, spread);
 	GD_HIP(hipGetLastError());
-	// ---- G1b / G2 ---------------------------------------------------------------------------------------------------------------
-	// ShortReads: the box stage on the device (map_sr_box_kernel / map_sr_fill_kernel): the candidates never visit the host; what comes
-	// back are the dense per-box tables the DP planner and the record stage read.  GDIET_SR_BOXES=host keeps the host stages.
-	const bool sr_dev = is_sr && ctx->sr_boxes_on_device && (int64_t)n * std::min<int64_t>(O.af_max_loc, GDM_MAX_VT) < ((int64_t)1 << 28);
+	return GDIET_OK;
+}
+
+static int gd_aux_layout(GdMapCall &c) // d_coff | d_ex | d_score | d_ncig in one buffer, the last three 256-byte aligned as their host copies
+{
+	gdiet_ctx *ctx = c.ctx;
+	const int nb = c.T.nb;
+	c.nbp = ((size_t)std::max(nb, 1) + 63) & ~(size_t)63;
+	int rc;
+	if ((rc = gd_grow(ctx, ctx->m_aux, sizeof(int64_t) * (nb + 1) + sizeof(int32_t) * 3 * c.nbp + 1024))) return rc;
+	c.d_coff = (int64_t *)ctx->m_aux.p;
+	c.d_ex = (int32_t *)(((uintptr_t)(c.d_coff + nb + 1) + 255) & ~(uintptr_t)255), c.d_score = c.d_ex + c.nbp, c.d_ncig = c.d_score + c.nbp;
+	return GDIET_OK;
+}
+
+// the reads a box stage gave up on (a degenerate DP box): counted, and the last one named in the context's warning
+static void gd_note_failed(gdiet_ctx *ctx, int64_t n_failed, int last_bad)
+{
+	ctx->failed_last = n_failed, ctx->failed_total += n_failed;
+	if (n_failed) ctx->warn = gd_failed_reads_warning(n_failed, last_bad);
+}
+
+// the contig table of the index on the device (once), for the device-side box stage
+static int gd_index_seq_table(gdiet_ctx *ctx, const gdiet_index *ix)
+{
 	const GdRefView R = ix->h.ref();
-	std::vector<int> cfirst(n + 1, 0), ccount(n, 0), box_first(n + 1, 0);
-	GdCandBox *cflat = nullptr;
-	int nb = 0;
-	MapBox *boxes = nullptr;
-	std::vector<int64_t> qoff, toff, coff;
-	std::vector<int32_t> bw, ex;
-	size_t nbp = 64;
-	int64_t *d_coff = nullptr;
-	int32_t *d_ex = nullptr, *d_score = nullptr, *d_ncig = nullptr;
-	auto aux_layout = [&]() -> int { // d_coff | d_ex | d_score | d_ncig in one buffer, the last three 256-byte aligned as their host copies
-		nbp = ((size_t)std::max(nb, 1) + 63) & ~(size_t)63;
-		int rc2;
-		if ((rc2 = gd_grow(ctx, ctx->m_aux, sizeof(int64_t) * (nb + 1) + sizeof(int32_t) * 3 * nbp + 1024))) return rc2;
-		d_coff = (int64_t *)ctx->m_aux.p;
-		d_ex = (int32_t *)(((uintptr_t)(d_coff + nb + 1) + 255) & ~(uintptr_t)255), d_score = d_ex + nbp, d_ncig = d_score + nbp;
-		return GDIET_OK;
-	};
-	if (sr_dev) {
-		const int slots = (int)std::min<int64_t>(O.af_max_loc, GDM_MAX_VT);
-		{ // the contig table of the index on the device (once)
-			gdiet_index *ixm = const_cast<gdiet_index *>(ix);
-			std::lock_guard<std::mutex> lk(ixm->seq_mu);
-			if (!ixm->d_seq_len) {
-				std::vector<uint32_t> sl(R.n_seq);
-				std::vector<uint64_t> so(R.n_seq);
-				for (uint32_t q = 0; q < R.n_seq; ++q) sl[q] = R.seq[q].len, so[q] = R.seq[q].offset;
-				uint32_t *dl = nullptr;
-				uint64_t *d_o = nullptr;
-				GD_HIP(hipMalloc(&dl, sizeof(uint32_t) * std::max<size_t>(R.n_seq, 1)));
-				GD_HIP(hipMalloc(&d_o, sizeof(uint64_t) * std::max<size_t>(R.n_seq, 1)));
-				GD_HIP(hipMemcpy(dl, sl.data(), sizeof(uint32_t) * R.n_seq, hipMemcpyHostToDevice));
-				GD_HIP(hipMemcpy(d_o, so.data(), sizeof(uint64_t) * R.n_seq, hipMemcpyHostToDevice));
-				ixm->d_seq_off = d_o, ixm->d_seq_len = dl;
-			}
-		}
-		// per-read tables: cnt[n] | box_first[n + 1] (int32), sumlen[n] | len_first[n + 1] (int64), totals
-		const size_t tab_bytes = sizeof(int64_t) * (2 * (size_t)n + 2) + sizeof(int32_t) * (2 * (size_t)n + 2) + sizeof(MapSrTotals) + 64;
-		if ((rc = gd_grow(ctx, ctx->m_srtab, tab_bytes))) return rc;
-		if ((rc = gd_grow(ctx, ctx->m_srbox, sizeof(GdCandBox) * (size_t)n * slots))) return rc;
-		int64_t *d_sumlen = (int64_t *)ctx->m_srtab.p, *d_lenfirst = d_sumlen + n;
-		int32_t *d_cnt = (int32_t *)(d_lenfirst + n + 1), *d_boxfirst = d_cnt + n;
-		MapSrTotals *d_tot = (MapSrTotals *)(d_boxfirst + n + 1);
-		static const char *fault_env = getenv("GDIET_FAULT_BOX");
-		const MapSrTotals zero = {0, -1};
-		GD_HIP(hipMemcpyAsync(d_tot, &zero, sizeof zero, hipMemcpyHostToDevice, s));
-		hipLaunchKernelGGL(map_sr_box_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, d_roff, (const MapVoteOut *)ctx->m_voteout.p, (const uint32_t *)ix->d_seq_len, R.n_seq,
-		                   O.k, O.a, slots, fault_env ? atoi(fault_env) : -1, (GdCandBox *)ctx->m_srbox.p, d_cnt, d_sumlen, d_tot);
-		// exclusive scans over n + 1 entries (the last input is never read as a value: the scans' last outputs are the totals)
-		size_t b1 = 0, b2 = 0;
-		GD_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, d_cnt, d_boxfirst, n + 1, s));
-		GD_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, d_sumlen, d_lenfirst, n + 1, s));
-		if ((rc = gd_grow(ctx, ctx->m_srscan, std::max(b1, b2) + 64))) return rc;
-		size_t bb = ctx->m_srscan.cap;
-		GD_HIP(hipcub::DeviceScan::ExclusiveSum(ctx->m_srscan.p, bb, d_cnt, d_boxfirst, n + 1, s));
-		bb = ctx->m_srscan.cap;
-		GD_HIP(hipcub::DeviceScan::ExclusiveSum(ctx->m_srscan.p, bb, d_sumlen, d_lenfirst, n + 1, s));
-		// the two totals and the failure count: 24 bytes, the only thing the host waits for before it can size the batch's buffers
-		struct { int32_t nb; int32_t pad; int64_t bases; MapSrTotals t; } h_tot;
-		GD_HIP(hipMemcpyAsync(&h_tot.nb, d_boxfirst + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-		GD_HIP(hipMemcpyAsync(&h_tot.bases, d_lenfirst + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-		GD_HIP(hipMemcpyAsync(&h_tot.t, d_tot, sizeof(MapSrTotals), hipMemcpyDeviceToHost, s));
-		GD_HIP(gd_stream_wait(ctx, s));
-		ctx->stage_s[1] += gd_now() - t0, t0 = gd_now();
-		mark("vote");
-		nb = h_tot.nb;
-		ctx->failed_last = h_tot.t.n_failed, ctx->failed_total += h_tot.t.n_failed;
-		if (h_tot.t.n_failed) {
-			char msg[160];
-			snprintf(msg, sizeof msg, "%lld read(s) of the batch left unmapped: degenerate DP box (candidate window outside the read / contig), last: read %d of the call",
-			         (long long)h_tot.t.n_failed, h_tot.t.last_failed);
-			ctx->warn = msg;
-		}
-		if ((rc = aux_layout())) return rc;
-		if (nb > 0) {
-			if ((rc = gd_grow(ctx, ctx->m_boxes, sizeof(MapBox) * (size_t)nb))) return rc;
-			if ((rc = gd_grow(ctx, ctx->m_srcand, sizeof(GdCandBox) * (size_t)nb + sizeof(int64_t) * ((size_t)nb + 1) + sizeof(int32_t) * (size_t)nb + 256))) return rc;
-			GdCandBox *d_cand = (GdCandBox *)ctx->m_srcand.p;
-			int64_t *d_qoff = (int64_t *)(((uintptr_t)(d_cand + nb) + 63) & ~(uintptr_t)63);
-			int32_t *d_bw = (int32_t *)(d_qoff + nb + 1);
-			MapSrFillOut FO = {(MapBox *)ctx->m_boxes.p, d_cand, d_qoff, d_coff, d_bw, d_ex};
-			hipLaunchKernelGGL(map_sr_fill_kernel, dim3((n + 1 + 63) / 64), dim3(64), 0, s, n, d_roff, (const int32_t *)d_cnt, (const int32_t *)d_boxfirst, (const int64_t *)d_lenfirst,
-			                   (const GdCandBox *)ctx->m_srbox.p, slots, (const uint32_t *)ix->d_seq_len, (const uint64_t *)ix->d_seq_off, R.n_seq, D.sr, FO);
-			// host copies of what the planner and the record stage read
-			if ((rc = gd_host_grow(ctx, ctx->h_cand, sizeof(GdCandBox) * (size_t)nb))) return rc;
-			cflat = (GdCandBox *)ctx->h_cand.p;
-			qoff.resize(nb + 1), coff.resize(nb + 1), bw.resize(nb), ex.resize(nb);
-			GD_HIP(hipMemcpyAsync(cflat, d_cand, sizeof(GdCandBox) * (size_t)nb, hipMemcpyDeviceToHost, s));
-			GD_HIP(hipMemcpyAsync(qoff.data(), d_qoff, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyDeviceToHost, s));
-			GD_HIP(hipMemcpyAsync(coff.data(), d_coff, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyDeviceToHost, s));
-			GD_HIP(hipMemcpyAsync(bw.data(), d_bw, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, s));
-			GD_HIP(hipMemcpyAsync(ex.data(), d_ex, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, s));
-		} else qoff.assign(1, 0), coff.assign(1, 0);
-		GD_HIP(hipMemcpyAsync(ccount.data(), d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-		// the windows can be gathered while the tables travel (same stream: the gather kernel is queued behind the fill kernel)
-		if (nb > 0) {
-			if ((rc = gd_grow(ctx, ctx->m_q, (size_t)h_tot.bases + 64))) return rc;
-			if ((rc = gd_grow(ctx, ctx->m_t, (size_t)h_tot.bases + 64))) return rc;
-			if ((rc = gd_grow(ctx, ctx->m_cig, sizeof(uint32_t) * (2 * (size_t)h_tot.bases + 1)))) return rc;
-			hipLaunchKernelGGL(map_gather_kernel, dim3(nb), dim3(64), 0, s, nb, (const MapBox *)ctx->m_boxes.p, d_reads, (const uint32_t *)ix->d_S,
-			                   (uint8_t *)ctx->m_q.p, (uint8_t *)ctx->m_t.p);
-		}
-		GD_HIP(gd_stream_wait(ctx, s));
-		for (int i = 0; i < n; ++i) box_first[i + 1] = box_first[i] + ccount[i];
-		cfirst = box_first;
-		if (box_first[n] != nb) { ctx->err = "box tables of the device and the host disagree"; return GDIET_E_HIP; }
-		toff = qoff;
-	} else {
-	// only the head of every record can be in use: n_cand + at most AF_max_loc (ShortReads) / vt_nb_loc + 2 (LongReads) candidates;
-	// the host copy is packed to that size (a full-size array would be 680 B per read: 178 MB to allocate and clear per 262 k short reads)
-	const size_t vo_head = offsetof(MapVoteOut, cand) + sizeof(GdVt) * std::min<size_t>(is_sr ? (size_t)O.af_max_loc : (size_t)O.vt_nb_loc + 2, GDM_MAX_VT);
+	gdiet_index *ixm = const_cast<gdiet_index *>(ix);
+	std::lock_guard<std::mutex> lk(ixm->seq_mu);
+	if (ixm->d_seq_len) return GDIET_OK;
+	std::vector<uint32_t> sl(R.n_seq);
+	std::vector<uint64_t> so(R.n_seq);
+	for (uint32_t q = 0; q < R.n_seq; ++q) sl[q] = R.seq[q].len, so[q] = R.seq[q].offset;
+	uint32_t *dl = nullptr;
+	uint64_t *d_o = nullptr;
+	GD_HIP(hipMalloc(&dl, sizeof(uint32_t) * std::max<size_t>(R.n_seq, 1)));
+	GD_HIP(hipMalloc(&d_o, sizeof(uint64_t) * std::max<size_t>(R.n_seq, 1)));
+	GD_HIP(hipMemcpy(dl, sl.data(), sizeof(uint32_t) * R.n_seq, hipMemcpyHostToDevice));
+	GD_HIP(hipMemcpy(d_o, so.data(), sizeof(uint64_t) * R.n_seq, hipMemcpyHostToDevice));
+	ixm->d_seq_off = d_o, ixm->d_seq_len = dl;
+	return GDIET_OK;
+}
+
+// G2 on the device (ShortReads; map_sr_box_kernel / map_sr_fill_kernel): the candidates never visit the host; what comes back are the
+// dense per-box tables the DP planner and the record stage read.  Leaves the windows gathered.
+static int gd_stage_boxes_device(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const gdiet_index *ix = c.ix;
+	const GdMapOpt &O = c.O;
+	GdBoxTables &T = c.T;
+	const int n = c.B.n;
+	const int64_t *d_roff = c.B.d_roff;
+	hipStream_t s = ctx->stream;
+	const uint32_t n_seq = ix->h.ref().n_seq;
+	const int slots = (int)std::min<int64_t>(O.af_max_loc, GDM_MAX_VT);
+	int rc;
+	T.reset(n);
+	if ((rc = gd_index_seq_table(ctx, ix))) return rc;
+	// per-read tables: sumlen[n + 1] | len_first[n + 1] (int64), cnt[n + 1] | box_first[n + 1] (int32), totals.  (The last entry of cnt and
+	// of sumlen is never written: the scans below read it, but no output of an exclusive scan depends on its last input.)
+	const size_t tab_bytes = sizeof(int64_t) * (2 * (size_t)n + 2) + sizeof(int32_t) * (2 * (size_t)n + 2) + sizeof(MapSrTotals) + 64;
+	if ((rc = gd_grow(ctx, ctx->m_srtab, tab_bytes))) return rc;
+	if ((rc = gd_grow(ctx, ctx->m_srbox, sizeof(GdCandBox) * (size_t)n * slots))) return rc;
+	int64_t *d_sumlen = (int64_t *)ctx->m_srtab.p, *d_lenfirst = d_sumlen + n + 1;
+	int32_t *d_cnt = (int32_t *)(d_lenfirst + n + 1), *d_boxfirst = d_cnt + n + 1;
+	MapSrTotals *d_tot = (MapSrTotals *)(d_boxfirst + n + 1);
+	const MapSrTotals zero = {0, -1};
+	GD_HIP(hipMemcpyAsync(d_tot, &zero, sizeof zero, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(map_sr_box_kernel, dim3((n + 63) / 64), dim3(64), 0, s, n, d_roff, (const MapVoteOut *)ctx->m_voteout.p, (const uint32_t *)ix->d_seq_len, n_seq,
+	                   O.k, O.a, slots, gd_fault_box(), (GdCandBox *)ctx->m_srbox.p, d_cnt, d_sumlen, d_tot);
+	// exclusive scans over n + 1 entries, input and output apart: the scans' last outputs are the totals
+	size_t b1 = 0, b2 = 0;
+	GD_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b1, d_cnt, d_boxfirst, n + 1, s));
+	GD_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, d_sumlen, d_lenfirst, n + 1, s));
+	if ((rc = gd_grow(ctx, ctx->m_srscan, std::max(b1, b2) + 64))) return rc;
+	size_t bb = ctx->m_srscan.cap;
+	GD_HIP(hipcub::DeviceScan::ExclusiveSum(ctx->m_srscan.p, bb, d_cnt, d_boxfirst, n + 1, s));
+	bb = ctx->m_srscan.cap;
+	GD_HIP(hipcub::DeviceScan::ExclusiveSum(ctx->m_srscan.p, bb, d_sumlen, d_lenfirst, n + 1, s));
+	// the two totals and the failure count: 24 bytes, the only thing the host waits for before it can size the batch's buffers
+	struct { int32_t nb; int32_t pad; int64_t bases; MapSrTotals t; } h_tot;
+	GD_HIP(hipMemcpyAsync(&h_tot.nb, d_boxfirst + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+	GD_HIP(hipMemcpyAsync(&h_tot.bases, d_lenfirst + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+	GD_HIP(hipMemcpyAsync(&h_tot.t, d_tot, sizeof(MapSrTotals), hipMemcpyDeviceToHost, s));
+	GD_HIP(gd_stream_wait(ctx, s));
+	gd_lap(c, 1);
+	c.mark("vote");
+	const int nb = T.nb = h_tot.nb;
+	gd_note_failed(ctx, h_tot.t.n_failed, h_tot.t.last_failed);
+	if ((rc = gd_aux_layout(c))) return rc;
+	if (nb > 0) {
+		if ((rc = gd_grow(ctx, ctx->m_boxes, sizeof(MapBox) * (size_t)nb))) return rc;
+		if ((rc = gd_grow(ctx, ctx->m_srcand, sizeof(GdCandBox) * (size_t)nb + sizeof(int64_t) * ((size_t)nb + 1) + sizeof(int32_t) * (size_t)nb + 256))) return rc;
+		GdCandBox *d_cand = (GdCandBox *)ctx->m_srcand.p;
+		int64_t *d_qoff = (int64_t *)(((uintptr_t)(d_cand + nb) + 63) & ~(uintptr_t)63);
+		int32_t *d_bw = (int32_t *)(d_qoff + nb + 1);
+		MapSrFillOut FO = {(MapBox *)ctx->m_boxes.p, d_cand, d_qoff, c.d_coff, d_bw, c.d_ex};
+		hipLaunchKernelGGL(map_sr_fill_kernel, dim3((n + 1 + 63) / 64), dim3(64), 0, s, n, d_roff, (const int32_t *)d_cnt, (const int32_t *)d_boxfirst, (const int64_t *)d_lenfirst,
+		                   (const GdCandBox *)ctx->m_srbox.p, slots, (const uint32_t *)ix->d_seq_len, (const uint64_t *)ix->d_seq_off, n_seq, c.D.sr, FO);
+		// host copies of what the planner and the record stage read
+		if ((rc = gd_host_grow(ctx, ctx->h_cand, sizeof(GdCandBox) * (size_t)nb))) return rc;
+		T.cflat = (GdCandBox *)ctx->h_cand.p;
+		T.qoff.resize(nb + 1), T.coff.resize(nb + 1), T.bw.resize(nb), T.ex.resize(nb);
+		GD_HIP(hipMemcpyAsync(T.cflat, d_cand, sizeof(GdCandBox) * (size_t)nb, hipMemcpyDeviceToHost, s));
+		GD_HIP(hipMemcpyAsync(T.qoff.data(), d_qoff, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyDeviceToHost, s));
+		GD_HIP(hipMemcpyAsync(T.coff.data(), c.d_coff, sizeof(int64_t) * ((size_t)nb + 1), hipMemcpyDeviceToHost, s));
+		GD_HIP(hipMemcpyAsync(T.bw.data(), d_bw, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, s));
+		GD_HIP(hipMemcpyAsync(T.ex.data(), c.d_ex, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, s));
+	} else T.qoff.assign(1, 0), T.coff.assign(1, 0);
+	GD_HIP(hipMemcpyAsync(T.ccount.data(), d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+	// the windows can be gathered while the tables travel (same stream: the gather kernel is queued behind the fill kernel)
+	if (nb > 0) {
+		if ((rc = gd_grow(ctx, ctx->m_q, (size_t)h_tot.bases + 64))) return rc;
+		if ((rc = gd_grow(ctx, ctx->m_t, (size_t)h_tot.bases + 64))) return rc;
+		if ((rc = gd_grow(ctx, ctx->m_cig, sizeof(uint32_t) * (2 * (size_t)h_tot.bases + 1)))) return rc;
+		hipLaunchKernelGGL(map_gather_kernel, dim3(nb), dim3(64), 0, s, nb, (const MapBox *)ctx->m_boxes.p, c.B.d_reads, (const uint32_t *)ix->d_S,
+		                   (uint8_t *)ctx->m_q.p, (uint8_t *)ctx->m_t.p);
+	}
+	GD_HIP(gd_stream_wait(ctx, s));
+	for (int i = 0; i < n; ++i) T.box_first[i + 1] = T.box_first[i] + T.ccount[i];
+	T.cfirst = T.box_first;
+	if (T.box_first[n] != nb) { ctx->err = "box tables of the device and the host disagree"; return GDIET_E_HIP; }
+	T.toff = T.qoff;
+	return GDIET_OK;
+}
+
+// G1b / G2 on host threads (map_plan.h): the vote records come to the host, linking + DP boxes, the box tables
+static int gd_stage_boxes_host(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const GdBatchView &B = c.B;
+	GdBoxTables &T = c.T;
+	const int n = B.n;
+	hipStream_t s = ctx->stream;
+	const GdRefView R = c.ix->h.ref();
+	auto run = [&](int m, auto f) { gd_parallel_for(ctx, ctx->lane_threads, m, f); };
+	int rc;
+	T.reset(n);
+	const size_t vo_head = gd_vote_head_bytes(c.O); // the host copy is packed to the head of every record
 	if (ctx->h_vo.size() < vo_head * (size_t)n) ctx->h_vo.resize(vo_head * (size_t)n + (vo_head * (size_t)n >> 2));
 	const uint8_t *vo_raw = ctx->h_vo.data();
 	GD_HIP(hipMemcpy2DAsync(ctx->h_vo.data(), vo_head, ctx->m_voteout.p, sizeof(MapVoteOut), vo_head, (size_t)n, hipMemcpyDeviceToHost, s));
 	GD_HIP(gd_stream_wait(ctx, s));
-	ctx->stage_s[1] += gd_now() - t0, t0 = gd_now();
-	mark("vote");
-	// ---- G1b: linking + DP boxes (host threads) ------------------------------------------------------------------------
+	gd_lap(c, 1);
+	c.mark("vote");
 	// candidates of all reads in one flat array (capacity: what the vote kernel reported; the box stage may drop some).  Per-read
 	// vectors would be allocated by the workers and released by this thread -- a quarter of a million cross-thread frees per
 	// short-read batch, each contending for another thread's malloc arena.
-	for (int i = 0; i < n; ++i) cfirst[i + 1] = cfirst[i] + (int)reinterpret_cast<const MapVoteOut *>(vo_raw + vo_head * (size_t)i)->n_cand;
-	if ((rc = gd_host_grow(ctx, ctx->h_cand, sizeof(GdCandBox) * (size_t)cfirst[n]))) return rc;
-	cflat = (GdCandBox *)ctx->h_cand.p; // entries [cfirst[i], cfirst[i] + ccount[i]) are written below, nothing else is read
-	mark("g:prefix");
-	gd_parallel_for(ctx, ctx->lane_threads, n, [&](int i) {
-		const MapVoteOut &vo_i = *reinterpret_cast<const MapVoteOut *>(vo_raw + vo_head * (size_t)i); // head of the record only
-		const unsigned nc = vo_i.n_cand;
-		if (!nc) return;
-		if (is_sr) { // straight into the flat array: a quarter of a million reads per batch, nothing allocated per read
-			int k = 0;
-			for (unsigned j = 0; j < nc; ++j)
-				if (gd_sr_box_one(vo_i.cand[j], O, R, (uint32_t)(B.roff[i + 1] - B.roff[i]), cflat[(size_t)cfirst[i] + k])) ++k;
-			ccount[i] = k;
-			return;
-		}
-		std::vector<GdCand> C(nc);
-		for (unsigned j = 0; j < nc; ++j) C[j].v = vo_i.cand[j];
-		gd_lr_link_and_boxes(C, O, R, (uint32_t)(B.roff[i + 1] - B.roff[i]));
-		ccount[i] = (int)std::min<size_t>(C.size(), nc);
-		for (int j = 0; j < ccount[i]; ++j) cflat[(size_t)cfirst[i] + j] = gd_cand_box(C[j]);
-	});
-	// A DP box that lies outside its read or is absurdly large (a wrapped coordinate: the reference reads stale heap memory there, its
-	// result is undefined) fails ITS READ -- it comes back unmapped (n_regs = 0) and is counted -- not the batch: a production run
-	// must not be lost to one pathological read.  GDIET_FAULT_BOX=<read index> (fault injection for the tests: no read built so far
-	// produces such a box) marks the boxes of that read of every batch as degenerate.
-	{
-		static const char *fault_env = getenv("GDIET_FAULT_BOX");
-		const int fault = fault_env ? atoi(fault_env) : -1;
-		int64_t n_failed = 0;
-		int last_bad = -1;
-		for (int i = 0; i < n; ++i) {
-			const uint32_t rl = (uint32_t)(B.roff[i + 1] - B.roff[i]);
-			bool bad = i == fault && ccount[i] > 0;
-			for (int j = 0; j < ccount[i] && !bad; ++j) {
-				const GdCandBox &c = cflat[(size_t)cfirst[i] + j];
-				bad = c.qlen == 0 || c.tlen == 0 || c.qlen > rl || c.qseq_off + c.qlen > rl || c.tlen > 8u * rl + 100000u;
-			}
-			if (bad) ccount[i] = 0, ++n_failed, last_bad = i;
-		}
-		ctx->failed_last = n_failed, ctx->failed_total += n_failed;
-		if (n_failed) {
-			char msg[160];
-			snprintf(msg, sizeof msg, "%lld read(s) of the batch left unmapped: degenerate DP box (candidate window outside the read / contig), last: read %d of the call",
-			         (long long)n_failed, last_bad);
-			ctx->warn = msg;
-		}
-	}
-	for (int i = 0; i < n; ++i) box_first[i + 1] = box_first[i] + ccount[i];
-	mark("g:boxes");
-	nb = box_first[n];
-	if ((rc = gd_host_grow(ctx, ctx->h_boxes, sizeof(MapBox) * (size_t)std::max(nb, 1)))) return rc;
-	boxes = (MapBox *)ctx->h_boxes.p;
-	qoff.assign(nb + 1, 0), toff.assign(nb + 1, 0), coff.assign(nb + 1, 0);
-	bw.resize(nb), ex.resize(nb);
-	// window offsets: a running sum over the boxes in batch order; the boxes themselves are filled by the host threads
-	for (int i = 0; i < n; ++i)
-		for (int j = 0; j < ccount[i]; ++j) {
-			const GdCandBox &c = cflat[(size_t)cfirst[i] + j];
-			const int b = box_first[i] + j;
-			qoff[b + 1] = qoff[b] + c.qlen, toff[b + 1] = toff[b] + c.tlen;
-			coff[b + 1] = coff[b] + c.qlen + c.tlen;
-		}
-	mark("g:offsets");
-	gd_parallel_for(ctx, ctx->lane_threads, n, [&](int i) {
-		const uint32_t rl = (uint32_t)(B.roff[i + 1] - B.roff[i]);
-		for (int j = 0; j < ccount[i]; ++j) {
-			const GdCandBox &c = cflat[(size_t)cfirst[i] + j];
-			const int b = box_first[i] + j;
-			MapBox &M = boxes[b];
-			M.read_off = B.roff[i], M.read_len = rl, M.qseq_off = c.qseq_off, M.qlen = c.qlen, M.tlen = c.tlen, M.rev = c.v.str;
-			// a window hanging off a contig (or a wrapped coordinate) reads stale memory in the reference; here the part that
-			// does not exist is zero-filled and absurd sizes are refused
-			uint32_t avail = 0;
-			uint64_t src = 0;
-			if (c.target_id < R.n_seq && c.target_start < R.seq[c.target_id].len) {
-				avail = std::min<uint32_t>(c.tlen, R.seq[c.target_id].len - c.target_start);
-				src = R.seq[c.target_id].offset + c.target_start;
-			}
-			M.t_avail = avail, M.t_src = src;
-			M.q_dst = qoff[b], M.t_dst = toff[b];
-			bw[b] = is_sr ? (int32_t)gd_sr_bw((int)rl, D.sr) : (int32_t)O.bw, ex[b] = c.exact_score; // SR/map.c:624-631,925 ; LR/map.c:1800
-		}
-	});
-	}
-	ctx->stage_s[2] += gd_now() - t0, t0 = gd_now();
-	mark("g:fill");
+	if ((rc = gd_host_grow(ctx, ctx->h_cand, sizeof(GdCandBox) * (size_t)gd_box_slots(T, n, vo_raw, vo_head)))) return rc;
+	T.cflat = (GdCandBox *)ctx->h_cand.p;
+	c.mark("g:prefix");
+	gd_box_candidates(T, n, B.roff, vo_raw, vo_head, c.O, R, run);
+	int last_bad;
+	const int64_t n_failed = gd_box_fail_degenerate(T, n, B.roff, gd_fault_box(), &last_bad);
+	gd_note_failed(ctx, n_failed, last_bad);
+	c.mark("g:boxes");
+	if ((rc = gd_host_grow(ctx, ctx->h_boxes, sizeof(MapBox) * (size_t)std::max(T.nb, 1)))) return rc;
+	gd_box_fill(T, n, B.roff, c.O, c.D.sr, R, (MapBox *)ctx->h_boxes.p, run, c.mark);
+	return GDIET_OK;
+}
+
+// after the host box stage: the tables go to the device and the windows are gathered (the device box stage has left both done)
+static int gd_upload_boxes(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const GdBoxTables &T = c.T;
+	const int nb = T.nb;
+	hipStream_t s = ctx->stream;
+	int rc;
+	if ((rc = gd_grow(ctx, ctx->m_boxes, sizeof(MapBox) * nb))) return rc;
+	if ((rc = gd_grow(ctx, ctx->m_q, (size_t)T.qoff[nb] + 64))) return rc;
+	if ((rc = gd_grow(ctx, ctx->m_t, (size_t)T.toff[nb] + 64))) return rc;
+	if ((rc = gd_aux_layout(c))) return rc;
+	if ((rc = gd_grow(ctx, ctx->m_cig, sizeof(uint32_t) * ((size_t)T.coff[nb] + 1)))) return rc;
+	GD_HIP(hipMemcpyAsync(ctx->m_boxes.p, ctx->h_boxes.p, sizeof(MapBox) * nb, hipMemcpyHostToDevice, s));
+	GD_HIP(hipMemcpyAsync(c.d_coff, T.coff.data(), sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, s));
+	GD_HIP(hipMemcpyAsync(c.d_ex, T.ex.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(map_gather_kernel, dim3(nb), dim3(64), 0, s, nb, (const MapBox *)ctx->m_boxes.p, c.B.d_reads, (const uint32_t *)c.ix->d_S,
+	                   (uint8_t *)ctx->m_q.p, (uint8_t *)ctx->m_t.p);
+	return GDIET_OK;
+}
+
+// host buffers of the DP results
+static int gd_result_tables(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const int nb = c.T.nb;
+	int rc;
 	// scores | CIGAR lengths come back in ONE copy with both ends 256-byte aligned.  (As two copies the second, starting at an address
 	// that is not a multiple of 16, took the runtime's dword copy kernel with 1024-thread workgroups: 16 wavefronts that need four
 	// free slots on every SIMD of one CU, which the DP kernel of the next batch -- five wavefronts per SIMD -- never leaves.  That
 	// 37 KB copy then finished only in the tail of the other batch's DP kernel, 45-60 ms later (kernel trace, round 2): invisible in
 	// the throughput with three batches in flight, but it is the batch's latency.  Pinned host buffers were tried as well and cost 8 %
 	// of the step: the host stages write these tables.)
-	nbp = ((size_t)std::max(nb, 1) + 63) & ~(size_t)63;
-	if ((rc = gd_host_grow(ctx, ctx->h_res, sizeof(int32_t) * 2 * nbp))) return rc;
-	int32_t *h_score = (int32_t *)ctx->h_res.p, *h_ncig = h_score + nbp;
+	c.nbp = ((size_t)std::max(nb, 1) + 63) & ~(size_t)63;
+	if ((rc = gd_host_grow(ctx, ctx->h_res, sizeof(int32_t) * 2 * c.nbp))) return rc;
+	c.h_score = (int32_t *)ctx->h_res.p, c.h_ncig = c.h_score + c.nbp;
 	if ((rc = gd_host_grow(ctx, ctx->h_post, sizeof(GdPostOut) * (size_t)std::max(nb, 1)))) return rc;
-	const GdPostOut *h_post = (const GdPostOut *)ctx->h_post.p;
-	uint32_t *h_cig = nullptr;
-	bool exported = false; // the DP results came to the host with map_post_kernel's own stores
-	std::vector<int64_t> poff(1, 0);
+	c.h_post = (const GdPostOut *)ctx->h_post.p;
+	return GDIET_OK;
+}
+
+// the DP batch over the gathered windows (gd_ksw_batch_dev), P1 on the device behind it, the results to the host
+static int gd_stage_dp(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const GdMapOpt &O = c.O;
+	const GdBoxTables &T = c.T;
+	const int nb = T.nb;
+	const size_t nbp = c.nbp;
+	hipStream_t s = ctx->stream;
+	int rc;
 	// an async lane shares its parent's backtrace arena (two whole-batch arenas do not fit in HBM, and concurrent DP kernels of
 	// smaller batches measured slower): the DP stages take turns
 	std::unique_lock<std::mutex> dp_lock;
-	if (nb > 0) {
-		if (!sr_dev) { // (device-side box stage: the tables are on the device already and the windows gathered)
-			if ((rc = gd_grow(ctx, ctx->m_boxes, sizeof(MapBox) * nb))) return rc;
-			if ((rc = gd_grow(ctx, ctx->m_q, (size_t)qoff[nb] + 64))) return rc;
-			if ((rc = gd_grow(ctx, ctx->m_t, (size_t)toff[nb] + 64))) return rc;
-			if ((rc = aux_layout())) return rc;
-			if ((rc = gd_grow(ctx, ctx->m_cig, sizeof(uint32_t) * ((size_t)coff[nb] + 1)))) return rc;
-			GD_HIP(hipMemcpyAsync(ctx->m_boxes.p, boxes, sizeof(MapBox) * nb, hipMemcpyHostToDevice, s));
-			GD_HIP(hipMemcpyAsync(d_coff, coff.data(), sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, s));
-			GD_HIP(hipMemcpyAsync(d_ex, ex.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, s));
-			hipLaunchKernelGGL(map_gather_kernel, dim3(nb), dim3(64), 0, s, nb, (const MapBox *)ctx->m_boxes.p, d_reads, (const uint32_t *)ix->d_S,
-			                   (uint8_t *)ctx->m_q.p, (uint8_t *)ctx->m_t.p);
-		}
-		gdiet_ksw_score_t ks;
-		ks.match = (int8_t)O.a, ks.mismatch = (int8_t)(O.b < 0 ? O.b : -O.b), ks.sc_ambi = 0, ks.q = (int8_t)O.q, ks.e = (int8_t)O.e, ks.q2 = (int8_t)O.q2, ks.e2 = (int8_t)O.e2;
-		ks.reserved = 0, ks.flag = GDIET_EZ_APPROX_MAX;
-		// In an async lane the DP stage (pre-filter, DP + backtrack kernels) runs on a stream of its own and is ENQUEUED behind the
-		// DP stage of whichever lane used the shared arena last (arena_ev), so that consecutive DP kernels follow each other on the
-		// GPU without a host round trip in between; dp_mu only orders the enqueueing.
-		hipStream_t sd = s;
-		if (ctx->parent) {
-			sd = ctx->stream_dp;
-			GD_HIP(hipEventRecord(ctx->gather_ev, s)); // windows gathered (and everything else queued on s)
-			GD_HIP(hipStreamWaitEvent(sd, ctx->gather_ev, 0));
-			dp_lock = std::unique_lock<std::mutex>(ctx->parent->dp_mu, std::defer_lock); // taken inside, after the planning
-		}
-		rc = gd_ksw_batch_dev(ctx, nb, (const uint8_t *)ctx->m_q.p, (const uint8_t *)ctx->m_t.p, d_ex, &ks, d_score, d_ncig, (uint32_t *)ctx->m_cig.p, d_coff,
-		                      qoff.data(), toff.data(), bw.data(), sd, coff.data(), ex.data(), ctx->parent ? ctx->parent->arena_ev : nullptr,
-		                      ctx->parent ? &dp_lock : nullptr);
-		if (rc) { // kernels of this stage may already be queued in the shared arena: let them finish before the next lane takes its turn
-			(void)hipStreamSynchronize(sd);
-			return rc; // (the lock, if taken, is released by dp_lock's destructor)
-		}
-	mark("d:plan+enqueue");
-		if (ctx->parent) {
-			if (!ctx->own_arena) GD_HIP(hipEventRecord(ctx->parent->arena_ev, sd)); // the backtrack is done by then: the CIGARs sit in this lane's own buffer
-			if (dp_lock.owns_lock()) dp_lock.unlock();
-		}
-		{ // P1 on the device, behind the backtrack of this stage (reads this lane's own windows and CIGAR slots, not the arena)
-			if ((rc = gd_grow(ctx, ctx->m_post, sizeof(GdPostOut) * (size_t)nb))) { (void)hipStreamSynchronize(sd); return rc; }
-			MapPostOpt PO;
-			const int g_ = O.a, bb_ = O.b < 0 ? O.b : -O.b;
-			for (int i = 0; i < 25; ++i) PO.mat[i] = (i / 5 == 4 || i % 5 == 4) ? 0 : (i / 5 == i % 5 ? (int8_t)g_ : (int8_t)bb_);
-			PO.q = (int8_t)O.q, PO.e = (int8_t)O.e, PO.log_gap = !(O.flag & GD_F_SR);
-			// A batch of wide-band alignments (the checkpointed kernels: four wavefronts of 128 registers per SIMD, i.e. no room for anything
-			// else while they run): the device-to-host copies below are kernels of the runtime and would start only when DP wavefronts of
-			// the NEXT batch retire -- ~1 s for 400 KB, and that second is part of the lane's cycle (kernel trace of the ONT path, round 2).
-			// map_post_kernel starts in the gap between the two DP kernels, so it writes the results to page-locked host memory itself.
-			// long alignments: one wavefront per alignment (mm_fix_cigar on lane 0, the walk over the bases by all lanes: 22 -> ~2 ms per HiFi
-			// batch); short reads keep one alignment per thread (hundreds of thousands of 150-base walks).  GDIET_POST_WAVE=0 / 1 forces one.
-			static const char *pw_env = getenv("GDIET_POST_WAVE");
-			const bool post_wave = pw_env ? atoi(pw_env) != 0 : coff[nb] / std::max(nb, 1) >= 2000;
-			const bool xport = (ctx->last_mask & 8) != 0;
-			if (xport) {
-				const size_t need = sizeof(GdPostOut) * (size_t)nb + sizeof(int32_t) * 2 * nbp + 256;
-				if (need > ctx->h_pin.cap) {
-					(void)ctx->h_pin.release();
-					ctx->h_pin.kind = DevBuf::PINNED;
-					if (hipHostMalloc(&ctx->h_pin.p, need + need / 2, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->h_pin.p = nullptr; }
-					else ctx->h_pin.cap = need + need / 2;
-				}
-			}
-			exported = xport && ctx->h_pin.p;
-			// outputs: the page-locked export buffer, else m_post (copied to h_post below, with the scores and CIGAR lengths)
-			GdPostOut *o_post = (GdPostOut *)ctx->m_post.p;
-			int32_t *o_score = nullptr, *o_ncig = nullptr;
-			if (exported) {
-				o_score = (int32_t *)ctx->h_pin.p, o_ncig = o_score + nbp, o_post = (GdPostOut *)(o_ncig + nbp);
-				h_score = o_score, h_ncig = o_ncig, h_post = o_post;
-			}
-			if (post_wave) {
-				hipLaunchKernelGGL(map_fix_cigar_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-				                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, o_post);
-				hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-				                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, PO, o_post, o_score, o_ncig);
-			}
-			else hipLaunchKernelGGL(map_post_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-			                   (const uint8_t *)ctx->m_t.p, (const int64_t *)d_coff, (uint32_t *)ctx->m_cig.p, d_ncig, (const int32_t *)d_score, PO, o_post, o_score, o_ncig);
-		}
-		if (!exported) {
-			GD_HIP(hipMemcpyAsync(ctx->h_post.p, ctx->m_post.p, sizeof(GdPostOut) * (size_t)nb, hipMemcpyDeviceToHost, sd));
-			GD_HIP(hipMemcpyAsync(h_score, d_score, sizeof(int32_t) * 2 * nbp, hipMemcpyDeviceToHost, sd));
-		}
-		GD_HIP(gd_stream_wait(ctx, sd));
-	mark("d:wait");
-		// CIGARs are short compared with their capacity (qlen+tlen): pack them on the device, then one copy
-		for (int b = 0; b < nb; ++b) if (h_ncig[b] > coff[b + 1] - coff[b]) { ctx->err = "CIGAR capacity exceeded"; return GDIET_E_CIGAR_CAP; }
-		poff.assign(nb + 1, 0);
-		for (int b = 0; b < nb; ++b) poff[b + 1] = poff[b] + std::max(h_ncig[b], 0);
-		if ((rc = gd_host_grow(ctx, ctx->h_cig, sizeof(uint32_t) * ((size_t)poff[nb] + 1)))) return rc;
-		h_cig = (uint32_t *)ctx->h_cig.p;
-		if (poff[nb] > 0) {
-			if ((rc = gd_grow(ctx, ctx->m_pack, sizeof(uint32_t) * (size_t)poff[nb] + sizeof(int64_t) * (nb + 1) + 64))) return rc;
-			int64_t *d_poff = (int64_t *)ctx->m_pack.p;
-			uint32_t *d_packed = (uint32_t *)(d_poff + nb + 1);
-			GD_HIP(hipMemcpyAsync(d_poff, poff.data(), sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, s));
-			hipLaunchKernelGGL(map_pack_cigar_kernel, dim3(nb), dim3(64), 0, s, nb, (const uint32_t *)ctx->m_cig.p, (const int64_t *)d_coff, (const int64_t *)d_poff, d_packed);
-			GD_HIP(hipMemcpyAsync(h_cig, d_packed, sizeof(uint32_t) * (size_t)poff[nb], hipMemcpyDeviceToHost, s));
-			GD_HIP(gd_stream_wait(ctx, s));
+	gdiet_ksw_score_t ks;
+	ks.match = (int8_t)O.a, ks.mismatch = (int8_t)(O.b < 0 ? O.b : -O.b), ks.sc_ambi = 0, ks.q = (int8_t)O.q, ks.e = (int8_t)O.e, ks.q2 = (int8_t)O.q2, ks.e2 = (int8_t)O.e2;
+	ks.reserved = 0, ks.flag = GDIET_EZ_APPROX_MAX;
+	// In an async lane the DP stage (pre-filter, DP + backtrack kernels) runs on a stream of its own and is ENQUEUED behind the
+	// DP stage of whichever lane used the shared arena last (arena_ev), so that consecutive DP kernels follow each other on the
+	// GPU without a host round trip in between; dp_mu only orders the enqueueing.
+	hipStream_t sd = s;
+	if (ctx->parent) {
+		sd = ctx->stream_dp;
+		GD_HIP(hipEventRecord(ctx->gather_ev, s)); // windows gathered (and everything else queued on s)
+		GD_HIP(hipStreamWaitEvent(sd, ctx->gather_ev, 0));
+		dp_lock = std::unique_lock<std::mutex>(ctx->parent->dp_mu, std::defer_lock); // taken inside, after the planning
+	}
+	rc = gd_ksw_batch_dev(ctx, nb, (const uint8_t *)ctx->m_q.p, (const uint8_t *)ctx->m_t.p, c.d_ex, &ks, c.d_score, c.d_ncig, (uint32_t *)ctx->m_cig.p, c.d_coff,
+	                      T.qoff.data(), T.toff.data(), T.bw.data(), sd, T.coff.data(), T.ex.data(), ctx->parent ? ctx->parent->arena_ev : nullptr,
+	                      ctx->parent ? &dp_lock : nullptr);
+	if (rc) { // kernels of this stage may already be queued in the shared arena: let them finish before the next lane takes its turn
+		(void)hipStreamSynchronize(sd);
+		return rc; // (the lock, if taken, is released by dp_lock's destructor)
+	}
+	c.mark("d:plan+enqueue");
+	if (ctx->parent) {
+		if (!ctx->own_arena) GD_HIP(hipEventRecord(ctx->parent->arena_ev, sd)); // the backtrack is done by then: the CIGARs sit in this lane's own buffer
+		if (dp_lock.owns_lock()) dp_lock.unlock();
+	}
+	// P1 on the device, behind the backtrack of this stage (reads this lane's own windows and CIGAR slots, not the arena)
+	if ((rc = gd_grow(ctx, ctx->m_post, sizeof(GdPostOut) * (size_t)nb))) { (void)hipStreamSynchronize(sd); return rc; }
+	MapPostOpt PO;
+	const int g_ = O.a, bb_ = O.b < 0 ? O.b : -O.b;
+	for (int i = 0; i < 25; ++i) PO.mat[i] = (i / 5 == 4 || i % 5 == 4) ? 0 : (i / 5 == i % 5 ? (int8_t)g_ : (int8_t)bb_);
+	PO.q = (int8_t)O.q, PO.e = (int8_t)O.e, PO.log_gap = !(O.flag & GD_F_SR);
+	// A batch of wide-band alignments (the checkpointed kernels: four wavefronts of 128 registers per SIMD, i.e. no room for anything
+	// else while they run): the device-to-host copies below are kernels of the runtime and would start only when DP wavefronts of
+	// the NEXT batch retire -- ~1 s for 400 KB, and that second is part of the lane's cycle (kernel trace of the ONT path, round 2).
+	// map_post_kernel starts in the gap between the two DP kernels, so it writes the results to page-locked host memory itself.
+	// long alignments: one wavefront per alignment (mm_fix_cigar on lane 0, the walk over the bases by all lanes: 22 -> ~2 ms per HiFi
+	// batch); short reads keep one alignment per thread (hundreds of thousands of 150-base walks).  GDIET_POST_WAVE=0 / 1 forces one.
+	static const char *pw_env = getenv("GDIET_POST_WAVE");
+	const bool post_wave = pw_env ? atoi(pw_env) != 0 : T.coff[nb] / std::max(nb, 1) >= 2000;
+	const bool xport = (ctx->last_mask & 8) != 0;
+	if (xport) {
+		const size_t need = sizeof(GdPostOut) * (size_t)nb + sizeof(int32_t) * 2 * nbp + 256;
+		if (need > ctx->h_pin.cap) {
+			(void)ctx->h_pin.release();
+			ctx->h_pin.kind = DevBuf::PINNED;
+			if (hipHostMalloc(&ctx->h_pin.p, need + need / 2, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->h_pin.p = nullptr; }
+			else ctx->h_pin.cap = need + need / 2;
 		}
 	}
-	if (dp_lock.owns_lock()) dp_lock.unlock();
-	ctx->stage_s[3] += gd_now() - t0, t0 = gd_now();
-	mark("d:pack");
-	// ---- P1-P3 (host threads) ---------------------------------------------------------------------------------------------
+	const bool exported = xport && ctx->h_pin.p; // the DP results come to the host with map_post_kernel's own stores
+	// outputs: the page-locked export buffer, else m_post (copied to h_post below, with the scores and CIGAR lengths)
+	GdPostOut *o_post = (GdPostOut *)ctx->m_post.p;
+	int32_t *o_score = nullptr, *o_ncig = nullptr;
+	if (exported) {
+		o_score = (int32_t *)ctx->h_pin.p, o_ncig = o_score + nbp, o_post = (GdPostOut *)(o_ncig + nbp);
+		c.h_score = o_score, c.h_ncig = o_ncig, c.h_post = o_post;
+	}
+	if (post_wave) {
+		hipLaunchKernelGGL(map_fix_cigar_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
+		                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, o_post);
+		hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
+		                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
+	}
+	else hipLaunchKernelGGL(map_post_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
+	                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
+	if (!exported) {
+		GD_HIP(hipMemcpyAsync(ctx->h_post.p, ctx->m_post.p, sizeof(GdPostOut) * (size_t)nb, hipMemcpyDeviceToHost, sd));
+		GD_HIP(hipMemcpyAsync(c.h_score, c.d_score, sizeof(int32_t) * 2 * nbp, hipMemcpyDeviceToHost, sd));
+	}
+	GD_HIP(gd_stream_wait(ctx, sd));
+	c.mark("d:wait");
+	return GDIET_OK;
+}
+
+// CIGARs are short compared with their capacity (qlen+tlen): pack them on the device, then one copy
+static int gd_stage_pack(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const GdBoxTables &T = c.T;
+	const int nb = T.nb;
+	std::vector<int64_t> &poff = c.poff;
+	hipStream_t s = ctx->stream;
+	int rc;
+	for (int b = 0; b < nb; ++b) if (c.h_ncig[b] > T.coff[b + 1] - T.coff[b]) { ctx->err = "CIGAR capacity exceeded"; return GDIET_E_CIGAR_CAP; }
+	poff.assign(nb + 1, 0);
+	for (int b = 0; b < nb; ++b) poff[b + 1] = poff[b] + std::max(c.h_ncig[b], 0);
+	if ((rc = gd_host_grow(ctx, ctx->h_cig, sizeof(uint32_t) * ((size_t)poff[nb] + 1)))) return rc;
+	c.h_cig = (uint32_t *)ctx->h_cig.p;
+	if (poff[nb] > 0) {
+		if ((rc = gd_grow(ctx, ctx->m_pack, sizeof(uint32_t) * (size_t)poff[nb] + sizeof(int64_t) * (nb + 1) + 64))) return rc;
+		int64_t *d_poff = (int64_t *)ctx->m_pack.p;
+		uint32_t *d_packed = (uint32_t *)(d_poff + nb + 1);
+		GD_HIP(hipMemcpyAsync(d_poff, poff.data(), sizeof(int64_t) * (nb + 1), hipMemcpyHostToDevice, s));
+		hipLaunchKernelGGL(map_pack_cigar_kernel, dim3(nb), dim3(64), 0, s, nb, (const uint32_t *)ctx->m_cig.p, (const int64_t *)c.d_coff, (const int64_t *)d_poff, d_packed);
+		GD_HIP(hipMemcpyAsync(c.h_cig, d_packed, sizeof(uint32_t) * (size_t)poff[nb], hipMemcpyDeviceToHost, s));
+		GD_HIP(gd_stream_wait(ctx, s));
+	}
+	return GDIET_OK;
+}
+
+// P1-P3 (host threads): the records of every read, in slabs
+static int gd_stage_records(GdMapCall &c)
+{
+	gdiet_ctx *ctx = c.ctx;
+	const GdMapOpt &O = c.O;
+	const GdBatchView &B = c.B;
+	const GdBoxTables &T = c.T;
+	const int n = B.n;
+	const bool is_sr = c.is_sr;
+	const GdRefView R = c.ix->h.ref();
 	static std::atomic<uint64_t> call_counter{0};
 	const uint64_t call_id = ++call_counter; // names the slabs of this call (GdRegSlab)
 	std::atomic<int> no_mem{0};
@@ -900,40 +926,73 @@ static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O
 		GdRegCursor &cursor = gd_reg_cursor();
 		const int i_end = std::min(n, (ch + 1) * post_chunk);
 		for (int i = ch * post_chunk; i < i_end; ++i) {
-			n_regs[i] = 0, regs[i] = nullptr;
-			const size_t nc = (size_t)ccount[i];
+			c.n_regs[i] = 0, c.regs[i] = nullptr;
+			const size_t nc = (size_t)T.ccount[i];
 			if (!nc) continue;
 			// the records grow CIGARs: this thread's copy.  (ShortReads: gd_sr_finish reads the box fields only, which gd_cand_unbox sets all of --
 			// the elements are reused as they are; LongReads: fresh records, concatenate_cigars works inside them)
 			if (is_sr) C.resize(nc);
 			else C.assign(nc, GdCand());
-			for (size_t j = 0; j < nc; ++j) gd_cand_unbox(cflat[(size_t)cfirst[i] + j], C[j]);
+			for (size_t j = 0; j < nc; ++j) gd_cand_unbox(T.cflat[(size_t)T.cfirst[i] + j], C[j]);
 			const uint32_t rl = (uint32_t)(B.roff[i + 1] - B.roff[i]);
 			const uint8_t *enc = B.enc + B.roff[i];
 			// the reverse-complemented read: only where a reverse-strand candidate may be concatenated (P2)
 			bool need_rev = false;
-			for (auto &c : C) need_rev |= c.v.str != 0 && c.next >= 0;
+			for (auto &cd : C) need_rev |= cd.v.str != 0 && cd.next >= 0;
 			if (need_rev) { rev.resize(rl); for (uint32_t j = 0; j < rl; ++j) rev[rl - 1 - j] = enc[j] ^ 3; }
 			dp.resize(nc);
 			for (size_t j = 0; j < nc; ++j) {
-				const int b = box_first[i] + (int)j;
-				dp[j].score = h_score[b], dp[j].n_cigar = h_ncig[b], dp[j].cigar = h_cig + poff[b];
+				const int b = T.box_first[i] + (int)j;
+				dp[j].score = c.h_score[b], dp[j].n_cigar = c.h_ncig[b], dp[j].cigar = c.h_cig + c.poff[b];
 			}
 			out.clear();
-			const GdPostOut *pre = h_post + box_first[i];
+			const GdPostOut *pre = c.h_post + T.box_first[i];
 			if (is_sr) gd_sr_finish(C, dp, O, R, rl, enc, need_rev ? rev.data() : enc, out, pre);
 			else gd_lr_finish(C, dp, O, R, rl, enc, need_rev ? rev.data() : enc, out, nullptr, pre);
 			if (out.empty()) continue;
 			bool head = false;
 			void *at = gd_reg_slab_take(cursor, call_id, gd_regs_bytes(out), head);
 			if (!at) { no_mem.store(1); continue; }
-			gd_regs_fill(out, at, head, &n_regs[i], &regs[i]);
+			gd_regs_fill(out, at, head, &c.n_regs[i], &c.regs[i]);
 		}
 	});
-	if (no_mem.load()) { gdiet_hip_free_regs(n, n_regs, regs); ctx->err = "out of host memory for the records"; return GDIET_E_NOMEM; }
-	ctx->stage_s[4] += gd_now() - t0;
-	mark("post");
-	if (mark.on) fprintf(stderr, "[gdiet stages, ms] lane=%p start=%.2f end=%.2f n=%d%s\n", (void *)ctx, 1e3 * fmod(mark.t0, 1000.0), 1e3 * fmod(gd_now(), 1000.0), n, mark.s.c_str());
+	if (no_mem.load()) { gdiet_hip_free_regs(n, c.n_regs, c.regs); ctx->err = "out of host memory for the records"; return GDIET_E_NOMEM; }
+	return GDIET_OK;
+}
+
+// the whole per-read path for one slice, on ctx's own stream and buffers (ctx is a lane: the parent context or one of its children)
+static int gd_map_range(gdiet_ctx *ctx, const gdiet_index *ix, const GdMapOpt &O, const GdBatchView &B, int32_t *n_regs, gdiet_reg_t **regs, GdSeedExport *sx = nullptr)
+{
+	GdMapCall c = {ctx, ix, O, B, n_regs, regs};
+	(void)hipSetDevice(ctx->device);
+	const int n = B.n;
+	for (int i = 0; i < 6; ++i) ctx->stage_s[i] = 0;
+	if (n == 0) return GDIET_OK;
+	if (!sx) for (int i = 0; i < n; ++i) n_regs[i] = 0, regs[i] = nullptr; // whatever happens below, gdiet_hip_free_regs on these arrays is safe
+	int rc;
+	c.t0 = gd_now();
+	if ((rc = gd_stage_setup(c))) return rc;
+	gd_lap(c, 5);
+	if ((rc = gd_stage_seed(c))) return rc;
+	gd_lap(c, 0);
+	c.mark("seed");
+	if (sx) return gd_seed_export(c, *sx);
+	if ((rc = gd_stage_vote(c))) return rc;
+	if ((rc = c.sr_dev ? gd_stage_boxes_device(c) : gd_stage_boxes_host(c))) return rc; // (both close stage 1 behind the vote kernel, mark "vote")
+	gd_lap(c, 2);
+	c.mark("g:fill");
+	if ((rc = gd_result_tables(c))) return rc;
+	if (c.T.nb > 0) {
+		if (!c.sr_dev && (rc = gd_upload_boxes(c))) return rc; // (device-side box stage: the tables are on the device already and the windows gathered)
+		if ((rc = gd_stage_dp(c))) return rc;
+		if ((rc = gd_stage_pack(c))) return rc;
+	}
+	gd_lap(c, 3);
+	c.mark("d:pack");
+	if ((rc = gd_stage_records(c))) return rc;
+	ctx->stage_s[4] += gd_now() - c.t0;
+	c.mark("post");
+	if (c.mark.on) fprintf(stderr, "[gdiet stages, ms] lane=%p start=%.2f end=%.2f n=%d%s\n", (void *)ctx, 1e3 * fmod(c.mark.t0, 1000.0), 1e3 * fmod(gd_now(), 1000.0), n, c.mark.s.c_str());
 	return GDIET_OK;
 }
 
@@ -1184,6 +1243,7 @@ extern "C" int gdiet_hip_seed_batch(gdiet_ctx *ctx, const gdiet_index *ix, const
 	for (int64_t j = 0; j < seed_off[n]; ++j) {
 		const GdSeed &g = sx.seeds[(size_t)j];
 		sd[j].n = g.n, sd[j].q_pos = g.q_pos;
+		if (at + g.n > occ_off[n] || (uint64_t)g.start + g.n > ix->h.pos.size()) { free(sd), free(oc); ctx->err = "seed tables disagree"; return GDIET_E_HIP; } // (before the copy: oc holds occ_off[n])
 		for (uint32_t t = 0; t < g.n; ++t) oc[at++] = ix->h.pos[(size_t)g.start + t];
 	}
 	if (at != occ_off[n]) { free(sd), free(oc); ctx->err = "seed tables disagree"; return GDIET_E_HIP; }
@@ -1196,13 +1256,7 @@ extern "C" size_t gdiet_hip_sam_record(const gdiet_index *ix, const char *qname,
 {
 	if (!ix) return 0;
 	std::vector<GdReg> v(n_regs > 0 ? n_regs : 0);
-	for (int i = 0; i < n_regs; ++i) {
-		const gdiet_reg_t &r = regs[i];
-		GdReg &g = v[i];
-		g.id = r.id, g.cnt = r.cnt, g.rid = r.rid, g.score = r.score, g.qs = r.qs, g.qe = r.qe, g.rs = r.rs, g.re = r.re, g.parent = r.parent, g.subsc = r.subsc;
-		g.mlen = r.mlen, g.blen = r.blen, g.mapq = r.mapq, g.rev = r.rev, g.sam_pri = r.sam_pri, g.dp_score = r.dp_score, g.dp_max = r.dp_max, g.n_ambi = r.n_ambi;
-		g.has_p = true, g.cigar.assign(r.cigar, r.cigar + r.n_cigar);
-	}
+	for (int i = 0; i < n_regs; ++i) gd_reg_from_c(regs[i], v[i]);
 	std::string s;
 	gd_write_sam(s, ix->h.ref(), qname, seq, qual, l_seq, v, reg_idx, opt_flag);
 	if (buf && cap) { const size_t m = std::min(cap - 1, s.size()); memcpy(buf, s.data(), m); buf[m] = 0; }
@@ -1256,11 +1310,7 @@ static size_t gd_sam_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_rea
 			const int nr = n_regs[i];
 			v.resize(nr > 0 ? nr : 0);
 			for (int j = 0; j < nr; ++j) {
-				const gdiet_reg_t &r = regs[i][j];
-				GdReg &g = v[j];
-				g.id = r.id, g.cnt = r.cnt, g.rid = r.rid, g.score = r.score, g.qs = r.qs, g.qe = r.qe, g.rs = r.rs, g.re = r.re, g.parent = r.parent, g.subsc = r.subsc;
-				g.mlen = r.mlen, g.blen = r.blen, g.mapq = r.mapq, g.rev = r.rev, g.sam_pri = r.sam_pri, g.dp_score = r.dp_score, g.dp_max = r.dp_max, g.n_ambi = r.n_ambi;
-				g.has_p = true, g.cigar.assign(r.cigar, r.cigar + r.n_cigar);
+				gd_reg_from_c(regs[i][j], v[j]);
 			}
 			const char *q = quals ? quals[i] : nullptr;
 			if (nr <= 0) gd_write_sam(s, ix->h.ref(), qnames[i], seqs[i], q, lens[i], v, -1, opt_flag), s += '\n'; // (the writer appends)
@@ -1330,11 +1380,7 @@ extern "C" size_t gdiet_hip_paf_batch(gdiet_ctx *ctx, const gdiet_index *ix, int
 			const int nr = n_regs[i];
 			v.resize(nr > 0 ? nr : 0);
 			for (int j = 0; j < nr; ++j) {
-				const gdiet_reg_t &r = regs[i][j];
-				GdReg &g = v[j];
-				g.id = r.id, g.cnt = r.cnt, g.rid = r.rid, g.score = r.score, g.qs = r.qs, g.qe = r.qe, g.rs = r.rs, g.re = r.re, g.parent = r.parent, g.subsc = r.subsc;
-				g.mlen = r.mlen, g.blen = r.blen, g.mapq = r.mapq, g.rev = r.rev, g.sam_pri = r.sam_pri, g.dp_score = r.dp_score, g.dp_max = r.dp_max, g.n_ambi = r.n_ambi;
-				g.has_p = true, g.cigar.assign(r.cigar, r.cigar + r.n_cigar);
+				gd_reg_from_c(regs[i][j], v[j]);
 			}
 			if (nr <= 0) {
 				if (opt_flag & GD_F_PAF_NO_HIT) gd_write_paf(s, ix->h.ref(), qnames[i], lens[i], v, -1, opt_flag), s += '\n';

@@ -824,3 +824,54 @@ GDM_HD bool gd_sr_box_core(const GdVt &v, int k_, int a_, uint32_t qlen_sum, int
 	b.exact_score = qlen_sum < 300 ? (int32_t)(qlen_sum * (uint32_t)a_) : GD_NEG_INF_SCORE; // :873-908
 	return true;
 }
+
+// ---- per-batch tables shared by the kernels (map_kernels.hip.h) and the host-only planner of a mapping call (map_plan.h) ------------
+struct MapReadScratch { // per-read slices of the batch scratch arena (element offsets)
+	uint64_t mv_off;     // GdMini[mv_cap]
+	uint64_t u64_off;    // uint64[2*mv_cap]
+	uint64_t seed_off;   // GdSeed[mv_cap]
+	uint32_t mv_cap;
+	uint32_t pad;
+};
+
+#define MAP_SORT_CAP 2048      // hashes of one read the seed kernel sorts in LDS: at least (16 KB) ...
+#define MAP_SORT_CAP_MAX 16384 // ... and at most (128 KB: ONT reads of up to ~180 kbp), chosen per batch from its longest read
+
+struct MapVoteOut {
+	uint32_t n_cand, pad;
+	GdVt cand[GDM_MAX_VT];
+};
+
+// one DP box: where its query / target windows come from and where they go in the packed ksw batch buffers
+struct MapBox {
+	int64_t read_off;   // offset of the read in the nt4 read buffer
+	int64_t q_dst, t_dst; // destination offsets in the packed query / target buffers
+	uint64_t t_src;     // absolute base offset in S (contig offset + target_start)
+	uint32_t read_len, qseq_off, qlen, tlen, t_avail; // t_avail: bases that exist (window clipped at the contig end)
+	uint32_t rev;       // query window taken from the reverse-complemented read
+};
+
+// A DP box that lies outside its read (of rl bases) or is absurdly large (a wrapped coordinate: the reference reads stale heap memory
+// there, its result is undefined).  Such a box fails its read, on the device (map_sr_box_kernel) and on the host (map_plan.h) alike.
+GDM_HDI bool gd_box_degenerate(const GdCandBox &c, uint32_t rl)
+{
+	return c.qlen == 0 || c.tlen == 0 || c.qlen > rl || c.qseq_off + c.qlen > rl || c.tlen > 8u * rl + 100000u;
+}
+
+// The MapBox of one candidate of the read at read_off (rl bases).  contig_len / contig_off: where the length of the contig c.target_id
+// and its base offset in S are found; contig_len = nullptr: no such contig.  A window hanging off a contig (or a wrapped coordinate)
+// reads stale memory in the reference; here the part that does not exist is zero-filled (t_avail bases exist) and absurd sizes are
+// refused (gd_box_degenerate).
+GDM_HDI MapBox gd_map_box(const GdCandBox &c, int64_t read_off, uint32_t rl, const uint32_t *contig_len, const uint64_t *contig_off, int64_t q_dst, int64_t t_dst)
+{
+	MapBox M;
+	M.read_off = read_off, M.read_len = rl, M.qseq_off = c.qseq_off, M.qlen = c.qlen, M.tlen = c.tlen, M.rev = c.v.str;
+	uint32_t avail = 0;
+	uint64_t src = 0;
+	if (contig_len && c.target_start < *contig_len) {
+		const uint32_t left = *contig_len - c.target_start;
+		avail = c.tlen < left ? c.tlen : left, src = *contig_off + c.target_start;
+	}
+	M.t_avail = avail, M.t_src = src, M.q_dst = q_dst, M.t_dst = t_dst;
+	return M;
+}

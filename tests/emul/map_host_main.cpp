@@ -287,7 +287,7 @@ int main(int argc, char **argv)
 				else gd_lr_link_and_boxes(C, O, R, (uint32_t)len);
 				if (stats) { // boxes the batch planner of the GPU path refuses (map_pipeline.hip.h: the reference's behaviour is undefined there)
 					bool bad = false;
-					for (unsigned i = 0; i < nc; ++i) bad |= C[i].qlen == 0 || C[i].tlen == 0 || C[i].qlen > (uint32_t)len || C[i].qseq_off + C[i].qlen > (uint32_t)len || C[i].tlen > 8u * (uint32_t)len + 100000u;
+					for (unsigned i = 0; i < nc; ++i) bad |= gd_box_degenerate(gd_cand_box(C[i]), (uint32_t)len);
 					if (bad) { ++st_degenerate; fprintf(stderr, "[stats] degenerate box in read %s\n", qn[ri].c_str()); }
 				}
 				if (trace && !sr_variant) {
