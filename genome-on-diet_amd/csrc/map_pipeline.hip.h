@@ -205,6 +205,10 @@ extern "C" int gdiet_hip_set_host_threads(gdiet_ctx *ctx, int n)
 	return GDIET_OK;
 }
 
+// batches whose seed stage overflowed its first scratch layout and ran again with the hard bound (process-wide: lanes are contexts of their own)
+static std::atomic<int64_t> gd_scratch_retries{0};
+extern "C" int64_t gdiet_hip_map_scratch_retries(void) { return gd_scratch_retries.load(); }
+
 extern "C" int gdiet_hip_map_stage_seconds(const gdiet_ctx *ctx, double out[6])
 {
 	if (!ctx || !out) return GDIET_E_PARAM;
@@ -430,7 +434,7 @@ static int gd_scratch_grow(GdMapCall &c, bool full)
 {
 	gdiet_ctx *ctx = c.ctx;
 	const int n = c.B.n;
-	const uint64_t tot = gd_scratch_layout(n, c.B.roff, c.O.w, full, c.sc.data());
+	const uint64_t tot = gd_scratch_layout(n, c.B.roff, c.O.w, c.O.pat, c.O.max_seeds, full, c.sc.data());
 	int rc;
 	if ((rc = gd_grow(ctx, ctx->m_sc, sizeof(MapReadScratch) * n))) return rc;
 	if ((rc = gd_grow(ctx, ctx->m_mv, sizeof(GdMini) * tot))) return rc;
@@ -519,7 +523,8 @@ static int gd_stage_seed(GdMapCall &c)
 		bool overflow = false;
 		for (int i = 0; i < n; ++i) overflow |= so[i].n_seeds < 0;
 		if (!overflow) break;
-		if (attempt == 1) { ctx->err = "minimizer scratch overflow even with one entry per base"; return GDIET_E_NOMEM; }
+		if (attempt == 1) { ctx->err = "minimizer scratch overflow even with the hard bound"; return GDIET_E_NOMEM; }
+		++gd_scratch_retries;
 		if ((rc = gd_scratch_grow(c, true))) return rc;
 	}
 	return GDIET_OK;

@@ -60,15 +60,28 @@ static inline void gd_seed_classes(const GdPattern &pat, int w, int n, const int
 }
 
 // ---- scratch layout ----------------------------------------------------------------------------------------------------------------
+// mm_sketch2 keeps the minimizers of all W pattern phases back to back (LR/sketch.c:2185-2223): a phase has at most one per sparsified
+// base, (len / W + 1) * ones; with -i < 1 phase 0 sees only the first max_seeds * len bases and the later phases stop at its count, with
+// -i >= 1 every phase stops at (uint32_t)max_seeds.  For "10" and -i 0.2 that is a fifth of the read; a long pattern with many ones and
+// a small window passes one entry per base (40 ones, w = 1, -i 0.2: eight per base).
+static inline uint64_t gd_sketch2_bound(const GdPattern &pat, float max_seeds, uint32_t len)
+{
+	const uint64_t per_full = ((uint64_t)len / (uint32_t)pat.W + 1) * (uint32_t)pat.ones;
+	const uint64_t per = max_seeds < 1 ? ((uint64_t)(uint32_t)((float)max_seeds * len) / (uint32_t)pat.W + 1) * (uint32_t)pat.ones : (uint64_t)(uint32_t)max_seeds;
+	return (uint64_t)pat.W * std::min(per, per_full);
+}
+
 // minimizer lists: len/3 + 512 entries per read cover every density the presets produce; a read that overflows its list
-// (tiny windows, homopolymer reads) makes the whole batch retry once with the hard bound (full).  Returns the total of the capacities.
-static inline uint64_t gd_scratch_layout(int n, const int64_t *roff, int w, bool full, MapReadScratch *sc)
+// (tiny windows, homopolymer reads, long patterns) makes the whole batch retry once with the hard bound (full).  Returns the total of the capacities.
+static inline uint64_t gd_scratch_layout(int n, const int64_t *roff, int w, const GdPattern &pat, float max_seeds, bool full, MapReadScratch *sc)
 {
 	uint64_t tot = 0;
 	for (int i = 0; i < n; ++i) {
 		const uint32_t len = (uint32_t)(roff[i + 1] - roff[i]);
-		// hard bound: one minimizer per base, plus the per-lane staging lists of the wavefront sketch (64 lists of ceil(len/64) + w + 2)
-		sc[i].mv_cap = full ? len + 64 * (uint32_t)(w + 4) : len / 3 + 512, sc[i].mv_off = tot, sc[i].u64_off = 2 * tot, sc[i].seed_off = tot, sc[i].pad = 0;
+		// hard bound: one minimizer per base (mm_sketch3) or the list of mm_sketch2, whichever is longer, plus the per-lane staging lists of
+		// the wavefront sketch (64 lists of ceil(len/64) + w + 2)
+		const uint32_t hard = (uint32_t)std::max<uint64_t>(len, gd_sketch2_bound(pat, max_seeds, len));
+		sc[i].mv_cap = full ? hard + 64 * (uint32_t)(w + 4) : len / 3 + 512, sc[i].mv_off = tot, sc[i].u64_off = 2 * tot, sc[i].seed_off = tot, sc[i].pad = 0;
 		tot += sc[i].mv_cap;
 	}
 	return tot;

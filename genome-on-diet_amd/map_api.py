@@ -84,6 +84,8 @@ def _bind(lib):
     lib.gdiet_hip_batch_destroy.argtypes = [vp, vp]
     lib.gdiet_hip_batch_destroy.restype = None
     lib.gdiet_hip_map_stage_seconds.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.gdiet_hip_map_scratch_retries.argtypes = []
+    lib.gdiet_hip_map_scratch_retries.restype = C.c_int64
     lib.gdiet_hip_set_host_threads.argtypes = [vp, C.c_int]
     lib.gdiet_hip_set_map_lanes.argtypes = [vp, C.c_int]
     lib.gdiet_hip_sam_record.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(Reg), C.c_int32, C.c_int32,
@@ -364,6 +366,10 @@ class Mapper:
 
     def free_batch(self, batch):
         self.lib.gdiet_hip_batch_destroy(self.ctx._h, batch[0])
+
+    def scratch_retries(self):
+        """gdiet_hip_map_scratch_retries: batches of this process whose seeding stage ran twice (first scratch estimate too small)"""
+        return int(self.lib.gdiet_hip_map_scratch_retries())
 
     def stage_seconds(self):
         out = (C.c_double * 6)()

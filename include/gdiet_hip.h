@@ -204,7 +204,10 @@ typedef struct gdiet_index gdiet_index;
  * as mm_idx_gen of GDiet_avx: LR/index.c:306-412, LR/sketch.c:156/1577) and upload it.  pattern/pattern_len = -Z/-W.
  * Limits, refused with GDIET_E_PARAM: 1 <= k <= 28 as in the reference (LR/main.c), and 1 <= w <= 64 -- the reference accepts
  * w < 256; the winnowing windows of the sketch kernels live in registers / LDS sized for 64 (every preset uses w <= 19).  For
- * w in {2, 3, 5, 6} the reference's own scalar and AVX-512 sketches disagree; this library follows the scalar one. */
+ * every w from 2 to 7 the reference's own scalar (GDiet) and AVX-512 (GDiet_avx) sketches disagree; at w = 1 and w >= 8 they agree.
+ * This library follows the scalar one: its pattern phases and seed hits equal GDiet's at w = 1 .. 12 on the reads DESIGN.md names
+ * ("Known divergence"), and two rows of tests/golden/opts/grid.json written by scalar GDiet at w = 4 pin that
+ * (tests/test_map_host.py on the CPU, tests/test_option_grid_gpu.py on the GPU). */
 int gdiet_hip_index_build(gdiet_ctx *ctx, gdiet_index **idx, int n_seq, const char *const *names,
                           const char *const *seqs, const uint32_t *lens, int k, int w, const char *pattern,
                           int pattern_len, int n_threads);
@@ -331,6 +334,9 @@ int gdiet_hip_map_wait(gdiet_ctx *ctx, gdiet_map_ticket *ticket);
 /* seconds spent in the stages of the most recent map call: [0] seed kernel, [1] vote kernel, [2] host geometry,
  * [3] gather + DP + backtrack kernels, [4] host post-processing, [5] transfers/other */
 int gdiet_hip_map_stage_seconds(const gdiet_ctx *ctx, double out[6]);
+/* How many batches of this process had to run their seeding stage a second time because a read produced more minimizers than the first
+ * per-read scratch estimate holds (tiny windows, dense or long patterns).  The retry is exact; the count is for tests and tuning. */
+int64_t gdiet_hip_map_scratch_retries(void);
 /* software-pipeline depth of gdiet_hip_map_uploaded / gdiet_hip_map_batch: the batch is cut into slices that run the whole
  * chain on `n` independent lanes (stream + workspace + host threads each), overlapping the latency-bound stages of one slice
  * with the DP kernel of the others.  1 (default) = no pipelining.  Results do not depend on it. */

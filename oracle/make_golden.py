@@ -18,8 +18,9 @@ Repeat-rich sets (tests/golden/rep/, kinds *_rep): reference and reads come from
 branches they exist for (the product's host emulator, --stats) are printed next to the file names.
 Read sets: hifi_sv.fq / ont_sv.fq come from tools/synth.py (--kind hifi_sv / ont_sv; seeds below); the older read sets
 were made by tools/synth.py / tools/synth_sr_var.py and hand-written edge.fq files and are only read here.
-Nothing of the product is involved in what is written: tests never write into tests/golden, this script is the only writer (the
---stats counts are printed, not stored)."""
+Nothing of the product is involved in what is written: tests never write into tests/golden, this script and its sibling
+oracle/make_grid_golden.py (the option grid under tests/golden/opts/, same style) are the only writers (the --stats counts are printed,
+not stored)."""
 import argparse
 import gzip
 import json

@@ -4,7 +4,8 @@
 // (oracle/_ref/gdiet_lr_avx) and against the committed golden SAM.  This is how the seeding/voting/geometry/
 // post-processing code is validated in a container without a GPU; the GPU path replaces only the executors.
 //
-//   map_host_main [-x map-hifi|map-ont] [-k K] [-w W] [-Z pat] [-W n] [-i f] [-r bw] [-s min_dp] [-N n] [--vt_dis=..] ... ref.fa reads.fq
+//   map_host_main [-x map-hifi|map-ont|sr] [-k K] [-w W] [-Z pat] [-W n] [-i f] [-r bw] [-s min_dp] [-N n] [--vt_dis=..] [--for-only|--rev-only]
+//                 [-A a] [-B b] [-O q[,q2]] [-E e[,e2]] ... ref.fa reads.fq
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -136,6 +137,18 @@ int main(int argc, char **argv)
 			}
 			else if (a == "-s") { v = argv[++i]; if (pass) O.min_dp_max = atoi(v); }
 			else if (a == "-N") { v = argv[++i]; if (pass) O.best_n = atoi(v); }
+			else if (a == "--for-only") { if (pass) O.flag |= GDM_F_FOR_ONLY; } // LR/main.c:326-329
+			else if (a == "--rev-only") { if (pass) O.flag |= GDM_F_REV_ONLY; }
+			else if (a == "-A") { v = argv[++i]; if (pass) O.a = atoi(v); }       // LR/main.c:264-267
+			else if (a == "-B") { v = argv[++i]; if (pass) O.b = atoi(v); }
+			else if (a == "-O") { // LR/main.c:474-476: -O INT[,INT]
+				v = argv[++i];
+				if (pass) { char *e; O.q = O.q2 = (int)strtol(v, &e, 10); if (*e == ',') O.q2 = (int)strtol(e + 1, &e, 10); }
+			}
+			else if (a == "-E") { // LR/main.c:477-479: -E INT[,INT]
+				v = argv[++i];
+				if (pass) { char *e; O.e = O.e2 = (int)strtol(v, &e, 10); if (*e == ',') O.e2 = (int)strtol(e + 1, &e, 10); }
+			}
 			else if (a.compare(0, 2, "-F") == 0) { if (a.size() == 2) ++i; }
 			else if ((v = val("vt_dis"))) { if (pass) O.vt_dis = (uint32_t)strtoul(v, 0, 10); }
 			else if ((v = val("vt_nb_loc"))) { if (pass) O.vt_nb_loc = (uint32_t)strtoul(v, 0, 10); }
@@ -189,7 +202,7 @@ int main(int argc, char **argv)
 	// reads are independent: a few worker threads, results printed in input order (the oracle's scalar DP is the slow part)
 	std::vector<std::string> sam_of(qs.size()), trace_of(qs.size());
 	// --stats: reads on which each high-occurrence branch of the seeding stage fires
-	std::atomic<long> st_mzflt{0}, st_mzflt_dropped{0}, st_high{0}, st_over_max{0}, st_heap_replace{0}, st_big_strand{0}, st_max_hits{0}, st_flt_rescued{0}, st_degenerate{0};
+	std::atomic<long> st_mzflt{0}, st_mzflt_dropped{0}, st_high{0}, st_over_max{0}, st_heap_replace{0}, st_big_strand{0}, st_max_hits{0}, st_flt_rescued{0}, st_degenerate{0}, st_over_scratch{0};
 	auto map_one = [&](size_t ri) {
 		std::string out;
 		char *tbuf = nullptr;
@@ -202,11 +215,11 @@ int main(int argc, char **argv)
 			std::vector<uint8_t> enc(len), rev(len);
 			for (int j = 0; j < len; ++j) enc[j] = gd_nt4((unsigned char)seq[j]);
 			for (int j = 0; j < len; ++j) rev[len - 1 - j] = enc[j] ^ 3; // N (4) becomes 7 exactly as qs_rev does (LR/map.c:1634,:1641)
-			const unsigned maxm = (unsigned)len + 64;
+			unsigned maxm = (unsigned)len + 64;
 			std::vector<GdMini> mv(maxm);
 			std::vector<uint32_t> shift_n(O.pat.W);
-			unsigned tot = gd_sketch2(enc.data(), len, O.w, O.k, O.pat, O.max_seeds, mv.data(), maxm, shift_n.data());
-			(void)tot;
+			// mm_sketch2 keeps the seeds of all W phases: with a long pattern and a small window more than one per base (the reference's vector grows)
+			while (gd_sketch2(enc.data(), len, O.w, O.k, O.pat, O.max_seeds, mv.data(), maxm, shift_n.data()) == ~0u) maxm *= 2, mv.resize(maxm);
 			const int shift = (int)gd_get_shift(V, mv.data(), shift_n.data(), O.pat.W);
 			if (trace) fprintf(terr, "QR\t%s\nFinal shift: %d\n", qn[ri].c_str(), shift);
 			unsigned n_mv = 0;
@@ -217,6 +230,7 @@ int main(int argc, char **argv)
 			if (O.q_occ_frac > 0.0f) n_mv = gd_mz_flt(mv.data(), n_mv, O.mid_occ, O.q_occ_frac, scratch.data());
 			if (stats) {
 				if (n_mv < n_mv0) ++st_mzflt, st_mzflt_dropped += n_mv0 - n_mv;
+				if (n_mv0 > (unsigned)len / 3 + 512) ++st_over_scratch; // more minimizers than the GPU path's first per-read estimate (map_plan.h gd_scratch_layout): the batch retries
 				// the seeds present in the index, in sketch order: streaks of n > mid_occ (LR/seed.c:66-106)
 				std::vector<std::pair<uint32_t, uint32_t>> pr; // (n, q_pos >> 1)
 				for (unsigned i = 0; i < n_mv; ++i) {
@@ -361,8 +375,8 @@ int main(int argc, char **argv)
 			}
 		fprintf(stderr, "[stats] index: keys=%llu multi=%llu keys>mid_occ(%d)=%llu keys>max_max_occ(%d)=%llu max_count=%llu\n", (unsigned long long)I.n_keys, (unsigned long long)multi,
 		        O.mid_occ, (unsigned long long)over_mid, O.max_max_occ, (unsigned long long)over_max, (unsigned long long)max_cnt);
-		fprintf(stderr, "[stats] reads=%zu mz_flt_drops=%ld (minimizers dropped %ld) high_occ_streak=%ld rescue=%ld heap_replace=%ld over_max_max_occ=%ld strand>4096hits=%ld max_strand_hits=%ld degenerate_box_reads=%ld\n",
-		        qs.size(), st_mzflt.load(), st_mzflt_dropped.load(), st_high.load(), st_flt_rescued.load(), st_heap_replace.load(), st_over_max.load(), st_big_strand.load(), st_max_hits.load(), st_degenerate.load());
+		fprintf(stderr, "[stats] reads=%zu mz_flt_drops=%ld (minimizers dropped %ld) high_occ_streak=%ld rescue=%ld heap_replace=%ld over_max_max_occ=%ld strand>4096hits=%ld max_strand_hits=%ld degenerate_box_reads=%ld over_first_scratch=%ld\n",
+		        qs.size(), st_mzflt.load(), st_mzflt_dropped.load(), st_high.load(), st_flt_rescued.load(), st_heap_replace.load(), st_over_max.load(), st_big_strand.load(), st_max_hits.load(), st_degenerate.load(), st_over_scratch.load());
 	}
 	for (size_t ri = 0; ri < qs.size(); ++ri) {
 		fputs(trace_of[ri].c_str(), stderr);

@@ -106,20 +106,35 @@ static void check_classes(const char *name, const std::vector<int> &lens, int w,
 }
 
 // ---- scratch layout ---------------------------------------------------------------------------------------------------------------
-static void check_layout(const char *name, const std::vector<int> &lens, int w)
+// Z / max_seeds: -Z / -i (the hard bound must also hold mm_sketch2's list of all pattern phases)
+static void check_layout(const char *name, const std::vector<int> &lens, int w, const char *Z = "10", float max_seeds = 0.2f)
 {
+	GdPattern P;
+	REQUIRE(gd_pattern_init(P, Z, (int)strlen(Z)), "pattern %s", Z);
 	const int n = (int)lens.size();
 	const std::vector<int64_t> roff = offsets_of(lens);
 	uint64_t tots[2];
 	for (int full = 0; full < 2; ++full) {
 		std::vector<MapReadScratch> sc(n);
 		memset(sc.data(), 0xff, sizeof(MapReadScratch) * n);
-		const uint64_t tot = gd_scratch_layout(n, roff.data(), w, full != 0, sc.data());
+		const uint64_t tot = gd_scratch_layout(n, roff.data(), w, P, max_seeds, full != 0, sc.data());
 		uint64_t sum = 0;
 		for (int i = 0; i < n; ++i) {
 			REQUIRE(sc[i].mv_off == sum && sc[i].seed_off == sum && sc[i].u64_off == 2 * sum && sc[i].pad == 0, "full=%d read %d: offsets %llu %llu %llu, running sum %llu", full, i,
 			        (unsigned long long)sc[i].mv_off, (unsigned long long)sc[i].seed_off, (unsigned long long)sc[i].u64_off, (unsigned long long)sum);
-			REQUIRE(sc[i].mv_cap == (full ? (uint32_t)lens[i] + 64u * (uint32_t)(w + 4) : (uint32_t)lens[i] / 3 + 512), "full=%d read %d of %d bases: capacity %u", full, i, lens[i], sc[i].mv_cap);
+			// what mm_sketch2 can emit, counted phase by phase: a phase has at most its sparsified bases, phase 0 those of the cropped read, later phases phase 0's count
+			uint64_t s2 = 0, cap0 = 0;
+			for (int sh = 0; sh < P.W; ++sh) {
+				const uint64_t all = gd_diet_len(P, (unsigned)lens[i], (unsigned)sh);
+				uint64_t m = max_seeds < 1 ? (sh == 0 ? gd_diet_len(P, (unsigned)(max_seeds * lens[i]), 0) : std::min(all, cap0)) : std::min<uint64_t>(all, (uint32_t)max_seeds);
+				if (sh == 0) cap0 = m;
+				s2 += m;
+			}
+			const uint32_t hard = (uint32_t)std::max<uint64_t>((uint64_t)lens[i], gd_sketch2_bound(P, max_seeds, (uint32_t)lens[i]));
+			REQUIRE(gd_sketch2_bound(P, max_seeds, (uint32_t)lens[i]) >= s2, "read %d of %d bases: mm_sketch2 can emit %llu minimizers, bound %llu", i, lens[i], (unsigned long long)s2,
+			        (unsigned long long)gd_sketch2_bound(P, max_seeds, (uint32_t)lens[i]));
+			REQUIRE(sc[i].mv_cap == (full ? hard + 64u * (uint32_t)(w + 4) : (uint32_t)lens[i] / 3 + 512), "full=%d read %d of %d bases: capacity %u", full, i, lens[i], sc[i].mv_cap);
+			if (!strcmp(Z, "10") && max_seeds < 1) REQUIRE(hard == (uint32_t)lens[i], "read %d: the presets' hard bound is one entry per base, got %u", i, hard);
 			sum += sc[i].mv_cap;
 		}
 		REQUIRE(tot == sum, "full=%d: total %llu, sum %llu", full, (unsigned long long)tot, (unsigned long long)sum);
@@ -395,6 +410,11 @@ int main()
 	check_classes("classes_two_reads", std::vector<int>{150000, 3000}, 10, P);
 	check_layout("layout_ont", ont_lengths(3000), 10);
 	check_layout("layout_sr", uniform_lengths(5000, 76, 151), 11);
+	// patterns of the option grid whose mm_sketch2 list is longer than the read (tests/golden/opts/grid.json)
+	check_layout("layout_40ones_w10", ont_lengths(300), 10, "11110111101111011110111101111011110111101111011110", 0.2f);
+	check_layout("layout_W36_w1", ont_lengths(300), 1, "100000001000100000001000100000001000", 0.2f);
+	check_layout("layout_40ones_w1_i64", ont_lengths(300), 1, "11110111101111011110111101111011110111101111011110", 64.0f);
+	check_layout("layout_1_w1", ont_lengths(100), 1, "1", 0.5f);
 	check_votes("votes_sr", true, 6000);
 	check_votes("votes_lr", false, 1500);
 	check_seeded_tables("tables_sr", true);

@@ -1,6 +1,7 @@
 // CPU check of the exact-slicing property the wave-parallel seed kernel relies on: the concatenation of 64 (or any number
 // of) gd_sketch_slice() outputs equals the sequential gd_sketch_core() output, including reads with Ns, tandem repeats and
 // low-complexity runs (where the "identical k-mer" emission rules fire).
+//   sketch_slice_test [seed [iters [k w pattern]]]   -- k / w / pattern given: every iteration at that setting (tests/golden/opts/grid.json)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,11 +19,12 @@ int main(int argc, char **argv)
 	const int iters = argc > 2 ? atoi(argv[2]) : 300;
 	int bad = 0;
 	for (int it = 0; it < iters; ++it) {
-		const int k = it % 3 == 0 ? 15 : it % 3 == 1 ? 19 : 21, w = it % 3 == 0 ? 10 : it % 3 == 1 ? 19 : 11;
+		const bool fixed = argc > 5;
+		const int k = fixed ? atoi(argv[3]) : it % 3 == 0 ? 15 : it % 3 == 1 ? 19 : 21, w = fixed ? atoi(argv[4]) : it % 3 == 0 ? 10 : it % 3 == 1 ? 19 : 11;
 		GdPattern P;
 		const char *pats[] = {"10", "110", "1", "1110", "100"};
-		const char *pz = pats[it % 5];
-		gd_pattern_init(P, pz, (int)strlen(pz));
+		const char *pz = fixed ? argv[5] : pats[it % 5];
+		if (!gd_pattern_init(P, pz, (int)strlen(pz)) || k < 1 || k > 28 || w < 1 || w > GDM_MAX_W) { fprintf(stderr, "bad k / w / pattern\n"); return 2; }
 		const unsigned len = 100 + g() % 20000;
 		std::vector<uint8_t> s(len + 8);
 		for (auto &c : s) c = g() & 3;

@@ -2,11 +2,13 @@
 tools/synth_sr_var.py, golden SAM by the reference binaries oracle/_ref/gdiet_{lr,sr}_avx with the command in *.cmd)"""
 import gzip
 import hashlib
+import json
 import os
 
 LR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lr")
 SR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sr")
 REP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rep")
+OPTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "opts")
 # kind -> (directory, read set / golden stem, Mapper preset)
 # "hifi_w1": the first 8 reads of hifi.fq with -k 15 -w 1 (every sparsified base is a minimizer: the per-read scratch of the
 # seeding kernel overflows its first estimate and the batch is retried with the hard bound)
@@ -128,3 +130,157 @@ def cmd_of(kind):
     d, stem, _ = SETS[kind]
     name = {"hifi_edge": "hifi", "ont_edge": "ont", "sr_edge": "sr"}.get(kind, stem)
     return open(os.path.join(d, name + ".cmd")).read().split()
+
+
+# ---- the option grid (tests/golden/opts/grid.json): the mapping path away from the README command lines -----------------------------
+# A row = a kind of SETS above (its reference, read file, .cmd and Mapper preset / OVERRIDES), n_reads reads of that file from
+# first_read on, command-line options appended to the .cmd ("extra") and the same options as Mapper overrides.  The three
+# reverse-strand reads over the reference's N run (hifi_27 / hifi_sv_61 / ont_sv_3) are left out: their ms:i tag is an out-of-bounds
+# read in the reference (test_map_host.py::_norm_ms) and may change from run to run.
+# "build": which of the reference's two builds printed the row's goldens ("avx" = GDiet_avx; "scalar" = GDiet, only at window sizes
+# where the two disagree: DESIGN.md).
+# "min_mapped": the share of the reads the reference itself must map (a row must not pass on unmapped reads alone).
+# "sensitive": the option groups of "extra"; the reference prints something else when any one of them is left out (asserted by the
+# writer, and by test_map_host.py with the host path), so no option of a row rides along without effect.
+# "tags" select rows: "kw" (pattern / k / w rows: both seed executors, host- and device-built index), "boxes", "post", "mmi" (index
+# file digest in opts/mmi.sha256.json), "strand" (--for-only / --rev-only: mapped and unmapped reads), "mz_flt" (the query-side
+# minimizer filter must fire), "retry" (more minimizers per read than the GPU path's first scratch estimate), "sv" (reads with a
+# structural difference: second voting round, links), "vote_cap" / "vote_min" (reads of the repeat-rich reference with more vote
+# candidates than any preset keeps / than vt_nb_loc = 1 keeps).
+# oracle/make_grid_golden.py writes, per row, <name>.golden.sam.gz (SEQ and QUAL printed as "*": echoes of the input, pinned by the
+# full goldens of SETS) and <name>.trace.gz (the --print-seeds trace reduced as for TRACED kinds, SD lines always digested).
+PRESET_PATTERN = {"hifi": (19, 19), "ont": (15, 10), "sr": (21, 11)}  # (k, w) of the .cmd files a row builds on
+
+
+def grid_rows(tag=None):
+    rows = json.load(open(os.path.join(OPTS, "grid.json")))["rows"]
+    return [r for r in rows if tag is None or tag in r["tags"]]
+
+
+def grid_ids(tag=None):
+    return [r["name"] for r in grid_rows(tag)]
+
+
+def grid_row(name):
+    return next(r for r in grid_rows() if r["name"] == name)
+
+
+def grid_reads(row):
+    return reads_of(row["kind"])[row["first_read"]:row["first_read"] + row["n_reads"]]
+
+
+def grid_cmd(row, without=None):
+    """the row's command line; without: one of the row's option groups (row["sensitive"]) left out"""
+    extra = row["extra"]
+    if without is not None:
+        assert without in row["sensitive"] and extra.count(without) == 1
+        extra = extra.replace(without, "")
+    return cmd_of(row["kind"]) + extra.split()
+
+
+def grid_mapper_args(row):
+    """(directory of ref.fa.gz, Mapper preset, Mapper overrides) of a row"""
+    d, _, preset = SETS[row["kind"]]
+    ov = dict(OVERRIDES.get(row["kind"], {}))
+    ov.update(row["overrides"])
+    return d, preset, ov
+
+
+def star_seq_qual(line):
+    """a SAM line with SEQ and QUAL replaced by "*" (the form of the grid's goldens)"""
+    f = line.split("\t")
+    if len(f) > 10:
+        f[9] = f[10] = "*"
+    return "\t".join(f)
+
+
+def grid_golden_sam(row):
+    return [l.rstrip("\n") for l in gzip.open(os.path.join(OPTS, row["name"] + ".golden.sam.gz"), "rt")]
+
+
+def grid_trace(row):
+    return [l.rstrip("\n") for l in gzip.open(os.path.join(OPTS, row["name"] + ".trace.gz"), "rt")]
+
+
+def mapped_share(sam_lines):
+    """(reads with at least one mapped record, reads) of a SAM body"""
+    names, mapped = set(), set()
+    for l in sam_lines:
+        f = l.split("\t")
+        names.add(f[0])
+        if f[2] != "*":
+            mapped.add(f[0])
+    return len(mapped), len(names)
+
+
+# ---- B4: the output of gdiet_hip_seed_batch against a --print-seeds trace ---------------------------------------------------------
+def seed_trace_per_read(lines):
+    """per read of a trace: its "Final shift" line, its "RS" line and its SD / SDX lines, sorted"""
+    out, cur = [], None
+    for l in lines:
+        if l.startswith("Final shift"):
+            cur = {"shift": l, "RS": None, "SD": []}
+            out.append(cur)
+        elif cur is not None and l.startswith("RS "):
+            cur["RS"] = l
+        elif cur is not None and l.startswith(("SD\t", "SDX\t")):
+            cur["SD"].append(l)
+    for r in out:
+        r["SD"].sort()
+    return out
+
+
+def assert_seed_batch_matches_trace(got, want, names, digested, flag=0):
+    """got: Mapper.seed_batch's list; want: seed_trace_per_read of the reference's trace; names: the reference's contig names.  Every
+    kept seed's occurrences are expanded as collect_seed_hits does (LR/map.c:861-955) and compared with the read's pattern phase, hit
+    counts and SD lines (as a multiset; digested: as their count and sha1).  flag: the MM_F_* bits of the mapping options -- the seed level
+    hands back every occurrence; with --for-only / --rev-only collect_seed_hits drops those of the other strand (skip_seed,
+    LR/map.c:724-730), so the expansion here does too.  Returns the number of seed hits compared."""
+    assert len(got) == len(want)
+    n_sd = 0
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert "Final shift: %d" % g["shift"] == w["shift"], (i, g["shift"], w["shift"])
+        lines, nf, nr = [], 0, 0
+        at = 0
+        for n_occ, q_pos in g["seeds"]:
+            qpos, qstrand = int(q_pos) >> 1, int(q_pos) & 1
+            for y in g["occ"][at:at + int(n_occ)]:
+                y = int(y)
+                rid, loc, strand = y >> 32, (y & 0xffffffff) >> 1, y & 1
+                if flag & (0x200000 if strand == qstrand else 0x100000):  # MM_F_REV_ONLY drops same-strand hits, MM_F_FOR_ONLY the others
+                    continue
+                if strand ^ qstrand:  # reverse: target = loc + qpos, printed as (uint32)target + 1   (LR/map.c:897-903, :1335)
+                    lines.append("SD\t%s\t%d\t-\t%d" % (names[rid], ((loc + qpos) & 0xffffffff) + 1, qpos))
+                    nr += 1
+                else:  # forward: target = loc + tmp_extracted_len - qpos, printed as (int32)target + 1 - tmp_extracted_len   (:904-910, :1331)
+                    t = (loc + g["tel"] - qpos) & 0xffffffff
+                    t = t - (1 << 32) if t >= 1 << 31 else t
+                    lines.append("SD\t%s\t%d\t+\t%d" % (names[rid], t + 1 - g["tel"], qpos))
+                    nf += 1
+            at += int(n_occ)
+        assert at == len(g["occ"])
+        assert "RS n_a_for: %d, n_a_rev: %d" % (nf, nr) == w["RS"], (i, nf, nr, w["RS"])
+        mine = sorted(digest_sd(lines) if digested else lines)
+        assert mine == w["SD"], (i, mine[:2], w["SD"][:2])
+        n_sd += nf + nr
+    return n_sd
+
+
+def flat_index(pkg, names, seqs, preset, overrides, builder, monkeypatch):
+    """(keys, counts, positions in key order, S, mid_occ, n_keys) of the index a fresh context builds with GDIET_INDEX_BUILD=builder
+    ("host" / "device": chosen when the context is created)"""
+    import numpy as np
+    monkeypatch.setenv("GDIET_INDEX_BUILD", builder)
+    ctx = pkg.Context(0)
+    try:
+        m = pkg.Mapper(ctx, names, seqs, preset=preset, **overrides)
+        try:
+            f = m.export_index()
+            order = np.argsort(f["keys"], kind="stable")
+            start = np.concatenate([[0], np.cumsum(f["cnt"].astype(np.int64))])
+            pos = np.concatenate([f["pos"][start[j]:start[j + 1]] for j in order]) if len(order) else f["pos"]
+            return f["keys"][order], f["cnt"][order], pos, f["S"], m.mid_occ, m.n_keys()
+        finally:
+            m.close()
+    finally:
+        ctx.close()

@@ -10,7 +10,8 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-from fixture_io import LR, PAF_KINDS, REP, SD_DIGESTED, SETS, SR, TRACE_PREFIXES, cmd_of, digest_sd, golden_paf, golden_sam, paf_cmd_of, reads_of, trace_of
+from fixture_io import (LR, PAF_KINDS, REP, SD_DIGESTED, SETS, SR, TRACE_PREFIXES, cmd_of, digest_sd, golden_paf, golden_sam, grid_cmd, grid_golden_sam, grid_ids,
+                        grid_reads, grid_row, grid_rows, grid_trace, mapped_share, paf_cmd_of, reads_of, star_seq_qual, trace_of)
 
 
 @pytest.fixture(scope="module")
@@ -265,3 +266,143 @@ def test_committed_goldens_are_what_the_reference_prints():
         pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
     r = subprocess.run(["python3", os.path.join(ROOT, "oracle", "make_golden.py")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+# ---- the option grid (tests/golden/opts/grid.json): patterns, k, w, vote / gap / band options, strand flags and scorings away from
+# the README command lines; goldens by the reference binaries (oracle/make_grid_golden.py) ----------------------------------------
+@pytest.mark.parametrize("name", grid_ids())
+def test_grid_host_path_matches_committed_sam_and_trace(host_driver, tmp_path, name):
+    """every row of the grid through the product's stage code on the host: the SAM the reference printed (SEQ / QUAL starred on both
+    sides) and its stage trace (pattern phase, seed hits of both strands as count + sha1, vote candidates of both rounds, boxes, DP
+    scores, concatenations), line for line.  Rows with "build": "scalar" hold what scalar GDiet printed at a window size where GDiet_avx
+    sketches differently ("Known divergence"): the library's choice between the two is pinned here."""
+    import re
+    exe, d = host_driver
+    row = grid_row(name)
+    ref_fa = os.path.join(d, os.path.basename(SETS[row["kind"]][0]), "ref.fa")
+    fq = str(tmp_path / "reads.fq")
+    reads = grid_reads(row)
+    assert len(reads) == row["n_reads"]
+    with open(fq, "w") as f:
+        for qn, seq, qual in reads:
+            f.write("@%s\n%s\n+\n%s\n" % (qn, seq, qual))
+    out = subprocess.run([exe] + THREADS + grid_cmd(row) + ["--print-seeds", "--stats", ref_fa, fq], capture_output=True, text=True, check=True)
+    got, want = [star_seq_qual(l) for l in out.stdout.rstrip("\n").split("\n")], grid_golden_sam(row)
+    assert len(got) == len(want)
+    for a, b in zip(got, want):
+        assert a == b, (a[:300], b[:300])
+    mine = digest_sd([l for l in out.stderr.split("\n") if l.startswith(TRACE_PREFIXES)])
+    want_t, got_t = _split_trace(grid_trace(row)), _split_trace(mine)
+    assert len(want_t) == len(got_t) == len(reads)
+    for a, b in zip(want_t, got_t):
+        assert a == b
+    st = dict(re.findall(r"([a-z_>0-9()]+)=(\d+)", " ".join(l for l in out.stderr.split("\n") if l.startswith("[stats]"))))
+    if "mz_flt" in row["tags"]:  # -f low enough for the query-side filter of the ShortReads variant (see "sr_rep_f60" in fixture_io.py)
+        assert int(st["mz_flt_drops"]) >= 5
+    if "retry" in row["tags"]:  # reads whose minimizers overflow the first scratch estimate of the GPU path (map_plan.h gd_scratch_layout)
+        assert int(st["over_first_scratch"]) >= row["n_reads"] // 2
+
+
+@pytest.mark.parametrize("name", [r["name"] for r in grid_rows() if not {"kw", "strand"} & set(r["tags"])])
+def test_grid_options_are_not_inert(host_driver, tmp_path, name):
+    """the vote / gap / band / capacity / scoring rows: leaving out any one option group of the row makes the host path print something
+    other than the committed SAM and trace -- every option the row names decides part of its golden (the writer asserts the same of
+    the reference for every row)"""
+    exe, d = host_driver
+    row = grid_row(name)
+    ref_fa = os.path.join(d, os.path.basename(SETS[row["kind"]][0]), "ref.fa")
+    fq = str(tmp_path / "reads.fq")
+    with open(fq, "w") as f:
+        for qn, seq, qual in grid_reads(row):
+            f.write("@%s\n%s\n+\n%s\n" % (qn, seq, qual))
+    want = (grid_golden_sam(row), _split_trace(grid_trace(row)))
+    assert row["sensitive"]
+    for group in row["sensitive"]:
+        out = subprocess.run([exe] + THREADS + grid_cmd(row, group) + ["--print-seeds", ref_fa, fq], capture_output=True, text=True, check=True)
+        sam = [star_seq_qual(l) for l in out.stdout.rstrip("\n").split("\n")]
+        trace = _split_trace(digest_sd([l for l in out.stderr.split("\n") if l.startswith(TRACE_PREFIXES)]))
+        assert (sam, trace) != want, (name, group)
+
+
+def test_grid_rows_cannot_pass_vacuously():
+    """what oracle/make_grid_golden.py asserts when it writes the fixtures, again on the committed files: the reference maps at least
+    min_mapped of every row's reads (0.9 for LongReads rows; 0.4 where the row is built to starve seeds or keeps one strand of a
+    two-strand read set; 0.5 for ShortReads rows on var.fq), strand rows hold mapped and unmapped reads, the *_sv rows reach the
+    second voting round's concatenations, every read has a trace"""
+    for row in grid_rows():
+        sam, trace = grid_golden_sam(row), grid_trace(row)
+        mapped, n = mapped_share(sam)
+        assert n == row["n_reads"] and mapped >= row["min_mapped"] * n, (row["name"], mapped, n)
+        floor = 0.25 if row["kind"] in ("sr", "sr_rep") else 0.5 if row["variant"] == "sr" else 0.4 if ("strand" in row["tags"] or row["overrides"].get("k") == 28) else 0.9
+        assert row["min_mapped"] >= floor, row["name"]
+        if "strand" in row["tags"]:
+            assert 0 < mapped < n, row["name"]
+            flags = {int(l.split("\t")[1]) & 16 for l in sam if l.split("\t")[2] != "*"}
+            assert flags == ({0} if "--for-only" in row["extra"] else {16}), row["name"]
+        if "sv" in row["tags"]:
+            assert sum(1 for l in trace if l.startswith("CONQ")) >= 5, row["name"]
+        if "vote_cap" in row["tags"]:  # reads of the repeat-rich reference with more candidates than any preset's vt_nb_loc + 2 = 7 keeps
+            per_read = [len(r["VT"]) for r in _split_trace(trace)]
+            assert sum(1 for c in per_read if c > 7) >= 10, (row["name"], per_read)
+        assert sum(1 for l in trace if l.startswith("Final shift")) == n and all(l.split("\t")[9] == "*" for l in sam)
+
+
+def test_grid_covers_what_it_was_built_for():
+    """the table itself: between them the rows reach the patterns, k / w limits, vote capacities, flags and scorings no README command
+    line reaches; both the command-line form and the Mapper overrides of a row name the same options"""
+    rows = grid_rows()
+    assert len({r["name"] for r in rows}) == len(rows)
+    ov = [dict(r["overrides"], variant=r["variant"], build=r["build"]) for r in rows]
+    pats = [o["Z"] for o in ov if "Z" in o]
+    assert sum(1 for z in set(pats) if z.count("1") > 1) >= 3 and any(z[0] == "0" and z.count("1") > 1 for z in pats)
+    assert "1" in pats and any(len(z) >= 32 and z.count("1") <= 8 for z in pats) and any(z.count("1") == 40 for z in pats)
+    ks, ws = {o.get("k") for o in ov}, {o.get("w") for o in ov}
+    assert 28 in ks and any(k is not None and k <= 12 for k in ks) and 64 in ws and ws & {8, 9} and any("retry" in r["tags"] for r in rows)
+    lr, sr = [o for o in ov if o["variant"] == "lr"], [o for o in ov if o["variant"] == "sr"]
+    assert {22, 1} <= {o.get("vt_nb_loc") for o in lr} and any(o.get("max_seeds", 0) >= 1 for o in lr) and any(0 < o.get("max_seeds", 0) < 1 for o in lr)
+    for key in ("vt_dis", "vt_df1", "vt_df2", "vt_cov", "vt_f", "max_min_gap", "max_max_gap", "bw"):
+        assert any(key in o for o in lr), key
+    assert any(o.get("best_n", 1) > 1 for o in lr)
+    assert {24, 1} <= {o.get("AF_max_loc") for o in sr} and any("bw_max" in o for o in sr) and any("rec_threshold_frac" in o for o in sr)
+    assert any("mz_flt" in r["tags"] for r in rows)
+    for var in ("lr", "sr"):
+        fl = {o.get("flag", 0) & 0x300000 for o in ov if o["variant"] == var}
+        assert {0x100000, 0x200000} <= fl, var
+        # one row per variant pinned to the scalar build, at a window size in 2..7 -- and no GDiet_avx row there
+        assert [o["w"] for o in ov if o["variant"] == var and o["build"] == "scalar"] == [4]
+    assert all(not (2 <= o.get("w", 10) <= 7) for o in ov if o["build"] == "avx")
+    assert sum(1 for o in ov if "q2" in o) >= 2 and len(grid_rows("mmi")) == 3
+    for r in rows:  # every option of a row is one of its sensitive groups
+        assert " ".join(r["sensitive"]).split() == r["extra"].split(), r["name"]
+    for r in rows:  # the two forms of a row agree on the options both can be read from
+        toks = r["extra"].replace("=", " ").split()
+        for opt, key in (("-k", "k"), ("-w", "w"), ("-Z", "Z"), ("-W", "W"), ("-N", "best_n"), ("--vt_nb_loc", "vt_nb_loc"), ("--AF_max_loc", "AF_max_loc"), ("-A", "a"), ("-B", "b")):
+            assert (opt in toks) == (key in r["overrides"]), (r["name"], opt)
+            if opt in toks:
+                assert str(r["overrides"][key]) == toks[toks.index(opt) + 1], (r["name"], opt)
+
+
+def test_grid_goldens_are_what_the_reference_prints():
+    """oracle/make_grid_golden.py in check mode: every committed file of the grid is reproduced by the reference binaries compiled here,
+    and the conditions it asserts on them hold (skipped where the reference's sources, hence oracle/_ref, do not exist)"""
+    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "gdiet_lr_avx")):
+        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
+    r = subprocess.run(["python3", os.path.join(ROOT, "oracle", "make_grid_golden.py")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
+def test_grid_mmi_files_are_the_reference_s(host_driver, tmp_path):
+    """the host index builder + .mmi writer at three non-preset k / w / pattern settings: size and sha256 of the file the reference wrote"""
+    import hashlib
+    import json
+    from fixture_io import OPTS
+    exe, d = host_driver
+    want = json.load(open(os.path.join(OPTS, "mmi.sha256.json")))
+    fq = str(tmp_path / "none.fq")
+    open(fq, "w").write("@r\nACGT\n+\nIIII\n")
+    for row in grid_rows("mmi"):
+        ours = str(tmp_path / (row["name"] + ".mmi"))
+        ref_fa = os.path.join(d, os.path.basename(SETS[row["kind"]][0]), "ref.fa")
+        subprocess.run([exe] + grid_cmd(row) + ["--dump-mmi=" + ours, ref_fa, fq], capture_output=True, check=True)
+        data = open(ours, "rb").read()
+        assert len(data) == want[row["name"]]["size"] and hashlib.sha256(data).hexdigest() == want[row["name"]]["sha256"], row["name"]
