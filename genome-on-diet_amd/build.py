@@ -11,11 +11,12 @@ RES = os.path.join(HERE, "build_resources.txt")  # the compiler's per-kernel res
 # Register budgets the design depends on (checked against the compiler's own resource report after every build):
 #   * the 64-lane DP kernel: 96 VGPRs = 5 wavefronts per SIMD, and nothing of its row loop in scratch memory;
 #   * the kernels that must be able to start BESIDE a full house of those DP wavefronts (5 x 96 of a SIMD's 512 registers are taken):
-#     at most 32 VGPRs (map_kernels.hip.h: map_post_wave_kernel).
+#     at most 32 VGPRs (map_kernels.hip.h: map_post_wave_kernel; map_diffstr.hip.h: the cs / MD tag pass of batch i runs beside the DP of batch i+1).
 BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           "_Z21ksw_extd2_pipe_kernelILb1E": dict(vgprs=128, scratch=320),  # four wavefronts per SIMD; the spills sit in the once-per-alignment staging code, none in the steps
           "_Z20map_post_wave_kernel": dict(vgprs=32, scratch=0),
-          "_Z21map_pack_cigar_kernel": dict(vgprs=32, scratch=0)}
+          "_Z21map_pack_cigar_kernel": dict(vgprs=32, scratch=0),
+          "_Z18map_diffstr_kernel": dict(vgprs=32, scratch=0)}  # every instance: count / write pass x MD / cs / cs=long (map_diffstr.hip.h)
 
 
 def _newest_source():

@@ -112,6 +112,13 @@ struct gdiet_ctx {
 	// with n_regs = 0 while the rest of the batch is mapped.  failed_total: since the context was created.
 	int64_t failed_last = 0, failed_total = 0;
 	std::string warn;                  // what the last such read was (gdiet_hip_map_failed_reads)
+	// cs / MD difference strings (map_diffstr_driver.hip.h): a stream and buffers of their own behind a mutex of their own, because the
+	// formatters call it from a writer thread while map tickets are open on the other streams
+	std::mutex ds_mu;
+	std::string ds_err;                // text of the last failing difference-string pass (written under ds_mu; gdiet_hip_strerror)
+	hipStream_t ds_stream = nullptr;
+	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff;
+	std::vector<uint8_t> ds_enc;       // host copy of the reads a call without a resident batch encodes
 };
 
 #define GD_HIP(call)                                                                              \
@@ -255,8 +262,9 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 		if (ctx->async_lane[i]) gdiet_hip_destroy(ctx->async_lane[i]), ctx->async_lane[i] = nullptr;
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+	if (ctx->ds_stream) (void)hipStreamSynchronize(ctx->ds_stream);
 	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev};
-	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream};
+	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream};
 	delete ctx; // every DevBuf of the context releases itself here: before the streams and events go
 	for (hipEvent_t e : events)
 		if (e) (void)hipEventDestroy(e);
@@ -294,7 +302,12 @@ extern "C" int gdiet_hip_last_dp_clock(gdiet_ctx *ctx, double *sclk_mhz_median, 
 }
 
 
-extern "C" const char *gdiet_hip_strerror(const gdiet_ctx *ctx) { return ctx ? ctx->err.c_str() : "no context"; }
+static const char *gd_ds_err_of(const gdiet_ctx *ctx); // map_diffstr_driver.hip.h
+extern "C" const char *gdiet_hip_strerror(const gdiet_ctx *ctx)
+{
+	if (const char *ds = gd_ds_err_of(ctx)) return ds; // this thread's last failure on the context was a difference-string pass
+	return ctx ? ctx->err.c_str() : "no context";
+}
 
 extern "C" int gdiet_hip_device_name(const gdiet_ctx *ctx, char *buf, size_t len)
 {

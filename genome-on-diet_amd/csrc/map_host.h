@@ -621,7 +621,20 @@ static inline void gd_write_tags(std::string &s, const GdReg &r)
 #define GD_F_OUT_CG 0x020
 #define GD_F_PAF_NO_HIT 0x8000000
 #define GD_F_QSTRAND (0x100000000LL)
-static inline void gd_write_paf(std::string &s, const GdRefView &R, const char *qname, int l_seq, const std::vector<GdReg> &regs, int reg_idx, int64_t opt_flag)
+#define GD_F_OUT_CS 0x40
+#define GD_F_OUT_CS_LONG 0x800
+#define GD_F_OUT_MD 0x1000000
+// "\tcs:Z:<ds>" / "\tMD:Z:<ds>" (LR/format.c:153,205; the two flags together mean MD, :261).  ds: the record's difference string, computed
+// elsewhere (on the device: map_diffstr.hip.h); nullptr: the caller has none, and no tag is written
+static inline void gd_write_ds_tag(std::string &s, int64_t opt_flag, const char *ds, size_t ds_len)
+{
+	if (!ds || !(opt_flag & (GD_F_OUT_CS | GD_F_OUT_MD))) return;
+	s += (opt_flag & GD_F_OUT_MD) ? "\tMD:Z:" : "\tcs:Z:";
+	s.append(ds, ds_len);
+}
+
+static inline void gd_write_paf(std::string &s, const GdRefView &R, const char *qname, int l_seq, const std::vector<GdReg> &regs, int reg_idx, int64_t opt_flag,
+                                const char *ds = nullptr, size_t ds_len = 0)
 {
 	s += qname; s += '\t'; gd_fmt_int(s, l_seq);
 	if (reg_idx < 0 || reg_idx >= (int)regs.size()) { s += "\t0\t0\t*\t*\t0\t0\t0\t0\t0\t0\trl:i:0"; return; }
@@ -637,10 +650,11 @@ static inline void gd_write_paf(std::string &s, const GdRefView &R, const char *
 		s += "\tcg:Z:";
 		for (uint32_t cg : r.cigar) { gd_fmt_int(s, cg >> 4); s += "MIDNSHP=XB"[cg & 0xf]; }
 	}
+	if (r.has_p && !r.cigar.empty()) gd_write_ds_tag(s, opt_flag, ds, ds_len); // :354-356
 }
 
 static inline void gd_write_sam(std::string &s, const GdRefView &R, const char *qname, const char *seq, const char *qual, int l_seq,
-                                const std::vector<GdReg> &regs, int reg_idx, int64_t opt_flag)
+                                const std::vector<GdReg> &regs, int reg_idx, int64_t opt_flag, const char *ds = nullptr, size_t ds_len = 0)
 {
 	static const char comp_tab[] = "TVGHEFCDIJMLKNOPQYSAABWXRZ"; // seq_comp_table (LR/bseq.c) restricted to letters
 	const GdReg *r = reg_idx >= 0 && reg_idx < (int)regs.size() ? &regs[reg_idx] : nullptr;
@@ -718,6 +732,6 @@ static inline void gd_write_sam(std::string &s, const GdRefView &R, const char *
 			}
 		}
 	}
+	if (r && r->has_p && !r->cigar.empty()) gd_write_ds_tag(s, opt_flag, ds, ds_len); // :593-594, behind the SA tag
 	s += "\trl:i:0"; // rep_len is never set on this path (bug-compat item 8): mm_write_sam3 prints rl:i:0
-	(void)opt_flag;
 }

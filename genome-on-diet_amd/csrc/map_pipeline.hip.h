@@ -42,6 +42,8 @@ struct gdiet_read_batch {
 #include "host_pool.h"
 #include "nt4_encode.h"
 
+static void gd_ds_clear_mark(); // map_diffstr_driver.hip.h: this thread's "my last failure was a difference-string pass" mark
+
 static void gd_pool_free(void *pool) { delete (GdPool *)pool; }
 
 static GdPool *gd_pool(gdiet_ctx *ctx)
@@ -218,6 +220,7 @@ extern "C" int gdiet_hip_map_stage_seconds(const gdiet_ctx *ctx, double out[6])
 
 extern "C" int gdiet_hip_batch_upload(gdiet_ctx *ctx, gdiet_read_batch **out, int n, const char *const *seqs, const int32_t *lens)
 {
+	gd_ds_clear_mark();
 	if (!ctx || !out || n < 0 || (n && (!seqs || !lens))) return GDIET_E_PARAM;
 	(void)hipSetDevice(ctx->device);
 	const bool trace = gd_trace_stages();
@@ -1019,6 +1022,7 @@ extern "C" int gdiet_hip_set_map_lanes(gdiet_ctx *ctx, int n)
 extern "C" int gdiet_hip_map_uploaded(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_mapopt_t *copt, gdiet_read_batch *B,
                                       int32_t *n_regs, gdiet_reg_t **regs)
 {
+	gd_ds_clear_mark();
 	if (!ctx || !ix || !copt || !B || !n_regs || !regs) return GDIET_E_PARAM;
 	(void)hipSetDevice(ctx->device);
 	const int n = B->n;
@@ -1130,6 +1134,7 @@ extern "C" int gdiet_hip_set_inflight(gdiet_ctx *ctx, int n)
 extern "C" int gdiet_hip_map_submit(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_mapopt_t *copt, gdiet_read_batch *B, int32_t *n_regs,
                                     gdiet_reg_t **regs, gdiet_map_ticket **out)
 {
+	gd_ds_clear_mark();
 	if (!ctx || !ix || !copt || !B || !n_regs || !regs || !out) return GDIET_E_PARAM;
 	(void)hipSetDevice(ctx->device);
 	std::lock_guard<std::mutex> guard(ctx->async_mu); // (submit and wait may come from different threads of the caller's pipeline)
@@ -1165,6 +1170,7 @@ extern "C" int gdiet_hip_map_submit(gdiet_ctx *ctx, const gdiet_index *ix, const
 
 extern "C" int gdiet_hip_map_wait(gdiet_ctx *ctx, gdiet_map_ticket *t)
 {
+	gd_ds_clear_mark();
 	if (!ctx || !t) return GDIET_E_PARAM;
 	if (t->th.joinable()) t->th.join();
 	std::lock_guard<std::mutex> guard(ctx->async_mu);
@@ -1214,6 +1220,7 @@ extern "C" int gdiet_hip_seed_batch(gdiet_ctx *ctx, const gdiet_index *ix, const
                                     int32_t *shift, uint32_t *tmp_extracted_len, uint32_t *n_mv, int64_t *seed_off, int64_t *occ_off, gdiet_seed_t **seeds,
                                     uint64_t **occ)
 {
+	gd_ds_clear_mark();
 	if (!ctx || !ix || !copt || n < 0 || (n && (!seqs || !lens)) || !shift || !tmp_extracted_len || !n_mv || !seed_off || !occ_off || !seeds || !occ) return GDIET_E_PARAM;
 	*seeds = nullptr, *occ = nullptr;
 	seed_off[0] = occ_off[0] = 0;
@@ -1255,6 +1262,8 @@ extern "C" int gdiet_hip_seed_batch(gdiet_ctx *ctx, const gdiet_index *ix, const
 	*seeds = sd, *occ = oc;
 	return GDIET_OK;
 }
+
+#include "map_diffstr_driver.hip.h"
 
 extern "C" size_t gdiet_hip_sam_record(const gdiet_index *ix, const char *qname, const char *seq, const char *qual, int32_t l_seq,
                                        const gdiet_reg_t *regs, int32_t n_regs, int32_t reg_idx, int64_t opt_flag, char *buf, size_t cap)
@@ -1301,6 +1310,10 @@ static size_t gd_sam_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_rea
                                 const char *const *quals, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
                                 int64_t opt_flag, char **buf_io, size_t *cap_io /* null: *buf_io is malloc'd to size */)
 {
+	// --cs / --MD: one difference-string call for the whole batch, on the device, before the chunks are formatted; every record's slice
+	// is then appended behind its tags (mm_write_sam3 never passes qstrand: LR/format.c:594)
+	GdDsText ds;
+	if (gd_ds_mode(opt_flag) >= 0 && gd_ds_for_batch(ctx, ix, n_reads, seqs, lens, n_regs, regs, opt_flag & ~GD_F_QSTRAND, ds)) return 0;
 	const int CH = gd_fmt_chunk(ctx, n_reads), n_ch = (n_reads + CH - 1) / CH;
 	std::vector<std::string> rec((size_t)n_ch);
 	gd_fmt_take(ctx, rec);
@@ -1309,7 +1322,7 @@ static size_t gd_sam_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_rea
 		std::string &s = rec[c];
 		const int i1 = std::min(n_reads, (c + 1) * CH);
 		size_t guess = 0;
-		for (int i = c * CH; i < i1; ++i) guess += (2 * (size_t)lens[i] + 200) * (size_t)std::max(1, n_regs[i]);
+		for (int i = c * CH; i < i1; ++i) guess += (2 * (size_t)lens[i] + 200) * (size_t)std::max(1, n_regs[i]) + ds.bytes_of_read(i);
 		s.reserve(guess);
 		for (int i = c * CH; i < i1; ++i) {
 			const int nr = n_regs[i];
@@ -1322,7 +1335,7 @@ static size_t gd_sam_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_rea
 			else
 				for (int j = 0; j < nr; ++j) {
 					if ((opt_flag & GD_F_NO_PRINT_2ND) && v[j].id != v[j].parent) continue;
-					gd_write_sam(s, ix->h.ref(), qnames[i], seqs[i], q, lens[i], v, j, opt_flag), s += '\n';
+					gd_write_sam(s, ix->h.ref(), qnames[i], seqs[i], q, lens[i], v, j, opt_flag, ds.str(i, j), ds.len(i, j)), s += '\n';
 				}
 		}
 	});
@@ -1370,11 +1383,13 @@ extern "C" size_t gdiet_hip_sam_batch_into(gdiet_ctx *ctx, const gdiet_index *ix
 
 // All PAF lines of a batch (mm_write_paf3, LR/format.c:326-367, as step 2 prints them when MM_F_OUT_SAM is off: LR/map.c:2163-2185).
 // opt_flag: MM_F_OUT_CG adds the cg:Z: tag, MM_F_PAF_NO_HIT the lines of unmapped reads, MM_F_NO_PRINT_2ND drops secondary records.
-extern "C" size_t gdiet_hip_paf_batch(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const int32_t *lens,
-                                      const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out)
+// seqs == nullptr: gdiet_hip_paf_batch, which has no reads and hence no difference tags
+static size_t gd_paf_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs, const int32_t *lens,
+                                const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out)
 {
-	if (!ctx || !ix || n_reads < 0 || !qnames || !lens || !n_regs || !regs || !out) return 0;
 	*out = nullptr;
+	GdDsText ds; // --cs / --MD: as in gd_sam_batch_impl; MM_F_QSTRAND reaches the strings here (LR/format.c:355-356)
+	if (seqs && gd_ds_mode(opt_flag) >= 0 && gd_ds_for_batch(ctx, ix, n_reads, seqs, lens, n_regs, regs, opt_flag, ds)) return 0;
 	const int CH = 512, n_ch = (n_reads + CH - 1) / CH;
 	std::vector<std::string> rec((size_t)n_ch);
 	gd_parallel_for(ctx, ctx->host_threads, n_ch, [&](int c) {
@@ -1392,7 +1407,7 @@ extern "C" size_t gdiet_hip_paf_batch(gdiet_ctx *ctx, const gdiet_index *ix, int
 			} else
 				for (int j = 0; j < nr; ++j) {
 					if ((opt_flag & GD_F_NO_PRINT_2ND) && v[j].id != v[j].parent) continue;
-					gd_write_paf(s, ix->h.ref(), qnames[i], lens[i], v, j, opt_flag), s += '\n';
+					gd_write_paf(s, ix->h.ref(), qnames[i], lens[i], v, j, opt_flag, ds.str(i, j), ds.len(i, j)), s += '\n';
 				}
 		}
 	});
@@ -1405,4 +1420,19 @@ extern "C" size_t gdiet_hip_paf_batch(gdiet_ctx *ctx, const gdiet_index *ix, int
 	buf[tot] = 0;
 	*out = buf;
 	return tot;
+}
+
+extern "C" size_t gdiet_hip_paf_batch(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const int32_t *lens,
+                                      const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out)
+{
+	if (!ctx || !ix || n_reads < 0 || !qnames || !lens || !n_regs || !regs || !out) return 0;
+	return gd_paf_batch_impl(ctx, ix, n_reads, qnames, nullptr, lens, n_regs, regs, opt_flag, out);
+}
+
+// gdiet_hip_paf_batch with the reads: MM_F_OUT_CS / MM_F_OUT_CS_LONG / MM_F_OUT_MD add the cs:Z: / MD:Z: tag behind cg:Z: (LR/format.c:354-356)
+extern "C" size_t gdiet_hip_paf_batch_seqs(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs,
+                                           const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out)
+{
+	if (!ctx || !ix || n_reads < 0 || !qnames || !seqs || !lens || !n_regs || !regs || !out) return 0;
+	return gd_paf_batch_impl(ctx, ix, n_reads, qnames, seqs, lens, n_regs, regs, opt_flag, out);
 }

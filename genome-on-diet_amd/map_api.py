@@ -11,6 +11,7 @@ import numpy as np
 from .hip_abi import GdietError, load_library
 
 F_NO_PRINT_2ND = 0x4000
+F_OUT_CS, F_OUT_CS_LONG, F_OUT_MD, F_QSTRAND = 0x40, 0x800, 0x1000000, 0x100000000  # --cs, --cs=long (with F_OUT_CS), --MD, --qstrand
 F_SR, F_FRAG_MODE = 0x1000, 0x2000
 
 
@@ -95,6 +96,10 @@ def _bind(lib):
     lib.gdiet_hip_sam_batch.restype = C.c_size_t
     lib.gdiet_hip_paf_batch.argtypes = [vp, vp, C.c_int, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp)]
     lib.gdiet_hip_paf_batch.restype = C.c_size_t
+    lib.gdiet_hip_paf_batch_seqs.argtypes = [vp, vp, C.c_int, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp)]
+    lib.gdiet_hip_paf_batch_seqs.restype = C.c_size_t
+    lib.gdiet_hip_diffstr_batch.argtypes = [vp, vp, vp, C.c_int, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp),
+                                            C.POINTER(vp)]
     lib._map_bound = True
 
 
@@ -323,15 +328,23 @@ class Mapper:
                                                   self.opt.flag, C.byref(self._sam_buf), C.byref(self._sam_cap))
             if m:
                 sink.write(memoryview((C.c_char * m).from_address(self._sam_buf.value)))
+            elif n:
+                self._format_failed("gdiet_hip_sam_batch_into")
             return m
         out = C.c_void_p()
         m = self.lib.gdiet_hip_sam_batch(self.ctx._h, self._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp), lens, res.n_regs, res.regs,
                                          self.opt.flag, C.byref(out))
+        if n and not out.value:
+            self._format_failed("gdiet_hip_sam_batch")
         try:
             return C.string_at(out.value, m) if out.value else b""
         finally:
             if out.value:
                 C.CDLL(None).free(C.c_void_p(out.value))
+
+    def _format_failed(self, what):
+        """a batch formatter returned no text for a batch with reads: the difference-string pass refused a record, or memory ran out"""
+        raise GdietError("%s: %s" % (what, self.lib.gdiet_hip_strerror(self.ctx._h).decode()))
 
     def map_uploaded(self, batch):
         h, n = batch
@@ -387,6 +400,8 @@ class Mapper:
         out = C.c_void_p()
         m = self.lib.gdiet_hip_sam_batch(self.ctx._h, self._idx, n, qn, sq, ql, lens.ctypes.data_as(C.POINTER(C.c_int32)), res.n_regs, res.regs,
                                          self.opt.flag, C.byref(out))
+        if n and not out.value:
+            self._format_failed("gdiet_hip_sam_batch")
         try:
             return C.string_at(out.value, m).decode() if out.value else ""
         finally:
@@ -408,6 +423,48 @@ class Mapper:
         finally:
             if out.value:
                 C.CDLL(None).free(C.c_void_p(out.value))
+
+    def paf_batch_seqs(self, res, reads, flag=0):
+        """gdiet_hip_paf_batch_seqs: paf_batch with the reads, so that F_OUT_CS / F_OUT_CS_LONG / F_OUT_MD in flag (or in the mapper's
+        options) add the cs:Z: / MD:Z: tag behind cg:Z:; F_QSTRAND reaches the tag as in the reference"""
+        n = len(reads)
+        enc = lambda x: x if isinstance(x, bytes) else x.encode()
+        qn = (C.c_char_p * n)(*[enc(r[0]) for r in reads])
+        sq = (C.c_char_p * n)(*[enc(r[1]) for r in reads])
+        lens = np.array([len(r[1]) for r in reads], np.int32)
+        out = C.c_void_p()
+        m = self.lib.gdiet_hip_paf_batch_seqs(self.ctx._h, self._idx, n, qn, sq, lens.ctypes.data_as(C.POINTER(C.c_int32)), res.n_regs, res.regs,
+                                              self.opt.flag | flag, C.byref(out))
+        if n and not out.value:
+            self._format_failed("gdiet_hip_paf_batch_seqs")
+        try:
+            return C.string_at(out.value, m).decode()
+        finally:
+            C.CDLL(None).free(C.c_void_p(out.value))
+
+    def diffstr(self, res, reads, flag, batch=None):
+        """gdiet_hip_diffstr_batch: per read the list of its records' difference strings (bytes, no tag prefix) -- MD with F_OUT_MD in
+        flag, else cs with F_OUT_CS (long form with F_OUT_CS_LONG), empty strings with neither; F_QSTRAND as in mm_write_paf3.
+        reads: sequences or (qname, seq, ...) tuples; batch: a resident batch of upload() holding the same reads, used in their place"""
+        seqs = [r if isinstance(r, (str, bytes)) else r[1] for r in reads]
+        n, seqs, arr, lens = self._arrays(seqs)
+        text, off = C.c_void_p(), C.c_void_p()
+        rc = self.lib.gdiet_hip_diffstr_batch(self.ctx._h, self._idx, batch[0] if batch is not None else None, n, arr,
+                                              lens.ctypes.data_as(C.POINTER(C.c_int32)), res.n_regs, res.regs, flag, C.byref(text), C.byref(off))
+        self.ctx._check(rc)
+        try:
+            n_rec = sum(max(0, res.n_regs[i]) for i in range(n))
+            o = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_int64)), shape=(n_rec + 1,)).copy()
+            raw = C.string_at(text.value, int(o[n_rec]))
+        finally:
+            libc = C.CDLL(None)
+            libc.free(text), libc.free(off)
+        out, k = [], 0
+        for i in range(n):
+            m = max(0, res.n_regs[i])
+            out.append([raw[o[k + j]:o[k + j + 1]] for j in range(m)])
+            k += m
+        return out
 
     def sam(self, res, i, qname, seq, qual=None):
         """SAM lines of read i of a MapResult, as the reference's output step prints them (map.c step 2)."""

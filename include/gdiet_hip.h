@@ -52,6 +52,9 @@ typedef struct {
 int gdiet_hip_init(gdiet_ctx **ctx, int device_ordinal);   /* replaces nothing: GPU context for one device */
 void gdiet_hip_destroy(gdiet_ctx *ctx);
 const char *gdiet_hip_strerror(const gdiet_ctx *ctx);       /* text of the last failure on this context */
+/* (The difference-string pass -- gdiet_hip_diffstr_batch, and gdiet_hip_sam_batch[_into] / gdiet_hip_paf_batch_seqs under --cs / --MD -- may
+ * refuse a record on a writer thread while map calls run on another: its text is kept apart, and gdiet_hip_strerror returns it to the thread
+ * whose call failed, until that thread's next difference-string, upload or map call.) */
 int gdiet_hip_device_name(const gdiet_ctx *ctx, char *buf, size_t len);
 /* which kernel variants handled the last batch: bit0 = register-resident 64-lane wave kernel, bit1 = generic LDS kernel,
  * bit2 = register-resident short-alignment kernels (several alignments per wavefront), bit3 = two-blocks-per-lane kernel (wide bands),
@@ -347,14 +350,43 @@ int gdiet_hip_set_host_threads(gdiet_ctx *ctx, int n);
  * with -t (LR/main.c:85 n_threads); a caller that derives -t from the machine should use this figure. */
 int gdiet_hip_effective_cpus(void);
 
+/* ---- the per-base difference strings of --cs[=short|long] and --MD -------------------------------------------------------------------
+ * Replaces mm_gen_cs_or_MD (LR/format.c:270-281; mm_gen_cs / mm_gen_MD :283-290; write_cs_core / write_MD_core / write_cs_or_MD
+ * :150-268) for every record of a mini-batch, on the GPU: one wavefront per record walks the CIGAR over the encoded read and the 4-bit
+ * reference, both already in HBM.  Bits of opt_flag that are read: MM_F_OUT_MD (0x1000000) selects MD, else MM_F_OUT_CS (0x40) selects
+ * cs, in its long form with MM_F_OUT_CS_LONG (0x800) -- both MD and cs set mean MD, as in the reference --, and MM_F_QSTRAND
+ * (0x100000000: the forward read against mm_idx_getseq2's reverse target, what mm_write_paf3 passes).  With neither 0x40 nor 0x1000000
+ * every string is empty and nothing is launched.
+ * batch: the resident reads of gdiet_hip_batch_upload (seqs / lens are then ignored), or NULL: seqs / lens (ASCII) are encoded and
+ * uploaded by the call.  Output: *text (NUL-terminated) and *off, both malloc'd (free() them): record k's string is
+ * text[off[k] .. off[k + 1]), records counted read-major in the order of regs[i]; off has one entry per record plus one.  The strings
+ * carry no "cs:Z:" / "MD:Z:" prefix.  A record without a CIGAR (n_cigar == 0: mm_reg1_t::p == NULL) gets the empty string.
+ * The reference's assertions (LR/format.c:156,199,232) are errors here, checked on the host before anything is launched: a record
+ * whose CIGAR lengths do not sum to qe - qs and re - rs, with an operation other than M I D N = X, with rid out of range, re past its
+ * contig or qe past its read, or (cs only) with an N operation shorter than 2 fails the whole call with GDIET_E_PARAM and a one-line
+ * gdiet_hip_strerror.  The call works on a stream and buffers of its own: it may run on another caller thread while map tickets
+ * (gdiet_hip_map_submit) are open on the context. */
+#define GDIET_F_OUT_CS      0x40
+#define GDIET_F_OUT_CS_LONG 0x800
+#define GDIET_F_OUT_MD      0x1000000
+int gdiet_hip_diffstr_batch(gdiet_ctx *ctx, const gdiet_index *idx, const gdiet_read_batch *batch /* or NULL */, int n_reads,
+                            const char *const *seqs, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
+                            int64_t opt_flag, char **text, int64_t **off);
+
 /* One SAM record exactly as mm_write_sam3 prints it for a single-segment read (LR/format.c:412-599); reg_idx < 0 writes
- * the unmapped record.  Returns the number of bytes needed (excluding the terminating NUL); writes at most cap bytes. */
+ * the unmapped record.  Returns the number of bytes needed (excluding the terminating NUL); writes at most cap bytes.
+ * This call has no context, hence no device: the cs:Z: / MD:Z: difference tags exist in the batch calls below only, and
+ * MM_F_OUT_CS / MM_F_OUT_MD in opt_flag are ignored here. */
 size_t gdiet_hip_sam_record(const gdiet_index *idx, const char *qname, const char *seq, const char *qual, int32_t l_seq,
                             const gdiet_reg_t *regs, int32_t n_regs, int32_t reg_idx, int64_t opt_flag, char *buf, size_t cap);
 
 /* All records of a batch, in input order, one per line (the body of a SAM file without the header), formatted on the context's
  * host threads -- step 2 of worker_pipeline (LR/map.c:2139-2170) for a whole mini-batch.  *out is malloc'd (free() it); returns
- * its length.  quals may be NULL, and so may its entries. */
+ * its length.  quals may be NULL, and so may its entries.
+ * MM_F_OUT_CS / MM_F_OUT_CS_LONG / MM_F_OUT_MD in opt_flag (--cs[=long] / --MD) add "\tcs:Z:..." or "\tMD:Z:..." to every record with a
+ * CIGAR, behind its SA:Z: tag, if any, and in front of rl:i:0 (LR/format.c:593-597): one gdiet_hip_diffstr_batch pass over the batch on
+ * the GPU before the records are formatted.  Without those bits nothing is launched and the text is what it always was.  A record
+ * that pass refuses makes the call return 0 with *out == NULL; gdiet_hip_strerror says why. */
 size_t gdiet_hip_sam_batch(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
                            const char *const *quals, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
                            int64_t opt_flag, char **out);
@@ -368,9 +400,15 @@ size_t gdiet_hip_sam_batch_into(gdiet_ctx *ctx, const gdiet_index *idx, int n_re
 
 /* The same for PAF output: mm_write_paf3 (LR/format.c:326-367) as step 2 prints it when MM_F_OUT_SAM is off (LR/map.c:2163-2185).
  * opt_flag: MM_F_OUT_CG (0x20, `-c`) adds the cg:Z: tag, MM_F_PAF_NO_HIT (0x8000000, --paf-no-hit) the lines of unmapped reads,
- * MM_F_NO_PRINT_2ND drops secondary records, MM_F_QSTRAND is honoured.  *out is malloc'd; returns its length. */
+ * MM_F_NO_PRINT_2ND drops secondary records, MM_F_QSTRAND is honoured.  *out is malloc'd; returns its length.
+ * This call is not given the reads, so MM_F_OUT_CS / MM_F_OUT_MD stay ignored here: gdiet_hip_paf_batch_seqs prints the tags. */
 size_t gdiet_hip_paf_batch(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const int32_t *lens,
                            const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out);
+/* gdiet_hip_paf_batch plus the reads (ASCII): mm_write_paf3 with MM_F_OUT_CS / MM_F_OUT_CS_LONG / MM_F_OUT_MD, which add the cs:Z: /
+ * MD:Z: tag behind cg:Z: (LR/format.c:354-356); MM_F_QSTRAND reaches the tag as it does there.  One gdiet_hip_diffstr_batch pass
+ * per call; failure as in gdiet_hip_sam_batch. */
+size_t gdiet_hip_paf_batch_seqs(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
+                                const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out);
 
 /* Read input, step 0 of worker_pipeline (LR/map.c:2095-2131): FASTA / FASTQ, plain or gzip ("-" = stdin), one mini-batch per
  * call.  Replaces mm_bseq_open / mm_bseq_read3 / mm_bseq_close (LR/bseq.c:38-58, 80-121) with the same record grammar

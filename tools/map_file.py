@@ -2,7 +2,7 @@
 map with several batches in flight (gdiet_hip_map_submit / _wait) -> SAM records (gdiet_hip_sam_batch) -> output file.
 No Python object is made per read: the C arrays of the reader go straight into the upload and the SAM formatter.
 
-    python tools/map_file.py --preset sr ref.fa reads.fq[.gz] -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4]
+    python tools/map_file.py --preset sr ref.fa reads.fq[.gz] -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
 
 Writes the SAM body (the records; the header lines of the reference's CLI are not part of the path)."""
 import argparse
@@ -158,6 +158,8 @@ def main():
     ap.add_argument("-K", type=int, default=0, help="bases per mini-batch (default: 39321600 for sr = 262144 reads of 150, 80e6 for long reads)")
     ap.add_argument("--inflight", type=int, default=3)
     ap.add_argument("--reader-threads", type=int, default=4)
+    ap.add_argument("--MD", action="store_true", help="MD:Z: tag on every record with a CIGAR (MM_F_OUT_MD)")
+    ap.add_argument("--cs", nargs="?", const="short", choices=["short", "long"], help="cs:Z: tag (MM_F_OUT_CS; long: MM_F_OUT_CS_LONG as well); with --MD, MD is printed")
     a = ap.parse_args()
     pkg = _load_pkg()
     from fixture_io import read_fasta
@@ -168,7 +170,9 @@ def main():
     else:
         names, seqs = read_fasta(a.ref)
     t0 = time.perf_counter()
+    tag_bits = (0x1000000 if a.MD else 0) | (0x40 if a.cs else 0) | (0x800 if a.cs == "long" else 0)
     m = pkg.Mapper(ctx, names, seqs, preset=a.preset, n_threads=pkg.effective_cpus())
+    m.opt.flag |= tag_bits  # read by the SAM formatter alone (gdiet_hip_sam_batch); the mapping path does not interpret them
     m.set_host_threads(pkg.effective_cpus())
     t_idx = time.perf_counter() - t0
     chunk = a.K or (39321600 if a.preset == "sr" else 80_000_000)
@@ -181,7 +185,7 @@ def main():
         ctx.close()
         sys.exit(1)
     print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), "mini_batch_bases": chunk,
-                      "inflight": a.inflight, "reader_threads": a.reader_threads, "out": a.out, "caller_seconds": map_file.last_stage_seconds}))
+                      "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "out": a.out, "caller_seconds": map_file.last_stage_seconds}))
     m.close()
     ctx.close()
 
