@@ -16,6 +16,7 @@
 #define GD_F_NO_PRINT_2ND 0x4000
 #define GD_F_SR 0x1000
 #define GD_F_FRAG_MODE 0x2000
+#define GD_F_EQX 0x4000000 // interpreted with GD_F_SR only (SR/map.c:954; the LongReads tree rewrites before concatenate_cigars: not built)
 #define GD_NEG_INF_SCORE (-0x40000000)
 
 // the fields of mm_mapopt_t / mm_idxopt_t the path reads (LR/minimap.h:137-214)
@@ -197,13 +198,20 @@ static inline void gd_apply_post(GdReg &r, const GdPostOut &P)
 	r.mlen = P.mlen, r.blen = P.blen, r.n_ambi += P.n_ambi, r.dp_max = P.dp_max;
 }
 
-static inline void gd_update_extra(GdReg &r, const uint8_t *qseq, const uint8_t *tseq, const int8_t *mat, int8_t q, int8_t e, int log_gap)
+static inline void gd_update_extra(GdReg &r, const uint8_t *qseq, const uint8_t *tseq, const int8_t *mat, int8_t q, int8_t e, int log_gap, int is_eqx = 0)
 {
 	if (!r.has_p) return;
 	uint32_t n = (uint32_t)r.cigar.size();
 	GdPostOut P;
 	gdp_update_extra(r.cigar.data(), &n, qseq, tseq, mat, q, e, log_gap, &P);
 	r.cigar.resize(n);
+	if (is_eqx && n > 0) { // mm_update_cigar_eqx, SR/align.c:315-317: the vector stands for the device's qlen + tlen slot
+		uint32_t n_eqx, n_m;
+		const uint32_t n_new = gdp_cigar_eqx_count(r.cigar.data(), n, qseq + P.qshift, tseq + P.tshift, &n_eqx, &n_m);
+		r.cigar.resize(n_new > n ? n_new : n);
+		gdp_cigar_eqx_write(r.cigar.data(), n, n_new, n_eqx, n_m, qseq + P.qshift, tseq + P.tshift);
+		r.cigar.resize(n_new);
+	}
 	gd_apply_post(r, P);
 }
 
@@ -488,7 +496,7 @@ static inline void gd_lr_finish(std::vector<GdCand> &C, const std::vector<GdDpRe
 			tseq.assign((size_t)c.tlen + 16, 0);
 			gd_getseq(R, c.target_id, c.target_start, c.target_end + 1, tseq.data());
 			const uint8_t *qseq = (c.v.str ? enc_rev : enc_for) + c.qseq_off;
-			gd_update_extra(r, qseq, tseq.data(), mat, (int8_t)O.q, (int8_t)O.e, !(O.flag & GD_F_SR));
+			gd_update_extra(r, qseq, tseq.data(), mat, (int8_t)O.q, (int8_t)O.e, !(O.flag & GD_F_SR), (O.flag & GD_F_SR) && (O.flag & GD_F_EQX));
 		}
 		const uint32_t clip0 = r.rev ? qlen_sum - r.qe : (uint32_t)r.qs, clip1 = r.rev ? (uint32_t)r.qs : qlen_sum - r.qe;
 		if (!(clip0 < qlen_sum && clip1 < qlen_sum)) { c.valid = 0; continue; }
@@ -569,7 +577,7 @@ static inline void gd_sr_finish(std::vector<GdCand> &C, const std::vector<GdDpRe
 			tseq.assign((size_t)c.tlen + 16, 0);
 			gd_getseq(R, c.target_id, c.target_start, c.target_end + 1, tseq.data());
 			const uint8_t *qseq = (c.v.str ? enc_rev : enc_for) + c.qseq_off;
-			gd_update_extra(r, qseq, tseq.data(), mat, (int8_t)O.q, (int8_t)O.e, !(O.flag & GD_F_SR));
+			gd_update_extra(r, qseq, tseq.data(), mat, (int8_t)O.q, (int8_t)O.e, !(O.flag & GD_F_SR), (O.flag & GD_F_SR) && (O.flag & GD_F_EQX));
 		}
 		const uint32_t clip0 = r.rev ? qlen_sum - r.qe : (uint32_t)r.qs, clip1 = r.rev ? (uint32_t)r.qs : qlen_sum - r.qe;
 		if (!(clip0 < qlen_sum && clip1 < qlen_sum) || r.dp_score < O.min_dp_max) continue;

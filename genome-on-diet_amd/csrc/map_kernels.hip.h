@@ -403,7 +403,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(32))) void map_p
 // right behind the backtrack.  The CIGAR is rewritten in its slot, n_cigar updated, and the scalars the host needs for the record
 // (shifts of qs / qe / rs, mlen, blen, n_ambi, dp_max) land in post[b].  The windows are the ones the DP read (qbuf / tbuf): the
 // host then needs neither the 4-bit reference nor the reverse-complemented read for P1.
+// EQX (MM_F_EQX of the ShortReads variant, SR/map.c:954): mm_update_cigar_eqx behind it -- the M operations become runs of = and X in the
+// slot (qlen + tlen words: every operation consumes a base of the read or of the reference, so the rewritten CIGAR fits; one that would
+// not is left as it is with its length reported, and the host answers GDIET_E_CIGAR_CAP).  EQX = false is the kernel without any of this.
 struct MapPostOpt { int8_t mat[25]; int8_t q, e; int32_t log_gap; };
+template <bool EQX>
 __global__ __launch_bounds__(64) void map_post_kernel(int nb, const MapBox *__restrict__ boxes, const uint8_t *__restrict__ qbuf, const uint8_t *__restrict__ tbuf,
                                                       const int64_t *__restrict__ coff, uint32_t *__restrict__ cig, int32_t *__restrict__ n_cigar,
                                                       const int32_t *__restrict__ score, MapPostOpt O, GdPostOut *__restrict__ post,
@@ -417,6 +421,13 @@ __global__ __launch_bounds__(64) void map_post_kernel(int nb, const MapBox *__re
 	if (score[b] != GD_NEG_INF_SCORE_DEV && n0 > 0 && (int64_t)n0 <= coff[b + 1] - coff[b]) { // (an overflowing CIGAR is reported by the host)
 		uint32_t n = (uint32_t)n0;
 		gdp_update_extra(cig + coff[b], &n, qbuf + boxes[b].q_dst, tbuf + boxes[b].t_dst, O.mat, O.q, O.e, O.log_gap, &P);
+		if (EQX) {
+			const uint8_t *qs = qbuf + boxes[b].q_dst + P.qshift, *ts = tbuf + boxes[b].t_dst + P.tshift;
+			uint32_t n_eqx, n_m;
+			const uint32_t n_new = gdp_cigar_eqx_count(cig + coff[b], n, qs, ts, &n_eqx, &n_m);
+			if ((int64_t)n_new <= coff[b + 1] - coff[b]) gdp_cigar_eqx_write(cig + coff[b], n, n_new, n_eqx, n_m, qs, ts);
+			n = n_new;
+		}
 		n_cigar[b] = (int32_t)n;
 	}
 	post[b] = P;

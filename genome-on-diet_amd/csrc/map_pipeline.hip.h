@@ -843,7 +843,8 @@ static int gd_stage_dp(GdMapCall &c)
 	// long alignments: one wavefront per alignment (mm_fix_cigar on lane 0, the walk over the bases by all lanes: 22 -> ~2 ms per HiFi
 	// batch); short reads keep one alignment per thread (hundreds of thousands of 150-base walks).  GDIET_POST_WAVE=0 / 1 forces one.
 	static const char *pw_env = getenv("GDIET_POST_WAVE");
-	const bool post_wave = pw_env ? atoi(pw_env) != 0 : T.coff[nb] / std::max(nb, 1) >= 2000;
+	const bool eqx = c.is_sr && (O.flag & GD_F_EQX); // (--eqx: the ShortReads variant only; its rewrite is part of the thread-per-alignment kernel)
+	const bool post_wave = !eqx && (pw_env ? atoi(pw_env) != 0 : T.coff[nb] / std::max(nb, 1) >= 2000);
 	const bool xport = (ctx->last_mask & 8) != 0;
 	if (xport) {
 		const size_t need = sizeof(GdPostOut) * (size_t)nb + sizeof(int32_t) * 2 * nbp + 256;
@@ -868,7 +869,9 @@ static int gd_stage_dp(GdMapCall &c)
 		hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
 		                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
 	}
-	else hipLaunchKernelGGL(map_post_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
+	else if (eqx) hipLaunchKernelGGL(map_post_kernel<true>, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
+	                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
+	else hipLaunchKernelGGL(map_post_kernel<false>, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
 	                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
 	if (!exported) {
 		GD_HIP(hipMemcpyAsync(ctx->h_post.p, ctx->m_post.p, sizeof(GdPostOut) * (size_t)nb, hipMemcpyDeviceToHost, sd));

@@ -203,3 +203,106 @@ GDP_HD void gdp_update_extra(uint32_t *cg, uint32_t *n_io, const uint8_t *qseq, 
 	out->qshift = qshift, out->tshift = tshift, out->mlen = mlen, out->blen = blen, out->n_ambi = n_ambi_tot;
 	out->dp_max = (int32_t)(mx + .499);
 }
+
+// ---- mm_update_cigar_eqx (SR/align.c:174-257; --eqx of the ShortReads variant): every M becomes its runs of = (7) and X (8) -------------
+// Called where the reference calls it (SR/align.c:315-317): behind mm_update_extra, on the CIGAR as gdp_fix_cigar leaves it (no
+// zero-length operation) and on the sequences moved by the shifts that function returned.  "Equal" is equality of the two bytes, as in the
+// reference: an N of a forward read (4) against a target N (4) is =, an N of a reverse-complemented read (7: SR/map.c:748,755, and what the
+// device windows hold) against a target N is X.
+// bit j of the result: byte j of a and b differ
+GDP_HD uint32_t gdp_diff8(uint64_t a, uint64_t b)
+{
+	const uint64_t x = a ^ b;
+	const uint64_t h = (((x & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | x) & 0x8080808080808080ull;
+	return (uint32_t)(((h >> 7) * 0x0102040810204080ull) >> 56);
+}
+
+// The reference's first pass (:180-210): the number of = / X runs of all M operations (*n_eqx) and of M operations (*n_m); returns the
+// length of the rewritten CIGAR.  Eight bases per load: a group adds the number of places where its difference mask changes.
+GDP_HD uint32_t gdp_cigar_eqx_count(const uint32_t *cg, uint32_t n, const uint8_t *qseq, const uint8_t *tseq, uint32_t *n_eqx, uint32_t *n_m)
+{
+	uint32_t toff = 0, qoff = 0, runs = 0, n_M = 0;
+	for (uint32_t k = 0; k < n; ++k) {
+		const uint32_t op = cg[k] & 0xf, len = cg[k] >> 4;
+		if (op == 0) {
+			uint32_t prev = 0, l = 0;
+			bool first = true;
+			for (; l + 8 <= len; l += 8) {
+				uint64_t a, b;
+				__builtin_memcpy(&a, qseq + qoff + l, 8), __builtin_memcpy(&b, tseq + toff + l, 8);
+				const uint32_t m = gdp_diff8(a, b);
+				runs += (uint32_t)__builtin_popcount((m ^ (m << 1 | (first ? ~m & 1 : prev))) & 0xff);
+				prev = m >> 7, first = false;
+			}
+			for (; l < len; ++l) {
+				const uint32_t d = qseq[qoff + l] != tseq[toff + l];
+				runs += first || d != prev;
+				prev = d, first = false;
+			}
+			++n_M;
+			toff += len, qoff += len;
+		} else if (op == 1) qoff += len;
+		else if (op == 2 || op == 3) toff += len;
+	}
+	*n_eqx = runs, *n_m = n_M;
+	return runs == n_M ? n : n + runs - n_M; // (:212 and :220; runs >= n_M where no M is empty)
+}
+
+// The reference's second half on the slot itself (it copies into a new allocation: :219-256).  Count rule (:212-218): as many runs as M
+// operations -- every M is relabelled =, whatever its bases are.  Otherwise the CIGAR grows to n_new = gdp_cigar_eqx_count(...) operations in
+// place, written from the last operation backwards: operation k's runs end where operation k + 1's begin, and as every operation in
+// front of k yields at least one, nothing is written over an operation not yet read.  cg must have room for n_new words.
+GDP_HD void gdp_cigar_eqx_write(uint32_t *cg, uint32_t n, uint32_t n_new, uint32_t n_eqx, uint32_t n_m, const uint8_t *qseq, const uint8_t *tseq)
+{
+	if (n_eqx == n_m) {
+		for (uint32_t k = 0; k < n; ++k)
+			if ((cg[k] & 0xf) == 0) cg[k] = cg[k] >> 4 << 4 | 7;
+		return;
+	}
+	uint32_t toff = 0, qoff = 0;
+	for (uint32_t k = 0; k < n; ++k) { // the ends of the two sequences
+		const uint32_t op = cg[k] & 0xf, len = cg[k] >> 4;
+		if (op == 0) toff += len, qoff += len;
+		else if (op == 1) qoff += len;
+		else if (op == 2 || op == 3) toff += len;
+	}
+	uint32_t m = n_new;
+	for (uint32_t k = n; k-- > 0;) { // (n_new - n + n_M runs and n - n_M other operations: exactly n_new stores)
+		const uint32_t c = cg[k], op = c & 0xf, len = c >> 4;
+		if (op != 0) {
+			if (op == 1) qoff -= len;
+			else if (op == 2 || op == 3) toff -= len;
+			cg[--m] = c;
+			continue;
+		}
+		toff -= len, qoff -= len;
+		uint32_t cur = 0, cnt = 0, l = len; // the run being collected, from the M's last base towards its first
+		while (l >= 8) {
+			l -= 8;
+			uint64_t a, b;
+			__builtin_memcpy(&a, qseq + qoff + l, 8), __builtin_memcpy(&b, tseq + toff + l, 8);
+			const uint32_t d8 = gdp_diff8(a, b);
+			if (cnt && d8 == (cur ? 0xffu : 0u)) { cnt += 8; continue; }
+			for (int j = 7; j >= 0; --j) {
+				const uint32_t d = d8 >> j & 1;
+				if (cnt && d != cur) { cg[--m] = cnt << 4 | (cur ? 8 : 7); cnt = 0; }
+				cur = d, ++cnt;
+			}
+		}
+		while (l > 0) {
+			--l;
+			const uint32_t d = qseq[qoff + l] != tseq[toff + l];
+			if (cnt && d != cur) { cg[--m] = cnt << 4 | (cur ? 8 : 7); cnt = 0; }
+			cur = d, ++cnt;
+		}
+		if (cnt) cg[--m] = cnt << 4 | (cur ? 8 : 7);
+	}
+}
+
+GDP_HD void gdp_cigar_eqx(uint32_t *cg, uint32_t *n_io, const uint8_t *qseq, const uint8_t *tseq)
+{
+	uint32_t n_eqx, n_m;
+	const uint32_t n = *n_io, n_new = gdp_cigar_eqx_count(cg, n, qseq, tseq, &n_eqx, &n_m);
+	gdp_cigar_eqx_write(cg, n, n_new, n_eqx, n_m, qseq, tseq);
+	*n_io = n_new;
+}

@@ -13,6 +13,7 @@ from .hip_abi import GdietError, load_library
 F_NO_PRINT_2ND = 0x4000
 F_OUT_CS, F_OUT_CS_LONG, F_OUT_MD, F_QSTRAND = 0x40, 0x800, 0x1000000, 0x100000000  # --cs, --cs=long (with F_OUT_CS), --MD, --qstrand
 F_SR, F_FRAG_MODE = 0x1000, 0x2000
+F_EQX = 0x4000000  # --eqx: =/X in place of M; interpreted with F_SR only, e.g. Mapper(..., preset="sr", flag=F_SR | F_FRAG_MODE | F_EQX)
 
 
 class MapOpt(C.Structure):

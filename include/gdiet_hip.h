@@ -240,7 +240,12 @@ uint64_t gdiet_hip_index_n_keys(const gdiet_index *idx);
 
 /* the fields of mm_mapopt_t (LR/minimap.h:145-214) this path reads; fill them from the reference's struct */
 typedef struct {
-	int64_t flag;                 /* MM_F_* bits; only NO_PRINT_2ND, SR (selects the variant), FRAG_MODE, FOR_ONLY, REV_ONLY are interpreted */
+	int64_t flag;                 /* MM_F_* bits; only NO_PRINT_2ND, SR (selects the variant), FRAG_MODE, FOR_ONLY, REV_ONLY and, with SR, EQX are
+	                               * interpreted.  MM_F_EQX (0x4000000, --eqx) with MM_F_SR: every entry point that maps (gdiet_hip_map_batch, _map_uploaded,
+	                               * _map_submit / _map_wait, _map_batch_multi, _map_frag) returns CIGARs with = (7) and X (8) in place of M, as
+	                               * mm_update_cigar_eqx writes them (SR/align.c:174-257, its count-based shortcut included); n_cigar is the rewritten length,
+	                               * no other field of a record changes.  Without MM_F_SR the bit is NOT interpreted: the LongReads tree rewrites before
+	                               * concatenate_cigars, which knows no = / X, and aborts under --eqx --MD. */
 	int32_t a, b, q, e, q2, e2;
 	uint32_t bw;
 	int32_t min_dp_max, best_n;

@@ -57,7 +57,10 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--inflight", type=int, default=1)
     ap.add_argument("--host-threads", type=int, default=0)
+    ap.add_argument("--eqx", action="store_true", help="--kind sr: MM_F_EQX, =/X CIGARs written by the EQX form of map_post_kernel")
     a = ap.parse_args()
+    if a.eqx and a.kind != "sr":
+        ap.error("--eqx is interpreted for --kind sr only")
     n = a.batch or (262144 if a.kind == "sr" else 12288)
     pkg = _load_pkg()
     ctx = pkg.Context(0)
@@ -66,6 +69,8 @@ def main():
     m = pkg.Mapper(ctx, names, contigs, preset=a.kind, n_threads=pkg.effective_cpus())
     t_idx = time.time() - t0
     m.set_host_threads(a.host_threads or pkg.effective_cpus())
+    if a.eqx:
+        m.opt.flag |= 0x4000000
     reads = synth_reads(np.random.default_rng(7), contigs, n, a.kind)
     batch = m.upload(reads)
     bases = sum(len(r) for r in reads)
@@ -98,7 +103,7 @@ def main():
     dp, bt = ctx.last_kernel_ms()
     cells, alg = ctx.last_dp_work()
     s = np.mean(np.array(st), axis=0)
-    print(json.dumps({"kind": a.kind, "reads_per_step": n, "bases_per_step": bases, "mapped_fraction": mapped / bases, "ms_per_step": 1e3 * dt,
+    print(json.dumps({"kind": a.kind, "eqx": a.eqx, "reads_per_step": n, "bases_per_step": bases, "mapped_fraction": mapped / bases, "ms_per_step": 1e3 * dt,
                       "mapped_Mbases_per_s": mapped / dt / 1e6, "reads_per_s": n / dt, "index_build_s": round(t_idx, 1), "ref_mbp": a.ref_mbp,
                       "stage_ms": {"seed": 1e3 * s[0], "vote": 1e3 * s[1], "host_geometry": 1e3 * s[2], "gather_dp_backtrack": 1e3 * s[3],
                                    "host_post": 1e3 * s[4], "other": 1e3 * s[5]},

@@ -160,7 +160,10 @@ def main():
     ap.add_argument("--reader-threads", type=int, default=4)
     ap.add_argument("--MD", action="store_true", help="MD:Z: tag on every record with a CIGAR (MM_F_OUT_MD)")
     ap.add_argument("--cs", nargs="?", const="short", choices=["short", "long"], help="cs:Z: tag (MM_F_OUT_CS; long: MM_F_OUT_CS_LONG as well); with --MD, MD is printed")
+    ap.add_argument("--eqx", action="store_true", help="=/X in place of M in every CIGAR (MM_F_EQX); --preset sr only, as in the reference's ShortReads tree")
     a = ap.parse_args()
+    if a.eqx and a.preset != "sr":
+        ap.error("--eqx is interpreted for --preset sr only (the LongReads variant does not interpret MM_F_EQX)")
     pkg = _load_pkg()
     from fixture_io import read_fasta
     ctx = pkg.Context(0)
@@ -173,6 +176,8 @@ def main():
     tag_bits = (0x1000000 if a.MD else 0) | (0x40 if a.cs else 0) | (0x800 if a.cs == "long" else 0)
     m = pkg.Mapper(ctx, names, seqs, preset=a.preset, n_threads=pkg.effective_cpus())
     m.opt.flag |= tag_bits  # read by the SAM formatter alone (gdiet_hip_sam_batch); the mapping path does not interpret them
+    if a.eqx:
+        m.opt.flag |= 0x4000000  # MM_F_EQX: read by the mapping path (the CIGARs are rewritten on the device)
     m.set_host_threads(pkg.effective_cpus())
     t_idx = time.perf_counter() - t0
     chunk = a.K or (39321600 if a.preset == "sr" else 80_000_000)
@@ -185,7 +190,7 @@ def main():
         ctx.close()
         sys.exit(1)
     print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), "mini_batch_bases": chunk,
-                      "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "out": a.out, "caller_seconds": map_file.last_stage_seconds}))
+                      "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "eqx": a.eqx, "out": a.out, "caller_seconds": map_file.last_stage_seconds}))
     m.close()
     ctx.close()
 
