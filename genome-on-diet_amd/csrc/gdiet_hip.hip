@@ -108,6 +108,10 @@ struct gdiet_ctx {
 	int seed_thread_kernel = 0;
 	double stage_s[6] = {0, 0, 0, 0, 0, 0};
 	uint64_t last_cells = 0, last_alg_bytes = 0; // of the most recent DP launch
+	int narrow_band = 1;               // GDIET_NARROW_BAND=0: the 64-lane DP kernel runs every alignment at its full band (ksw_wave.hip.h, "NARROW BAND FIRST")
+	DevBuf narrow_cnt;                 // two counters of the most recent 64-lane DP launch: alignments that tried the narrow band, certified ones
+	bool narrow_launched = false;      // that launch had a 64-lane kernel at all
+	uint64_t async_narrow[2] = {0, 0}; // the lane's counters, copied at gdiet_hip_map_wait
 	// reads the most recent map call gave up on (a DP box outside its read / contig: undefined behaviour in the reference); they come back
 	// with n_regs = 0 while the rest of the batch is mapped.  failed_total: since the context was created.
 	int64_t failed_last = 0, failed_total = 0;
@@ -242,6 +246,8 @@ extern "C" int gdiet_hip_init(gdiet_ctx **out, int device)
 		if (ib) ctx->index_on_device = strcmp(ib, "host") != 0;
 		const char *sb = getenv("GDIET_SR_BOXES");
 		if (sb) ctx->sr_boxes_on_device = strcmp(sb, "host") != 0;
+		const char *nb = getenv("GDIET_NARROW_BAND");
+		if (nb) ctx->narrow_band = atoi(nb) != 0;
 	}
 	*out = ctx;
 	return GDIET_OK;
@@ -452,9 +458,16 @@ static int gd_dp_launch(gdiet_ctx *ctx, const GdPlan &P, int n, const KswConst &
 	// The 64-lane, two-wavefront and two-blocks-per-lane kernels walk their own alignments back (status TRACED: the backtrack below skips them).
 	const int n64 = (int)P.n_kind[GD_KIND_WAVE64];
 	const bool single = ctx->single_affine && K.q == K.q2 && K.e == K.e2;
-	if (n64 > 0)
+	ctx->narrow_launched = false;
+	ctx->last_was_async = false; // this context's own launch is now its most recent one (a lane's flag is never set; gdiet_hip_map_wait sets the root's after the lane's batch)
+	if (n64 > 0) {
+		if ((rc = gd_grow(ctx, ctx->narrow_cnt, 2 * sizeof(uint32_t)))) return rc;
+		GD_HIP(hipMemsetAsync(ctx->narrow_cnt.p, 0, 2 * sizeof(uint32_t), stream));
+		ctx->narrow_launched = true;
 		gd_launch_wave64(d_tasks, d_ids + P.id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
-		                 ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves);
+		                 ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves, (ctx->parent ? ctx->parent->narrow_band : ctx->narrow_band) ? GD_W_NARROW : 0,
+		                 (uint32_t *)ctx->narrow_cnt.p);
+	}
 	if (P.n_kind[GD_KIND_WAVE16]) {
 		// The short-alignment kernels CAN walk their own alignments back (every group's first lane, gd_bt_thread_walk), but it does not pay:
 		// a wavefront then holds its slot for a few hundred dependent steps of six lanes -- DP kernel 7.6 -> 10.8 ms per 262 144 short reads
@@ -627,6 +640,23 @@ extern "C" int gdiet_hip_last_dp_work(const gdiet_ctx *ctx, uint64_t *cells, uin
 	if (!ctx) return GDIET_E_PARAM;
 	if (cells) *cells = ctx->last_cells;
 	if (alg_bytes) *alg_bytes = ctx->last_alg_bytes;
+	return GDIET_OK;
+}
+
+// the narrow-band counters of the most recent DP launch (call after the batch has completed)
+extern "C" int gdiet_hip_last_narrow_band(gdiet_ctx *ctx, uint64_t *tried, uint64_t *certified)
+{
+	if (!ctx) return GDIET_E_PARAM;
+	uint64_t v[2] = {0, 0};
+	if (ctx->last_was_async) v[0] = ctx->async_narrow[0], v[1] = ctx->async_narrow[1];
+	else if (ctx->narrow_launched && ctx->narrow_cnt.p) {
+		uint32_t h[2] = {0, 0};
+		(void)hipSetDevice(ctx->device);
+		GD_HIP(hipMemcpy(h, ctx->narrow_cnt.p, sizeof(h), hipMemcpyDeviceToHost));
+		v[0] = h[0], v[1] = h[1];
+	}
+	if (tried) *tried = v[0];
+	if (certified) *certified = v[1];
 	return GDIET_OK;
 }
 

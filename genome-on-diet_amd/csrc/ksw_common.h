@@ -23,7 +23,7 @@ struct KswTask {
 	int32_t cig_cap;      // capacity of the CIGAR slot in ops
 	int32_t exact_score;  // GD_NEG_INF: no exact-match pre-filter
 	int32_t kind;         // GD_KIND_*
-	int32_t pad;
+	int32_t pad;          // 64-lane kernel: GD_NARROW_* (ksw_wave_core.h), set by the planner; 0 elsewhere
 };
 
 // Scoring constants after the reference's normalisation (SR/ksw2_extd2_sse.c:78-105)

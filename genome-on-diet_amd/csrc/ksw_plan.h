@@ -96,7 +96,7 @@ static void gd_plan_batch(GdPlan &P, const GdPlanOpt &O, int n, const int64_t *h
 	std::vector<PlanSlice> slices((size_t)n_sl);
 	{
 		run_slices(n_sl, [&](int sl) {
-			struct { int qlen = -1, tlen = -1, w = 0; int32_t kind = 0, row_bytes = 0; } memo;
+			struct { int qlen = -1, tlen = -1, w = 0; int32_t kind = 0, row_bytes = 0, narrow = 0; } memo;
 			PlanSlice &S = slices[sl];
 			const int i0 = (int)((int64_t)n * sl / n_sl), i1 = (int)((int64_t)n * (sl + 1) / n_sl);
 			for (int k = 0; k < 4; ++k) S.ids[k].reserve((size_t)(i1 - i0));
@@ -109,10 +109,13 @@ static void gd_plan_batch(GdPlan &P, const GdPlanOpt &O, int n, const int64_t *h
 				T.exact_score = h_ex ? h_ex[i] : GD_NEG_INF;
 				T.pad = 0, T.bt_off = 0;
 				if (T.qlen <= 0 || T.tlen <= 0) { S.err |= 1; continue; } // (refused below)
-				if (T.qlen == memo.qlen && T.tlen == memo.tlen && T.w == memo.w) T.kind = memo.kind, T.row_bytes = memo.row_bytes;
+				if (T.qlen == memo.qlen && T.tlen == memo.tlen && T.w == memo.w) T.kind = memo.kind, T.row_bytes = memo.row_bytes, T.pad = memo.narrow;
 				else {
 					gd_plan_one(O, T.qlen, T.tlen, T.w, T.kind, T.row_bytes);
-					memo.qlen = T.qlen, memo.tlen = T.tlen, memo.w = T.w, memo.kind = T.kind, memo.row_bytes = T.row_bytes;
+					// the 64-lane kernel's boxes that try the band GD_W_NARROW first, or run their own narrow band on the half-block rows (the
+					// kernel's argument decides whether it looks at the mark; the slot is sized for the full-band rows either way)
+					T.pad = T.kind == GD_KIND_WAVE64 && !O.single_affine ? gd_narrow_mode(T.qlen, T.tlen, T.w) : GD_NARROW_NO;
+					memo.qlen = T.qlen, memo.tlen = T.tlen, memo.w = T.w, memo.kind = T.kind, memo.row_bytes = T.row_bytes, memo.narrow = T.pad;
 				}
 				if (O.kernel_mode == 2 && T.kind == GD_KIND_GENERIC) S.err |= 2;
 				if (T.kind == GD_KIND_GENERIC) {

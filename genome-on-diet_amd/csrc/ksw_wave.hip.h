@@ -53,6 +53,122 @@ __device__ __forceinline__ const uint8_t *gdw_uniform_ptr(const uint8_t *p, int 
 	return (const uint8_t *)((uintptr_t)hi << 32 | lo);
 }
 
+// ---- the narrow form of the 64-lane kernel: one HALF block per lane (ksw_wave_core.h, "the narrow form") ---------------------------
+// The DP rows of one alignment at band w <= GD_W_NARROW on a ring of 64 half blocks: the row loop of ksw_extd2_wave_kernel<64> -- general
+// rows at the corners of the matrix, paired steady rows in the middle -- with four packed registers per state array.  Backtrace rows
+// of 512 bytes from bt_rsrc's base.  Returns 8 x the score, wave-uniform.  tests/emul/narrow_emul.cpp mirrors it statement by statement.
+__device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *query_u /* wave-uniform copy */, const uint8_t *query, int qlen,
+                                               const uint8_t *target, int tlen, int w, int lane, __amdgpu_buffer_rsrc_t bt_rsrc)
+{
+	typedef u32 gdw_u32x2 __attribute__((ext_vector_type(2)));
+	const int rend = qlen + tlen - 2, mlast = (tlen - 1) >> 4, sl = (tlen - 1) & 15;
+	WaveHalf H;
+	gdw_load_half(H, K, lane >> 1, lane & 1, 0, query, qlen, target, tlen);
+	bool any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
+	int prev_st_ = 0, prev_st0 = -1, prev_up = -1, prev_en0 = -1, have_f = 0, Rf = 0;
+	auto store_row = [&](const int r, const u32 out[2]) __attribute__((always_inline)) {
+		const gdw_u32x2 d = {out[0], out[1]};
+		__builtin_amdgcn_raw_buffer_store_b64(d, bt_rsrc, lane * 8, r * 512, 0);
+	};
+	auto dp_row = [&](const int r, auto steady_tag) __attribute__((always_inline)) {
+		constexpr bool STEADY = decltype(steady_tag)::value;
+		WaveRow W;
+		W.r = r;
+		gdw_band_uniform(r, qlen, tlen, w, W.st0, W.en0);
+		W.st_ = W.st0 >> 4, W.en_ = W.en0 >> 4;
+		W.up = W.st0 + (((W.en0 - W.st0 + 16) >> 4) << 4);
+		const int advanced = W.st_ > prev_st_;
+		W.use_array = advanced;
+		W.v1key = STEADY ? K.key_open : (W.st_ == 0 ? gdw_edge_key(K, r) : K.key_open);
+		W.set_tr = STEADY ? 0 : (W.en0 | 15) >= r;
+		W.ukey = STEADY ? 0 : gdw_edge_key(K, r);
+		const u32 pX = gdw_ror1<64>(H.X[3]), pV = gdw_ror1<64>(H.V[3]), pX2 = gdw_ror1<64>(H.X2[3]), pQ = gdw_ror1<64>(H.Qc[1]);
+		if (STEADY || r > 0) gdw_shift_query_half(H, pQ, H.blk == prev_st_ && H.half == 0, gdw_seam_byte(query_u, qlen, r - (prev_st_ << 4)));
+		if (advanced) { // the two lanes whose block fell below the window take over block +32
+			if (H.blk < W.st_) gdw_load_half(H, K, H.blk + 32, H.half, r, query, qlen, target, tlen);
+			any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
+		}
+		if (!STEADY && W.set_tr) gdw_reset_tr_half(H, K, W);
+		if (W.st0 != prev_st0 || W.up != prev_up || advanced) gdw_make_sel_half(H, W.st0, W.up);
+		gdw_update_scores_half(H, K, any_tn);
+		if (H.blk <= W.en_) {
+			u32 out[2];
+			gdw_compute_half<true>(H, K, W, pX, pV, pX2, out);
+			store_row(r, out);
+		}
+		if (!STEADY && r == 0) H.R = gdw_lo(H.V[0]) - K.B1 - K.qe8;
+		else H.R += gdw_lo(H.V[0]) - K.B1;
+		if ((STEADY || r > 0) && W.en0 != prev_en0 && (W.en0 & 7) == 0) { // a half block enters the band
+			const int hh = (int)gdw_ror1<64>((u32)gdw_track_handoff_half(H));
+			if (H.blk == W.en_ && H.half == ((W.en0 >> 3) & 1)) H.R = hh + gdw_lo(H.U[0]);
+		}
+		if (!STEADY && W.en0 == tlen - 1) {
+			if (H.blk == mlast && H.half == (sl >> 3)) {
+				if (!have_f) Rf = gdw_track_to_slot_half(H, sl & 7);
+				else Rf += gdw_cell_half(H.V, sl & 7) - K.B1;
+			}
+			have_f = 1;
+		}
+		prev_st_ = W.st_, prev_st0 = W.st0, prev_up = W.up, prev_en0 = W.en0;
+	};
+	const int nblkA = (w - 1 + 16) >> 4, nblkB = (w + 16) >> 4;
+	u32 m_lowest = 0; // 0 / ~0: this lane holds the first half of the lowest block of the window (of the row just done)
+	auto pair_row = [&](const int r, const int m, auto a_tag) __attribute__((always_inline)) {
+		constexpr bool ROW_A = decltype(a_tag)::value;
+		WaveRow W;
+		W.r = r, W.st0 = m, W.en0 = ROW_A ? m + w - 1 : m + w;
+		W.st_ = m >> 4, W.en_ = W.en0 >> 4;
+		W.up = m + ((ROW_A ? nblkA : nblkB) << 4);
+		const int advanced = ROW_A && (m & 15) == 0;
+		const int pst_ = W.st_ - advanced; // st_ of the row before
+		W.use_array = advanced, W.v1key = K.key_open, W.set_tr = 0, W.ukey = 0;
+		const u32 pX = gdw_ror1<64>(H.X[3]), pV = gdw_ror1<64>(H.V[3]), pX2 = gdw_ror1<64>(H.X2[3]), pQ = gdw_ror1<64>(H.Qc[1]);
+		gdw_shift_query_half_m(H, pQ, m_lowest, gdw_seam_byte(query_u, qlen, r - (pst_ << 4))); // (the lane mask of the row before: its st_ is this row's pst_)
+		if (advanced) {
+			if (H.blk < W.st_) gdw_load_half(H, K, H.blk + 32, H.half, r, query, qlen, target, tlen);
+			any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
+		}
+		if (ROW_A || nblkA != nblkB) {
+			gdw_make_sel_half(H, W.st0, W.up);
+			m_lowest = (H.blk == W.st_ && H.half == 0) ? ~0u : 0u;
+		}
+		W.m_first_valid = 1, W.m_first_h = m_lowest;
+		gdw_update_scores_half(H, K, any_tn);
+		if (H.blk <= W.en_) {
+			u32 out[2];
+			gdw_compute_half<true>(H, K, W, pX, pV, pX2, out);
+			store_row(r, out);
+		}
+		H.R += gdw_lo(H.V[0]); // (the bias B1 of every V key is taken off once, after the loop)
+		if (!ROW_A && (W.en0 & 7) == 0) {
+			const int hh = (int)gdw_ror1<64>((u32)gdw_track_handoff_half(H));
+			if (H.blk == W.en_ && H.half == ((W.en0 >> 3) & 1)) H.R = hh + gdw_lo(H.U[0]);
+		}
+	};
+	{
+		int rA, rS;
+		gdw_steady_rows(qlen, tlen, w, rA, rS);
+		const int t1_ = tlen - 1, rB0 = 2 * t1_ - w, rB = rB0 > t1_ ? rB0 : t1_;
+		int r = 0;
+		for (; r <= rend && r < rA; ++r) dp_row(r, std::false_type());
+		if (r == rA && rS > rA) {
+			int m = (rA - w + 1) >> 1;
+			m_lowest = (H.blk == prev_st_ && H.half == 0) ? ~0u : 0u;
+			for (; r < rS; r += 2, ++m) {
+				pair_row(r, m, std::true_type());
+				pair_row(r + 1, m, std::false_type());
+			}
+			H.R -= (rS - rA) * K.B1;
+			--m; // the band of the last row, for the rows that follow
+			prev_st_ = m >> 4, prev_st0 = m, prev_up = m + (nblkB << 4), prev_en0 = m + w;
+		}
+		for (; r <= rend && r < rB; ++r) dp_row(r, std::true_type());
+		for (; r <= rend; ++r) dp_row(r, std::false_type());
+	}
+	// the tracker of the last cell lives in the lane of its half block
+	return __builtin_amdgcn_readlane(Rf, (2 * mlast + (sl >> 3)) & 63);
+}
+
 // LANES == 64: one alignment per wavefront (task_ids[slot]).
 // LANES == 16: four alignments OF IDENTICAL GEOMETRY (qlen, tlen, w) per wavefront, one per DPP row of 16 lanes
 //              (task_ids[4*slot + row]; -1 = empty row, which shadows row 0 without storing).  Identical geometry keeps every
@@ -69,6 +185,11 @@ __device__ __forceinline__ const uint8_t *gdw_uniform_ptr(const uint8_t *p, int 
 // DP rows -- four scalar stores per wavefront, nothing kept in registers in between -- so that the clock the kernel really sustained can be
 // reported beside its duration (gdiet_hip_last_dp_clock; bench.py roofline.sclk_mhz; profiles/r03_clock.md).  The table is shared by
 // the contexts of a process: with several DP kernels in flight the stamps of a slot are those of whichever wrote last; any of them do.
+// NARROW BAND FIRST (64-lane form, dual-affine): an alignment the planner marked GD_NARROW_TRY (its band is wider than GD_W_NARROW) runs the
+// half-block rows at band NA.w first, evaluates the certificate (gd_band_certified) on the scalar unit from its own score and, if it holds,
+// walks back from the 512-byte rows: score and CIGAR are provably those of the full band.  If not, the same wavefront goes on with the
+// full-band rows in the same backtrace slot.  GD_NARROW_OWN: the alignment's own band fits the half-block rows.  NA.w == 0: off.
+// narrow_cnt[0] / [1]: alignments that tried the narrow band / whose certificate held, added to by every such wavefront.
 #define GD_CLOCK_SLOTS 16384
 __device__ unsigned long long gd_clock_stamps[GD_CLOCK_SLOTS * 4];
 template <int LANES, int TAG = 0, bool DUAL = true>
@@ -79,7 +200,8 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
                                                              const uint8_t *__restrict__ tseq,
                                                              uint8_t *__restrict__ bt, int32_t *__restrict__ status,
                                                              int32_t *__restrict__ score_out, WaveK K,
-                                                             int32_t *__restrict__ n_cigar, uint32_t *__restrict__ cigar)
+                                                             int32_t *__restrict__ n_cigar, uint32_t *__restrict__ cigar,
+                                                             GdNarrowArg NA, uint32_t *__restrict__ narrow_cnt)
 {
 	constexpr int NG = 64 / LANES; // alignments per wavefront
 	const int lane = threadIdx.x & 63;
@@ -122,6 +244,31 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 			__builtin_amdgcn_raw_buffer_store_b128(d, bt_rsrc, lane * 16, r * (LANES * 16), 0); // (qlen + tlen < 2^21: gd_wave_supported)
 		} else if (live) *reinterpret_cast<uint4 *>(p + (size_t)r * (LANES * 16)) = make_uint4(out[0], out[1], out[2], out[3]);
 	};
+	if constexpr (LANES == 64 && DUAL) {
+		const int mode = NA.w > 0 && cigar != nullptr ? __builtin_amdgcn_readfirstlane(Tp->pad) : GD_NARROW_NO;
+		if (mode != GD_NARROW_NO) {
+			if (mode == GD_NARROW_OWN) NA.w = w;
+			const int s8 = gdw_narrow_rows(K, qg[0], query, qlen, target, tlen, NA.w, lane, bt_rsrc);
+			const bool certified = mode == GD_NARROW_OWN || gd_band_certified(NA, qlen, tlen, s8 >> 3);
+			if (mode == GD_NARROW_TRY && lane == 0) {
+				atomicAdd(narrow_cnt, 1u);
+				if (certified) atomicAdd(narrow_cnt + 1, 1u);
+			}
+			if (certified) {
+				if (lane == 0) {
+					gd_clock_stamps[(tid & (GD_CLOCK_SLOTS - 1)) * 4 + 2] = __builtin_amdgcn_s_memtime(), gd_clock_stamps[(tid & (GD_CLOCK_SLOTS - 1)) * 4 + 3] = __builtin_amdgcn_s_memrealtime();
+					score_out[tid] = s8 >> 3;
+					status[tid] = GD_ST_TRACED;
+				}
+				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); // this wavefront's own backtrace stores
+				GdWalk Wk;
+				gd_walk_init(Wk, qlen, tlen);
+				gd_walk_rows(Wk, *Tp, bt + Tp->bt_off, 0, qlen, tlen, NA.w, cigar, lane, 512, 0, true, true);
+				gd_walk_finish(Wk, *Tp, tid, n_cigar, cigar, lane);
+				return;
+			}
+		}
+	}
 	WaveLane L;
 	gdw_load_block(L, K, sub, 0, query, qlen, target, tlen);
 	bool any_tn = __builtin_amdgcn_ballot_w64(L.tn != 0) != 0; // wave-uniform: does any lane hold a target N?
@@ -278,17 +425,19 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 
 static inline void gd_launch_wave64(const KswTask *tasks, const int32_t *ids, int n, const uint8_t *q, const uint8_t *t,
                                     uint8_t *bt, int32_t *status, int32_t *score, KswConst C, hipStream_t s, bool single,
-                                    int32_t *n_cigar, uint32_t *cigar /* fused backtrack */, int waves_per_simd /* 4: see gdiet_hip_set_dp_waves */)
+                                    int32_t *n_cigar, uint32_t *cigar /* fused backtrack */, int waves_per_simd /* 4: see gdiet_hip_set_dp_waves */,
+                                    int narrow_w /* GD_W_NARROW, or 0: every alignment at its full band */, uint32_t *narrow_cnt /* tried, certified */)
 {
 	WaveK K;
 	gdw_make_consts(C, K);
+	const GdNarrowArg NA = gd_narrow_arg(C, narrow_cnt ? narrow_w : 0);
 	// one wavefront per workgroup: a finished wavefront frees its slot at once instead of waiting for its three block mates
 	const dim3 grid(n), block(64);
 	// Four wavefronts per SIMD instead of five: the kernel uses no LDS, so an (unused) dynamic allocation of a sixteenth of the CU's 160 KB
 	// per wavefront caps the CU at 16 of them; the fifth wavefront's 96 registers per SIMD then stay free for other kernels.
 	const size_t lds = waves_per_simd == 4 ? (size_t)(160 * 1024 / 16) : 0;
-	if (single) hipLaunchKernelGGL((ksw_extd2_wave_kernel<64, 0, false>), grid, block, lds, s, tasks, ids, n, q, t, bt, status, score, K, n_cigar, cigar);
-	else hipLaunchKernelGGL((ksw_extd2_wave_kernel<64, 0>), grid, block, lds, s, tasks, ids, n, q, t, bt, status, score, K, n_cigar, cigar);
+	if (single) hipLaunchKernelGGL((ksw_extd2_wave_kernel<64, 0, false>), grid, block, lds, s, tasks, ids, n, q, t, bt, status, score, K, n_cigar, cigar, NA, narrow_cnt);
+	else hipLaunchKernelGGL((ksw_extd2_wave_kernel<64, 0>), grid, block, lds, s, tasks, ids, n, q, t, bt, status, score, K, n_cigar, cigar, NA, narrow_cnt);
 }
 // ids: 64 / G task ids per wavefront (identical geometry; -1 pads an incomplete group), n_groups wavefronts; G = 16, 10 or 8
 template <int G> static inline void gd_launch_wave_groups(const KswTask *tasks, const int32_t *ids, int n_groups, const uint8_t *q, const uint8_t *t,
@@ -298,8 +447,10 @@ template <int G> static inline void gd_launch_wave_groups(const KswTask *tasks, 
 	WaveK K;
 	gdw_make_consts(C, K);
 	if (n_groups <= 0) return;
-	if (single) hipLaunchKernelGGL((ksw_extd2_wave_kernel<G, 0, false>), dim3((n_groups + 3) / 4), dim3(256), 0, s, tasks, ids, n_groups, q, t, bt, status, score, K, n_cigar, cigar);
-	else hipLaunchKernelGGL((ksw_extd2_wave_kernel<G, 0>), dim3((n_groups + 3) / 4), dim3(256), 0, s, tasks, ids, n_groups, q, t, bt, status, score, K, n_cigar, cigar);
+	const GdNarrowArg NA = gd_narrow_arg(C, 0); // (the 64-lane form only)
+	uint32_t *const narrow_cnt = nullptr;
+	if (single) hipLaunchKernelGGL((ksw_extd2_wave_kernel<G, 0, false>), dim3((n_groups + 3) / 4), dim3(256), 0, s, tasks, ids, n_groups, q, t, bt, status, score, K, n_cigar, cigar, NA, narrow_cnt);
+	else hipLaunchKernelGGL((ksw_extd2_wave_kernel<G, 0>), dim3((n_groups + 3) / 4), dim3(256), 0, s, tasks, ids, n_groups, q, t, bt, status, score, K, n_cigar, cigar, NA, narrow_cnt);
 }
 
 // ---- wide bands (ONT, w = 1300): 128 blocks in flight, TWO per lane ------------------------------------------------------

@@ -718,3 +718,106 @@ GDW_HD int gdw_track_to_slot_half(const WaveHalf &H, int sl)
 // The snapshots keep the 16-cell layout of WaveLane (register k = cells (k, k+8)) whatever held the block: a half block provides
 // the low (half 0) or high (half 1) 16 bits of the eight registers of each array -- cell k of the half is this value.
 GDW_HD u32 gdw_half_cell16(const u32 A[4], int k) { return (k & 4) ? (A[k & 3] >> 16) : (A[k & 3] & 0xffffu); }
+
+// ---- the narrow form of the 64-lane kernel: ONE HALF BLOCK per lane ------------------------------------------------------------------
+// Lane l holds the half block hidx = 2 blk + half with hidx mod 64 == l (half == l & 1 for good, blk mod 32 == l >> 1): a ring of 32
+// blocks, every block split over two neighbouring lanes, so both halves of a block enter and leave the reference's 16-aligned window
+// together and the half below is always the previous lane (wave_ror:1, lane 63 -> lane 0).  Four packed registers per state array: a row
+// costs half the recurrence instructions of the one-block-per-lane form.  Backtrace rows are 64 x 8 bytes, half block hidx at
+// (hidx & 63) * 8, bytes inside a half as gdw_compute_half writes them.
+// GD_W_NARROW: the widest band whose window plus score-row spill fits 32 blocks whatever the geometry -- the rewritten scores [st0, up)
+// span ((w + 16) >> 4) * 16 cells from any st0 mod 16, i.e. at most ((w + 16) >> 4) + 1 blocks (gd_ncol16 for long sequences).
+#define GD_W_NARROW 495
+// The admission test in terms of blocks (the 32-block ring) ...
+static inline bool gd_narrow_supported(int qlen, int tlen, int w)
+{
+	return qlen + tlen < (1 << 21) && gd_wave_geometry_ok(qlen, tlen, w, 32);
+}
+// ... its loop form (block by block; tests/emul/narrow_plan_test.cpp compares the two on random geometries) ...
+static inline bool gd_narrow_supported_loop(int qlen, int tlen, int w)
+{
+	return qlen + tlen < (1 << 21) && gd_wave_geometry_ok_loop(qlen, tlen, w, 32);
+}
+// ... and what the half-block rows themselves need, anti-diagonal by anti-diagonal, which every admitted geometry must satisfy (same
+// test): the band never empties; every half block the score row touches has a lane (a window of at most 64 half blocks from the lowest
+// computed block on); the half block that enters the band finds the tracker of the half below it (the band reaches down to that half's
+// first cell); the walk to the last cell starts in a half whose first cell is in the band.
+static inline bool gd_narrow_rows_ok(int qlen, int tlen, int w)
+{
+	if (w < 0) w = tlen > qlen ? tlen : qlen;
+	if (qlen < 1 || tlen < 1 || w < 1 || qlen + tlen >= (1 << 21)) return false;
+	if (gd_ncol16(qlen, tlen, w) > 32) return false; // (a row of the reference's own backtrace: what the slot is sized for is never less)
+	int prev_en0 = -1, have_f = 0;
+	for (int r = 0; r <= qlen + tlen - 2; ++r) {
+		int st0, en0;
+		gd_band(r, qlen, tlen, w, st0, en0);
+		if (st0 > en0) return false;
+		const int up = st0 + (((en0 - st0 + 16) >> 4) << 4);
+		if (((up - 1) >> 3) - 2 * (st0 >> 4) > 63) return false;
+		if (r > 0 && en0 != prev_en0 && (en0 & 7) == 0 && st0 > en0 - 8) return false;
+		if (en0 == tlen - 1 && !have_f) {
+			if (st0 > ((tlen - 1) & ~7)) return false;
+			have_f = 1;
+		}
+		prev_en0 = en0;
+	}
+	return true;
+}
+
+// The certificate: does the score S' of the alignment in the band wn prove that the alignment in any wider band is the same?  A path
+// that leaves the band |t - q| <= D = wn reaches a diagonal at distance > D on one side and comes back to the end corner at distance
+// delta = tlen - qlen: two gaps of net length >= D and >= D -/+ delta, and what is left of the shorter sequence scores at most a per column.
+//   UB+ = a min(qlen - (D - delta), tlen - D) - cost(D) - cost(D - delta)   (D - delta >= 0)
+//   UB- = a min(qlen - D, tlen - (D + delta)) - cost(D) - cost(D + delta)   (D + delta >= 0)
+//   cost(k) = min(q + k e, q2 + k e2), k > 0; 0 else.
+// With |delta| <= D and S' > max(UB+, UB-) every such path scores below S', so every cell on a co-optimal path has the same value in both
+// bands, and the strict-'>' priority chain and the continuation flags give the same bytes along the walk.
+// (a: the largest entry of the scoring matrix -- sc_mch for every scoring in use)
+struct GdNarrowArg {
+	int32_t w;             // the narrow band to try first (0: off)
+	int32_t a, q, e, q2, e2;
+};
+static inline GdNarrowArg gd_narrow_arg(const KswConst &C, int w)
+{
+	GdNarrowArg A;
+	A.w = w, A.q = C.q, A.e = C.e, A.q2 = C.q2, A.e2 = C.e2;
+	A.a = C.sc_mch > C.sc_mis ? C.sc_mch : C.sc_mis;
+	if (C.sc_N > A.a) A.a = C.sc_N;
+	return A;
+}
+GDW_HD int gd_gap_cost(const GdNarrowArg &A, int k)
+{
+	if (k <= 0) return 0;
+	const int c1 = A.q + k * A.e, c2 = A.q2 + k * A.e2;
+	return c1 < c2 ? c1 : c2;
+}
+GDW_HD bool gd_band_certified(const GdNarrowArg &A, int qlen, int tlen, int score)
+{
+	const int D = A.w, delta = tlen - qlen;
+	if (delta > D || -delta > D) return false;
+	bool ok = true;
+	if (D - delta >= 0) {
+		const int l1 = qlen - (D - delta), l2 = tlen - D;
+		const int ub = A.a * (l1 < l2 ? l1 : l2) - gd_gap_cost(A, D) - gd_gap_cost(A, D - delta);
+		ok = ok && score > ub;
+	}
+	if (D + delta >= 0) {
+		const int l1 = qlen - D, l2 = tlen - (D + delta);
+		const int ub = A.a * (l1 < l2 ? l1 : l2) - gd_gap_cost(A, D) - gd_gap_cost(A, D + delta);
+		ok = ok && score > ub;
+	}
+	return ok;
+}
+
+// what the planner writes into KswTask::pad of an alignment of the 64-lane kernel
+enum : int32_t { GD_NARROW_NO = 0,   // one block per lane at its own band
+                 GD_NARROW_TRY = 1,  // w > GD_W_NARROW: the half-block rows at GD_W_NARROW first, the full band if the certificate fails
+                 GD_NARROW_OWN = 2 };// w <= GD_W_NARROW: the half-block rows at its own band, nothing to certify
+static inline int32_t gd_narrow_mode(int qlen, int tlen, int w)
+{
+	if (w < 0) w = tlen > qlen ? tlen : qlen;
+	if (w <= GD_W_NARROW) return gd_narrow_supported(qlen, tlen, w) ? GD_NARROW_OWN : GD_NARROW_NO;
+	const int delta = tlen - qlen;
+	if (delta > GD_W_NARROW || -delta > GD_W_NARROW) return GD_NARROW_NO;
+	return gd_narrow_supported(qlen, tlen, GD_W_NARROW) ? GD_NARROW_TRY : GD_NARROW_NO;
+}

@@ -1188,7 +1188,8 @@ extern "C" int gdiet_hip_map_wait(gdiet_ctx *ctx, gdiet_map_ticket *t)
 	ctx->last_mask = c->last_mask, ctx->last_cells = c->last_cells, ctx->last_alg_bytes = c->last_alg_bytes;
 	if (!rc && c->last_cells) { // the lane's DP-stage events of this batch (its streams are idle: the thread has joined)
 		ctx->last_was_async = false;
-		if (gdiet_hip_last_kernel_ms(c, &ctx->async_dp_ms, &ctx->async_bt_ms) == GDIET_OK) ctx->last_was_async = true;
+		if (gdiet_hip_last_kernel_ms(c, &ctx->async_dp_ms, &ctx->async_bt_ms) == GDIET_OK &&
+		    gdiet_hip_last_narrow_band(c, &ctx->async_narrow[0], &ctx->async_narrow[1]) == GDIET_OK) ctx->last_was_async = true;
 	}
 	ctx->async_busy[t->lane] = false;
 	delete t;

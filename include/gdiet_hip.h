@@ -190,6 +190,11 @@ int gdiet_hip_last_dp_clock(gdiet_ctx *ctx, double *sclk_mhz_median, double *scl
 /* work of the most recent DP launch: DP cells = sum (qlen+tlen-1)*min(w+1,qlen,tlen), and the algorithmic bytes of
  * SURVEY.md 8d = cells + (qlen+tlen) + qlen + ceil(tlen/2) per alignment (what bench.py's roofline divides by the kernel time) */
 int gdiet_hip_last_dp_work(const gdiet_ctx *ctx, uint64_t *cells, uint64_t *alg_bytes);
+/* The 64-lane DP kernel aligns a box whose band is wider than 495 in a band of 495 first (half the arithmetic per row) and keeps the
+ * result when a bound on every path outside that band proves it to be the full band's; otherwise the same wavefront runs the full
+ * band.  Counters of the most recent DP launch: boxes that tried the narrow band, boxes whose certificate held.  Call after the
+ * batch has completed.  GDIET_NARROW_BAND=0 (read at gdiet_hip_init) switches the narrow band off. */
+int gdiet_hip_last_narrow_band(gdiet_ctx *ctx, uint64_t *tried, uint64_t *certified);
 
 /* ---- B1: the per-read mapping path for a whole batch of reads (LongReads variant; ShortReads variant with MM_F_SR) ----
  * Replaces step 1 of worker_pipeline -- kt_for(n_threads, worker_for, ...) -> mm_map_frag() per read

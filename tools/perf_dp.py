@@ -38,5 +38,6 @@ for mode in modes:
         sc, cg = ctx.ksw_extd2_batch(qs, ts, w, pkg.KswScore.from_preset(preset))
         dt = time.time() - t0
         dp, bt = ctx.last_kernel_ms()
-        print("mode %d mask %d rep %d: wall %.3fs  dp %.2f ms  backtrack %.2f ms  GCUPS(dp) %.1f  Mbases/s(dp+bt) %.1f  score0 %d"
-              % (mode, ctx.last_kernel_mask(), rep, dt, dp, bt, cells / dp / 1e6, sum(map(len, qs)) / (dp + bt) / 1e3, sc[0]))
+        tried, cert = ctx.last_narrow_band()
+        print("mode %d mask %d rep %d: wall %.3fs  dp %.2f ms  backtrack %.2f ms  GCUPS(dp) %.1f  Mbases/s(dp+bt) %.1f  score0 %d  narrow band tried %d certified %d"
+              % (mode, ctx.last_kernel_mask(), rep, dt, dp, bt, cells / dp / 1e6, sum(map(len, qs)) / (dp + bt) / 1e3, sc[0], tried, cert))
