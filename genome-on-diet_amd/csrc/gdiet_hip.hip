@@ -376,20 +376,13 @@ static int gd_consts(gdiet_ctx *ctx, const gdiet_ksw_score_t *sc, KswConst &K)
 		ctx->err = "only flag == GDIET_EZ_APPROX_MAX (the live path's mode) is implemented";
 		return GDIET_E_PARAM;
 	}
-	int q = sc->q, e = sc->e, q2 = sc->q2, e2 = sc->e2;
-	if (q2 + e2 < q + e) std::swap(q, q2), std::swap(e, e2); // SR/ksw2_extd2_sse.c:78
-	K.q = q, K.e = e, K.q2 = q2, K.e2 = e2;
-	K.sc_mch = sc->match, K.sc_mis = sc->mismatch;
-	K.sc_N = sc->sc_ambi == 0 ? -e2 : sc->sc_ambi;
+	K = gd_derive_consts(sc->match, sc->mismatch, sc->sc_ambi, sc->q, sc->e, sc->q2, sc->e2).K; // (ksw_common.h: shared with the host emulators)
+	const int q = K.q, e = K.e, q2 = K.q2, e2 = K.e2;
 	// :96-100 early return "if (-min_sc > 2 * (q + e)) return" leaves score = NEG_INF for every pair; the live
 	// path can never get there (mm_check_opt), so it is reported as a parameter error instead.
 	int min_sc = std::min<int>(std::min<int>(sc->mismatch, sc->match), std::min<int>(sc->sc_ambi, 0));
 	if (-min_sc > 2 * (q + e)) { ctx->err = "-min_sc > 2*(q+e): the reference returns without aligning"; return GDIET_E_PARAM; }
 	if ((q + e) + (q2 + e2) > 127) { ctx->err = "(q+e)+(q2+e2) > 127 (mm_check_opt, options.c:218)"; return GDIET_E_PARAM; }
-	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-	K.long_thres = long_thres;
-	K.long_diff = long_thres * (e - e2) - (q2 - q) - e2;
 	return GDIET_OK;
 }
 
@@ -447,7 +440,7 @@ static int gd_dp_launch(gdiet_ctx *ctx, const GdPlan &P, int n, const KswConst &
 	// (GDIET_DIAG_SHORTCUT=0: every short alignment goes through the DP and is walked back, also those the pre-filter could answer from the
 	// main diagonal's score -- see ksw_exact_match_kernel)
 	static const bool diag_shortcut = !(getenv("GDIET_DIAG_SHORTCUT") && atoi(getenv("GDIET_DIAG_SHORTCUT")) == 0);
-	const int score_bias = (int)(K.q + K.e) - (sc->q + sc->e); // 0 unless the caller passed the larger gap model first: ksw_score_bias_kernel
+	const int score_bias = gd_derive_consts(sc->match, sc->mismatch, sc->sc_ambi, sc->q, sc->e, sc->q2, sc->e2).score_bias; // 0 unless the caller passed the larger gap model first: ksw_score_bias_kernel
 	int32_t *d_diag = nullptr;
 	if (diag_shortcut && P.n_kind[GD_KIND_WAVE16]) {
 		if ((rc = gd_grow(ctx, ctx->diag, sizeof(int32_t) * (size_t)n))) return rc;

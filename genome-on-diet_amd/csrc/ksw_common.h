@@ -33,6 +33,34 @@ struct KswConst {
 	int32_t long_thres, long_diff; // :102-105
 };
 
+// The constants of a scoring as the CALLER passes it (mismatch and sc_ambi as scores; the two gap models in the caller's order), host only:
+// the one derivation the driver (gd_consts, gd_dp_launch) and the host emulators under tests/emul share.  No parameter checks: those are
+// gd_consts's.  score_bias: passed the larger gap model first, the reference walks its scores with the caller's q + e, not the smaller one
+// (SR/ksw2_extd2_sse.c:379), so every DP score it reports is off by (the smaller q+e) - (the caller's q+e); the kernels compute the
+// unshifted score and ksw_score_bias_kernel adds the bias afterwards.  0 for every other scoring.
+struct KswDerived {
+	KswConst K;
+	int32_t score_bias;
+};
+static inline KswDerived gd_derive_consts(int match, int mismatch, int sc_ambi, int q, int e, int q2, int e2)
+{
+	KswDerived D;
+	const int caller_qe = q + e;
+	if (q2 + e2 < q + e) { // SR/ksw2_extd2_sse.c:78
+		int t = q; q = q2, q2 = t;
+		t = e, e = e2, e2 = t;
+	}
+	D.K.q = q, D.K.e = e, D.K.q2 = q2, D.K.e2 = e2;
+	D.K.sc_mch = match, D.K.sc_mis = mismatch;
+	D.K.sc_N = sc_ambi == 0 ? -e2 : sc_ambi;
+	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
+	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
+	D.K.long_thres = long_thres;
+	D.K.long_diff = long_thres * (e - e2) - (q2 - q) - e2;
+	D.score_bias = (q + e) - caller_qe;
+	return D;
+}
+
 // per-alignment status written by the kernels
 enum : int32_t { GD_ST_PENDING = 0, GD_ST_EXACT = 1, GD_ST_DONE = 2, GD_ST_ZDROPPED = 3,
                  GD_ST_TRACED = 4 }; // DP and backtrack both done (the 64-lane kernel walks its own alignment back)

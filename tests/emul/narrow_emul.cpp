@@ -5,7 +5,7 @@
 // stored on every row, and no two lanes may hold the same half block.
 //
 //   g++ -O2 -I genome-on-diet_amd/csrc -I oracle tests/emul/narrow_emul.cpp oracle/gdo_ksw2.c -o narrow_emul
-//   ./narrow_emul <seed>
+//   ./narrow_emul <seed> [scoring a b q e q2 e2 sc_ambi]     (every pair at that scoring instead of the three presets in turn)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +15,7 @@
 #define __device__
 #include "ksw_wave_core.h"
 #include "gdo_ksw2.h"
+#include "emul_scoring.h"
 
 struct EmuResult { int score; std::vector<uint32_t> cigar; };
 static long g_pair_rows = 0, g_rows = 0;
@@ -224,9 +225,11 @@ static void make_query(std::mt19937 &g, const std::vector<uint8_t> &t, int qlen,
 
 int main(int argc, char **argv)
 {
+	int given[7];
+	const bool one_scoring = emu_scoring_arg(argc, argv, given);
 	const unsigned seed = argc > 1 ? atoi(argv[1]) : 1;
 	std::mt19937 g(seed);
-	const int presets[3][6] = {{1, 4, 6, 2, 26, 1}, {2, 8, 12, 2, 24, 1}, {2, 4, 4, 2, 24, 1}};
+	const int presets[3] = {1, 0, 2}; // hifi, sr, ont
 	const int bands[] = {GD_W_NARROW, GD_W_NARROW - 1, GD_W_NARROW - 2, 479, 247, 119};
 	const int mods[] = {0, 1, 7, 8, 9, 15};
 	int n_run = 0, n_bad = 0, n_skip = 0, it = 0;
@@ -242,27 +245,22 @@ int main(int argc, char **argv)
 					if (tlen <= dabs + 20) tlen += (dabs + 36) & ~15;
 					const int qlen = tlen - delta;
 					if (qlen < 20) { ++n_skip; continue; }
-					const int *P = presets[it % 3];
+					const int *P = one_scoring ? given : EMU_PRESETS[presets[it % 3]];
 					std::vector<uint8_t> t(tlen), q;
 					for (auto &c : t) c = g() & 3;
 					if (it % 3 == 1) for (auto &c : t) if ((g() % 1000) < 15) c = 4; // Ns in the target
 					make_query(g, t, qlen, q, it % 4 == 0 ? 0.06 : 0.01);
 					if (it % 5 == 2) for (auto &c : q) if ((g() % 300) == 0) c = (it & 1) ? 7 : 4; // ... and in the query (7: N of a reverse-complemented read)
-					KswConst C;
-					C.q = P[2], C.e = P[3], C.q2 = P[4], C.e2 = P[5];
-					if (C.q2 + C.e2 < C.q + C.e) std::swap(C.q, C.q2), std::swap(C.e, C.e2);
-					C.sc_mch = P[0], C.sc_mis = -P[1], C.sc_N = -C.e2;
-					C.long_thres = C.e != C.e2 ? (C.q2 - C.q) / (C.e - C.e2) - 1 : 0;
-					if (C.q2 + C.e2 + C.long_thres * C.e2 > C.q + C.e + C.long_thres * C.e) ++C.long_thres;
-					C.long_diff = C.long_thres * (C.e - C.e2) - (C.q2 - C.q) - C.e2;
+					int8_t mat[25];
+					const KswDerived D = emu_consts(P, false, mat);
+					const KswConst &C = D.K;
 					if (!gd_narrow_supported(qlen, tlen, w)) { ++n_skip; continue; }
 					if (!gd_narrow_rows_ok(qlen, tlen, w)) { fprintf(stderr, "admitted geometry fails the row-by-row test: %d %d %d\n", qlen, tlen, w); return 2; }
-					int8_t mat[25];
-					for (int i = 0; i < 25; ++i) mat[i] = (i / 5 == 4 || i % 5 == 4) ? 0 : (i / 5 == i % 5 ? P[0] : -P[1]);
 					gdo_extz_t ez;
 					memset(&ez, 0, sizeof(ez));
 					gdo_ksw_extd2(qlen, q.data(), tlen, t.data(), 5, mat, P[2], P[3], P[4], P[5], w, -1, 0, GDO_EZ_APPROX_MAX | GDO_EZ_AVX512_SC, &ez);
 					EmuResult e = emulate_narrow(q.data(), qlen, t.data(), tlen, w, C);
+					e.score += D.score_bias;
 					++n_run;
 					const bool ok = e.score == ez.score && (int)e.cigar.size() == ez.n_cigar && (ez.n_cigar == 0 || !memcmp(e.cigar.data(), ez.cigar, 4 * ez.n_cigar));
 					if (!ok) {

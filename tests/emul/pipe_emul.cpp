@@ -15,6 +15,7 @@
 #define __device__
 #include "ksw_pipe_core.h"
 #include "gdo_ksw2.h"
+#include "emul_scoring.h"
 
 struct Pair { std::vector<uint8_t> q, t; int live; };
 struct EmuOut { int score = GD_NEG_INF, done = 0; std::vector<uint8_t> bt, written; };
@@ -227,14 +228,15 @@ static void make_query(std::mt19937 &g, const std::vector<uint8_t> &t, int qlen,
 
 int main(int argc, char **argv)
 {
+	int given[7]; // ./pipe_emul ... scoring a b q e q2 e2 sc_ambi: every pipeline at that scoring instead of the three presets in turn
+	const bool one_scoring = emu_scoring_arg(argc, argv, given);
 	const unsigned seed = argc > 1 ? atoi(argv[1]) : 1;
 	const int n_pipes = argc > 2 ? atoi(argv[2]) : 20;
 	g_single = argc > 3 && !strcmp(argv[3], "single");
 	std::mt19937 g(seed);
-	const int presets[3][6] = {{2, 8, 12, 2, 24, 1}, {1, 4, 6, 2, 26, 1}, {2, 4, 4, 2, 24, 1}};
 	int n_run = 0, n_bad = 0, n_geo_refused = 0;
 	for (int it = 0; it < n_pipes; ++it) {
-		const int *Pz = presets[it % 3];
+		const int *Pz = one_scoring ? given : EMU_PRESETS[it % 3];
 		int tlen = it % 3 == 0 ? 150 : 17 + g() % 240, qlen = it % 3 == 0 ? 150 : tlen + (int)(g() % 31) - 15;
 		if (qlen < 17) qlen = 17;
 		const int wmax = tlen > qlen ? tlen : qlen;
@@ -244,13 +246,9 @@ int main(int argc, char **argv)
 		const PipeGeo Gm = gd_pipe_geo(qlen, tlen);
 		if (16 * (Gm.G - 1) >= Gm.P || Gm.QS < Gm.P + 1 || Gm.G < 2 || Gm.G > 16) { fprintf(stderr, "geometry invariants\n"); return 2; }
 		const int np = 1 + g() % 5, row_bytes = 16 * (tlen <= 128 ? 8 : tlen <= 160 ? 10 : 16); // (the planner's row stride: that of the 8- / 10- / 16-lane groups)
-		KswConst C;
-		C.q = Pz[2], C.e = Pz[3], C.q2 = g_single ? Pz[2] : Pz[4], C.e2 = g_single ? Pz[3] : Pz[5];
-		if (C.q2 + C.e2 < C.q + C.e) std::swap(C.q, C.q2), std::swap(C.e, C.e2);
-		C.sc_mch = Pz[0], C.sc_mis = -Pz[1], C.sc_N = -C.e2;
-		C.long_thres = C.e != C.e2 ? (C.q2 - C.q) / (C.e - C.e2) - 1 : 0;
-		if (C.q2 + C.e2 + C.long_thres * C.e2 > C.q + C.e + C.long_thres * C.e) ++C.long_thres;
-		C.long_diff = C.long_thres * (C.e - C.e2) - (C.q2 - C.q) - C.e2;
+		int8_t mat[25];
+		const KswDerived D = emu_consts(Pz, g_single, mat);
+		const KswConst &C = D.K;
 		const int cnt = np * Gm.NG - (int)(g() % Gm.NG); // np = ceil(cnt / NG)
 		std::vector<Pair> pairs((size_t)cnt);
 		for (size_t i = 0; i < pairs.size(); ++i) {
@@ -268,8 +266,6 @@ int main(int argc, char **argv)
 		}
 		std::vector<EmuOut> out;
 		emulate_pipe(pairs, np, cnt, qlen, tlen, row_bytes, C, out);
-		int8_t mat[25];
-		for (int i = 0; i < 25; ++i) mat[i] = (i / 5 == 4 || i % 5 == 4) ? 0 : (i / 5 == i % 5 ? Pz[0] : -Pz[1]);
 		for (size_t i = 0; i < pairs.size(); ++i) {
 			const Pair &p = pairs[i];
 			if (p.q.empty() || !p.live) {
@@ -282,14 +278,14 @@ int main(int argc, char **argv)
 			if (g_single) gdo_ksw_extz2(qlen, p.q.data(), tlen, p.t.data(), 5, mat, Pz[2], Pz[3], w, -1, 0, GDO_EZ_APPROX_MAX, &ez);
 			else gdo_ksw_extd2(qlen, p.q.data(), tlen, p.t.data(), 5, mat, Pz[2], Pz[3], Pz[4], Pz[5], w, -1, 0, GDO_EZ_APPROX_MAX | GDO_EZ_AVX512_SC, &ez);
 			++n_run;
-			bool ok = out[i].done && out[i].score == ez.score;
+			bool ok = out[i].done && out[i].score + D.score_bias == ez.score;
 			if (ok) {
 				const std::vector<uint32_t> cg = walk(out[i], qlen, tlen, w, row_bytes);
 				ok = (int)cg.size() == ez.n_cigar && (ez.n_cigar == 0 || !memcmp(cg.data(), ez.cigar, 4 * ez.n_cigar));
 			}
 			if (!ok) {
 				++n_bad;
-				if (n_bad <= 10) fprintf(stderr, "MISMATCH pipe=%d pair=%zu qlen=%d tlen=%d w=%d np=%d done=%d score emu=%d oracle=%d\n", it, i, qlen, tlen, w, np, out[i].done, out[i].score, ez.score);
+				if (n_bad <= 10) fprintf(stderr, "MISMATCH pipe=%d pair=%zu qlen=%d tlen=%d w=%d np=%d done=%d score emu=%d oracle=%d\n", it, i, qlen, tlen, w, np, out[i].done, out[i].score + D.score_bias, ez.score);
 			}
 			free(ez.cigar);
 		}

@@ -14,6 +14,7 @@
 #define __device__
 #include "ksw_wave_core.h"
 #include "gdo_ksw2.h"
+#include "emul_scoring.h"
 
 struct EmuResult { int score; std::vector<uint32_t> cigar; };
 
@@ -600,16 +601,17 @@ static void mutate(std::mt19937 &g, const std::vector<uint8_t> &t, std::vector<u
 
 int main(int argc, char **argv)
 {
+	int given[7]; // ./wave_emul ... scoring a b q e q2 e2 sc_ambi: every pair at that scoring instead of the three presets in turn
+	const bool one_scoring = emu_scoring_arg(argc, argv, given);
 	const unsigned seed = argc > 1 ? atoi(argv[1]) : 1;
 	const int n = argc > 2 ? atoi(argv[2]) : 200, LANES = argc > 3 ? atoi(argv[3]) : 64;
 	g_single = argc > 4 && !strcmp(argv[4], "single");
 	const bool ring96 = argc > 5 && !strcmp(argv[4], "ckpt96"); // ./wave_emul <seed> <n> 96 ckpt96 <rows per chunk>
 	const int ckpt = argc > 5 && (!strcmp(argv[4], "ckpt") || ring96) ? atoi(argv[5]) : 0; // ./wave_emul <seed> <n> 128 ckpt <rows per chunk>
 	std::mt19937 g(seed);
-	const int presets[3][6] = {{2, 8, 12, 2, 24, 1}, {1, 4, 6, 2, 26, 1}, {2, 4, 4, 2, 24, 1}};
 	int n_run = 0, n_bad = 0, n_skip = 0;
 	for (int it = 0; it < n; ++it) {
-		const int *P = presets[it % 3];
+		const int *P = one_scoring ? given : EMU_PRESETS[it % 3];
 		int tlen, w;
 		double sub = 0.01, ins = 0.003, del = 0.003, nfrac = (it % 7 == 0) ? 0.02 : 0.0;
 		if (LANES == 16) tlen = 100 + g() % 120, w = 32 + g() % 130;
@@ -637,23 +639,18 @@ int main(int argc, char **argv)
 		}
 		if (it % 4 == 1 && !g_single) for (auto &c : q) if (c == 4 || (g() % 400) == 0) c = 7; // N of a reverse-complemented read (LR/map.c:1634)
 		const int qlen = (int)q.size();
-		KswConst C;
-		C.q = P[2], C.e = P[3], C.q2 = g_single ? P[2] : P[4], C.e2 = g_single ? P[3] : P[5];
-		if (C.q2 + C.e2 < C.q + C.e) std::swap(C.q, C.q2), std::swap(C.e, C.e2);
-		C.sc_mch = P[0], C.sc_mis = -P[1], C.sc_N = -C.e2;
-		C.long_thres = C.e != C.e2 ? (C.q2 - C.q) / (C.e - C.e2) - 1 : 0;
-		if (C.q2 + C.e2 + C.long_thres * C.e2 > C.q + C.e + C.long_thres * C.e) ++C.long_thres;
-		C.long_diff = C.long_thres * (C.e - C.e2) - (C.q2 - C.q) - C.e2;
+		int8_t mat[25];
+		const KswDerived D = emu_consts(P, g_single, mat);
+		const KswConst &C = D.K;
 		// (the library's rule for the 10- / 8-lane groups: whatever the 16-lane form takes, if the target has at most 16 * lanes bases)
 		if (LANES == 10 || LANES == 8 ? !(gd_wave_geometry_ok(qlen, tlen, w, 16) && tlen <= 16 * LANES) : !gd_wave_geometry_ok(qlen, tlen, w, LANES)) { ++n_skip; continue; }
-		int8_t mat[25];
-		for (int i = 0; i < 25; ++i) mat[i] = (i / 5 == 4 || i % 5 == 4) ? 0 : (i / 5 == i % 5 ? P[0] : -P[1]);
 		gdo_extz_t ez;
 		memset(&ez, 0, sizeof(ez));
 		// (the extz2 oracle has the SSE score rule only: identical to the AVX-512 table except for query byte 7, which the single runs avoid)
 		if (g_single) gdo_ksw_extz2(qlen, q.data(), tlen, t.data(), 5, mat, P[2], P[3], w, -1, 0, GDO_EZ_APPROX_MAX, &ez);
 		else gdo_ksw_extd2(qlen, q.data(), tlen, t.data(), 5, mat, P[2], P[3], P[4], P[5], w, -1, 0, GDO_EZ_APPROX_MAX | GDO_EZ_AVX512_SC, &ez);
 		EmuResult e = ckpt ? emulate_ckpt(q.data(), qlen, t.data(), tlen, w, C, ckpt, ring96) : emulate(LANES, q.data(), qlen, t.data(), tlen, w, C);
+		e.score += D.score_bias;
 		++n_run;
 		bool ok = e.score == ez.score && (int)e.cigar.size() == ez.n_cigar && (ez.n_cigar == 0 || !memcmp(e.cigar.data(), ez.cigar, 4 * ez.n_cigar));
 		if (!ok) {

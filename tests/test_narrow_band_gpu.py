@@ -2,7 +2,6 @@
 on half-block rows at their own band; boxes at w = 1000 run the half-block rows at 495 first and keep the result when the certificate
 holds, otherwise the same wavefront runs the full band.  Scores and CIGARs against the oracle at the w given, and the counters of
 gdiet_hip_last_narrow_band against what the oracle's score at 495 makes the certificate say."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -10,62 +9,20 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from narrow_pairs import hifi_like, long_indels, point_errors, tandem
+import narrow_pairs
+from narrow_pairs import W_NARROW, expected_counters, load_cert_shim, long_indels, tandem
 
-W_NARROW = 495
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("cert") / "libcert_shim.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "genome-on-diet_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "emul", "cert_shim.cpp"), "-o", so])
-    lib = C.CDLL(so)
-    lib.cert_band_certified.argtypes = [C.c_int] * 11
-    assert lib.cert_w_narrow() == W_NARROW
-    return lib
-
-
-def _pair_of_lengths(rng, qlen, tlen, n_frac):
-    """a target of tlen bases and a query of exactly qlen: 1 % point errors, then one block inserted or removed"""
-    t = rng.integers(0, 4, size=tlen, dtype=np.uint8)
-    q = point_errors(rng, t, 0.01)
-    if len(q) < qlen:
-        pos = int(rng.integers(0, len(q)))
-        q = np.concatenate([q[:pos], rng.integers(0, 4, size=qlen - len(q), dtype=np.uint8), q[pos:]])
-    elif len(q) > qlen:
-        pos = int(rng.integers(0, qlen))
-        q = np.concatenate([q[:pos], q[pos + len(q) - qlen:]])
-    if n_frac:
-        t = t.copy()
-        t[rng.random(tlen) < n_frac] = 4
-    return np.ascontiguousarray(q, np.uint8), t
+    return load_cert_shim(tmp_path_factory.mktemp("cert"))
 
 
 @pytest.fixture(scope="module")
 def geometry_pairs():
-    """bands at the admission limit and 1-2 below (and 247), tlen mod 16 in {0, 1, 7, 8, 9, 15}, |tlen - qlen| in {0, 1, w - 1, w},
-    lengths 500-2100: around the band, and long enough for the paired steady rows; Ns in every third target"""
-    rng = np.random.default_rng(20261018)
-    pairs, bands = [], []
-    k = 0
-    for w in (W_NARROW, W_NARROW - 1, W_NARROW - 2, 247):
-        for mod in (0, 1, 7, 8, 9, 15):
-            for delta in (0, 1, -1, w - 1, -(w - 1), w, -w):
-                base = int(rng.integers(w + 20, w + 200)) if k % 2 else int(rng.integers(max(2 * w + 200, 700), 2000))
-                tlen = (base & ~15) + mod + (max(0, delta) if k % 2 == 0 else 0)
-                tlen = min(max(tlen, abs(delta) + 120), 2100)
-                tlen = (tlen & ~15) + mod if (tlen & ~15) + mod <= 2100 else ((tlen - 16) & ~15) + mod
-                qlen = tlen - delta
-                if qlen < 100 or qlen > 2100:
-                    tlen = ((abs(delta) + 600) & ~15) + mod
-                    qlen = tlen - delta
-                pairs.append(_pair_of_lengths(rng, qlen, tlen, 0.01 if k % 3 == 0 else 0.0))
-                bands.append(w)
-                k += 1
-    return pairs, bands
+    return narrow_pairs.geometry_pairs()
 
 
 def _oracle_all(oracle, pairs, ws):
@@ -78,26 +35,6 @@ def _oracle_all(oracle, pairs, ws):
 def _check(sc, cg, want, what):
     bad = [i for i, o in enumerate(want) if sc[i] != o["score"] or not np.array_equal(cg[i], o["cigar"])]
     assert not bad, "%s: %d of %d differ from the oracle, first %s" % (what, len(bad), len(want), bad[:5])
-
-
-def _expected_counters(shim, oracle, pairs, w_full):
-    """(tried, certified) as the planner's mark and the certificate on the oracle's score at GD_W_NARROW give them"""
-    gdo, lib = oracle
-    a, b, q, e, q2, e2 = gdo.PRESETS["hifi"]
-    mch, mis, n, q_, e_, q2_, e2_ = gdo.abi_consts(a, b, q, e, q2, e2)
-    mat = gdo.score_matrix(a, b)
-    tried = cert = 0
-    which = []
-    for qq, tt in pairs:
-        if shim.cert_planned_mode(len(qq), len(tt), w_full) != 1:  # (short ones go to the grouped kernels)
-            which.append(None)
-            continue
-        tried += 1
-        s = gdo.oracle_extd2(lib, qq, tt, mat, q, e, q2, e2, W_NARROW)["score"]
-        c = bool(shim.cert_band_certified(W_NARROW, mch, mis, n, q_, e_, q2_, e2_, len(qq), len(tt), s))
-        cert += c
-        which.append(c)
-    return tried, cert, which
 
 
 @pytest.mark.gpu
@@ -116,7 +53,7 @@ def test_same_pairs_at_w_1000_try_the_narrow_band(gpu_ctx, pkg, oracle, shim, ge
     sc, cg = gpu_ctx.ksw_extd2_batch([p[0] for p in pairs], [p[1] for p in pairs], 1000, pkg.KswScore.from_preset("hifi"))
     got = gpu_ctx.last_narrow_band()
     _check(sc, cg, _oracle_all(oracle, pairs, [1000] * len(pairs)), "w = 1000")
-    tried, cert, which = _expected_counters(shim, oracle, pairs, 1000)
+    tried, cert, which = expected_counters(shim, oracle, pairs, 1000)
     print("narrow band at w = 1000: tried %d certified %d of %d pairs" % (tried, cert, len(pairs)))
     assert got == (tried, cert)
     # every pair whose lengths differ by at most one certifies: it loses a few dozen against a bound 1 500 below the perfect score
@@ -146,7 +83,7 @@ def test_paths_outside_the_narrow_band_fall_back_to_the_full_band(gpu_ctx, pkg, 
     got = gpu_ctx.last_narrow_band()
     _check(sc, cg, full, "fallback")
     assert got == (len(pairs), 0)
-    assert _expected_counters(shim, oracle, pairs, 1000)[:2] == (len(pairs), 0)
+    assert expected_counters(shim, oracle, pairs, 1000)[:2] == (len(pairs), 0)
 
 
 @pytest.mark.gpu

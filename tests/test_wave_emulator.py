@@ -3,10 +3,16 @@ host lock-step emulator, reproduces the oracle's score and CIGAR bit for bit on 
 import os
 import subprocess
 
+import gdo
 import pytest
 
 from conftest import ROOT
 
+PRESETS = ("sr", "hifi", "ont")
+# the other scorings of the oracle's table that the register-resident kernels take: dual-affine, and in the single-affine form (q, e, q, e)
+OFF_PRESET = [k for k, v in gdo.SCORINGS.items() if gdo.wave_scoring_ok(*v) and k not in PRESETS]
+OFF_PRESET_SINGLE = [k for k in OFF_PRESET if gdo.wave_scoring_ok(*(gdo.SCORINGS[k][:4] + gdo.SCORINGS[k][2:4] + gdo.SCORINGS[k][6:]))]
+SCORING_LANES = [(64, 100), (16, 200)]  # (lanes, pairs): a run per scoring at each
 
 CORE = [(1, 64, 400), (2, 64, 400), (3, 16, 400), (4, 128, 60), (5, 10, 400), (6, 8, 400)]
 SINGLE = [16, 64, 10]
@@ -19,6 +25,11 @@ def _all_commands():
     cmds.update({("single", l): ["9", "300", str(l), "single"] for l in SINGLE})
     cmds.update({("cone",) + c: [str(c[0]), str(c[1]), "128", "ckpt", str(c[2])] for c in CONE})
     cmds.update({("ring96",) + c: [str(c[0]), str(c[1]), "96", "ckpt96", str(c[2])] for c in RING96})
+    for k in OFF_PRESET:  # every pair at one scoring of the table: `scoring a b q e q2 e2 sc_ambi`, the caller's order
+        sc = ["scoring"] + [str(x) for x in gdo.SCORINGS[k]]
+        cmds.update({("scoring", k, lanes): ["11", str(n), str(lanes)] + sc for lanes, n in SCORING_LANES})
+        if k in OFF_PRESET_SINGLE:
+            cmds.update({("scoring_single", k, lanes): ["12", str(n // 2), str(lanes), "single"] + sc for lanes, n in SCORING_LANES})
     return cmds
 
 
@@ -47,6 +58,24 @@ def test_wave_core_matches_oracle(emul, seed, lanes, n):
 def test_single_affine_form_matches_extz2_oracle(emul, lanes):
     """K3: gdw_compute<false> (no X2 / Y2 half) against the oracle's ksw_extz2"""
     out = emul[("single", lanes)].result()
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "mismatches=0" in out.stdout
+
+
+@pytest.mark.parametrize("lanes", [l for l, _ in SCORING_LANES])
+@pytest.mark.parametrize("name", OFF_PRESET)
+def test_wave_core_matches_oracle_off_preset(emul, name, lanes):
+    """the constants from the driver's own derivation (gd_derive_consts); the oracle gets the caller's order of the gap models and the score
+    of N in its matrix, and the emulator's score plus the bias of a swapped scoring is the oracle's"""
+    out = emul[("scoring", name, lanes)].result()
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "mismatches=0" in out.stdout
+
+
+@pytest.mark.parametrize("lanes", [l for l, _ in SCORING_LANES])
+@pytest.mark.parametrize("name", OFF_PRESET_SINGLE)
+def test_single_affine_form_matches_extz2_oracle_off_preset(emul, name, lanes):
+    out = emul[("scoring_single", name, lanes)].result()
     assert out.returncode == 0, out.stdout + out.stderr
     assert "mismatches=0" in out.stdout
 
@@ -86,5 +115,13 @@ def test_skewed_pipeline_matches_oracle(pipe_emul, seed, n, single):
     1..5 alignments per group, dead slots, Ns, error rates up to 15 % + 12 % indels, what a lane receives from a neighbour on another
     alignment -- score and CIGAR of every alignment against the oracle; every cell of a matrix must have been stored"""
     out = subprocess.run([pipe_emul, str(seed), str(n)] + (["single"] if single else []), capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "mismatches=0" in out.stdout
+
+
+@pytest.mark.parametrize("name,single", [(k, False) for k in OFF_PRESET] + [(k, True) for k in OFF_PRESET_SINGLE])
+def test_skewed_pipeline_matches_oracle_off_preset(pipe_emul, name, single):
+    out = subprocess.run([pipe_emul, "4", "30" if single else "60"] + (["single"] if single else []) + ["scoring"] + [str(x) for x in gdo.SCORINGS[name]],
+                         capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "mismatches=0" in out.stdout
