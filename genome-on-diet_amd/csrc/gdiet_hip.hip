@@ -123,6 +123,7 @@ struct gdiet_ctx {
 	hipStream_t ds_stream = nullptr;
 	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff;
 	std::vector<uint8_t> ds_enc;       // host copy of the reads a call without a resident batch encodes
+	std::string rg_line, rg_id;        // -R: the escaped @RG header line and its ID (gdiet_hip_set_read_group; read by the SAM formatters)
 };
 
 #define GD_HIP(call)                                                                              \

@@ -632,6 +632,11 @@ static inline void gd_write_tags(std::string &s, const GdReg &r)
 #define GD_F_OUT_CS 0x40
 #define GD_F_OUT_CS_LONG 0x800
 #define GD_F_OUT_MD 0x1000000
+#define GD_F_NO_QUAL 0x010
+#define GD_F_LONG_CIGAR 0x10000
+#define GD_F_SOFTCLIP 0x80000
+#define GD_F_COPY_COMMENT 0x2000000
+#define GD_F_SAM_HIT_ONLY 0x40000000
 // "\tcs:Z:<ds>" / "\tMD:Z:<ds>" (LR/format.c:153,205; the two flags together mean MD, :261).  ds: the record's difference string, computed
 // elsewhere (on the device: map_diffstr.hip.h); nullptr: the caller has none, and no tag is written
 static inline void gd_write_ds_tag(std::string &s, int64_t opt_flag, const char *ds, size_t ds_len)
@@ -642,7 +647,7 @@ static inline void gd_write_ds_tag(std::string &s, int64_t opt_flag, const char 
 }
 
 static inline void gd_write_paf(std::string &s, const GdRefView &R, const char *qname, int l_seq, const std::vector<GdReg> &regs, int reg_idx, int64_t opt_flag,
-                                const char *ds = nullptr, size_t ds_len = 0)
+                                const char *ds = nullptr, size_t ds_len = 0, const char *comment = nullptr)
 {
 	s += qname; s += '\t'; gd_fmt_int(s, l_seq);
 	if (reg_idx < 0 || reg_idx >= (int)regs.size()) { s += "\t0\t0\t*\t*\t0\t0\t0\t0\t0\t0\trl:i:0"; return; }
@@ -659,11 +664,19 @@ static inline void gd_write_paf(std::string &s, const GdRefView &R, const char *
 		for (uint32_t cg : r.cigar) { gd_fmt_int(s, cg >> 4); s += "MIDNSHP=XB"[cg & 0xf]; }
 	}
 	if (r.has_p && !r.cigar.empty()) gd_write_ds_tag(s, opt_flag, ds, ds_len); // :354-356
+	if ((opt_flag & GD_F_COPY_COMMENT) && comment) { s += '\t'; s += comment; } // :357, mapped lines only (the r == 0 branch returns at :332)
 }
 
+// mm_write_sam3 (LR/format.c:412-602).  opt_flag bits read: MM_F_SOFTCLIP (clips stay 'S' and SEQ / QUAL the whole read on 0x100 and 0x800 records, :402,:542),
+// MM_F_LONG_CIGAR (a CIGAR of more than 65 535 BAM operations moves into a CG:B:I tag, :476-490), MM_F_NO_QUAL (QUAL is '*': the
+// reference does not read the qualities at all, LR/map.c:2099), MM_F_COPY_COMMENT (the read's comment is the last field, :599) and the
+// cs / MD bits.  rg_id: the read group's id, printed as RG:Z: in front of every other tag, unmapped records included (:562).
 static inline void gd_write_sam(std::string &s, const GdRefView &R, const char *qname, const char *seq, const char *qual, int l_seq,
-                                const std::vector<GdReg> &regs, int reg_idx, int64_t opt_flag, const char *ds = nullptr, size_t ds_len = 0)
+                                const std::vector<GdReg> &regs, int reg_idx, int64_t opt_flag, const char *ds = nullptr, size_t ds_len = 0,
+                                const char *rg_id = nullptr, const char *comment = nullptr)
 {
+	if (opt_flag & GD_F_NO_QUAL) qual = nullptr;
+	bool cigar_in_tag = false;
 	static const char comp_tab[] = "TVGHEFCDIJMLKNOPQYSAABWXRZ"; // seq_comp_table (LR/bseq.c) restricted to letters
 	const GdReg *r = reg_idx >= 0 && reg_idx < (int)regs.size() ? &regs[reg_idx] : nullptr;
 	s += qname;
@@ -694,18 +707,24 @@ static inline void gd_write_sam(std::string &s, const GdRefView &R, const char *
 		put_seq(seq, l_seq, 0, 0);
 		s += '\t';
 		if (qual) put_seq(qual, l_seq, 0, 0); else s += '*';
+		if (rg_id && rg_id[0]) { s += "\tRG:Z:"; s += rg_id; }
 	} else {
 		s += '\t'; s += R.seq[r->rid].name; s += '\t'; gd_fmt_int(s, r->rs + 1); s += '\t'; gd_fmt_int(s, r->mapq); s += '\t';
+		if ((opt_flag & GD_F_LONG_CIGAR) && r->has_p && r->cigar.size() > 65535 - 2) // :476-481
+			cigar_in_tag = r->cigar.size() + (r->qs != 0) + (r->qe != l_seq) > 65535;
 		if (!r->has_p) s += '*';
-		else {
+		else if (cigar_in_tag) { // :482-490: a placeholder BAM can hold; the operations follow in the CG tag
+			const int slen = ((flag & 0x900) == 0 || (opt_flag & GD_F_SOFTCLIP)) ? l_seq : (flag & 0x100) ? 0 : r->qe - r->qs;
+			gd_fmt_int(s, slen); s += 'S'; gd_fmt_int(s, r->re - r->rs); s += 'N';
+		} else {
 			const uint32_t clip0 = r->rev ? (uint32_t)(l_seq - r->qe) : (uint32_t)r->qs, clip1 = r->rev ? (uint32_t)r->qs : (uint32_t)(l_seq - r->qe);
-			const char clip_char = (flag & 0x800) ? 'H' : 'S';
+			const char clip_char = (flag & 0x800) && !(opt_flag & GD_F_SOFTCLIP) ? 'H' : 'S';
 			if (clip0) { gd_fmt_int(s, clip0); s += clip_char; }
 			for (uint32_t cg : r->cigar) { gd_fmt_int(s, cg >> 4); s += "MIDNSHP=XB"[cg & 0xf]; }
 			if (clip1) { gd_fmt_int(s, clip1); s += clip_char; }
 		}
 		s += "\t*\t0\t0\t";
-		if ((flag & 0x900) == 0) {
+		if ((flag & 0x900) == 0 || (opt_flag & GD_F_SOFTCLIP)) {
 			put_seq(seq, l_seq, r->rev, r->rev);
 			s += '\t';
 			if (qual) put_seq(qual, l_seq, r->rev, 0); else s += '*';
@@ -715,6 +734,7 @@ static inline void gd_write_sam(std::string &s, const GdRefView &R, const char *
 			s += '\t';
 			if (qual) put_seq(qual + r->qs, r->qe - r->qs, r->rev, 0); else s += '*';
 		}
+		if (rg_id && rg_id[0]) { s += "\tRG:Z:"; s += rg_id; }
 		gd_write_tags(s, *r);
 		// SA tag for the primary line when supplementary alignments exist, :565-590
 		if (r->parent == r->id && r->has_p && regs.size() > 1) {
@@ -741,5 +761,59 @@ static inline void gd_write_sam(std::string &s, const GdRefView &R, const char *
 		}
 	}
 	if (r && r->has_p && !r->cigar.empty()) gd_write_ds_tag(s, opt_flag, ds, ds_len); // :593-594, behind the SA tag
+	if (cigar_in_tag) { // write_sam_cigar with in_tag, :394-400
+		const uint32_t clip0 = r->rev ? (uint32_t)(l_seq - r->qe) : (uint32_t)r->qs, clip1 = r->rev ? (uint32_t)r->qs : (uint32_t)(l_seq - r->qe);
+		const uint32_t clip_op = (flag & 0x800) && !(opt_flag & GD_F_SOFTCLIP) ? 5 : 4;
+		s += "\tCG:B:I";
+		if (clip0) { s += ','; gd_fmt_int(s, clip0 << 4 | clip_op); }
+		for (uint32_t cg : r->cigar) { s += ','; gd_fmt_int(s, cg); }
+		if (clip1) { s += ','; gd_fmt_int(s, clip1 << 4 | clip_op); }
+	}
 	s += "\trl:i:0"; // rep_len is never set on this path (bug-compat item 8): mm_write_sam3 prints rl:i:0
+	if ((opt_flag & GD_F_COPY_COMMENT) && comment) { s += '\t'; s += comment; }
+}
+
+// ---- read group and SAM header, LR/format.c:74-148 ------------------------------------------------------------------------------
+// sam_write_rg_line: s is the argument of -R ("@RG\tID:x..." with the tab spelled backslash-t).  On success `line` is the escaped header
+// line without its newline and `id` what RG:Z: prints; on failure `err` is the reference's message and both are empty.  mm_escape:
+// backslash-t becomes a tab, two backslashes one, and a backslash in front of any other character vanishes with that character.  A line
+// that ENDS in a single backslash makes mm_escape step over the terminator and read on (:78); it is refused here instead.
+static inline bool gd_parse_rg_line(const char *s, std::string &line, std::string &id, std::string &err)
+{
+	line.clear(), id.clear(), err.clear();
+	if (strncmp(s, "@RG", 3) != 0) { err = "the read group line is not started with @RG"; return false; }
+	if (strchr(s, '\t')) { err = "the read group line contained literal <tab> characters -- replace with escaped tabs: \\t"; return false; }
+	std::string esc;
+	for (const char *p = s; *p; ++p) {
+		if (*p != '\\') { esc += *p; continue; }
+		++p;
+		if (!*p) { err = "the read group line ends in a lone backslash"; return false; }
+		if (*p == 't') esc += '\t';
+		else if (*p == '\\') esc += '\\';
+	}
+	const size_t at = esc.find("\tID:");
+	if (at == std::string::npos) { err = "no ID within the read group line"; return false; }
+	size_t e = at + 4;
+	while (e < esc.size() && esc[e] != '\t' && esc[e] != '\n') ++e;
+	if (e - (at + 4) + 1 > 256) { err = "@RG:ID is longer than 255 characters"; return false; }
+	id = esc.substr(at + 4, e - (at + 4));
+	line.swap(esc);
+	return true;
+}
+
+// mm_write_sam_hdr (:128-148): @SQ per sequence, the read group line if any, @PG with the version and the command line (argv[0] is
+// replaced by "minimap2", as there)
+static inline std::string gd_sam_header(const GdRefView &R, const std::string &rg_line, const char *ver, int argc, const char *const *argv)
+{
+	std::string s;
+	for (uint32_t i = 0; i < R.n_seq; ++i) { s += "@SQ\tSN:"; s += R.seq[i].name; s += "\tLN:"; gd_fmt_int(s, (int32_t)R.seq[i].len); s += '\n'; }
+	if (!rg_line.empty()) { s += rg_line; s += '\n'; }
+	s += "@PG\tID:minimap2\tPN:minimap2";
+	if (ver) { s += "\tVN:"; s += ver; }
+	if (argc > 1 && argv) {
+		s += "\tCL:minimap2";
+		for (int i = 1; i < argc; ++i) { s += ' '; s += argv[i]; }
+	}
+	s += '\n';
+	return s;
 }

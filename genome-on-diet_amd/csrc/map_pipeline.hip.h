@@ -1312,8 +1312,14 @@ static int gd_fmt_chunk(const gdiet_ctx *ctx, int n_reads)
 
 static size_t gd_sam_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs,
                                 const char *const *quals, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
-                                int64_t opt_flag, char **buf_io, size_t *cap_io /* null: *buf_io is malloc'd to size */)
+                                int64_t opt_flag, char **buf_io, size_t *cap_io /* null: *buf_io is malloc'd to size */,
+                                const char *const *comments = nullptr /* or entries */)
 {
+	// opt_flag bits read here and in gd_write_sam: MM_F_NO_PRINT_2ND, MM_F_SAM_HIT_ONLY (no record for a read without alignments,
+	// LR/map.c:2177-2179), MM_F_NO_QUAL, MM_F_SOFTCLIP, MM_F_LONG_CIGAR, MM_F_COPY_COMMENT (comments are printed with it only), the cs /
+	// MD bits; the context's read group (gdiet_hip_set_read_group) gives every record its RG:Z: tag
+	const char *rg = ctx->rg_id.empty() ? nullptr : ctx->rg_id.c_str();
+	if (!(opt_flag & GD_F_COPY_COMMENT)) comments = nullptr;
 	// --cs / --MD: one difference-string call for the whole batch, on the device, before the chunks are formatted; every record's slice
 	// is then appended behind its tags (mm_write_sam3 never passes qstrand: LR/format.c:594)
 	GdDsText ds;
@@ -1326,7 +1332,8 @@ static size_t gd_sam_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_rea
 		std::string &s = rec[c];
 		const int i1 = std::min(n_reads, (c + 1) * CH);
 		size_t guess = 0;
-		for (int i = c * CH; i < i1; ++i) guess += (2 * (size_t)lens[i] + 200) * (size_t)std::max(1, n_regs[i]) + ds.bytes_of_read(i);
+		for (int i = c * CH; i < i1; ++i)
+			guess += (2 * (size_t)lens[i] + 200 + (comments && comments[i] ? strlen(comments[i]) + 1 : 0) + ctx->rg_id.size()) * (size_t)std::max(1, n_regs[i]) + ds.bytes_of_read(i);
 		s.reserve(guess);
 		for (int i = c * CH; i < i1; ++i) {
 			const int nr = n_regs[i];
@@ -1334,12 +1341,14 @@ static size_t gd_sam_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_rea
 			for (int j = 0; j < nr; ++j) {
 				gd_reg_from_c(regs[i][j], v[j]);
 			}
-			const char *q = quals ? quals[i] : nullptr;
-			if (nr <= 0) gd_write_sam(s, ix->h.ref(), qnames[i], seqs[i], q, lens[i], v, -1, opt_flag), s += '\n'; // (the writer appends)
-			else
+			const char *q = quals ? quals[i] : nullptr, *cm = comments ? comments[i] : nullptr;
+			if (nr <= 0) {
+				if (opt_flag & GD_F_SAM_HIT_ONLY) continue;
+				gd_write_sam(s, ix->h.ref(), qnames[i], seqs[i], q, lens[i], v, -1, opt_flag, nullptr, 0, rg, cm), s += '\n'; // (the writer appends)
+			} else
 				for (int j = 0; j < nr; ++j) {
 					if ((opt_flag & GD_F_NO_PRINT_2ND) && v[j].id != v[j].parent) continue;
-					gd_write_sam(s, ix->h.ref(), qnames[i], seqs[i], q, lens[i], v, j, opt_flag, ds.str(i, j), ds.len(i, j)), s += '\n';
+					gd_write_sam(s, ix->h.ref(), qnames[i], seqs[i], q, lens[i], v, j, opt_flag, ds.str(i, j), ds.len(i, j), rg, cm), s += '\n';
 				}
 		}
 	});
@@ -1385,13 +1394,24 @@ extern "C" size_t gdiet_hip_sam_batch_into(gdiet_ctx *ctx, const gdiet_index *ix
 	return gd_sam_batch_impl(ctx, ix, n_reads, qnames, seqs, quals, lens, n_regs, regs, opt_flag, buf, cap);
 }
 
+// ... and with the reads' comments (gdiet_hip_fastx_read's array; NULL, or NULL entries, where there is none): -y
+extern "C" size_t gdiet_hip_sam_batch_comments_into(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs,
+                                                    const char *const *quals, const char *const *comments, const int32_t *lens, const int32_t *n_regs,
+                                                    gdiet_reg_t *const *regs, int64_t opt_flag, char **buf, size_t *cap)
+{
+	if (!ctx || !ix || n_reads < 0 || !qnames || !seqs || !lens || !n_regs || !regs || !buf || !cap) return 0;
+	return gd_sam_batch_impl(ctx, ix, n_reads, qnames, seqs, quals, lens, n_regs, regs, opt_flag, buf, cap, comments);
+}
+
 // All PAF lines of a batch (mm_write_paf3, LR/format.c:326-367, as step 2 prints them when MM_F_OUT_SAM is off: LR/map.c:2163-2185).
-// opt_flag: MM_F_OUT_CG adds the cg:Z: tag, MM_F_PAF_NO_HIT the lines of unmapped reads, MM_F_NO_PRINT_2ND drops secondary records.
+// opt_flag: MM_F_OUT_CG adds the cg:Z: tag, MM_F_PAF_NO_HIT the lines of unmapped reads, MM_F_NO_PRINT_2ND drops secondary records,
+// MM_F_COPY_COMMENT appends the read's comment to its mapped lines (:357; the unmapped line returns before it, :332).
 // seqs == nullptr: gdiet_hip_paf_batch, which has no reads and hence no difference tags
 static size_t gd_paf_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs, const int32_t *lens,
-                                const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out)
+                                const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out, const char *const *comments = nullptr)
 {
 	*out = nullptr;
+	if (!(opt_flag & GD_F_COPY_COMMENT)) comments = nullptr;
 	GdDsText ds; // --cs / --MD: as in gd_sam_batch_impl; MM_F_QSTRAND reaches the strings here (LR/format.c:355-356)
 	if (seqs && gd_ds_mode(opt_flag) >= 0 && gd_ds_for_batch(ctx, ix, n_reads, seqs, lens, n_regs, regs, opt_flag, ds)) return 0;
 	const int CH = 512, n_ch = (n_reads + CH - 1) / CH;
@@ -1411,7 +1431,7 @@ static size_t gd_paf_batch_impl(gdiet_ctx *ctx, const gdiet_index *ix, int n_rea
 			} else
 				for (int j = 0; j < nr; ++j) {
 					if ((opt_flag & GD_F_NO_PRINT_2ND) && v[j].id != v[j].parent) continue;
-					gd_write_paf(s, ix->h.ref(), qnames[i], lens[i], v, j, opt_flag, ds.str(i, j), ds.len(i, j)), s += '\n';
+					gd_write_paf(s, ix->h.ref(), qnames[i], lens[i], v, j, opt_flag, ds.str(i, j), ds.len(i, j), comments ? comments[i] : nullptr), s += '\n';
 				}
 		}
 	});
@@ -1439,4 +1459,41 @@ extern "C" size_t gdiet_hip_paf_batch_seqs(gdiet_ctx *ctx, const gdiet_index *ix
 {
 	if (!ctx || !ix || n_reads < 0 || !qnames || !seqs || !lens || !n_regs || !regs || !out) return 0;
 	return gd_paf_batch_impl(ctx, ix, n_reads, qnames, seqs, lens, n_regs, regs, opt_flag, out);
+}
+
+// ... and with the reads' comments, as gdiet_hip_sam_batch_comments_into
+extern "C" size_t gdiet_hip_paf_batch_comments(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs,
+                                               const char *const *comments, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
+                                               int64_t opt_flag, char **out)
+{
+	if (!ctx || !ix || n_reads < 0 || !qnames || !seqs || !lens || !n_regs || !regs || !out) return 0;
+	return gd_paf_batch_impl(ctx, ix, n_reads, qnames, seqs, lens, n_regs, regs, opt_flag, out, comments);
+}
+
+// -R: sam_write_rg_line (LR/format.c:90-126).  The escaped line and the id live in the context: set before formatting starts
+extern "C" int gdiet_hip_set_read_group(gdiet_ctx *ctx, const char *rg_line)
+{
+	if (!ctx) return GDIET_E_PARAM;
+	ctx->rg_line.clear(), ctx->rg_id.clear();
+	if (!rg_line) return GDIET_OK;
+	std::string err;
+	if (!gd_parse_rg_line(rg_line, ctx->rg_line, ctx->rg_id, err)) {
+		gd_ds_clear_mark(); // (gdiet_hip_strerror is to return this text, not that of an earlier difference-string pass)
+		ctx->err = err;
+		return GDIET_E_PARAM;
+	}
+	return GDIET_OK;
+}
+
+// mm_write_sam_hdr (LR/format.c:128-148)
+extern "C" size_t gdiet_hip_sam_header(gdiet_ctx *ctx, const gdiet_index *ix, const char *version, int argc, const char *const *argv, char **out)
+{
+	if (!ctx || !ix || !out || argc < 0 || (argc > 1 && !argv)) return 0;
+	*out = nullptr;
+	const std::string s = gd_sam_header(ix->h.ref(), ctx->rg_line, version, argc, argv);
+	char *buf = (char *)malloc(s.size() + 1);
+	if (!buf) return 0;
+	memcpy(buf, s.c_str(), s.size() + 1);
+	*out = buf;
+	return s.size();
 }

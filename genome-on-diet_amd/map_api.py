@@ -13,6 +13,8 @@ from .hip_abi import GdietError, load_library
 F_NO_PRINT_2ND = 0x4000
 F_OUT_CS, F_OUT_CS_LONG, F_OUT_MD, F_QSTRAND = 0x40, 0x800, 0x1000000, 0x100000000  # --cs, --cs=long (with F_OUT_CS), --MD, --qstrand
 F_SR, F_FRAG_MODE = 0x1000, 0x2000
+# output options read by the SAM / PAF formatters alone: -Q, -L, -Y, -y, --sam-hit-only
+F_NO_QUAL, F_LONG_CIGAR, F_SOFTCLIP, F_COPY_COMMENT, F_SAM_HIT_ONLY = 0x10, 0x10000, 0x80000, 0x2000000, 0x40000000
 F_EQX = 0x4000000  # --eqx: =/X in place of M; interpreted with F_SR only, e.g. Mapper(..., preset="sr", flag=F_SR | F_FRAG_MODE | F_EQX)
 
 
@@ -99,6 +101,15 @@ def _bind(lib):
     lib.gdiet_hip_paf_batch.restype = C.c_size_t
     lib.gdiet_hip_paf_batch_seqs.argtypes = [vp, vp, C.c_int, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp)]
     lib.gdiet_hip_paf_batch_seqs.restype = C.c_size_t
+    lib.gdiet_hip_sam_batch_comments_into.argtypes = [vp, vp, C.c_int, cpp, cpp, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64,
+                                                      C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lib.gdiet_hip_sam_batch_comments_into.restype = C.c_size_t
+    lib.gdiet_hip_paf_batch_comments.argtypes = [vp, vp, C.c_int, cpp, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp)]
+    lib.gdiet_hip_paf_batch_comments.restype = C.c_size_t
+    lib.gdiet_hip_set_read_group.argtypes = [vp, C.c_char_p]
+    lib.gdiet_hip_set_read_group.restype = C.c_int
+    lib.gdiet_hip_sam_header.argtypes = [vp, vp, C.c_char_p, C.c_int, cpp, C.POINTER(vp)]
+    lib.gdiet_hip_sam_header.restype = C.c_size_t
     lib.gdiet_hip_diffstr_batch.argtypes = [vp, vp, vp, C.c_int, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp),
                                             C.POINTER(vp)]
     lib._map_bound = True
@@ -316,22 +327,36 @@ class Mapper:
         self.ctx._check(self.lib.gdiet_hip_batch_upload(self.ctx._h, C.byref(h), n, C.cast(seqs, C.POINTER(C.c_char_p)), lens))
         return (h, n)
 
-    def sam_batch_raw(self, res, n, names, seqs, quals, lens, sink=None):
+    def sam_batch_raw(self, res, n, names, seqs, quals, lens, sink=None, comments=None):
         """gdiet_hip_sam_batch on C arrays.  With sink (a binary file object) the text is formatted into a buffer kept by this mapper
-        (gdiet_hip_sam_batch_into) and written from it without a copy, and its length returned; otherwise bytes are returned."""
+        (gdiet_hip_sam_batch_into) and written from it without a copy, and its length returned; otherwise bytes are returned.
+        comments: the reader's array of comments, printed under F_COPY_COMMENT (gdiet_hip_sam_batch_comments_into)."""
         cpp = C.POINTER(C.c_char_p)
-        if sink is not None:
-            if not hasattr(self, "_sam_buf"):
+        if sink is not None or comments is not None:
+            if sink is not None and not hasattr(self, "_sam_buf"):
                 self._sam_buf, self._sam_cap = C.c_void_p(), C.c_size_t(0)
                 self.lib.gdiet_hip_sam_batch_into.restype = C.c_size_t
                 self.lib.gdiet_hip_sam_batch_into.argtypes = self.lib.gdiet_hip_sam_batch.argtypes[:-1] + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-            m = self.lib.gdiet_hip_sam_batch_into(self.ctx._h, self._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp), lens, res.n_regs, res.regs,
-                                                  self.opt.flag, C.byref(self._sam_buf), C.byref(self._sam_cap))
-            if m:
-                sink.write(memoryview((C.c_char * m).from_address(self._sam_buf.value)))
-            elif n:
-                self._format_failed("gdiet_hip_sam_batch_into")
-            return m
+            buf, cap = (self._sam_buf, self._sam_cap) if sink is not None else (C.c_void_p(), C.c_size_t(0))
+            try:
+                if comments is not None:
+                    what = "gdiet_hip_sam_batch_comments_into"
+                    m = self.lib.gdiet_hip_sam_batch_comments_into(self.ctx._h, self._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp),
+                                                                   C.cast(comments, cpp), lens, res.n_regs, res.regs, self.opt.flag, C.byref(buf), C.byref(cap))
+                else:
+                    what = "gdiet_hip_sam_batch_into"
+                    m = self.lib.gdiet_hip_sam_batch_into(self.ctx._h, self._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp), lens, res.n_regs,
+                                                          res.regs, self.opt.flag, C.byref(buf), C.byref(cap))
+                if not m and n and not (self.opt.flag & F_SAM_HIT_ONLY):  # (with --sam-hit-only a batch of unmapped reads has no text)
+                    self._format_failed(what)
+                if sink is None:
+                    return C.string_at(buf.value, m) if m else b""
+                if m:
+                    sink.write(memoryview((C.c_char * m).from_address(buf.value)))
+                return m
+            finally:
+                if sink is None and buf.value:
+                    C.CDLL(None).free(C.c_void_p(buf.value))
         out = C.c_void_p()
         m = self.lib.gdiet_hip_sam_batch(self.ctx._h, self._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp), lens, res.n_regs, res.regs,
                                          self.opt.flag, C.byref(out))
@@ -342,6 +367,27 @@ class Mapper:
         finally:
             if out.value:
                 C.CDLL(None).free(C.c_void_p(out.value))
+
+    def set_read_group(self, rg_line):
+        """-R: gdiet_hip_set_read_group.  rg_line as on the command line ("@RG\\tID:x\\tSM:y", tabs spelled backslash-t), or None to clear it.
+        The read group belongs to the context: set it before formatting starts.  Raises GdietError with the reference's message."""
+        if rg_line is not None and not isinstance(rg_line, bytes):
+            rg_line = rg_line.encode()
+        self.ctx._check(self.lib.gdiet_hip_set_read_group(self.ctx._h, rg_line))
+
+    def sam_header(self, version=None, argv=()):
+        """gdiet_hip_sam_header: the @SQ lines of the index, the @RG line of set_read_group, and @PG with VN:version and
+        CL:minimap2 argv[1] ... (argv[0] is not printed, as in mm_write_sam_hdr)"""
+        enc = lambda x: x if isinstance(x, bytes) else x.encode()
+        av = (C.c_char_p * max(1, len(argv)))(*[enc(x) for x in argv])
+        out = C.c_void_p()
+        m = self.lib.gdiet_hip_sam_header(self.ctx._h, self._idx, None if version is None else enc(version), len(argv), av, C.byref(out))
+        if not out.value:
+            raise GdietError("gdiet_hip_sam_header failed")
+        try:
+            return C.string_at(out.value, m).decode()
+        finally:
+            C.CDLL(None).free(C.c_void_p(out.value))
 
     def _format_failed(self, what):
         """a batch formatter returned no text for a batch with reads: the difference-string pass refused a record, or memory ran out"""
@@ -391,7 +437,8 @@ class Mapper:
         return list(out)
 
     def sam_batch(self, res, reads):
-        """every SAM record of a MapResult as one string (gdiet_hip_sam_batch); reads = [(qname, seq, qual or None), ...]"""
+        """every SAM record of a MapResult as one string (gdiet_hip_sam_batch); reads = [(qname, seq, qual or None[, comment or None]), ...];
+        a comment is printed under F_COPY_COMMENT (gdiet_hip_sam_batch_comments_into)"""
         n = len(reads)
         enc = lambda x: x if isinstance(x, bytes) else x.encode()
         qn = (C.c_char_p * n)(*[enc(r[0]) for r in reads])
@@ -399,8 +446,14 @@ class Mapper:
         ql = (C.c_char_p * n)(*[None if len(r) < 3 or r[2] is None else enc(r[2]) for r in reads])
         lens = np.array([len(r[1]) for r in reads], np.int32)
         out = C.c_void_p()
-        m = self.lib.gdiet_hip_sam_batch(self.ctx._h, self._idx, n, qn, sq, ql, lens.ctypes.data_as(C.POINTER(C.c_int32)), res.n_regs, res.regs,
-                                         self.opt.flag, C.byref(out))
+        if any(len(r) > 3 and r[3] is not None for r in reads):
+            cm = (C.c_char_p * n)(*[None if len(r) < 4 or r[3] is None else enc(r[3]) for r in reads])
+            cap = C.c_size_t(0)
+            m = self.lib.gdiet_hip_sam_batch_comments_into(self.ctx._h, self._idx, n, qn, sq, ql, cm, lens.ctypes.data_as(C.POINTER(C.c_int32)), res.n_regs,
+                                                           res.regs, self.opt.flag, C.byref(out), C.byref(cap))
+        else:
+            m = self.lib.gdiet_hip_sam_batch(self.ctx._h, self._idx, n, qn, sq, ql, lens.ctypes.data_as(C.POINTER(C.c_int32)), res.n_regs, res.regs,
+                                             self.opt.flag, C.byref(out))
         if n and not out.value:
             self._format_failed("gdiet_hip_sam_batch")
         try:
@@ -427,15 +480,17 @@ class Mapper:
 
     def paf_batch_seqs(self, res, reads, flag=0):
         """gdiet_hip_paf_batch_seqs: paf_batch with the reads, so that F_OUT_CS / F_OUT_CS_LONG / F_OUT_MD in flag (or in the mapper's
-        options) add the cs:Z: / MD:Z: tag behind cg:Z:; F_QSTRAND reaches the tag as in the reference"""
+        options) add the cs:Z: / MD:Z: tag behind cg:Z:; F_QSTRAND reaches the tag as in the reference.  A 4th tuple element is the
+        read's comment, appended to its mapped lines under F_COPY_COMMENT (gdiet_hip_paf_batch_comments)"""
         n = len(reads)
         enc = lambda x: x if isinstance(x, bytes) else x.encode()
         qn = (C.c_char_p * n)(*[enc(r[0]) for r in reads])
         sq = (C.c_char_p * n)(*[enc(r[1]) for r in reads])
+        cm = (C.c_char_p * n)(*[None if len(r) < 4 or r[3] is None else enc(r[3]) for r in reads])
         lens = np.array([len(r[1]) for r in reads], np.int32)
         out = C.c_void_p()
-        m = self.lib.gdiet_hip_paf_batch_seqs(self.ctx._h, self._idx, n, qn, sq, lens.ctypes.data_as(C.POINTER(C.c_int32)), res.n_regs, res.regs,
-                                              self.opt.flag | flag, C.byref(out))
+        m = self.lib.gdiet_hip_paf_batch_comments(self.ctx._h, self._idx, n, qn, sq, cm, lens.ctypes.data_as(C.POINTER(C.c_int32)), res.n_regs, res.regs,
+                                                  self.opt.flag | flag, C.byref(out))
         if n and not out.value:
             self._format_failed("gdiet_hip_paf_batch_seqs")
         try:

@@ -386,7 +386,9 @@ int gdiet_hip_diffstr_batch(gdiet_ctx *ctx, const gdiet_index *idx, const gdiet_
 /* One SAM record exactly as mm_write_sam3 prints it for a single-segment read (LR/format.c:412-599); reg_idx < 0 writes
  * the unmapped record.  Returns the number of bytes needed (excluding the terminating NUL); writes at most cap bytes.
  * This call has no context, hence no device: the cs:Z: / MD:Z: difference tags exist in the batch calls below only, and
- * MM_F_OUT_CS / MM_F_OUT_MD in opt_flag are ignored here. */
+ * MM_F_OUT_CS / MM_F_OUT_MD in opt_flag are ignored here.  For the same reason it prints no RG:Z: tag (the read group lives in a
+ * context) and, having no comment argument, no comment: MM_F_COPY_COMMENT is ignored.  MM_F_SOFTCLIP, MM_F_LONG_CIGAR and MM_F_NO_QUAL
+ * are honoured as in the batch calls. */
 size_t gdiet_hip_sam_record(const gdiet_index *idx, const char *qname, const char *seq, const char *qual, int32_t l_seq,
                             const gdiet_reg_t *regs, int32_t n_regs, int32_t reg_idx, int64_t opt_flag, char *buf, size_t cap);
 
@@ -396,7 +398,23 @@ size_t gdiet_hip_sam_record(const gdiet_index *idx, const char *qname, const cha
  * MM_F_OUT_CS / MM_F_OUT_CS_LONG / MM_F_OUT_MD in opt_flag (--cs[=long] / --MD) add "\tcs:Z:..." or "\tMD:Z:..." to every record with a
  * CIGAR, behind its SA:Z: tag, if any, and in front of rl:i:0 (LR/format.c:593-597): one gdiet_hip_diffstr_batch pass over the batch on
  * the GPU before the records are formatted.  Without those bits nothing is launched and the text is what it always was.  A record
- * that pass refuses makes the call return 0 with *out == NULL; gdiet_hip_strerror says why. */
+ * that pass refuses makes the call return 0 with *out == NULL; gdiet_hip_strerror says why.
+ * The other output bits of mm_mapopt_t::flag that are read (all host work, LR/format.c:387-602, LR/map.c:2166-2185):
+ *   MM_F_NO_PRINT_2ND   (0x4000, --secondary=no) no record with 0x100
+ *   MM_F_SAM_HIT_ONLY   (0x40000000, --sam-hit-only) no record for a read without alignments
+ *   MM_F_NO_QUAL        (0x10, -Q)  QUAL is "*" whatever quals holds
+ *   MM_F_SOFTCLIP       (0x80000, -Y) supplementary records clip with S instead of H, and supplementary and secondary records carry
+ *                       the whole read as SEQ / QUAL
+ *   MM_F_LONG_CIGAR     (0x10000, -L) a CIGAR of more than 65 535 operations, clips included, is printed as "<l>S<ref span>N" with
+ *                       the operations in a CG:B:I tag behind the cs / MD tag
+ *   MM_F_COPY_COMMENT   (0x2000000, -y) the read's comment is the last field; only the calls that take `comments` have one to print
+ * and, with a read group set on the context (gdiet_hip_set_read_group), RG:Z:<id> is the first tag of every record, unmapped ones
+ * included.  Paired-end fields of mm_write_sam3 (n_seg > 1) are not written: every read is a segment of its own. */
+#define GDIET_F_NO_QUAL       0x10
+#define GDIET_F_LONG_CIGAR    0x10000
+#define GDIET_F_SOFTCLIP      0x80000
+#define GDIET_F_COPY_COMMENT  0x2000000
+#define GDIET_F_SAM_HIT_ONLY  0x40000000
 size_t gdiet_hip_sam_batch(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
                            const char *const *quals, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
                            int64_t opt_flag, char **out);
@@ -407,6 +425,25 @@ size_t gdiet_hip_sam_batch(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, 
 size_t gdiet_hip_sam_batch_into(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
                                 const char *const *quals, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
                                 int64_t opt_flag, char **buf, size_t *cap);
+/* gdiet_hip_sam_batch_into with the reads' comments (the array gdiet_hip_fastx_read hands out with with_comment; NULL, or NULL entries,
+ * where a read has none).  A comment is printed only with MM_F_COPY_COMMENT set, behind rl:i:0, on unmapped records too
+ * (LR/format.c:599).  gdiet_hip_sam_batch and gdiet_hip_sam_batch_into are this call with comments == NULL. */
+size_t gdiet_hip_sam_batch_comments_into(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
+                                         const char *const *quals, const char *const *comments, const int32_t *lens, const int32_t *n_regs,
+                                         gdiet_reg_t *const *regs, int64_t opt_flag, char **buf, size_t *cap);
+
+/* -R: the read group (sam_write_rg_line, LR/format.c:90-126).  rg_line is the option's argument, "@RG\tID:x\tSM:y" with every tab
+ * spelled as backslash-t; mm_escape turns backslash-t into a tab and two backslashes into one, and drops a backslash together with any
+ * other character behind it.  GDIET_E_PARAM, with the reference's message in gdiet_hip_strerror, when the line does not start with
+ * @RG, holds a literal tab, has no "	ID:" after escaping, or has an ID of more than 255 bytes -- and when it ends in a lone backslash,
+ * where the reference reads past the terminator.  After a failure, and with rg_line == NULL, no read group is set.
+ * The escaped line and the ID are kept in the context and read by gdiet_hip_sam_header and the SAM batch formatters: set it before
+ * formatting starts, not while a formatter call runs on another thread. */
+int gdiet_hip_set_read_group(gdiet_ctx *ctx, const char *rg_line);
+/* The SAM header, mm_write_sam_hdr (LR/format.c:128-148): "@SQ	SN:<name>	LN:<length>" per index sequence, the context's @RG line
+ * if one is set, then "@PG	ID:minimap2	PN:minimap2", "	VN:<version>" unless version is NULL, "	CL:minimap2 argv[1] ... argv[argc-1]"
+ * when argc > 1, and the final newline.  *out is malloc'd (free() it); returns its length, 0 with *out == NULL on failure. */
+size_t gdiet_hip_sam_header(gdiet_ctx *ctx, const gdiet_index *idx, const char *version, int argc, const char *const *argv, char **out);
 
 /* The same for PAF output: mm_write_paf3 (LR/format.c:326-367) as step 2 prints it when MM_F_OUT_SAM is off (LR/map.c:2163-2185).
  * opt_flag: MM_F_OUT_CG (0x20, `-c`) adds the cg:Z: tag, MM_F_PAF_NO_HIT (0x8000000, --paf-no-hit) the lines of unmapped reads,
@@ -419,6 +456,12 @@ size_t gdiet_hip_paf_batch(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, 
  * per call; failure as in gdiet_hip_sam_batch. */
 size_t gdiet_hip_paf_batch_seqs(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
                                 const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **out);
+/* ... and with the reads' comments (as gdiet_hip_sam_batch_comments_into): under MM_F_COPY_COMMENT the comment is the last field of
+ * every MAPPED line (LR/format.c:357); the lines of --paf-no-hit carry none (:329-333).  gdiet_hip_paf_batch_seqs is this call with
+ * comments == NULL. */
+size_t gdiet_hip_paf_batch_comments(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
+                                    const char *const *comments, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
+                                    int64_t opt_flag, char **out);
 
 /* Read input, step 0 of worker_pipeline (LR/map.c:2095-2131): FASTA / FASTQ, plain or gzip ("-" = stdin), one mini-batch per
  * call.  Replaces mm_bseq_open / mm_bseq_read3 / mm_bseq_close (LR/bseq.c:38-58, 80-121) with the same record grammar

@@ -3,8 +3,13 @@ map with several batches in flight (gdiet_hip_map_submit / _wait) -> SAM records
 No Python object is made per read: the C arrays of the reader go straight into the upload and the SAM formatter.
 
     python tools/map_file.py --preset sr ref.fa reads.fq[.gz] -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
+                             [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only]
 
-Writes the SAM body (the records; the header lines of the reference's CLI are not part of the path)."""
+Writes the SAM body (the records).  --header puts the header lines of the reference's CLI in front (gdiet_hip_sam_header: @SQ per
+contig, the @RG line of -R, @PG with this tool's version and command line); it is opt-in, so that the default output stays the body alone.
+-R, -Y, -L, -y, -Q and --sam-hit-only mean what they mean to the reference (LR/main.c): a read group on every record, soft clips and
+whole reads on supplementary records, long CIGARs in the CG tag, the FASTQ comment as the last field (read with with_comment), no
+qualities (not even read: with_qual off), no record for an unmapped read."""
 import argparse
 import json
 import os
@@ -19,7 +24,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from __graft_entry__ import _load_pkg  # noqa: E402
 
 
-def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads):
+VERSION = "gdiet-hip-map_file"  # the VN: field of --header's @PG line
+
+
+def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False):
     """returns (reads, seconds).  Three stages on three threads, as the reference's kt_pipeline runs its three steps (LR/map.c:2094-2170):
     read -> upload + submit -> wait + format + write; the C calls release the interpreter lock, so the stages overlap.
     A failure in any stage stops all three: `stop` is set, the writer keeps draining q_done (every open ticket is still waited for and
@@ -58,7 +66,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads):
     def reader():
         try:
             while not stop.is_set():
-                item = timed("read", fx.read_raw, chunk, detach=True)
+                item = timed("read", fx.read_raw, chunk, with_qual=with_qual, with_comment=with_comment, detach=True)
                 if not put(q_read, item):
                     if item[0]:
                         fx.release(item[6])
@@ -73,7 +81,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads):
             item = q_done.get()
             if item is None:
                 return
-            ticket, token, n, names, seqs, quals, lens, batch = item
+            ticket, token, n, names, seqs, quals, lens, batch, comments = item
             res = None
             try:  # the ticket is waited for whatever happened before: only then is its lane idle
                 res = timed("wait", mapper.wait, ticket)
@@ -82,7 +90,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads):
             open_tickets.release()
             try:
                 if res is not None and not stop.is_set():
-                    timed("sam+write", mapper.sam_batch_raw, res, n, names, seqs, quals, lens, out)
+                    timed("sam+write", mapper.sam_batch_raw, res, n, names, seqs, quals, lens, out, comments if with_comment else None)
             except Exception as e:  # noqa: BLE001
                 fail(e)
             try:
@@ -120,7 +128,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads):
                 except Exception:
                     open_tickets.release()
                     raise
-                q_done.put((ticket, token, n, names, seqs, quals, lens, batch))
+                q_done.put((ticket, token, n, names, seqs, quals, lens, batch, comments))
             except Exception as e:  # noqa: BLE001
                 if batch is not None:
                     mapper.free_batch(batch)
@@ -161,6 +169,13 @@ def main():
     ap.add_argument("--MD", action="store_true", help="MD:Z: tag on every record with a CIGAR (MM_F_OUT_MD)")
     ap.add_argument("--cs", nargs="?", const="short", choices=["short", "long"], help="cs:Z: tag (MM_F_OUT_CS; long: MM_F_OUT_CS_LONG as well); with --MD, MD is printed")
     ap.add_argument("--eqx", action="store_true", help="=/X in place of M in every CIGAR (MM_F_EQX); --preset sr only, as in the reference's ShortReads tree")
+    ap.add_argument("--header", action="store_true", help="write the SAM header (@SQ, @RG, @PG) in front of the records")
+    ap.add_argument("-R", dest="rg", metavar="LINE", help="read group line, tabs spelled \\t: '@RG\\tID:x\\tSM:y' (RG:Z: on every record; @RG under --header)")
+    ap.add_argument("-Y", dest="softclip", action="store_true", help="soft clipping and whole-read SEQ/QUAL on supplementary and secondary records (MM_F_SOFTCLIP)")
+    ap.add_argument("-L", dest="long_cigar", action="store_true", help="CIGARs of more than 65535 operations go to the CG:B:I tag (MM_F_LONG_CIGAR)")
+    ap.add_argument("-y", dest="copy_comment", action="store_true", help="copy the FASTA/FASTQ comment to the end of each record (MM_F_COPY_COMMENT)")
+    ap.add_argument("-Q", dest="no_qual", action="store_true", help="no base qualities: QUAL is * (MM_F_NO_QUAL)")
+    ap.add_argument("--sam-hit-only", action="store_true", help="no record for a read without an alignment (MM_F_SAM_HIT_ONLY)")
     a = ap.parse_args()
     if a.eqx and a.preset != "sr":
         ap.error("--eqx is interpreted for --preset sr only (the LongReads variant does not interpret MM_F_EQX)")
@@ -178,12 +193,25 @@ def main():
     m.opt.flag |= tag_bits  # read by the SAM formatter alone (gdiet_hip_sam_batch); the mapping path does not interpret them
     if a.eqx:
         m.opt.flag |= 0x4000000  # MM_F_EQX: read by the mapping path (the CIGARs are rewritten on the device)
+    # -Y / -L / -y / -Q / --sam-hit-only: read by the SAM formatter alone, like the tag bits
+    m.opt.flag |= (0x80000 if a.softclip else 0) | (0x10000 if a.long_cigar else 0) | (0x2000000 if a.copy_comment else 0) | (0x10 if a.no_qual else 0) | \
+        (0x40000000 if a.sam_hit_only else 0)
+    if a.rg is not None:
+        try:
+            m.set_read_group(a.rg)
+        except pkg.GdietError as e:
+            print("map_file: -R: %s" % (e,), file=sys.stderr)
+            m.close()
+            ctx.close()
+            sys.exit(1)
     m.set_host_threads(pkg.effective_cpus())
     t_idx = time.perf_counter() - t0
     chunk = a.K or (39321600 if a.preset == "sr" else 80_000_000)
     try:
         with open(a.out, "wb") as out:
-            n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads)
+            if a.header:
+                out.write(m.sam_header(VERSION, sys.argv).encode())
+            n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment)
     except Exception as e:  # noqa: BLE001  (every ticket has been waited for by now: the context can be closed)
         print("map_file failed: %r" % (e,), file=sys.stderr)
         m.close()
