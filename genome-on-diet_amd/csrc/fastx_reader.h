@@ -4,6 +4,10 @@
 //
 // What differs from the reference is the mechanics: one large buffer refilled by gzread, lines located with memchr, all strings
 // of a batch parsed straight into one arena (no allocation per read), plain files read without zlib's extra copy.
+//
+// Optional device mode (GdFastx::dev, installed by gdiet_hip_fastx_attach): the strict four-line FASTQ prefix of every block is parsed
+// by an executor -- on the GPU, fastx_dev.hip.h -- and the sequential grammar below takes over at the first record that is not strict,
+// exactly as it does behind a wrong seam.  This header itself stays free of HIP.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -20,6 +24,7 @@
 #include <errno.h>
 #include <fcntl.h>
 #include <unistd.h>
+#include "fastx_dev.h"
 
 // Record parser over a byte range held in memory (kseq_read's grammar); the reader below feeds it blocks of the file.
 struct GdFastxParser {
@@ -106,9 +111,34 @@ struct GdFastxParser {
 	}
 };
 
+// Block buffers of device-parsed chunks on their way back to the reader.  A chunk of a batch in flight dies on the thread that frees the
+// batch, long after the reader has moved on (or has been closed: the pool belongs to whoever holds it last); fresh pages for every 8 MiB
+// block would cost more than parsing it.
+struct GdFastxBufPool {
+	std::mutex mu;
+	std::vector<std::vector<unsigned char>> bufs;
+};
+
 // The parsed records of one stretch of the file, in file order
 struct GdFastxChunk {
 	std::string arena;
+	// a device-parsed chunk owns the bytes of its block in place of an arena: the strings are the lines themselves, NUL-terminated in place
+	std::vector<unsigned char> buf;
+	const char *text = nullptr;   // the block inside buf (off[] counts from here)
+	std::vector<GdxRec> rec;      // the device's record table
+	std::shared_ptr<void> dev;    // the executor's copy of the block and of the table, alive until every record is handed out and its batch built
+	bool on_device = false;
+	std::shared_ptr<GdFastxBufPool> home; // where buf goes when the chunk dies
+	const char *base() const { return on_device ? text : arena.data(); }
+	GdFastxChunk() = default;
+	GdFastxChunk(const GdFastxChunk &) = delete;
+	GdFastxChunk &operator=(const GdFastxChunk &) = delete;
+	~GdFastxChunk()
+	{
+		if (!home || !buf.capacity()) return;
+		std::lock_guard<std::mutex> lk(home->mu);
+		if (home->bufs.size() < 24) home->bufs.push_back(std::move(buf));
+	}
 	std::vector<int64_t> off;     // 4 per record: name, comment, seq, qual (-1 = none)
 	std::vector<int32_t> len;     // sequence length per record
 	std::vector<uint8_t> err;     // per record: a malformed record (kseq_read < -1) FOLLOWED this one ...
@@ -116,8 +146,19 @@ struct GdFastxChunk {
 	size_t next = 0;              // records handed out so far
 };
 
+// What parses the strict prefix of a block (fastx_dev.h) somewhere else.  parse() fills rec with the records [0, n_acc) of b[0, n) and
+// returns n_acc (0: nothing for the device in this block; < 0: the device failed); dev keeps its copy of the block for the batches.
+struct GdFastxDevice {
+	virtual ~GdFastxDevice() {}
+	virtual long parse(const unsigned char *b, size_t n, std::vector<GdxRec> &rec, std::shared_ptr<void> &dev) = 0;
+};
+
 struct GdFastx {
 	gzFile fp = nullptr; // gzip input, or stdin
+	std::shared_ptr<GdFastxDevice> dev; // device mode, from the next block on
+	std::shared_ptr<GdFastxBufPool> bufpool = std::make_shared<GdFastxBufPool>();
+	bool dev_error = false;
+	int64_t n_rec_device = 0, n_rec_host = 0, n_blocks = 0, n_blocks_handed = 0; // who parsed what since the reader was opened
 	int fd = -1;         // plain file: read() straight into the block (gzread would copy it once more)
 	bool file_end = false, io_error = false;
 	int n_threads = 1;
@@ -139,6 +180,7 @@ struct GdFastx {
 	bool with_qual = true, with_comment = false, flags_set = false;
 	std::vector<const char *> v_name, v_comment, v_seq, v_qual;
 	std::vector<int32_t> v_len;
+	std::vector<int32_t> v_chunk, v_rec; // where read i of the batch came from: lent[v_chunk[i]], its record v_rec[i]
 
 	static size_t qname_len(const char *s) // mm_qname_len (LR/bseq.h:30-36)
 	{
@@ -250,12 +292,51 @@ struct GdFastx {
 		}
 		if (!c) c.reset(new GdFastxChunk());
 		c->arena.clear(), c->off.clear(), c->len.clear(), c->err.clear(), c->err_first = false, c->next = 0;
+		c->rec.clear(), c->dev.reset(), c->on_device = false, c->text = nullptr; // (buf keeps its memory for the next block it takes over)
 		return c;
+	}
+	// Device mode: the strict prefix of the current block becomes a chunk that takes the block over; returns where the host parser starts
+	size_t parse_on_device(std::vector<std::shared_ptr<GdFastxChunk>> &parts)
+	{
+		std::shared_ptr<GdFastxChunk> c = fresh_chunk();
+		const long na = fill < ((size_t)1 << 31) ? dev->parse(bp, fill, c->rec, c->dev) : 0; // (the record table holds 32-bit offsets)
+		if (na < 0) dev_error = true;
+		if (na <= 0) {
+			c->dev.reset();
+			if (pool.size() < 64) pool.push_back(std::move(c));
+			return 0;
+		}
+		unsigned char *w = const_cast<unsigned char *>(bp); // (the block is this reader's own buffer)
+		c->off.resize(4 * (size_t)na), c->len.resize((size_t)na), c->err.assign((size_t)na, 0);
+		for (long r = 0; r < na; ++r) {
+			const GdxRec &R = c->rec[(size_t)r];
+			int64_t *o = c->off.data() + 4 * r;
+			o[0] = R.name_off, o[2] = R.seq_off;
+			o[1] = with_comment && R.comment_off != GDX_NONE ? (int64_t)R.comment_off : -1;
+			o[3] = with_qual ? (int64_t)R.qual_off : -1;
+			c->len[(size_t)r] = (int32_t)R.seq_len;
+			w[R.name_off + R.name_len] = 0;              // the delimiter behind the name, or the '\n' of the header line
+			w[R.seq_off - 1] = 0;                        // the '\n' of the header line: the end of the comment
+			w[R.seq_off + R.seq_len] = 0, w[R.qual_off + R.seq_len] = 0;
+		}
+		const GdxRec &L = c->rec[(size_t)na - 1];
+		const size_t from = (size_t)L.qual_off + L.seq_len + 1;
+		c->buf.swap(block); // (bp keeps pointing into it; `block` gets the buffer this chunk owned before, if any)
+		c->home = bufpool;
+		if (block.empty()) { // ... or one that a dead chunk sent back
+			std::lock_guard<std::mutex> lk(bufpool->mu);
+			if (!bufpool->bufs.empty()) block.swap(bufpool->bufs.back()), bufpool->bufs.pop_back();
+		}
+		c->text = (const char *)bp, c->on_device = true;
+		n_rec_device += na;
+		parts.push_back(std::move(c));
+		return from;
 	}
 	// read and parse one more block; false when the input is exhausted
 	bool parse_more()
 	{
-		size_t want = block_size * (size_t)n_threads;
+		// (device mode: the parser threads have nothing to do -- the device takes the strict prefix and the rest is parsed in sequence -- so a block is one thread's)
+		size_t want = block_size * (size_t)(dev && !dev_error ? 1 : n_threads);
 		for (;;) {
 			if (!io_pending) { // the very first block: nothing was read ahead
 				if (file_end) return false;
@@ -268,7 +349,9 @@ struct GdFastx {
 			// split points: record starts verified by look-ahead; whether they ARE boundaries of the sequential grammar is checked
 			// afterwards (every stretch must end exactly where the next one began) -- if not, the rest is parsed again in sequence
 			std::vector<size_t> cut(1, 0);
-			if (n_threads > 1 && fill >= std::min<size_t>((size_t)1 << 20, block_size))
+			std::vector<std::shared_ptr<GdFastxChunk>> dparts;
+			if (dev && !dev_error) cut[0] = parse_on_device(dparts); // the rest goes through parse_range in sequence, as behind a wrong seam
+			else if (n_threads > 1 && fill >= std::min<size_t>((size_t)1 << 20, block_size))
 				for (int k = 1; k < n_threads; ++k) {
 					const size_t c = find_seam(std::max(cut.back() + 1, fill / (size_t)n_threads * (size_t)k));
 					if (c >= fill) break;
@@ -297,6 +380,12 @@ struct GdFastx {
 				pos = parse_range(*parts[good], endpos[good - 1], fill, file_end);
 			}
 			size_t n_rec = 0;
+			for (auto &c : parts) if (c) n_rec_host += (int64_t)c->len.size();
+			++n_blocks;
+			if (!dparts.empty()) {
+				for (auto &c : parts) if (c && (!c->len.empty() || c->err_first)) { ++n_blocks_handed; break; }
+				parts.insert(parts.begin(), dparts.begin(), dparts.end());
+			}
 			for (auto &c : parts) if (c) { n_rec += c->len.size() + (c->err_first ? 1 : 0); if (!c->len.empty() || c->err_first) ready.push_back(std::move(c)); else if (pool.size() < 64) pool.push_back(std::move(c)); }
 			// the unparsed tail (a record cut off by the block end) goes in front of the next stretch of the file, which is read while
 			// the caller works on what was parsed
@@ -307,13 +396,23 @@ struct GdFastx {
 			if (n_rec) return true;
 		}
 	}
+	// U -> T in the host strings of the last batch's reads from device-parsed chunks (kseq2bseq, LR/bseq.c:71-73; read_record does it
+	// for the host's own).  For a caller that takes no resident batch: the encode kernel flags the reads that need it otherwise.
+	void u_to_t_on_host()
+	{
+		for (size_t i = 0; i < v_len.size() && n_rec_device; ++i)
+			if (lent[(size_t)v_chunk[i]]->on_device) {
+				char *q = const_cast<char *>(v_seq[i]);
+				for (int32_t k = 0; k < v_len[i]; ++k) if (gdx_is_u((unsigned char)q[k])) --q[k];
+			}
+	}
 	// mm_bseq_read3 (LR/bseq.c:80-121); returns the number of reads of the batch (0 at the end of the file), < 0 on a read error
 	int read_batch(int64_t chunk_size, bool wq, bool wc, bool frag_mode, bool *parse_error)
 	{
 		if (!flags_set) with_qual = wq, with_comment = wc, flags_set = true; // (the flags of the first call hold for the whole file)
 		for (auto &c : lent) if (c.use_count() == 1 && pool.size() < 64) pool.push_back(std::move(c)); // (not in `ready` any more, not detached)
 		lent.clear();
-		v_name.clear(), v_comment.clear(), v_seq.clear(), v_qual.clear(), v_len.clear();
+		v_name.clear(), v_comment.clear(), v_seq.clear(), v_qual.clear(), v_len.clear(), v_chunk.clear(), v_rec.clear();
 		if (parse_error) *parse_error = false;
 		int64_t size = 0;
 		bool closing = false; // the batch is full: only mates of its last read may still join (fragment mode)
@@ -325,7 +424,8 @@ struct GdFastx {
 			if (C.err_first) { C.err_first = false; if (parse_error) *parse_error = true; break; } // the reference warns and returns what it has
 			if (C.next >= C.len.size()) continue;
 			const size_t i = C.next;
-			const char *nm = C.arena.data() + C.off[4 * i];
+			const char *const base = C.base();
+			const char *nm = base + C.off[4 * i];
 			if (closing) {
 				const char *prev = v_name.back();
 				const size_t l1 = qname_len(nm), l2 = qname_len(prev);
@@ -333,10 +433,11 @@ struct GdFastx {
 			}
 			if (lent.empty() || lent.back().get() != &C) lent.push_back(ready.front());
 			v_name.push_back(nm);
-			v_comment.push_back(C.off[4 * i + 1] < 0 ? nullptr : C.arena.data() + C.off[4 * i + 1]);
-			v_seq.push_back(C.arena.data() + C.off[4 * i + 2]);
-			v_qual.push_back(C.off[4 * i + 3] < 0 ? nullptr : C.arena.data() + C.off[4 * i + 3]);
+			v_comment.push_back(C.off[4 * i + 1] < 0 ? nullptr : base + C.off[4 * i + 1]);
+			v_seq.push_back(base + C.off[4 * i + 2]);
+			v_qual.push_back(C.off[4 * i + 3] < 0 ? nullptr : base + C.off[4 * i + 3]);
 			v_len.push_back(C.len[i]);
+			v_chunk.push_back((int32_t)lent.size() - 1), v_rec.push_back((int32_t)i);
 			size += C.len[i];
 			++C.next;
 			if (C.err[i]) { C.err[i] = 0; if (parse_error) *parse_error = true; break; }
@@ -346,7 +447,7 @@ struct GdFastx {
 			}
 		}
 		// (pointers into chunks still in `ready` stay valid: a chunk is only released from `lent`, at the next call)
-		if (io_error) return -1;
+		if (io_error || dev_error) return -1;
 		return (int)v_len.size();
 	}
 };

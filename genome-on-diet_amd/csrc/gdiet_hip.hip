@@ -123,6 +123,12 @@ struct gdiet_ctx {
 	hipStream_t ds_stream = nullptr;
 	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff;
 	std::vector<uint8_t> ds_enc;       // host copy of the reads a call without a resident batch encodes
+	// FASTQ blocks parsed on the device (fastx_dev.hip.h; the driver is at the end of this file): like the difference strings, a stream,
+	// a scan buffer and a mutex of their own, because the reader thread of a file route calls it while map tickets are open
+	std::mutex fx_mu;
+	std::string fx_err;                // text of the last failing device parse (written under fx_mu; gdiet_hip_strerror)
+	hipStream_t fx_stream = nullptr;
+	DevBuf fx_scan;
 	std::string rg_line, rg_id;        // -R: the escaped @RG header line and its ID (gdiet_hip_set_read_group; read by the SAM formatters)
 };
 
@@ -270,8 +276,9 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
 	if (ctx->ds_stream) (void)hipStreamSynchronize(ctx->ds_stream);
+	if (ctx->fx_stream) (void)hipStreamSynchronize(ctx->fx_stream);
 	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev};
-	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream};
+	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream, ctx->fx_stream};
 	delete ctx; // every DevBuf of the context releases itself here: before the streams and events go
 	for (hipEvent_t e : events)
 		if (e) (void)hipEventDestroy(e);
@@ -310,9 +317,11 @@ extern "C" int gdiet_hip_last_dp_clock(gdiet_ctx *ctx, double *sclk_mhz_median, 
 
 
 static const char *gd_ds_err_of(const gdiet_ctx *ctx); // map_diffstr_driver.hip.h
+static const char *gd_fx_err_of(const gdiet_ctx *ctx); // the reader's device mode, at the end of this file
 extern "C" const char *gdiet_hip_strerror(const gdiet_ctx *ctx)
 {
 	if (const char *ds = gd_ds_err_of(ctx)) return ds; // this thread's last failure on the context was a difference-string pass
+	if (const char *fx = gd_fx_err_of(ctx)) return fx; // ... or a device parse of the reader
 	return ctx ? ctx->err.c_str() : "no context";
 }
 
@@ -980,7 +989,7 @@ extern "C" int gdiet_hip_debug_seed_prof(unsigned long long *out8) { return (int
 #endif
 // ---- read input (input half) ---------------------------------------------------------------------------
 #include "fastx_reader.h"
-struct gdiet_fastx { GdFastx *r; };
+#include "fastx_dev_driver.hip.h" // struct gdiet_fastx; the device mode of the reader
 
 extern "C" int gdiet_hip_fastx_open(gdiet_fastx **fx, const char *path)
 {
@@ -988,7 +997,8 @@ extern "C" int gdiet_hip_fastx_open(gdiet_fastx **fx, const char *path)
 	*fx = nullptr;
 	GdFastx *r = gd_fastx_open(path);
 	if (!r) return GDIET_E_PARAM;
-	*fx = new gdiet_fastx{r};
+	*fx = new gdiet_fastx();
+	(*fx)->r = r;
 	return GDIET_OK;
 }
 
@@ -999,12 +1009,69 @@ extern "C" int gdiet_hip_fastx_read(gdiet_fastx *fx, int64_t chunk_size, int wit
 	if (!fx || !fx->r || !n_reads || !names || !seqs || !lens) return GDIET_E_PARAM;
 	bool bad = false;
 	const int n = fx->r->read_batch(chunk_size, with_qual != 0, with_comment != 0, frag_mode != 0, &bad);
-	if (n < 0) return GDIET_E_PARAM;
+	if (n < 0) return fx->r->dev_error ? GDIET_E_HIP : GDIET_E_PARAM;
+	fx->r->u_to_t_on_host(); // (an attached reader without a resident batch: nobody encodes these reads on the device)
+	gd_fx_release_done(*fx->r);
 	*n_reads = n;
 	*names = fx->r->v_name.data(), *seqs = fx->r->v_seq.data(), *lens = fx->r->v_len.data();
 	if (comments) *comments = fx->r->v_comment.data();
 	if (quals) *quals = fx->r->v_qual.data();
 	return bad ? GDIET_W_TRUNCATED : GDIET_OK;
+}
+
+extern "C" int gdiet_hip_fastx_attach(gdiet_fastx *fx, gdiet_ctx *ctx)
+{
+	if (!fx || !fx->r) return GDIET_E_PARAM;
+	fx->ctx = ctx;
+	if (ctx) fx->r->dev = std::make_shared<GdFxExecutor>(ctx);
+	else fx->r->dev.reset();
+	return GDIET_OK;
+}
+
+extern "C" int gdiet_hip_fastx_read_resident(gdiet_fastx *fx, int64_t chunk_size, int with_qual, int with_comment, int frag_mode, int32_t *n_reads,
+                                             const char *const **names, const char *const **comments, const char *const **seqs,
+                                             const char *const **quals, const int32_t **lens, gdiet_read_batch **batch)
+{
+	if (!fx || !fx->r || !n_reads || !names || !seqs || !lens || !batch) return GDIET_E_PARAM;
+	*batch = nullptr;
+	if (!fx->ctx) return GDIET_E_PARAM; // the batch belongs to a context: attach first
+	bool bad = false;
+	const int n = fx->r->read_batch(chunk_size, with_qual != 0, with_comment != 0, frag_mode != 0, &bad);
+	if (n < 0) return fx->r->dev_error ? GDIET_E_HIP : GDIET_E_PARAM;
+	if (n > 0) {
+		const int rc = gd_fx_build_batch(fx->ctx, *fx->r, batch);
+		if (rc) return rc;
+	}
+	gd_fx_release_done(*fx->r);
+	*n_reads = n;
+	*names = fx->r->v_name.data(), *seqs = fx->r->v_seq.data(), *lens = fx->r->v_len.data();
+	if (comments) *comments = fx->r->v_comment.data();
+	if (quals) *quals = fx->r->v_qual.data();
+	return bad ? GDIET_W_TRUNCATED : GDIET_OK;
+}
+
+extern "C" int gdiet_hip_fastx_stats(const gdiet_fastx *fx, int64_t *records_device, int64_t *records_host, int64_t *blocks, int64_t *blocks_handed_over)
+{
+	if (!fx || !fx->r) return GDIET_E_PARAM;
+	if (records_device) *records_device = fx->r->n_rec_device;
+	if (records_host) *records_host = fx->r->n_rec_host;
+	if (blocks) *blocks = fx->r->n_blocks;
+	if (blocks_handed_over) *blocks_handed_over = fx->r->n_blocks_handed;
+	return GDIET_OK;
+}
+
+extern "C" int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n, int64_t *roff, uint8_t *enc_host, uint8_t *enc_device)
+{
+	if (!ctx || !b) return GDIET_E_PARAM;
+	if (n) *n = b->n;
+	if (roff) memcpy(roff, b->roff.data(), sizeof(int64_t) * ((size_t)b->n + 1));
+	const size_t total = (size_t)b->roff[(size_t)b->n];
+	if (enc_host && total) memcpy(enc_host, b->enc.data(), total);
+	if (enc_device && total) {
+		(void)hipSetDevice(ctx->device);
+		GD_HIP(hipMemcpy(enc_device, b->d_reads, total, hipMemcpyDeviceToHost));
+	}
+	return GDIET_OK;
 }
 
 struct gdiet_fastx_batch { GdFastxBatch *b; };

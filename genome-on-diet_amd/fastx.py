@@ -8,7 +8,11 @@ W_TRUNCATED = 1
 
 
 class FastxReader:
-    def __init__(self, path, threads=1):
+    """ctx: a Context; the reader is then attached to it (gdiet_hip_fastx_attach): the strict four-line FASTQ records at the front of
+    every block are parsed on its device, and read_raw(..., resident=True) returns the resident batch next to the host arrays.  The
+    records, batches and truncation flags do not depend on it.  Close the reader before the context."""
+
+    def __init__(self, path, threads=1, ctx=None):
         self.lib = load_library()
         L = self.lib
         cpp = C.POINTER(C.c_char_p)
@@ -24,6 +28,13 @@ class FastxReader:
         L.gdiet_hip_fastx_set_threads.argtypes = [C.c_void_p, C.c_int]
         if threads > 1:
             L.gdiet_hip_fastx_set_threads(self._h, threads)
+        L.gdiet_hip_fastx_attach.argtypes = [C.c_void_p, C.c_void_p]
+        L.gdiet_hip_fastx_read_resident.argtypes = L.gdiet_hip_fastx_read.argtypes + [C.POINTER(C.c_void_p)]
+        i64p = C.POINTER(C.c_int64)
+        L.gdiet_hip_fastx_stats.argtypes = [C.c_void_p, i64p, i64p, i64p, i64p]
+        self.ctx = ctx
+        if ctx is not None and L.gdiet_hip_fastx_attach(self._h, ctx._h) != 0:
+            raise GdietError("gdiet_hip_fastx_attach failed")
 
     def read(self, chunk_size, with_qual=True, with_comment=False, frag_mode=False):
         """next mini-batch as a list of (name, seq, qual or None, comment or None), all bytes; [] at the end of the input"""
@@ -33,7 +44,7 @@ class FastxReader:
         rc = self.lib.gdiet_hip_fastx_read(self._h, chunk_size, int(with_qual), int(with_comment), int(frag_mode), C.byref(n), C.byref(names),
                                            C.byref(comments), C.byref(seqs), C.byref(quals), C.byref(lens))
         if rc < 0:
-            raise GdietError("read error")
+            raise GdietError("read error" + (": " + self.lib.gdiet_hip_strerror(self.ctx._h).decode() if self.ctx is not None else ""))
         self.truncated_now = rc == W_TRUNCATED  # this batch was closed by a malformed record
         self.truncated = self.truncated or self.truncated_now
         out = []
@@ -43,16 +54,25 @@ class FastxReader:
             out.append((names[i], s, quals[i], comments[i]))
         return out
 
-    def read_raw(self, chunk_size, with_qual=True, with_comment=False, frag_mode=False, detach=False):
+    def read_raw(self, chunk_size, with_qual=True, with_comment=False, frag_mode=False, detach=False, resident=False):
         """next mini-batch as C arrays: (n, names, comments, seqs, quals, lens, token).  With detach=True the arrays stay valid until
-        release(token) (several mini-batches in flight); otherwise until the next read."""
+        release(token) (several mini-batches in flight); otherwise until the next read.  With resident=True (a reader made with ctx) an
+        eighth element follows: the resident batch of these reads (gdiet_hip_fastx_read_resident) as Mapper.upload_raw would return it,
+        for Mapper.submit / map_uploaded / free_batch -- None when n is 0."""
         cpp = C.POINTER(C.c_char_p)
         n = C.c_int32()
         names, comments, seqs, quals, lens = cpp(), cpp(), cpp(), cpp(), C.POINTER(C.c_int32)()
-        rc = self.lib.gdiet_hip_fastx_read(self._h, chunk_size, int(with_qual), int(with_comment), int(frag_mode), C.byref(n), C.byref(names),
-                                           C.byref(comments), C.byref(seqs), C.byref(quals), C.byref(lens))
+        if resident:
+            if self.ctx is None:
+                raise GdietError("a resident batch needs a reader made with ctx")
+            bh = C.c_void_p()
+            rc = self.lib.gdiet_hip_fastx_read_resident(self._h, chunk_size, int(with_qual), int(with_comment), int(frag_mode), C.byref(n), C.byref(names),
+                                                        C.byref(comments), C.byref(seqs), C.byref(quals), C.byref(lens), C.byref(bh))
+        else:
+            rc = self.lib.gdiet_hip_fastx_read(self._h, chunk_size, int(with_qual), int(with_comment), int(frag_mode), C.byref(n), C.byref(names),
+                                               C.byref(comments), C.byref(seqs), C.byref(quals), C.byref(lens))
         if rc < 0:
-            raise GdietError("read error")
+            raise GdietError("read error" + (": " + self.lib.gdiet_hip_strerror(self.ctx._h).decode() if self.ctx is not None else ""))
         self.truncated_now = rc == W_TRUNCATED
         self.truncated = self.truncated or self.truncated_now
         token = None
@@ -60,7 +80,15 @@ class FastxReader:
             self.lib.gdiet_hip_fastx_detach.restype = C.c_void_p
             self.lib.gdiet_hip_fastx_detach.argtypes = [C.c_void_p]
             token = C.c_void_p(self.lib.gdiet_hip_fastx_detach(self._h))
+        if resident:
+            return n.value, names, comments, seqs, quals, lens, token, ((bh, n.value) if bh.value else None)
         return n.value, names, comments, seqs, quals, lens, token
+
+    def stats(self):
+        """gdiet_hip_fastx_stats: who parsed what since the reader was opened"""
+        v = [C.c_int64() for _ in range(4)]
+        self.lib.gdiet_hip_fastx_stats(self._h, *[C.byref(x) for x in v])
+        return dict(zip(("records_device", "records_host", "blocks", "blocks_handed_over"), (x.value for x in v)))
 
     def release(self, token):
         if token:

@@ -87,6 +87,7 @@ def _bind(lib):
     lib.gdiet_hip_set_inflight.argtypes = [vp, C.c_int]
     lib.gdiet_hip_batch_destroy.argtypes = [vp, vp]
     lib.gdiet_hip_batch_destroy.restype = None
+    lib.gdiet_hip_batch_export.argtypes = [vp, vp, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
     lib.gdiet_hip_map_stage_seconds.argtypes = [vp, C.POINTER(C.c_double)]
     lib.gdiet_hip_map_scratch_retries.argtypes = []
     lib.gdiet_hip_map_scratch_retries.restype = C.c_int64
@@ -326,6 +327,20 @@ class Mapper:
         h = C.c_void_p()
         self.ctx._check(self.lib.gdiet_hip_batch_upload(self.ctx._h, C.byref(h), n, C.cast(seqs, C.POINTER(C.c_char_p)), lens))
         return (h, n)
+
+    def export_batch(self, batch):
+        """gdiet_hip_batch_export: (roff, host copy, device copy) of a resident batch -- of upload / upload_raw, or one a FastxReader made --
+        as numpy arrays: int64[n + 1] and twice uint8[roff[n]]"""
+        h, n = batch
+        nn = C.c_int32()
+        roff = np.zeros(n + 1, np.int64)
+        self.ctx._check(self.lib.gdiet_hip_batch_export(self.ctx._h, h, C.byref(nn), roff.ctypes.data_as(C.POINTER(C.c_int64)), None, None))
+        if nn.value != n:
+            raise GdietError("the batch holds %d reads, not %d" % (nn.value, n))
+        host, dev = np.zeros(int(roff[n]), np.uint8), np.zeros(int(roff[n]), np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        self.ctx._check(self.lib.gdiet_hip_batch_export(self.ctx._h, h, None, None, host.ctypes.data_as(u8p), dev.ctypes.data_as(u8p)))
+        return roff, host, dev
 
     def sam_batch_raw(self, res, n, names, seqs, quals, lens, sink=None, comments=None):
         """gdiet_hip_sam_batch on C arrays.  With sink (a binary file object) the text is formatted into a buffer kept by this mapper

@@ -489,6 +489,30 @@ void gdiet_hip_fastx_batch_free(gdiet_fastx_batch *b);
 int gdiet_hip_fastx_set_threads(gdiet_fastx *fx, int n);
 void gdiet_hip_fastx_close(gdiet_fastx *fx);
 
+/* Device mode of the reader.  From the next block of the file on, the strict four-line FASTQ records at the front of every block are
+ * found on ctx's device (newline ballot, scan, one thread per record) in place of kseq_read (LR/kseq.h:191-232): a record is strict
+ * when its four lines are complete, start with '@' / not '@', '+', '>' / '+' / anything, hold no '\r', and sequence and quality are
+ * equally long and not empty -- for such a record kseq_read consumes exactly these lines.  The first record of a block that is not
+ * strict, and everything behind it, goes through the sequential grammar as before, so the records, batches (LR/bseq.c:80-121) and
+ * truncation flags are those of an unattached reader on every input.  ctx == NULL detaches.  Close the reader, and free the batches
+ * taken out of it, before ctx is destroyed.  Any thread may read while map tickets are open on ctx. */
+int gdiet_hip_fastx_attach(gdiet_fastx *fx, gdiet_ctx *ctx);
+/* gdiet_hip_fastx_read plus the resident batch of exactly those reads: *batch is what gdiet_hip_batch_upload(ctx, ..., n, seqs, lens)
+ * would have built (seq_nt4_table, LR/sketch.c:11-18), NULL when no read is returned.  Reads of device-parsed chunks are encoded on the
+ * device from the block that is already there -- their U / u becomes T / t in the host strings (LR/bseq.c:71-73) by a flag the encode
+ * kernel sets -- and reads the host parsed are encoded and copied as gdiet_hip_batch_upload does; one batch may hold both kinds.
+ * Release with gdiet_hip_batch_destroy.  Requires an attached reader (GDIET_E_PARAM otherwise).  gdiet_hip_fastx_detach and
+ * gdiet_hip_fastx_batch_free work on the host arrays as before. */
+int gdiet_hip_fastx_read_resident(gdiet_fastx *fx, int64_t chunk_size, int with_qual, int with_comment, int frag_mode, int32_t *n_reads,
+                                  const char *const **names, const char *const **comments, const char *const **seqs,
+                                  const char *const **quals, const int32_t **lens, gdiet_read_batch **batch);
+/* Who parsed what since the reader was opened: records found on the device, records the host grammar returned, blocks parsed, and
+ * blocks of an attached reader whose rest gave the host grammar at least one record (or a malformed one).  Any pointer may be NULL. */
+int gdiet_hip_fastx_stats(const gdiet_fastx *fx, int64_t *records_device, int64_t *records_host, int64_t *blocks, int64_t *blocks_handed_over);
+/* A resident batch as arrays, for tests and for a maintainer checking one: *n reads, roff[n + 1], and the roff[n] encoded bytes of the
+ * host copy (enc_host) and of the device copy, downloaded (enc_device).  Sizes first: every array argument may be NULL. */
+int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n, int64_t *roff, uint8_t *enc_host, uint8_t *enc_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,13 +3,15 @@ map with several batches in flight (gdiet_hip_map_submit / _wait) -> SAM records
 No Python object is made per read: the C arrays of the reader go straight into the upload and the SAM formatter.
 
     python tools/map_file.py --preset sr ref.fa reads.fq[.gz] -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
-                             [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only]
+                             [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
 
 Writes the SAM body (the records).  --header puts the header lines of the reference's CLI in front (gdiet_hip_sam_header: @SQ per
 contig, the @RG line of -R, @PG with this tool's version and command line); it is opt-in, so that the default output stays the body alone.
 -R, -Y, -L, -y, -Q and --sam-hit-only mean what they mean to the reference (LR/main.c): a read group on every record, soft clips and
 whole reads on supplementary records, long CIGARs in the CG tag, the FASTQ comment as the last field (read with with_comment), no
-qualities (not even read: with_qual off), no record for an unmapped read."""
+qualities (not even read: with_qual off), no record for an unmapped read.
+--device-reader attaches the reader to the context (gdiet_hip_fastx_attach): four-line FASTQ is parsed and encoded on the device, the
+reader hands out resident batches, and the upload stage disappears; the output is the same, and the JSON line gains reader_stats."""
 import argparse
 import json
 import os
@@ -27,7 +29,7 @@ from __graft_entry__ import _load_pkg  # noqa: E402
 VERSION = "gdiet-hip-map_file"  # the VN: field of --header's @PG line
 
 
-def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False):
+def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False):
     """returns (reads, seconds).  Three stages on three threads, as the reference's kt_pipeline runs its three steps (LR/map.c:2094-2170):
     read -> upload + submit -> wait + format + write; the C calls release the interpreter lock, so the stages overlap.
     A failure in any stage stops all three: `stop` is set, the writer keeps draining q_done (every open ticket is still waited for and
@@ -35,7 +37,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
     submitting loop give up at their next queue operation, and the first error is raised once the threads have ended."""
     import queue
     import threading
-    fx = pkg.FastxReader(reads_path, threads=reader_threads)
+    fx = pkg.FastxReader(reads_path, threads=reader_threads, ctx=mapper.ctx if device_reader else None)
     mapper.set_inflight(inflight)
     T = {"read": 0.0, "upload": 0.0, "submit": 0.0, "wait": 0.0, "sam+write": 0.0, "free": 0.0}
     q_read, q_done = queue.Queue(maxsize=2), queue.Queue()
@@ -63,13 +65,19 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
                 pass
         return False
 
+    def drop_item(item):
+        """a batch of the reader that nobody is going to map"""
+        if item[0]:
+            if device_reader and item[7] is not None:
+                mapper.free_batch(item[7])
+            fx.release(item[6])
+
     def reader():
         try:
             while not stop.is_set():
-                item = timed("read", fx.read_raw, chunk, with_qual=with_qual, with_comment=with_comment, detach=True)
+                item = timed("read", fx.read_raw, chunk, with_qual=with_qual, with_comment=with_comment, detach=True, resident=device_reader)
                 if not put(q_read, item):
-                    if item[0]:
-                        fx.release(item[6])
+                    drop_item(item)
                     return
                 if item[0] == 0:
                     return
@@ -109,7 +117,8 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
     try:
         while not stop.is_set():
             try:
-                n, names, comments, seqs, quals, lens, token = q_read.get(timeout=0.2)
+                item = q_read.get(timeout=0.2)
+                n, names, comments, seqs, quals, lens, token = item[:7]
             except queue.Empty:
                 if not th_r.is_alive() and q_read.empty():
                     break  # the reader ended without its end-of-file item: it failed
@@ -117,9 +126,10 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
             if n == 0:
                 break
             n_reads += n
-            batch = None
+            batch = item[7] if device_reader else None  # (the reader's resident batch: nothing to encode or copy here)
             try:
-                batch = timed("upload", mapper.upload_raw, n, seqs, lens)
+                if not device_reader:
+                    batch = timed("upload", mapper.upload_raw, n, seqs, lens)
                 while not open_tickets.acquire(timeout=0.2):
                     if stop.is_set():
                         raise RuntimeError("pipeline stopped")
@@ -142,14 +152,13 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
         if stop_was_set:  # unblock a reader waiting on a full queue
             while True:
                 try:
-                    item = q_read.get_nowait()
-                    if item[0]:
-                        fx.release(item[6])
+                    drop_item(q_read.get_nowait())
                 except queue.Empty:
                     break
         th_w.join()
         stop.set()  # (nothing is left to do: a reader that has not reached the end of the file stops here)
         th_r.join()
+        map_file.last_reader_stats = fx.stats()
         fx.close()
     if errors:
         raise errors[0]
@@ -176,6 +185,7 @@ def main():
     ap.add_argument("-y", dest="copy_comment", action="store_true", help="copy the FASTA/FASTQ comment to the end of each record (MM_F_COPY_COMMENT)")
     ap.add_argument("-Q", dest="no_qual", action="store_true", help="no base qualities: QUAL is * (MM_F_NO_QUAL)")
     ap.add_argument("--sam-hit-only", action="store_true", help="no record for a read without an alignment (MM_F_SAM_HIT_ONLY)")
+    ap.add_argument("--device-reader", action="store_true", help="parse and encode four-line FASTQ on the device (gdiet_hip_fastx_attach); the reader hands out resident batches")
     a = ap.parse_args()
     if a.eqx and a.preset != "sr":
         ap.error("--eqx is interpreted for --preset sr only (the LongReads variant does not interpret MM_F_EQX)")
@@ -211,14 +221,16 @@ def main():
         with open(a.out, "wb") as out:
             if a.header:
                 out.write(m.sam_header(VERSION, sys.argv).encode())
-            n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment)
+            n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment,
+                             device_reader=a.device_reader)
     except Exception as e:  # noqa: BLE001  (every ticket has been waited for by now: the context can be closed)
         print("map_file failed: %r" % (e,), file=sys.stderr)
         m.close()
         ctx.close()
         sys.exit(1)
     print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), "mini_batch_bases": chunk,
-                      "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "eqx": a.eqx, "out": a.out, "caller_seconds": map_file.last_stage_seconds}))
+                      "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "eqx": a.eqx, "out": a.out, "caller_seconds": map_file.last_stage_seconds,
+                      **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {})}))
     m.close()
     ctx.close()
 
