@@ -9,8 +9,9 @@ SRC = os.path.join(HERE, "csrc", "gdiet_hip.hip")
 RES = os.path.join(HERE, "build_resources.txt")  # the compiler's per-kernel resource remarks of the last build
 
 # Register budgets the design depends on (checked against the compiler's own resource report after every build):
-#   * the 64-lane DP kernel: 96 VGPRs = 5 wavefronts per SIMD, and nothing of its row loops in scratch memory -- the full-band rows and the
-#     half-block rows of the narrow band it tries first are one kernel (ksw_wave.hip.h, "NARROW BAND FIRST"), so one budget covers both;
+#   * the 64-lane DP kernel: 96 VGPRs = 5 wavefronts per SIMD, and nothing of its row loops in scratch memory -- the full-band rows, the
+#     half-block rows of the 495-wide band and the quarter-block rows of the 239-wide band it tries before them are one kernel
+#     (ksw_wave.hip.h, "NARROW BAND FIRST" / "THE QUARTER RUNG"), so one budget covers all three row loops;
 #   * the kernels that must be able to start BESIDE a full house of those DP wavefronts (5 x 96 of a SIMD's 512 registers are taken):
 #     at most 32 VGPRs (map_kernels.hip.h: map_post_wave_kernel; map_diffstr.hip.h: the cs / MD tag pass of batch i runs beside the DP of batch i+1).
 BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),

@@ -109,9 +109,12 @@ struct gdiet_ctx {
 	double stage_s[6] = {0, 0, 0, 0, 0, 0};
 	uint64_t last_cells = 0, last_alg_bytes = 0; // of the most recent DP launch
 	int narrow_band = 1;               // GDIET_NARROW_BAND=0: the 64-lane DP kernel runs every alignment at its full band (ksw_wave.hip.h, "NARROW BAND FIRST")
-	DevBuf narrow_cnt;                 // two counters of the most recent 64-lane DP launch: alignments that tried the narrow band, certified ones
+	DevBuf narrow_cnt;                 // six counters of the most recent 64-lane DP launch: alignments that tried a narrow band, certified ones; the same per rung (239, 495)
 	bool narrow_launched = false;      // that launch had a 64-lane kernel at all
-	uint64_t async_narrow[2] = {0, 0}; // the lane's counters, copied at gdiet_hip_map_wait
+	uint64_t async_narrow[6] = {0, 0, 0, 0, 0, 0}; // the lane's counters, copied at gdiet_hip_map_wait
+	int narrow_quarter = -1;           // GDIET_NARROW_QUARTER: 0 never offers the quarter rung (band 239), 1 always, unset (-1): auto
+	GdQuarterAuto quarter_auto;        // (root) auto mode: whether the next launches offer the rung (ksw_plan.h; read and written under dp_mu)
+	bool quarter_offered = false;      // this context's most recent DP launch offered the rung
 	// reads the most recent map call gave up on (a DP box outside its read / contig: undefined behaviour in the reference); they come back
 	// with n_regs = 0 while the rest of the batch is mapped.  failed_total: since the context was created.
 	int64_t failed_last = 0, failed_total = 0;
@@ -255,6 +258,8 @@ extern "C" int gdiet_hip_init(gdiet_ctx **out, int device)
 		if (sb) ctx->sr_boxes_on_device = strcmp(sb, "host") != 0;
 		const char *nb = getenv("GDIET_NARROW_BAND");
 		if (nb) ctx->narrow_band = atoi(nb) != 0;
+		const char *nq = getenv("GDIET_NARROW_QUARTER");
+		if (nq) ctx->narrow_quarter = atoi(nq) != 0;
 	}
 	*out = ctx;
 	return GDIET_OK;
@@ -464,12 +469,12 @@ static int gd_dp_launch(gdiet_ctx *ctx, const GdPlan &P, int n, const KswConst &
 	ctx->narrow_launched = false;
 	ctx->last_was_async = false; // this context's own launch is now its most recent one (a lane's flag is never set; gdiet_hip_map_wait sets the root's after the lane's batch)
 	if (n64 > 0) {
-		if ((rc = gd_grow(ctx, ctx->narrow_cnt, 2 * sizeof(uint32_t)))) return rc;
-		GD_HIP(hipMemsetAsync(ctx->narrow_cnt.p, 0, 2 * sizeof(uint32_t), stream));
+		if ((rc = gd_grow(ctx, ctx->narrow_cnt, 6 * sizeof(uint32_t)))) return rc;
+		GD_HIP(hipMemsetAsync(ctx->narrow_cnt.p, 0, 6 * sizeof(uint32_t), stream));
 		ctx->narrow_launched = true;
 		gd_launch_wave64(d_tasks, d_ids + P.id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
 		                 ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves, (ctx->parent ? ctx->parent->narrow_band : ctx->narrow_band) ? GD_W_NARROW : 0,
-		                 (uint32_t *)ctx->narrow_cnt.p);
+		                 (uint32_t *)ctx->narrow_cnt.p, ctx->quarter_offered ? GD_W_QUARTER : 0);
 	}
 	if (P.n_kind[GD_KIND_WAVE16]) {
 		// The short-alignment kernels CAN walk their own alignments back (every group's first lane, gd_bt_thread_walk), but it does not pay:
@@ -590,6 +595,14 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 	ctx->own_arena = own;
 	if (own) arena_free = nullptr, arena_turn = nullptr;
 	DevBuf &arena = ctx->parent && !own ? ctx->parent->arena : ctx->arena;
+	{ // does this launch offer the quarter rung?  (the root's switch and auto state; dp_mu is not yet held by this thread)
+		gdiet_ctx *root = ctx->parent ? ctx->parent : ctx;
+		ctx->quarter_offered = root->narrow_band && root->narrow_quarter != 0;
+		if (ctx->quarter_offered && root->narrow_quarter < 0 && P.n_kind[GD_KIND_WAVE64]) {
+			std::lock_guard<std::mutex> guard(root->dp_mu);
+			ctx->quarter_offered = gd_quarter_auto_offer(root->quarter_auto);
+		}
+	}
 	if (arena_turn) arena_turn->lock(); // everything above was this batch's own planning: only the use of the arena is ordered
 	if (ctx->parent && !own && bt > arena.cap) GD_HIP(hipEventSynchronize(ctx->parent->arena_ev)); // growing it: the previous user must be done
 	if ((rc = gd_grow(ctx, arena, bt))) {
@@ -646,20 +659,41 @@ extern "C" int gdiet_hip_last_dp_work(const gdiet_ctx *ctx, uint64_t *cells, uin
 	return GDIET_OK;
 }
 
+static int gd_narrow_counters(gdiet_ctx *ctx, uint64_t v[6])
+{
+	for (int i = 0; i < 6; ++i) v[i] = 0;
+	if (ctx->last_was_async) {
+		for (int i = 0; i < 6; ++i) v[i] = ctx->async_narrow[i];
+	} else if (ctx->narrow_launched && ctx->narrow_cnt.p) {
+		uint32_t h[6] = {0, 0, 0, 0, 0, 0};
+		(void)hipSetDevice(ctx->device);
+		GD_HIP(hipMemcpy(h, ctx->narrow_cnt.p, sizeof(h), hipMemcpyDeviceToHost));
+		for (int i = 0; i < 6; ++i) v[i] = h[i];
+	}
+	return GDIET_OK;
+}
+
 // the narrow-band counters of the most recent DP launch (call after the batch has completed)
 extern "C" int gdiet_hip_last_narrow_band(gdiet_ctx *ctx, uint64_t *tried, uint64_t *certified)
 {
 	if (!ctx) return GDIET_E_PARAM;
-	uint64_t v[2] = {0, 0};
-	if (ctx->last_was_async) v[0] = ctx->async_narrow[0], v[1] = ctx->async_narrow[1];
-	else if (ctx->narrow_launched && ctx->narrow_cnt.p) {
-		uint32_t h[2] = {0, 0};
-		(void)hipSetDevice(ctx->device);
-		GD_HIP(hipMemcpy(h, ctx->narrow_cnt.p, sizeof(h), hipMemcpyDeviceToHost));
-		v[0] = h[0], v[1] = h[1];
-	}
+	uint64_t v[6];
+	int rc;
+	if ((rc = gd_narrow_counters(ctx, v))) return rc;
 	if (tried) *tried = v[0];
 	if (certified) *certified = v[1];
+	return GDIET_OK;
+}
+
+// the same per rung of the ladder: out[0] / [1] alignments that evaluated the certificate at band 239 (quarter-block rows) / for which it
+// held, out[2] / [3] the same at band 495 (half-block rows)
+extern "C" int gdiet_hip_last_narrow_rungs(gdiet_ctx *ctx, uint64_t out[4])
+{
+	if (!ctx || !out) return GDIET_E_PARAM;
+	uint64_t v[6];
+	int rc;
+	if ((rc = gd_narrow_counters(ctx, v))) return rc;
+	for (int i = 0; i < 4; ++i) out[i] = v[2 + i];
 	return GDIET_OK;
 }
 

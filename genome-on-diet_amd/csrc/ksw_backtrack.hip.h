@@ -291,9 +291,11 @@ __device__ __forceinline__ void gd_walk_push(GdWalk &W, uint32_t *cg, int cap, i
 }
 // cone_stride > 0: rows of `chunk` hold the 64 blocks [cone_b0, cone_b0 + 63] (gdw_cone_row) instead of the blocks of the band
 // half_ring (with cone_half): the 64 half blocks of a row are a ring, half block h at position h mod 64 (gdw_narrow_rows)
+// quarter_ring: rows of 64 quarter blocks as a ring, quarter block q at position q mod 64, byte c of a quarter = cell c (gdw_quarter_rows):
+// target position t at byte t & 255
 __device__ __forceinline__ void gd_walk_rows(GdWalk &W, const KswTask &T, const uint8_t *__restrict__ chunk, int r0, int qlen, int tlen, int w,
                                              uint32_t *__restrict__ cigar, int lane, int cone_stride = 0, int cone_b0 = 0, bool cone_half = false,
-                                             bool half_ring = false)
+                                             bool half_ring = false, bool quarter_ring = false)
 {
 	uint32_t *cg = cigar + T.cig_off;
 	const int cap = __builtin_amdgcn_readfirstlane(T.cig_cap);
@@ -311,7 +313,8 @@ __device__ __forceinline__ void gd_walk_rows(GdWalk &W, const KswTask &T, const 
 			if (ik < off) fs = 2;
 			if (ik > off_end) fs = 1;
 			if (fs < 0) {
-				if (cone_half) { // rows of 64 half blocks (gdw_cone_row_half): cone_b0 is a half-block index, byte 4g + h = cell 2g + (h & 1) + 4 (h >> 1)
+				if (quarter_ring) pf = chunk[(size_t)(r - r0) * row_bytes + (size_t)(ik & 255)];
+				else if (cone_half) { // rows of 64 half blocks (gdw_cone_row_half): cone_b0 is a half-block index, byte 4g + h = cell 2g + (h & 1) + 4 (h >> 1)
 					const int c = ik & 7, g = (c & 3) >> 1, h = (c & 1) | ((c >> 2) << 1);
 					const int hpos = half_ring ? ((ik >> 3) & 63) : (ik >> 3) - cone_b0;
 					pf = chunk[(size_t)(r - r0) * row_bytes + (size_t)(hpos << 3) + (g << 2) + h];

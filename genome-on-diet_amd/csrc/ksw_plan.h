@@ -284,3 +284,34 @@ static void gd_plan_batch(GdPlan &P, const GdPlanOpt &O, int n, const int64_t *h
 	P.n_pipe_ids = pipe_ids.size();
 	P.cells = cells_sum, P.alg_bytes = alg_sum, P.max_cap = max_cap, P.bt = bt, P.wide_ck = wide_ck, P.n_ring96 = n_ring96;
 }
+
+// ---- auto mode of the quarter rung (ksw_wave.hip.h, "THE QUARTER RUNG") -----------------------------------------------------------------
+// A box whose certificate fails at GD_W_QUARTER has paid for the quarter-block rows for nothing: offering the rung costs every box
+// cost_quarter_row per anti-diagonal and saves a certified box cost_half_row, so it pays iff the certified share is above
+// cost_quarter_row / cost_half_row = GD_QUARTER_BREAK_EVEN_NUM / _DEN = 4 / 5, from the measured kernel times of the two row forms
+// (DESIGN.md section 3 has the derivation).  The context feeds the
+// counters of every finished launch that offered the rung into gd_quarter_auto_update; a launch with at least GD_QUARTER_AUTO_MIN tries and
+// a share below break-even makes the next GD_QUARTER_AUTO_HOLD launches not offer it, the one after probes again.  Results never depend
+// on it.  Pure host arithmetic (tests/emul/quarter_plan_test.cpp); the context calls both under its dp_mu.
+#define GD_QUARTER_BREAK_EVEN_NUM 4
+#define GD_QUARTER_BREAK_EVEN_DEN 5
+#define GD_QUARTER_AUTO_MIN 64
+#define GD_QUARTER_AUTO_HOLD 15
+struct GdQuarterAuto {
+	int32_t hold = 0; // launches still to come that do not offer the rung
+};
+// does the launch about to be made offer the rung?  (counts it)
+static inline bool gd_quarter_auto_offer(GdQuarterAuto &A)
+{
+	if (A.hold > 0) {
+		--A.hold;
+		return false;
+	}
+	return true;
+}
+// the counters of a finished launch that offered it
+static inline void gd_quarter_auto_update(GdQuarterAuto &A, uint64_t tried, uint64_t certified)
+{
+	if (tried < GD_QUARTER_AUTO_MIN) return;
+	if (certified * GD_QUARTER_BREAK_EVEN_DEN < tried * GD_QUARTER_BREAK_EVEN_NUM) A.hold = GD_QUARTER_AUTO_HOLD;
+}

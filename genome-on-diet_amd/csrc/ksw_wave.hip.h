@@ -169,6 +169,121 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 	return __builtin_amdgcn_readlane(Rf, (2 * mlast + (sl >> 3)) & 63);
 }
 
+// ---- the quarter form: one QUARTER block per lane (ksw_wave_core.h, "the quarter form") ------------------------------------------------
+// The DP rows of one alignment at band w <= GD_W_QUARTER on a ring of 64 quarter blocks: gdw_narrow_rows with two packed registers per state
+// array and one dword each of scores, target, query and selectors -- half the recurrence instructions of the half-block rows and less of
+// the per-row overhead.  Backtrace rows of 256 bytes from bt_rsrc's base.  Returns 8 x the score, wave-uniform.
+// tests/emul/quarter_emul.cpp mirrors it statement by statement.
+__device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *query_u /* wave-uniform copy */, const uint8_t *query, int qlen,
+                                               const uint8_t *target, int tlen, int w, int lane, __amdgpu_buffer_rsrc_t bt_rsrc)
+{
+	const int rend = qlen + tlen - 2, mlast = (tlen - 1) >> 4, sl = (tlen - 1) & 15;
+	WaveQuarter H;
+	gdw_load_quarter(H, K, lane >> 2, lane & 3, 0, query, qlen, target, tlen);
+	bool any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
+	int prev_st_ = 0, prev_st0 = -1, prev_up = -1, prev_en0 = -1, have_f = 0, Rf = 0;
+	auto store_row = [&](const int r, const u32 out) __attribute__((always_inline)) {
+		__builtin_amdgcn_raw_buffer_store_b32(out, bt_rsrc, lane * 4, r * 256, 0); // one buffer_store_dword per lane per row
+	};
+	auto dp_row = [&](const int r, auto steady_tag) __attribute__((always_inline)) {
+		constexpr bool STEADY = decltype(steady_tag)::value;
+		WaveRow W;
+		W.r = r;
+		gdw_band_uniform(r, qlen, tlen, w, W.st0, W.en0);
+		W.st_ = W.st0 >> 4, W.en_ = W.en0 >> 4;
+		W.up = W.st0 + (((W.en0 - W.st0 + 16) >> 4) << 4);
+		const int advanced = W.st_ > prev_st_;
+		W.use_array = advanced;
+		W.v1key = STEADY ? K.key_open : (W.st_ == 0 ? gdw_edge_key(K, r) : K.key_open);
+		W.set_tr = STEADY ? 0 : (W.en0 | 15) >= r;
+		W.ukey = STEADY ? 0 : gdw_edge_key(K, r);
+		const u32 pX = gdw_ror1<64>(H.X[1]), pV = gdw_ror1<64>(H.V[1]), pX2 = gdw_ror1<64>(H.X2[1]), pQ = gdw_ror1<64>(H.Qc);
+		if (STEADY || r > 0) gdw_shift_query_quarter(H, pQ, H.blk == prev_st_ && H.quarter == 0, gdw_seam_byte(query_u, qlen, r - (prev_st_ << 4)));
+		if (advanced) { // the four lanes whose block fell below the window take over block +16
+			if (H.blk < W.st_) gdw_load_quarter(H, K, H.blk + 16, H.quarter, r, query, qlen, target, tlen);
+			any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
+		}
+		if (!STEADY && W.set_tr) gdw_reset_tr_quarter(H, K, W);
+		if (W.st0 != prev_st0 || W.up != prev_up || advanced) gdw_make_sel_quarter(H, W.st0, W.up);
+		gdw_update_scores_quarter(H, K, any_tn);
+		if (H.blk <= W.en_) {
+			u32 out;
+			gdw_compute_quarter(H, K, W, pX, pV, pX2, out);
+			store_row(r, out);
+		}
+		if (!STEADY && r == 0) H.R = gdw_lo(H.V[0]) - K.B1 - K.qe8;
+		else H.R += gdw_lo(H.V[0]) - K.B1;
+		if ((STEADY || r > 0) && W.en0 != prev_en0 && (W.en0 & 3) == 0) { // a quarter block enters the band
+			const int hh = (int)gdw_ror1<64>((u32)gdw_track_handoff_quarter(H));
+			if (H.blk == W.en_ && H.quarter == ((W.en0 >> 2) & 3)) H.R = hh + gdw_lo(H.U[0]);
+		}
+		if (!STEADY && W.en0 == tlen - 1) {
+			if (H.blk == mlast && H.quarter == (sl >> 2)) {
+				if (!have_f) Rf = gdw_track_to_slot_quarter(H, sl & 3);
+				else Rf += gdw_cell_quarter(H.V, sl & 3) - K.B1;
+			}
+			have_f = 1;
+		}
+		prev_st_ = W.st_, prev_st0 = W.st0, prev_up = W.up, prev_en0 = W.en0;
+	};
+	const int nblkA = (w - 1 + 16) >> 4, nblkB = (w + 16) >> 4;
+	u32 m_lowest = 0; // 0 / ~0: this lane holds the first quarter of the lowest block of the window (of the row just done)
+	auto pair_row = [&](const int r, const int m, auto a_tag) __attribute__((always_inline)) {
+		constexpr bool ROW_A = decltype(a_tag)::value;
+		WaveRow W;
+		W.r = r, W.st0 = m, W.en0 = ROW_A ? m + w - 1 : m + w;
+		W.st_ = m >> 4, W.en_ = W.en0 >> 4;
+		W.up = m + ((ROW_A ? nblkA : nblkB) << 4);
+		const int advanced = ROW_A && (m & 15) == 0;
+		const int pst_ = W.st_ - advanced; // st_ of the row before
+		W.use_array = advanced, W.v1key = K.key_open, W.set_tr = 0, W.ukey = 0;
+		const u32 pX = gdw_ror1<64>(H.X[1]), pV = gdw_ror1<64>(H.V[1]), pX2 = gdw_ror1<64>(H.X2[1]), pQ = gdw_ror1<64>(H.Qc);
+		gdw_shift_query_quarter_m(H, pQ, m_lowest, gdw_seam_byte(query_u, qlen, r - (pst_ << 4))); // (the lane mask of the row before: its st_ is this row's pst_)
+		if (advanced) {
+			if (H.blk < W.st_) gdw_load_quarter(H, K, H.blk + 16, H.quarter, r, query, qlen, target, tlen);
+			any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
+		}
+		if (ROW_A || nblkA != nblkB) {
+			gdw_make_sel_quarter(H, W.st0, W.up);
+			m_lowest = (H.blk == W.st_ && H.quarter == 0) ? ~0u : 0u;
+		}
+		W.m_first_valid = 1, W.m_first_h = m_lowest;
+		gdw_update_scores_quarter(H, K, any_tn);
+		if (H.blk <= W.en_) {
+			u32 out;
+			gdw_compute_quarter(H, K, W, pX, pV, pX2, out);
+			store_row(r, out);
+		}
+		H.R += gdw_lo(H.V[0]); // (the bias B1 of every V key is taken off once, after the loop)
+		if (!ROW_A && (W.en0 & 3) == 0) {
+			const int hh = (int)gdw_ror1<64>((u32)gdw_track_handoff_quarter(H));
+			if (H.blk == W.en_ && H.quarter == ((W.en0 >> 2) & 3)) H.R = hh + gdw_lo(H.U[0]);
+		}
+	};
+	{
+		int rA, rS;
+		gdw_steady_rows(qlen, tlen, w, rA, rS);
+		const int t1_ = tlen - 1, rB0 = 2 * t1_ - w, rB = rB0 > t1_ ? rB0 : t1_;
+		int r = 0;
+		for (; r <= rend && r < rA; ++r) dp_row(r, std::false_type());
+		if (r == rA && rS > rA) {
+			int m = (rA - w + 1) >> 1;
+			m_lowest = (H.blk == prev_st_ && H.quarter == 0) ? ~0u : 0u;
+			for (; r < rS; r += 2, ++m) {
+				pair_row(r, m, std::true_type());
+				pair_row(r + 1, m, std::false_type());
+			}
+			H.R -= (rS - rA) * K.B1;
+			--m; // the band of the last row, for the rows that follow
+			prev_st_ = m >> 4, prev_st0 = m, prev_up = m + (nblkB << 4), prev_en0 = m + w;
+		}
+		for (; r <= rend && r < rB; ++r) dp_row(r, std::true_type());
+		for (; r <= rend; ++r) dp_row(r, std::false_type());
+	}
+	// the tracker of the last cell lives in the lane of its quarter block
+	return __builtin_amdgcn_readlane(Rf, (4 * mlast + (sl >> 2)) & 63);
+}
+
 // LANES == 64: one alignment per wavefront (task_ids[slot]).
 // LANES == 16: four alignments OF IDENTICAL GEOMETRY (qlen, tlen, w) per wavefront, one per DPP row of 16 lanes
 //              (task_ids[4*slot + row]; -1 = empty row, which shadows row 0 without storing).  Identical geometry keeps every
@@ -189,7 +304,12 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 // half-block rows at band NA.w first, evaluates the certificate (gd_band_certified) on the scalar unit from its own score and, if it holds,
 // walks back from the 512-byte rows: score and CIGAR are provably those of the full band.  If not, the same wavefront goes on with the
 // full-band rows in the same backtrace slot.  GD_NARROW_OWN: the alignment's own band fits the half-block rows.  NA.w == 0: off.
-// narrow_cnt[0] / [1]: alignments that tried the narrow band / whose certificate held, added to by every such wavefront.
+// THE QUARTER RUNG (NA.wq > 0): before that, a marked alignment whose band is wider than NA.wq = GD_W_QUARTER, with |tlen - qlen| <= NA.wq and
+// admitted there (gd_quarter_rung), runs the quarter-block rows at NA.wq and evaluates the same certificate with D = NA.wq; if it holds the
+// walk reads the 256-byte rows, if not the wavefront goes on with the half-block rows as above.  A GD_NARROW_OWN alignment with w <= NA.wq
+// that is admitted runs the quarter-block rows at its own band.  All in the same backtrace slot.
+// narrow_cnt[0] / [1]: GD_NARROW_TRY alignments that tried a narrow band / that finished in one; [2] / [3]: alignments that evaluated the
+// certificate at NA.wq / for which it held; [4] / [5]: the same at NA.w.  Added to by every such wavefront.
 #define GD_CLOCK_SLOTS 16384
 __device__ unsigned long long gd_clock_stamps[GD_CLOCK_SLOTS * 4];
 template <int LANES, int TAG = 0, bool DUAL = true>
@@ -247,14 +367,35 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 	if constexpr (LANES == 64 && DUAL) {
 		const int mode = NA.w > 0 && cigar != nullptr ? __builtin_amdgcn_readfirstlane(Tp->pad) : GD_NARROW_NO;
 		if (mode != GD_NARROW_NO) {
-			if (mode == GD_NARROW_OWN) NA.w = w;
-			const int s8 = gdw_narrow_rows(K, qg[0], query, qlen, target, tlen, NA.w, lane, bt_rsrc);
-			const bool certified = mode == GD_NARROW_OWN || gd_band_certified(NA, qlen, tlen, s8 >> 3);
+			// the ladder: quarter-block rows at NA.wq (or the box's own band up to it), half-block rows at NA.w (or its own band), full band
+			int s8 = 0, wn = 0, stride = 0;
+			const int wq = __builtin_amdgcn_readfirstlane(gd_quarter_rung(mode, qlen, tlen, w, NA.wq));
+			if (wq > 0) {
+				s8 = gdw_quarter_rows(K, qg[0], query, qlen, target, tlen, wq, lane, bt_rsrc);
+				GdNarrowArg NQ = NA;
+				NQ.w = wq;
+				const bool own = wq == w, ok = own || gd_band_certified(NQ, qlen, tlen, s8 >> 3);
+				if (!own && lane == 0) {
+					atomicAdd(narrow_cnt + 2, 1u);
+					if (ok) atomicAdd(narrow_cnt + 3, 1u);
+				}
+				if (ok) wn = wq, stride = 256;
+			}
+			if (wn == 0) {
+				if (mode == GD_NARROW_OWN) NA.w = w;
+				s8 = gdw_narrow_rows(K, qg[0], query, qlen, target, tlen, NA.w, lane, bt_rsrc);
+				const bool ok = mode == GD_NARROW_OWN || gd_band_certified(NA, qlen, tlen, s8 >> 3);
+				if (mode == GD_NARROW_TRY && lane == 0) {
+					atomicAdd(narrow_cnt + 4, 1u);
+					if (ok) atomicAdd(narrow_cnt + 5, 1u);
+				}
+				if (ok) wn = NA.w, stride = 512;
+			}
 			if (mode == GD_NARROW_TRY && lane == 0) {
 				atomicAdd(narrow_cnt, 1u);
-				if (certified) atomicAdd(narrow_cnt + 1, 1u);
+				if (wn > 0) atomicAdd(narrow_cnt + 1, 1u);
 			}
-			if (certified) {
+			if (wn > 0) {
 				if (lane == 0) {
 					gd_clock_stamps[(tid & (GD_CLOCK_SLOTS - 1)) * 4 + 2] = __builtin_amdgcn_s_memtime(), gd_clock_stamps[(tid & (GD_CLOCK_SLOTS - 1)) * 4 + 3] = __builtin_amdgcn_s_memrealtime();
 					score_out[tid] = s8 >> 3;
@@ -263,7 +404,7 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); // this wavefront's own backtrace stores
 				GdWalk Wk;
 				gd_walk_init(Wk, qlen, tlen);
-				gd_walk_rows(Wk, *Tp, bt + Tp->bt_off, 0, qlen, tlen, NA.w, cigar, lane, 512, 0, true, true);
+				gd_walk_rows(Wk, *Tp, bt + Tp->bt_off, 0, qlen, tlen, wn, cigar, lane, stride, 0, true, true, stride == 256);
 				gd_walk_finish(Wk, *Tp, tid, n_cigar, cigar, lane);
 				return;
 			}
@@ -404,7 +545,10 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 	// The 64-lane form (one alignment per wavefront) walks its own alignment back right away when given the CIGAR buffers: the
 	// walk is latency-bound and overlaps the DP of the other resident wavefronts, instead of a separate pass after the last one.
 	const bool fuse = cigar != nullptr; // (the grouped forms: given the CIGAR buffers, every group's first lane walks its alignment back, below)
-	if (LANES == 64 && lane == 0) // (the DP rows only: the walk below is latency-bound)
+	// (the lane index once more, from the execution mask -- all 64 lanes are active here: what follows then keeps no register alive across
+	// the row loops, which use all 96)
+	const int lane_w = LANES == 64 ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : lane;
+	if (LANES == 64 && lane_w == 0) // (the DP rows only: the walk below is latency-bound)
 		gd_clock_stamps[(tid & (GD_CLOCK_SLOTS - 1)) * 4 + 2] = __builtin_amdgcn_s_memtime(), gd_clock_stamps[(tid & (GD_CLOCK_SLOTS - 1)) * 4 + 3] = __builtin_amdgcn_s_memrealtime();
 	if (L.blk == mlast && live) {
 		score_out[tid] = Rf >> 3;
@@ -412,7 +556,7 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 	}
 	if (fuse) {
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); // this wavefront's own backtrace stores: complete, and not served from a stale L1 line
-		if (LANES == 64) gd_bt_wave_walk(*Tp, tid, bt, n_cigar, cigar, lane);
+		if (LANES == 64) gd_bt_wave_walk(*Tp, tid, bt, n_cigar, cigar, lane_w);
 		else if (live && sub == 0) {
 			// short alignments, several per wavefront: one walk per group on its first lane -- a few hundred dependent steps through bytes
 			// the wavefront has just written, while the SIMD's other wavefronts are in their DP rows; no separate backtrack pass after
@@ -426,11 +570,12 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 static inline void gd_launch_wave64(const KswTask *tasks, const int32_t *ids, int n, const uint8_t *q, const uint8_t *t,
                                     uint8_t *bt, int32_t *status, int32_t *score, KswConst C, hipStream_t s, bool single,
                                     int32_t *n_cigar, uint32_t *cigar /* fused backtrack */, int waves_per_simd /* 4: see gdiet_hip_set_dp_waves */,
-                                    int narrow_w /* GD_W_NARROW, or 0: every alignment at its full band */, uint32_t *narrow_cnt /* tried, certified */)
+                                    int narrow_w /* GD_W_NARROW, or 0: every alignment at its full band */, uint32_t *narrow_cnt /* six counters, see the kernel */,
+                                    int quarter_w /* GD_W_QUARTER, or 0: the quarter rung is not offered */)
 {
 	WaveK K;
 	gdw_make_consts(C, K);
-	const GdNarrowArg NA = gd_narrow_arg(C, narrow_cnt ? narrow_w : 0);
+	const GdNarrowArg NA = gd_narrow_arg(C, narrow_cnt ? narrow_w : 0, quarter_w);
 	// one wavefront per workgroup: a finished wavefront frees its slot at once instead of waiting for its three block mates
 	const dim3 grid(n), block(64);
 	// Four wavefronts per SIMD instead of five: the kernel uses no LDS, so an (unused) dynamic allocation of a sixteenth of the CU's 160 KB

@@ -461,7 +461,8 @@ static inline bool gd_wave_geometry_ok_loop(int qlen, int tlen, int w, int lanes
 // cross -- m = w / 16 (rs changes its form), rs = 2 qlen - w - 1 (the two non-constant terms of st0) -- so each of the two conditions,
 // an inequality between such a function and 16 m / 16 (m - 1), can only change its truth value next to a breakpoint or at an end of
 // [1, mlast]: it is enough to test a few m around each.
-static inline bool gd_wave_geometry_ok(int qlen, int tlen, int w, int lanes)
+// (GDW_HD: the 64-lane kernel asks it for the quarter rung of its ladder, once per alignment, with wave-uniform arguments)
+GDW_HD bool gd_wave_geometry_ok(int qlen, int tlen, int w, int lanes)
 {
 	if (w < 0) w = tlen > qlen ? tlen : qlen;
 	if (qlen < 1 || tlen < 1) return false;
@@ -477,9 +478,12 @@ static inline bool gd_wave_geometry_ok(int qlen, int tlen, int w, int lanes)
 	};
 	const int rx = 2 * qlen - w - 1; // the anti-diagonal on which r - qlen + 1 overtakes (r - w + 1) >> 1
 	const int around[4] = {w >> 4, rx > 0 ? (rx + w) / 32 : 0, rx > 0 ? rx / 16 : 0, mlast - 1};
+#pragma unroll
 	for (int a = 0; a < 4; ++a)
+#pragma unroll
 		for (int d = -2; d <= 2; ++d)
 			if (!block_ok(around[a] + d)) return false;
+#pragma unroll
 	for (int m = 1; m <= 3; ++m)
 		if (!block_ok(m)) return false;
 	{
@@ -776,11 +780,12 @@ static inline bool gd_narrow_rows_ok(int qlen, int tlen, int w)
 struct GdNarrowArg {
 	int32_t w;             // the narrow band to try first (0: off)
 	int32_t a, q, e, q2, e2;
+	int32_t wq;            // the band of the quarter-block rows, tried before it (GD_W_QUARTER; 0: that rung is not offered)
 };
-static inline GdNarrowArg gd_narrow_arg(const KswConst &C, int w)
+static inline GdNarrowArg gd_narrow_arg(const KswConst &C, int w, int wq = 0)
 {
 	GdNarrowArg A;
-	A.w = w, A.q = C.q, A.e = C.e, A.q2 = C.q2, A.e2 = C.e2;
+	A.w = w, A.wq = w > 0 ? wq : 0, A.q = C.q, A.e = C.e, A.q2 = C.q2, A.e2 = C.e2;
 	A.a = C.sc_mch > C.sc_mis ? C.sc_mch : C.sc_mis;
 	if (C.sc_N > A.a) A.a = C.sc_N;
 	return A;
@@ -820,4 +825,190 @@ static inline int32_t gd_narrow_mode(int qlen, int tlen, int w)
 	const int delta = tlen - qlen;
 	if (delta > GD_W_NARROW || -delta > GD_W_NARROW) return GD_NARROW_NO;
 	return gd_narrow_supported(qlen, tlen, GD_W_NARROW) ? GD_NARROW_TRY : GD_NARROW_NO;
+}
+
+// ---- the quarter form of the 64-lane kernel: ONE QUARTER BLOCK per lane -------------------------------------------------------------
+// Lane l holds the quarter block qidx = 4 blk + quarter with qidx mod 64 == l (quarter == l & 3 for good, blk mod 16 == l >> 2): a ring of
+// 16 blocks, every block spread over four neighbouring lanes, so the four quarters of a block enter and leave the reference's 16-aligned
+// window together and the quarter below is always the previous lane (wave_ror:1).  A quarter keeps its 4 cells as 2 packed registers per
+// state array, register j = cells (j, j + 2), so "cell t-1" is again the register before (j = 0: the incoming dword of the quarter below)
+// and it has ONE dword each of score bytes, target bytes, query bytes and selectors.  Everything that is defined per cell carries over with
+// the quarter's first target position tb = 16 blk + 4 quarter, exactly as for halves; the score tracker hands over every 4 cells.
+// Backtrace rows are 64 x 4 = 256 bytes, quarter block qidx at (qidx & 63) * 4, and inside a quarter BYTE c IS CELL c (the packed order
+// (0, 2 | 1, 3) of the registers and the byte order of gdw_compute's flag merge cancel): target position t of a row sits at byte t & 255.
+// GD_W_QUARTER: the widest band with ((w + 16) >> 4) + 1 <= 16 -- window plus score-row spill fit the 16 blocks whatever the geometry.
+#define GD_W_QUARTER 239
+struct WaveQuarter {
+	u32 U[2], V[2], X[2], Y[2], X2[2], Y2[2];
+	u32 Sb, Tb, Qc, SEL;
+	u32 tn;
+	int32_t blk, quarter;
+	int32_t R; // 8*H(r, tb): score tracker at the quarter's first cell
+};
+
+GDW_HD void gdw_load_quarter(WaveQuarter &H, const WaveK &K, int m, int quarter, int r, const uint8_t *query, int qlen, const uint8_t *target, int tlen)
+{
+	H.blk = m, H.quarter = quarter;
+	const int tb = (m << 4) + (quarter << 2);
+#pragma unroll
+	for (int k = 0; k < 2; ++k) H.U[k] = K.uv0, H.V[k] = K.uv0, H.X[k] = K.cx, H.Y[k] = K.cy, H.X2[k] = K.cx2, H.Y2[k] = K.cy2;
+	u32 tw = 0, qw = 0;
+#pragma unroll
+	for (int b = 0; b < 4; ++b) {
+		const int t = tb + b;
+		tw |= (t < tlen ? (u32)target[t] : 0u) << (8 * b);
+		qw |= gdw_qbyte(query, qlen, r - t) << (8 * b);
+	}
+	H.Tb = tw, H.Qc = qw, H.Sb = K.s0, H.SEL = 0x03020100u;
+	H.tn = H.Tb & 0x04040404u;
+	H.R = 0;
+}
+
+GDW_HD void gdw_make_sel_quarter(WaveQuarter &H, int st0, int up)
+{
+	const int tb = (H.blk << 4) + (H.quarter << 2);
+	int lo = st0 - tb, hi = up - tb;
+	lo = lo < 0 ? 0 : lo > 4 ? 4 : lo;
+	hi = hi < 0 ? 0 : hi > 4 ? 4 : hi;
+	const u32 n = hi > lo ? (((1u << (hi - lo)) - 1u) << lo) : 0u; // bit i: cell i is rewritten
+	const u32 spread = (n * 0x00204081u) & 0x01010101u;
+	H.SEL = 0x03020100u + (spread << 2);
+}
+
+// cell 0 takes the byte that cell 3 of the quarter below faced on the previous anti-diagonal: the top byte of the previous lane's Qc
+GDW_HD void gdw_shift_query_quarter(WaveQuarter &H, u32 below, bool is_lowest, u32 seam)
+{
+	const u32 in = is_lowest ? (seam << 24) : below;
+	H.Qc = gdw_alignbyte(H.Qc, in, 3);
+}
+GDW_HD void gdw_shift_query_quarter_m(WaveQuarter &H, u32 below, u32 m_lowest, u32 seam) // (the lowest quarter's lane as a 0 / ~0 mask)
+{
+	const u32 in = gdw_bfi_s(m_lowest, seam << 24, below);
+	H.Qc = gdw_alignbyte(H.Qc, in, 3);
+}
+
+GDW_HD void gdw_update_scores_quarter(WaveQuarter &H, const WaveK &K, bool any_tn)
+{
+	u32 x = H.Tb ^ H.Qc;
+	if (any_tn) x |= H.Tb & ~(H.Qc << 1) & 0x04040404u;
+	H.Sb = gdw_perm(gdw_perm(K.lut_hi, K.lut_lo, x), H.Sb, H.SEL);
+}
+
+GDW_HD void gdw_reset_tr_quarter(WaveQuarter &H, const WaveK &K, const WaveRow &W)
+{
+	if (H.blk != (W.r >> 4) || H.quarter != ((W.r >> 2) & 3)) return;
+	const int c = W.r & 3, k = c & 1;
+	const u32 mask = (c & 2) ? 0xffff0000u : 0x0000ffffu;
+	const u32 uk = gdw_pack2(W.ukey);
+#pragma unroll
+	for (int kk = 0; kk < 2; ++kk)
+		if (kk == k) {
+			H.U[kk] = gdw_bfi(mask, uk, H.U[kk]);
+			H.Y[kk] = gdw_bfi(mask, K.cy, H.Y[kk]);
+			H.Y2[kk] = gdw_bfi(mask, K.cy2, H.Y2[kk]);
+		}
+}
+
+// one anti-diagonal of an ACTIVE quarter block.  pX / pV / pX2: register 1 of X / V / X2 of the quarter below, row r-1 values (W.m_first_h:
+// "the first quarter of block st_").  bt: the quarter's 4 backtrace bytes, coded as in gdw_compute; byte c = cell c: the sign selectors
+// 0x0b090a08 pick (reg 0 low, reg 1 low, reg 0 high, reg 1 high) = cells (0, 1, 2, 3), and so does 0x06020400 for the priority-chain keys.
+GDW_HD void gdw_compute_quarter(WaveQuarter &H, const WaveK &K, const WaveRow &W, u32 pX, u32 pV, u32 pX2, u32 &bt)
+{
+	if (!W.use_array) {
+		const u32 first = W.m_first_valid ? W.m_first_h : ((H.blk == W.st_ && H.quarter == 0) ? ~0u : 0u);
+		pX = gdw_bfi_s(first, K.cx, pX), pV = gdw_bfi_s(first, gdw_pack2(W.v1key), pV), pX2 = gdw_bfi_s(first, K.cx2, pX2);
+	}
+	const u32 inX = gdw_alignbit(H.X[1], pX, 16), inV = gdw_alignbit(H.V[1], pV, 16), inX2 = gdw_alignbit(H.X2[1], pX2, 16);
+	u32 zk_hi = 0;
+#pragma unroll
+	for (int k = 1; k >= 0; --k) {
+		const u32 xin = k ? H.X[0] : inX, vin = k ? H.V[0] : inV, x2in = k ? H.X2[0] : inX2;
+		const u32 sk = gdw_perm(0u, H.Sb, 0x0c000c00u | (u32)k | (u32)(2 + k) << 16);
+		const u32 a = pk_add(xin, vin), b = pk_add(H.Y[k], H.U[k]);
+		const u32 a2 = pk_add(x2in, vin), b2 = pk_add(H.Y2[k], H.U[k]);
+		const u32 zk = pk_max(pk_max(pk_max(sk, a), b), pk_add(pk_max(a2, b2), K.c2));
+		const u32 z8 = pk_min(zk & 0xfff8fff8u, K.zmax);
+		const u32 nV = pk_sub(z8, H.U[k]), nU = pk_sub(z8, vin);
+		const u32 tE = pk_sub(z8, K.te), tE2 = pk_sub(z8, K.te2);
+		H.X[k] = pk_max(pk_sub(a, tE), K.cx), H.Y[k] = pk_max(pk_sub(b, tE), K.cy);
+		H.X2[k] = pk_max(pk_sub(a2, tE2), K.cx2), H.Y2[k] = pk_max(pk_sub(b2, tE2), K.cy2);
+		H.U[k] = nU, H.V[k] = nV;
+		if (k) zk_hi = zk;
+		else {
+			const u32 mX = gdw_perm(H.X[1], H.X[0], 0x0b090a08u), mY = gdw_perm(H.Y[1], H.Y[0], 0x0b090a08u);
+			const u32 mX2 = gdw_perm(H.X2[1], H.X2[0], 0x0b090a08u), mY2 = gdw_perm(H.Y2[1], H.Y2[0], 0x0b090a08u);
+			const u32 f = gdw_bfi_u(0x80808080u, mX, gdw_bfi_u(0x40404040u, mY, gdw_bfi_u(0x20202020u, mX2, mY2)));
+			bt = gdw_bfi_u(0xf0f0f0f0u, f, gdw_perm(zk_hi, zk, 0x06020400u));
+		}
+	}
+}
+
+GDW_HD int gdw_sum4(const u32 A[2])
+{
+	const u32 s = pk_add(A[0], A[1]);
+	return gdw_lo(s) + gdw_hi(s);
+}
+// what a quarter contributes to the tracker of the quarter above it: 8*H(r, tb + 4) = 8*H(r, tb) + sum_{i=1..3} U_i - sum_{i=0..3} V_i [+ U_0 there]
+GDW_HD int gdw_track_handoff_quarter(const WaveQuarter &H) { return H.R + gdw_sum4(H.U) - gdw_lo(H.U[0]) - gdw_sum4(H.V); }
+// key of cell `slot` (0..3) of a quarter's packed array
+GDW_HD int gdw_cell_quarter(const u32 A[2], int slot)
+{
+	const u32 a0 = A[0], a1 = A[1]; // (both read first: a select between values, never an indexed access)
+	const u32 v = (slot & 1) ? a1 : a0;
+	return (slot & 2) ? gdw_hi(v) : gdw_lo(v);
+}
+GDW_HD int gdw_track_to_slot_quarter(const WaveQuarter &H, int sl)
+{
+	int acc = H.R;
+	for (int i = 0; i < sl; ++i) acc += gdw_cell_quarter(H.U, i + 1) - gdw_cell_quarter(H.V, i);
+	return acc;
+}
+
+// The admission test in terms of blocks (the 16-block ring), usable in the kernel ...
+GDW_HD bool gd_quarter_supported(int qlen, int tlen, int w)
+{
+	return qlen + tlen < (1 << 21) && gd_wave_geometry_ok(qlen, tlen, w, 16);
+}
+// ... its loop form (tests/emul/quarter_plan_test.cpp compares the two on random geometries) ...
+static inline bool gd_quarter_supported_loop(int qlen, int tlen, int w)
+{
+	return qlen + tlen < (1 << 21) && gd_wave_geometry_ok_loop(qlen, tlen, w, 16);
+}
+// ... and what the quarter-block rows themselves need, anti-diagonal by anti-diagonal (gd_narrow_rows_ok with quarter indices): the band
+// never empties; every quarter the score row touches has a lane (a window of at most 64 quarters from the lowest computed block on); the
+// quarter that enters the band ((en0 & 3) == 0) finds the tracker of the quarter below it; the walk to the last cell starts in a quarter
+// whose first cell is in the band.
+static inline bool gd_quarter_rows_ok(int qlen, int tlen, int w)
+{
+	if (w < 0) w = tlen > qlen ? tlen : qlen;
+	if (qlen < 1 || tlen < 1 || w < 1 || qlen + tlen >= (1 << 21)) return false;
+	if (gd_ncol16(qlen, tlen, w) > 16) return false;
+	int prev_en0 = -1, have_f = 0;
+	for (int r = 0; r <= qlen + tlen - 2; ++r) {
+		int st0, en0;
+		gd_band(r, qlen, tlen, w, st0, en0);
+		if (st0 > en0) return false;
+		const int up = st0 + (((en0 - st0 + 16) >> 4) << 4);
+		if (((up - 1) >> 2) - 4 * (st0 >> 4) > 63) return false;
+		if (r > 0 && en0 != prev_en0 && (en0 & 3) == 0 && st0 > en0 - 4) return false;
+		if (en0 == tlen - 1 && !have_f) {
+			if (st0 > ((tlen - 1) & ~3)) return false;
+			have_f = 1;
+		}
+		prev_en0 = en0;
+	}
+	return true;
+}
+
+// The first rung of the kernel's ladder, decided in the kernel from the planner's mark and the geometry: the band at which a marked
+// alignment runs the quarter-block rows first, or 0.  A band wider than wq (GD_NARROW_TRY, or GD_NARROW_OWN with wq < w <= GD_W_NARROW):
+// at wq, to be certified with D = wq (gd_band_certified needs |delta| <= wq); GD_NARROW_OWN with w <= wq: at its own band, nothing to
+// certify.  wq == 0: the rung is not offered.  (w: the alignment's band, already made non-negative.)
+GDW_HD int gd_quarter_rung(int mode, int qlen, int tlen, int w, int wq)
+{
+	if (wq <= 0 || mode == GD_NARROW_NO) return 0;
+	if (w <= wq) return mode == GD_NARROW_OWN && gd_quarter_supported(qlen, tlen, w) ? w : 0;
+	const int delta = tlen - qlen;
+	if (delta > wq || -delta > wq) return 0;
+	return gd_quarter_supported(qlen, tlen, wq) ? wq : 0;
 }

@@ -1176,23 +1176,35 @@ extern "C" int gdiet_hip_map_wait(gdiet_ctx *ctx, gdiet_map_ticket *t)
 	gd_ds_clear_mark();
 	if (!ctx || !t) return GDIET_E_PARAM;
 	if (t->th.joinable()) t->th.join();
-	std::lock_guard<std::mutex> guard(ctx->async_mu);
-	for (size_t i = 0; i < ctx->open_tickets.size(); ++i)
-		if (ctx->open_tickets[i] == t) { ctx->open_tickets.erase(ctx->open_tickets.begin() + i); break; }
-	gdiet_ctx *c = ctx->async_lane[t->lane];
-	const int rc = t->rc;
-	if (rc) ctx->err = c->err;
-	ctx->failed_last = c->failed_last, ctx->failed_total += c->failed_last;
-	if (c->failed_last) ctx->warn = c->warn;
-	for (int i = 0; i < 6; ++i) ctx->stage_s[i] = c->stage_s[i];
-	ctx->last_mask = c->last_mask, ctx->last_cells = c->last_cells, ctx->last_alg_bytes = c->last_alg_bytes;
-	if (!rc && c->last_cells) { // the lane's DP-stage events of this batch (its streams are idle: the thread has joined)
-		ctx->last_was_async = false;
-		if (gdiet_hip_last_kernel_ms(c, &ctx->async_dp_ms, &ctx->async_bt_ms) == GDIET_OK &&
-		    gdiet_hip_last_narrow_band(c, &ctx->async_narrow[0], &ctx->async_narrow[1]) == GDIET_OK) ctx->last_was_async = true;
+	bool rung_offered = false;
+	uint64_t rung[2] = {0, 0};
+	int rc;
+	{
+		std::lock_guard<std::mutex> guard(ctx->async_mu);
+		for (size_t i = 0; i < ctx->open_tickets.size(); ++i)
+			if (ctx->open_tickets[i] == t) { ctx->open_tickets.erase(ctx->open_tickets.begin() + i); break; }
+		gdiet_ctx *c = ctx->async_lane[t->lane];
+		rc = t->rc;
+		if (rc) ctx->err = c->err;
+		ctx->failed_last = c->failed_last, ctx->failed_total += c->failed_last;
+		if (c->failed_last) ctx->warn = c->warn;
+		for (int i = 0; i < 6; ++i) ctx->stage_s[i] = c->stage_s[i];
+		ctx->last_mask = c->last_mask, ctx->last_cells = c->last_cells, ctx->last_alg_bytes = c->last_alg_bytes;
+		if (!rc && c->last_cells) { // the lane's DP-stage events of this batch (its streams are idle: the thread has joined)
+			ctx->last_was_async = false;
+			if (gdiet_hip_last_kernel_ms(c, &ctx->async_dp_ms, &ctx->async_bt_ms) == GDIET_OK &&
+			    gd_narrow_counters(c, ctx->async_narrow) == GDIET_OK) {
+				ctx->last_was_async = true;
+				rung_offered = c->narrow_launched && c->quarter_offered, rung[0] = ctx->async_narrow[2], rung[1] = ctx->async_narrow[3];
+			}
+		}
+		ctx->async_busy[t->lane] = false;
+		delete t;
 	}
-	ctx->async_busy[t->lane] = false;
-	delete t;
+	if (rung_offered && ctx->narrow_quarter < 0) { // auto mode learns from the launches that offered the quarter rung (after async_mu: a lane takes dp_mu first)
+		std::lock_guard<std::mutex> guard(ctx->dp_mu);
+		gd_quarter_auto_update(ctx->quarter_auto, rung[0], rung[1]);
+	}
 	return rc;
 }
 

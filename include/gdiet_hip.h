@@ -195,6 +195,11 @@ int gdiet_hip_last_dp_work(const gdiet_ctx *ctx, uint64_t *cells, uint64_t *alg_
  * band.  Counters of the most recent DP launch: boxes that tried the narrow band, boxes whose certificate held.  Call after the
  * batch has completed.  GDIET_NARROW_BAND=0 (read at gdiet_hip_init) switches the narrow band off. */
 int gdiet_hip_last_narrow_band(gdiet_ctx *ctx, uint64_t *tried, uint64_t *certified);
+/* The same per rung of the ladder the kernel climbs: before the 495-wide band a box tries the quarter-block rows in a 239-wide band with the
+ * same certificate (D = 239).  out[0] / out[1]: boxes that evaluated the certificate at 239 / for which it held; out[2] / out[3]: the
+ * same at 495.  GDIET_NARROW_QUARTER (read at gdiet_hip_init): 0 never offers the 239 rung, 1 always does; unset, a context stops
+ * offering it for 15 launches after one in which fewer than four fifths of at least 64 boxes certified there.  Results never depend on it. */
+int gdiet_hip_last_narrow_rungs(gdiet_ctx *ctx, uint64_t out[4]);
 
 /* ---- B1: the per-read mapping path for a whole batch of reads (LongReads variant; ShortReads variant with MM_F_SR) ----
  * Replaces step 1 of worker_pipeline -- kt_for(n_threads, worker_for, ...) -> mm_map_frag() per read
