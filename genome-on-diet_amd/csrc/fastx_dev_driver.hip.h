@@ -10,13 +10,13 @@
 #pragma once
 #include <hipcub/hipcub.hpp>
 #include "fastx_dev.hip.h"
+#include "bgzf_inflate.hip.h"
 
-static thread_local const gdiet_ctx *gd_fx_failed_on = nullptr;
 static const char *gd_fx_err_of(const gdiet_ctx *ctx) { return ctx && gd_fx_failed_on == ctx ? ctx->fx_err.c_str() : nullptr; }
 static int gd_fx_fail(gdiet_ctx *ctx, int rc, const std::string &what) // (the caller holds fx_mu)
 {
-	ctx->fx_err = what, gd_fx_failed_on = ctx;
 	gd_ds_clear_mark();
+	ctx->fx_err = what, gd_fx_failed_on = ctx; // (gd_fx_failed_on: map_diffstr_driver.hip.h)
 	return rc;
 }
 
@@ -38,9 +38,81 @@ static void gd_fx_block_free(void *p)
 	delete B;
 }
 
+// BGZF members on the device (bgzf_inflate.hip.h): the raw members and their table up, one wavefront per member, the inflated range down
+// into the block the reader asked for.  A stream and a lock of its own (gdiet_ctx::bz_stream, bz_mu): it runs on the reader's I/O thread
+// while parse() holds fx_mu on the reader thread, and sharing fx_mu would put the two in sequence.  Stream-ordered allocations; the stream
+// is synchronised before the host touches the bytes (it checks every member's length and CRC next).  Returns 0, -1 (the device failed)
+// or -2 (a member's stream is not valid deflate), with the reason in why.
+static int gd_bz_inflate_device(gdiet_ctx *ctx, const unsigned char *raw, size_t raw_len, const GdBgzfMember *m, size_t n, unsigned char *dst, size_t dst_len, uint32_t *out_len,
+                                std::string &why)
+{
+	if (n == 0) return 0;
+	for (size_t i = 0; i < n; ++i) // the kernel takes every range from this table: none may leave its buffer
+		if (m[i].in_off > raw_len || m[i].in_len > raw_len - m[i].in_off || m[i].isize > GD_BGZF_MAX_ISIZE || m[i].out_off > dst_len || m[i].isize > dst_len - m[i].out_off) {
+			why = "BGZF member " + std::to_string(i) + ": outside its buffers";
+			return -2;
+		}
+	std::lock_guard<std::mutex> lk(ctx->bz_mu);
+	(void)hipSetDevice(ctx->device);
+	hipError_t e = hipSuccess;
+	if (!ctx->bz_stream && (e = hipStreamCreateWithFlags(&ctx->bz_stream, hipStreamNonBlocking)) != hipSuccess) {
+		why = std::string("device inflate: stream: ") + hipGetErrorString(e);
+		return -1;
+	}
+	hipStream_t s = ctx->bz_stream;
+	for (hipEvent_t &ev : ctx->bz_ev)
+		if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) { ev = nullptr; why = std::string("device inflate: event: ") + hipGetErrorString(e); return -1; }
+	uint8_t *d_raw = nullptr, *d_out = nullptr;
+	GdBgzfMember *d_tab = nullptr;
+	GdzResult *d_res = nullptr;
+	auto fail = [&](hipError_t err, const char *what) {
+		(void)hipStreamSynchronize(s);
+		if (d_raw) (void)hipFreeAsync(d_raw, s);
+		if (d_out) (void)hipFreeAsync(d_out, s);
+		if (d_tab) (void)hipFreeAsync(d_tab, s);
+		if (d_res) (void)hipFreeAsync(d_res, s);
+		why = std::string("device inflate: ") + what + ": " + hipGetErrorString(err);
+		return -1;
+	};
+	std::vector<GdzResult> res(n);
+	if ((e = hipMallocAsync((void **)&d_raw, raw_len + 16, s)) != hipSuccess) return fail(e, "members");
+	if ((e = hipMallocAsync((void **)&d_out, dst_len + 16, s)) != hipSuccess) return fail(e, "output");
+	if ((e = hipMallocAsync((void **)&d_tab, sizeof(GdBgzfMember) * n, s)) != hipSuccess) return fail(e, "table");
+	if ((e = hipMallocAsync((void **)&d_res, sizeof(GdzResult) * n, s)) != hipSuccess) return fail(e, "results");
+	(void)hipEventRecord(ctx->bz_ev[0], s);
+	if ((e = hipMemcpyAsync(d_raw, raw, raw_len, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "members copy");
+	if ((e = hipMemcpyAsync(d_tab, m, sizeof(GdBgzfMember) * n, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "table copy");
+	if ((e = hipMemsetAsync(d_res, 0xff, sizeof(GdzResult) * n, s)) != hipSuccess) return fail(e, "results");
+	(void)hipEventRecord(ctx->bz_ev[1], s);
+	hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint8_t *)d_raw, (const GdBgzfMember *)d_tab, (uint32_t)n, d_out, d_res);
+	if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
+	(void)hipEventRecord(ctx->bz_ev[2], s);
+	if (dst_len && (e = hipMemcpyAsync(dst, d_out, dst_len, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "output copy");
+	if ((e = hipMemcpyAsync(res.data(), d_res, sizeof(GdzResult) * n, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "results copy");
+	(void)hipEventRecord(ctx->bz_ev[3], s);
+	if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "kernel");
+	for (int i = 0; i < 3; ++i) { // (for measurements: gdiet_hip_debug_bgzf_seconds)
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, ctx->bz_ev[i], ctx->bz_ev[i + 1]) == hipSuccess) ctx->bz_ms[i] += ms;
+	}
+	(void)hipFreeAsync(d_raw, s), (void)hipFreeAsync(d_out, s), (void)hipFreeAsync(d_tab, s), (void)hipFreeAsync(d_res, s);
+	for (size_t i = 0; i < n; ++i) {
+		out_len[i] = res[i].out_len;
+		if (res[i].rc != GDZ_OK) {
+			why = "BGZF member " + std::to_string(i) + ": " + gdz_strerror(res[i].rc);
+			return -2;
+		}
+	}
+	return 0;
+}
+
 struct GdFxExecutor : GdFastxDevice {
 	gdiet_ctx *ctx;
 	explicit GdFxExecutor(gdiet_ctx *c) : ctx(c) {}
+	int inflate(const unsigned char *raw, size_t raw_len, const GdBgzfMember *m, size_t n, unsigned char *dst, size_t dst_len, uint32_t *out_len, std::string &why) override
+	{
+		return gd_bz_inflate_device(ctx, raw, raw_len, m, n, dst, dst_len, out_len, why);
+	}
 	long parse(const unsigned char *b, size_t n, std::vector<GdxRec> &rec, std::shared_ptr<void> &dev) override
 	{
 		rec.clear(), dev.reset();

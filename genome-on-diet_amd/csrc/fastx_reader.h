@@ -8,6 +8,16 @@
 // Optional device mode (GdFastx::dev, installed by gdiet_hip_fastx_attach): the strict four-line FASTQ prefix of every block is parsed
 // by an executor -- on the GPU, fastx_dev.hip.h -- and the sequential grammar below takes over at the first record that is not strict,
 // exactly as it does behind a wrong seam.  This header itself stays free of HIP.
+//
+// BGZF input (bgzf.h) is a third source next to the plain file and zlib's gzread: a regular file whose first member is a BGZF member and
+// whose last 28 bytes are the BGZF end-of-file member is read raw, its members are located by their headers, and the members of one read
+// are inflated side by side -- by zlib's raw inflate on n_threads threads, or, attached, by GdFastxDevice::inflate -- into the block the
+// reader asked for (the file is read ahead until the members in hand inflate to the block's size, so a read is short of it by less than
+// one member whatever the compression ratio); behind that the reader sees plain bytes.  Every member, whoever inflated it, must come out ISIZE bytes long with the
+// trailer's CRC32 (checked on the reader's threads): anything else is a read error (io_error, io_msg; read_batch < 0), and so is a member
+// without a BC subfield in the middle of such a file (mixed streams are not read: GDIET_BGZF=0, read at open, sends every file through
+// gzread, as do stdin, single-stream gzip and a BGZF file without its end marker).  A read error surfaces when the block that holds it is
+// taken, so the number of reads of earlier blocks handed out before it is not gzread's count, which stops at the failing byte.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -15,6 +25,7 @@
 #include <string.h>
 #include <string>
 #include <algorithm>
+#include <atomic>
 #include <deque>
 #include <memory>
 #include <mutex>
@@ -24,7 +35,10 @@
 #include <errno.h>
 #include <fcntl.h>
 #include <unistd.h>
+#include <time.h>
+#include <sys/stat.h>
 #include "fastx_dev.h"
+#include "bgzf.h"
 
 // Record parser over a byte range held in memory (kseq_read's grammar); the reader below feeds it blocks of the file.
 struct GdFastxParser {
@@ -151,6 +165,15 @@ struct GdFastxChunk {
 struct GdFastxDevice {
 	virtual ~GdFastxDevice() {}
 	virtual long parse(const unsigned char *b, size_t n, std::vector<GdxRec> &rec, std::shared_ptr<void> &dev) = 0;
+	// BGZF: the deflate streams of the members m[0, n) of raw[0, raw_len) into dst[m[i].out_off ..), dst_len bytes in all; out_len[i] is what
+	// member i produced (the caller checks it, and the CRC).  0; -1 with the reason in why when the device failed (dev_error); -2 when a
+	// member's stream is not valid deflate (a read error).  Either way the read fails: nothing is inflated elsewhere for the same file.
+	virtual int inflate(const unsigned char *raw, size_t raw_len, const GdBgzfMember *m, size_t n, unsigned char *dst, size_t dst_len, uint32_t *out_len, std::string &why)
+	{
+		(void)raw, (void)raw_len, (void)m, (void)n, (void)dst, (void)dst_len, (void)out_len;
+		why = "this device does not inflate";
+		return -1;
+	}
 };
 
 struct GdFastx {
@@ -161,6 +184,15 @@ struct GdFastx {
 	int64_t n_rec_device = 0, n_rec_host = 0, n_blocks = 0, n_blocks_handed = 0; // who parsed what since the reader was opened
 	int fd = -1;         // plain file: read() straight into the block (gzread would copy it once more)
 	bool file_end = false, io_error = false;
+	// BGZF: fd is read raw; raw[raw_pos, raw_fill) is what no read has taken yet (an incomplete trailing member stays for the next one)
+	bool bgzf = false, raw_eof = false, io_dev_err = false;
+	std::vector<unsigned char> raw;
+	size_t raw_pos = 0, raw_fill = 0;
+	uint64_t raw_base = 0; // file offset of raw[0]
+	std::string io_msg;    // what the read error was
+	std::deque<z_stream> bz_zs; // (a deque: zlib refuses a stream that has moved, and more threads may be asked for in mid-file)
+	std::atomic<int64_t> bz_members_device{0}, bz_members_host{0}, bz_bytes_in{0}, bz_bytes_out{0};
+	std::atomic<int64_t> bz_ns[3] = {{0}, {0}, {0}}; // nanoseconds in: raw read, inflate (attached: copies and kernel), length / CRC check
 	int n_threads = 1;
 	size_t block_size = (size_t)8 << 20; // per parser thread
 	// The block being parsed is bp[0, fill) = the unparsed tail of the previous block + fresh bytes; bp points into block.  While it
@@ -188,10 +220,11 @@ struct GdFastx {
 		return l >= 3 && s[l - 1] >= '0' && s[l - 1] <= '9' && s[l - 2] == '/' ? l - 2 : l;
 	}
 	// read up to `want` bytes to dst; sets eof / err
-	void io_read(unsigned char *dst, size_t want, size_t *got_, bool *eof_, bool *err_)
+	void io_read(unsigned char *dst, size_t want, size_t *got_, bool *eof_, bool *err_, bool use_dev)
 	{
 		size_t got = 0;
 		*eof_ = *err_ = false;
+		if (bgzf) { bgzf_read(dst, want, got_, eof_, err_, use_dev); return; }
 		while (got < want) {
 			long n;
 			if (fd >= 0) {
@@ -203,16 +236,113 @@ struct GdFastx {
 		}
 		*got_ = got;
 	}
+	template <class F> void bz_parallel(size_t nt, size_t n, F f)
+	{
+		const size_t t = std::min<size_t>(nt, n);
+		if (t <= 1) { for (size_t k = 0; k < n; ++k) f(k, (size_t)0); return; }
+		std::atomic<size_t> next{0};
+		std::vector<std::thread> th;
+		auto run = [&](size_t w) { for (size_t k; (k = next++) < n;) f(k, w); };
+		for (size_t w = 1; w < t; ++w) th.emplace_back(run, w);
+		run(0);
+		for (auto &x : th) x.join();
+	}
+	static int64_t now_ns()
+	{
+		struct timespec ts;
+		clock_gettime(CLOCK_MONOTONIC, &ts);
+		return (int64_t)ts.tv_sec * 1000000000 + ts.tv_nsec;
+	}
+	// io_read of a BGZF file: whole members while the sum of their ISIZE stays within `want`, at least one (dst has room for want + 64 KiB:
+	// room_for), inflated to dst.  Returns with got > 0, or at the end of the file, or with an error.
+	void bgzf_read(unsigned char *dst, size_t want, size_t *got_, bool *eof_, bool *err_, bool use_dev)
+	{
+		*got_ = 0;
+		auto fail = [&](const std::string &what) { io_msg = what, *err_ = true, *eof_ = true; };
+		std::vector<GdBgzfMember> tab;
+		const size_t nt = (size_t)std::max(1, n_threads); // (once per read: gdiet_hip_fastx_set_threads may write it meanwhile)
+		// A member is at most 64 KiB: with `need` bytes unread, one is complete.  The first guess is that the members of `want` output bytes take
+		// half as many; when the walk below runs out of bytes before it has `want` output bytes, the file is read further and walked again,
+		// up to `cap` (data that does not compress: a stored member is 36 bytes larger than its output), so that a read is only short of
+		// `want` by less than one member, whatever the compression ratio.  The file is always read a quarter MiB past `need`, so that small
+		// reads do not move the rest of the buffer every time.
+		const size_t cap = want + want / 8 + 4 * (size_t)GD_BGZF_MAX_ISIZE;
+		size_t need = std::min(cap, want / 2 + (size_t)GD_BGZF_MAX_ISIZE);
+		for (;;) {
+			const size_t goal = need + ((size_t)4 << 16);
+			if (!raw_eof && raw_fill - raw_pos < need) {
+				const int64_t t0 = now_ns();
+				if (raw_pos) memmove(raw.data(), raw.data() + raw_pos, raw_fill - raw_pos), raw_fill -= raw_pos, raw_base += raw_pos, raw_pos = 0;
+				if (raw.size() < goal) raw.resize(goal);
+				while (raw_fill < goal) {
+					long n;
+					do n = (long)::read(fd, raw.data() + raw_fill, goal - raw_fill); while (n < 0 && errno == EINTR);
+					if (n < 0) { fail(std::string("read: ") + strerror(errno)); return; }
+					if (n == 0) { raw_eof = true; break; }
+					raw_fill += (size_t)n;
+				}
+				bz_ns[0] += now_ns() - t0;
+			}
+			const unsigned char *r = raw.data() + raw_pos;
+			const size_t avail = raw_fill - raw_pos;
+			size_t taken = 0, bad_at = 0;
+			std::string why;
+			bool full = false;
+			const int rc = gd_bgzf_scan(r, avail, tab, &taken, &bad_at, &why, want, &full);
+			if (rc == GD_BGZF_OK && !full && !raw_eof && need < cap) { need = std::min(cap, std::max(2 * need, avail + ((size_t)4 << 16))); continue; } // more members may fit: read on
+			if (rc < 0 && tab.empty()) {
+				fail("offset " + std::to_string(raw_base + raw_pos + bad_at) + ": " + why + ": not a BGZF member inside a BGZF file (set GDIET_BGZF=0 to read the file through zlib)");
+				return;
+			}
+			if (tab.empty()) {
+				if (avail) fail("offset " + std::to_string(raw_base + raw_pos) + ": the file ends inside a BGZF member");
+				else *eof_ = true;
+				return;
+			}
+			taken = (size_t)(tab.back().in_off + tab.back().in_len + 8); // (behind a member that is not one, the members in front of it are still read)
+			const size_t n = tab.size(), total = (size_t)(tab.back().out_off + tab.back().isize);
+			std::vector<uint32_t> out_len(n, 0);
+			std::vector<std::string> msg(n);
+			std::vector<uint8_t> ok(n, 1);
+			int64_t t0 = now_ns();
+			if (use_dev) {
+				const int drc = dev->inflate(r, taken, tab.data(), n, dst, total, out_len.data(), why);
+				if (drc < 0) { io_dev_err = drc == -1; fail(why); return; }
+				bz_ns[1] += now_ns() - t0, t0 = now_ns();
+				bz_parallel(nt, n, [&](size_t k, size_t) { ok[k] = gd_bgzf_check(tab[k], k, dst + tab[k].out_off, out_len[k], &msg[k]); });
+				bz_ns[2] += now_ns() - t0;
+				bz_members_device += (int64_t)n;
+			} else {
+				std::deque<z_stream> &zs = bz_zs; // (one per thread, kept for the file: zlib's state is 40 KiB to set up)
+				while (zs.size() < nt) { zs.emplace_back(); memset(&zs.back(), 0, sizeof(z_stream)); }
+				bz_parallel(nt, n, [&](size_t k, size_t w) {
+					ok[k] = gd_bgzf_inflate_host(&zs[w], r + tab[k].in_off, tab[k].in_len, dst + tab[k].out_off, tab[k].isize, &out_len[k], k, &msg[k]) &&
+					        gd_bgzf_check(tab[k], k, dst + tab[k].out_off, out_len[k], &msg[k]);
+				});
+				bz_ns[1] += now_ns() - t0;
+				bz_members_host += (int64_t)n;
+			}
+			for (size_t k = 0; k < n; ++k)
+				if (!ok[k]) { fail("offset " + std::to_string(raw_base + raw_pos + tab[k].in_off) + ": " + msg[k]); return; }
+			raw_pos += taken;
+			bz_bytes_in += (int64_t)taken, bz_bytes_out += (int64_t)total;
+			if (raw_eof && raw_pos == raw_fill) *eof_ = true;
+			if (total || *eof_) { *got_ = total; return; } // (only empty members so far: read on)
+		}
+	}
+	// bytes a block must have room for behind the place a read of `want` bytes starts at
+	size_t room_for(size_t want) const { return want + (bgzf ? (size_t)GD_BGZF_MAX_ISIZE : 0); }
 	// start reading the next `want` bytes into `other`, in front of which the tail bp[pos, fill) of the current block is placed
 	void prefetch(size_t pos, size_t want)
 	{
 		const size_t t = fill - pos;
 		io_tail = t, io_base = (t + 4095) & ~(size_t)4095;
-		if (other.size() < io_base + want) other.resize(io_base + want);
+		if (other.size() < io_base + room_for(want)) other.resize(io_base + room_for(want));
 		if (t) memcpy(other.data() + io_base - t, bp + pos, t);
 		if (file_end) { io_got = 0, io_eof = true, io_err = false, io_pending = true; return; } // nothing more to read: only the tail moves
 		unsigned char *dst = other.data() + io_base;
-		io = std::thread([this, dst, want] { io_read(dst, want, &io_got, &io_eof, &io_err); });
+		const bool use_dev = dev && !dev_error;
+		io = std::thread([this, dst, want, use_dev] { io_read(dst, want, &io_got, &io_eof, &io_err, use_dev); });
 		io_pending = true;
 	}
 	// make the prefetched stretch the current block
@@ -225,6 +355,7 @@ struct GdFastx {
 		fill = io_tail + io_got;
 		if (io_eof) file_end = true;
 		if (io_err) io_error = true;
+		if (io_dev_err) dev_error = true;
 	}
 	// Parse block[from, fill) sequentially into C, never starting a record at or after `stop` (the next parser's first record, or
 	// `fill`).  Returns where the next record would start: exactly `stop` when the stretch ends on the seam (or the range is
@@ -340,10 +471,11 @@ struct GdFastx {
 		for (;;) {
 			if (!io_pending) { // the very first block: nothing was read ahead
 				if (file_end) return false;
-				if (block.size() < want) block.resize(want);
+				if (block.size() < room_for(want)) block.resize(room_for(want));
 				bool e, r;
-				io_read(block.data(), want, &fill, &e, &r);
+				io_read(block.data(), want, &fill, &e, &r, dev && !dev_error);
 				bp = block.data(), file_end = e, io_error = r;
+				if (io_dev_err) dev_error = true;
 			} else take_prefetched();
 			if (fill == 0) return false;
 			// split points: record starts verified by look-ahead; whether they ARE boundaries of the sequential grammar is checked
@@ -466,6 +598,19 @@ static inline GdFastxBatch *gd_fastx_detach(GdFastx *fx)
 	return b;
 }
 
+// WHEN A FILE TAKES THE BGZF ROUTE: it is a regular file, its first member is a BGZF member, its last 28 bytes are the BGZF end-of-file
+// member, and GDIET_BGZF is not 0.  Everything else that starts with the gzip magic goes through gzread as before.
+static inline bool gd_fastx_takes_bgzf_route(int fd)
+{
+	if (const char *e = getenv("GDIET_BGZF")) if (!strcmp(e, "0")) return false;
+	struct stat st;
+	if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < (off_t)(18 + GD_BGZF_EOF_LEN)) return false;
+	unsigned char head[512], tail[GD_BGZF_EOF_LEN];
+	const long nh = (long)::pread(fd, head, sizeof(head), 0);
+	if (nh < 18 || !gd_bgzf_first_is_member(head, (size_t)nh)) return false;
+	return ::pread(fd, tail, sizeof(tail), st.st_size - (off_t)GD_BGZF_EOF_LEN) == (long)sizeof(tail) && gd_bgzf_ends_with_marker(tail, sizeof(tail));
+}
+
 static inline GdFastx *gd_fastx_open(const char *path)
 {
 	GdFastx *fx = new GdFastx();
@@ -475,7 +620,8 @@ static inline GdFastx *gd_fastx_open(const char *path)
 		if (fd < 0) { delete fx; return nullptr; }
 		unsigned char magic[2] = {0, 0};
 		const long n = (long)::pread(fd, magic, 2, 0);
-		if (n == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
+		if (n == 2 && magic[0] == 0x1f && magic[1] == 0x8b && gd_fastx_takes_bgzf_route(fd)) fx->fd = fd, fx->bgzf = true;
+		else if (n == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
 			::close(fd);
 			fx->fp = gzopen(path, "r");
 			if (!fx->fp) { delete fx; return nullptr; }
@@ -493,6 +639,7 @@ static inline void gd_fastx_close(GdFastx *fx)
 	if (!fx) return;
 	if (fx->io.joinable()) fx->io.join();
 	if (fx->fp) gzclose(fx->fp);
+	for (auto &z : fx->bz_zs) if (z.state) inflateEnd(&z);
 	if (fx->fd >= 0) ::close(fx->fd);
 	delete fx;
 }

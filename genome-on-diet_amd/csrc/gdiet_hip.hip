@@ -132,6 +132,12 @@ struct gdiet_ctx {
 	std::string fx_err;                // text of the last failing device parse (written under fx_mu; gdiet_hip_strerror)
 	hipStream_t fx_stream = nullptr;
 	DevBuf fx_scan;
+	// BGZF members inflated on the device (bgzf_inflate.hip.h): a stream and a mutex of their own again, because the reader's I/O thread
+	// inflates the next block while its reader thread parses the current one under fx_mu
+	std::mutex bz_mu;
+	hipStream_t bz_stream = nullptr;
+	hipEvent_t bz_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three steps of a read: copy up, kernel, copy down
+	double bz_ms[3] = {0, 0, 0};                                // ... and their sums since the context was created (under bz_mu)
 	std::string rg_line, rg_id;        // -R: the escaped @RG header line and its ID (gdiet_hip_set_read_group; read by the SAM formatters)
 };
 
@@ -282,8 +288,9 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
 	if (ctx->ds_stream) (void)hipStreamSynchronize(ctx->ds_stream);
 	if (ctx->fx_stream) (void)hipStreamSynchronize(ctx->fx_stream);
-	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev};
-	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream, ctx->fx_stream};
+	if (ctx->bz_stream) (void)hipStreamSynchronize(ctx->bz_stream);
+	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev, ctx->bz_ev[0], ctx->bz_ev[1], ctx->bz_ev[2], ctx->bz_ev[3]};
+	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream, ctx->fx_stream, ctx->bz_stream};
 	delete ctx; // every DevBuf of the context releases itself here: before the streams and events go
 	for (hipEvent_t e : events)
 		if (e) (void)hipEventDestroy(e);
@@ -1024,6 +1031,7 @@ extern "C" int gdiet_hip_debug_seed_prof(unsigned long long *out8) { return (int
 // ---- read input (input half) ---------------------------------------------------------------------------
 #include "fastx_reader.h"
 #include "fastx_dev_driver.hip.h" // struct gdiet_fastx; the device mode of the reader
+static int gd_fx_read_failed(gdiet_fastx *fx);
 
 extern "C" int gdiet_hip_fastx_open(gdiet_fastx **fx, const char *path)
 {
@@ -1043,7 +1051,7 @@ extern "C" int gdiet_hip_fastx_read(gdiet_fastx *fx, int64_t chunk_size, int wit
 	if (!fx || !fx->r || !n_reads || !names || !seqs || !lens) return GDIET_E_PARAM;
 	bool bad = false;
 	const int n = fx->r->read_batch(chunk_size, with_qual != 0, with_comment != 0, frag_mode != 0, &bad);
-	if (n < 0) return fx->r->dev_error ? GDIET_E_HIP : GDIET_E_PARAM;
+	if (n < 0) return gd_fx_read_failed(fx);
 	fx->r->u_to_t_on_host(); // (an attached reader without a resident batch: nobody encodes these reads on the device)
 	gd_fx_release_done(*fx->r);
 	*n_reads = n;
@@ -1071,7 +1079,7 @@ extern "C" int gdiet_hip_fastx_read_resident(gdiet_fastx *fx, int64_t chunk_size
 	if (!fx->ctx) return GDIET_E_PARAM; // the batch belongs to a context: attach first
 	bool bad = false;
 	const int n = fx->r->read_batch(chunk_size, with_qual != 0, with_comment != 0, frag_mode != 0, &bad);
-	if (n < 0) return fx->r->dev_error ? GDIET_E_HIP : GDIET_E_PARAM;
+	if (n < 0) return gd_fx_read_failed(fx);
 	if (n > 0) {
 		const int rc = gd_fx_build_batch(fx->ctx, *fx->r, batch);
 		if (rc) return rc;
@@ -1091,6 +1099,72 @@ extern "C" int gdiet_hip_fastx_stats(const gdiet_fastx *fx, int64_t *records_dev
 	if (records_host) *records_host = fx->r->n_rec_host;
 	if (blocks) *blocks = fx->r->n_blocks;
 	if (blocks_handed_over) *blocks_handed_over = fx->r->n_blocks_handed;
+	return GDIET_OK;
+}
+
+// a read error of the reader, kept where gdiet_hip_strerror finds it
+static int gd_fx_read_failed(gdiet_fastx *fx)
+{
+	const int rc = fx->r->dev_error ? GDIET_E_HIP : GDIET_E_PARAM;
+	if (fx->ctx && !fx->r->io_msg.empty()) {
+		std::lock_guard<std::mutex> lk(fx->ctx->fx_mu);
+		return gd_fx_fail(fx->ctx, rc, "read error: " + fx->r->io_msg);
+	}
+	return rc;
+}
+
+extern "C" const char *gdiet_hip_fastx_strerror(const gdiet_fastx *fx) { return fx && fx->r ? fx->r->io_msg.c_str() : "no reader"; }
+
+extern "C" int gdiet_hip_fastx_bgzf_stats(const gdiet_fastx *fx, int64_t *members_device, int64_t *members_host, int64_t *bytes_in, int64_t *bytes_out)
+{
+	if (!fx || !fx->r) return GDIET_E_PARAM;
+	if (members_device) *members_device = fx->r->bz_members_device;
+	if (members_host) *members_host = fx->r->bz_members_host;
+	if (bytes_in) *bytes_in = fx->r->bz_bytes_in;
+	if (bytes_out) *bytes_out = fx->r->bz_bytes_out;
+	return GDIET_OK;
+}
+
+// measurement only (tools/map_file.py; not declared in include/gdiet_hip.h): seconds the reader's I/O thread spent on a BGZF file -- reading raw
+// members; inflating (attached: the copies and the kernel; unattached: zlib and the checks together); checking lengths and CRCs (attached
+// only) -- and, of the attached reader's context since it was created, the device's side of inflating: copy up, kernel, copy down (HIP events)
+extern "C" int gdiet_hip_debug_bgzf_seconds(const gdiet_fastx *fx, double *out6)
+{
+	if (!fx || !fx->r || !out6) return GDIET_E_PARAM;
+	for (int i = 0; i < 3; ++i) out6[i] = 1e-9 * (double)fx->r->bz_ns[i], out6[3 + i] = 0;
+	if (fx->ctx) {
+		std::lock_guard<std::mutex> lk(fx->ctx->bz_mu);
+		for (int i = 0; i < 3; ++i) out6[3 + i] = 1e-3 * fx->ctx->bz_ms[i];
+	}
+	return GDIET_OK;
+}
+
+extern "C" int gdiet_hip_bgzf_inflate(gdiet_ctx *ctx, const uint8_t *raw, size_t raw_len, uint8_t *out, size_t out_cap, size_t *out_len)
+{
+	if (!ctx || (!raw && raw_len) || !out_len) return GDIET_E_PARAM;
+	*out_len = 0;
+	gd_ds_clear_mark(); // (an earlier refusal on this thread is not this call's text)
+	auto fail = [&](int rc, const std::string &what) {
+		std::lock_guard<std::mutex> lk(ctx->fx_mu);
+		return gd_fx_fail(ctx, rc, "gdiet_hip_bgzf_inflate: " + what);
+	};
+	std::vector<GdBgzfMember> tab;
+	size_t inc = 0, bad_at = 0;
+	std::string why;
+	if (gd_bgzf_scan(raw, raw_len, tab, &inc, &bad_at, &why) != GD_BGZF_OK) return fail(GDIET_E_PARAM, "offset " + std::to_string(bad_at) + ": " + why);
+	if (inc != raw_len) return fail(GDIET_E_PARAM, "offset " + std::to_string(inc) + ": the range ends inside a member");
+	const size_t total = tab.empty() ? 0 : (size_t)(tab.back().out_off + tab.back().isize);
+	*out_len = total;
+	if (!out) return GDIET_OK; // sizes first
+	if (total > out_cap) return fail(GDIET_E_PARAM, "the members inflate to " + std::to_string(total) + " bytes, out holds " + std::to_string(out_cap));
+	std::vector<uint32_t> lens(tab.size(), 0);
+	const int rc = gd_bz_inflate_device(ctx, raw, raw_len, tab.data(), tab.size(), out, total, lens.data(), why);
+	if (rc < 0) return fail(rc == -1 ? GDIET_E_HIP : GDIET_E_PARAM, why);
+	std::vector<std::string> msg(tab.size());
+	std::vector<uint8_t> ok(tab.size(), 1);
+	gd_parallel_for(ctx, ctx->host_threads, (int)tab.size(), [&](int k) { ok[(size_t)k] = gd_bgzf_check(tab[(size_t)k], (size_t)k, out + tab[(size_t)k].out_off, lens[(size_t)k], &msg[(size_t)k]); });
+	for (size_t k = 0; k < tab.size(); ++k)
+		if (!ok[k]) return fail(GDIET_E_PARAM, msg[k]);
 	return GDIET_OK;
 }
 

@@ -9,7 +9,10 @@
 // designed to refuse bad records on a writer thread while a mapping thread may be writing err.  gdiet_hip_strerror hands it to the thread
 // whose call failed (gd_ds_err_of below), until that thread's next difference-string, upload or map call on any context.
 static thread_local const gdiet_ctx *gd_ds_failed_on = nullptr;
-static void gd_ds_clear_mark() { gd_ds_failed_on = nullptr; }
+// the same mark of the reader's device mode and of the BGZF inflater (fastx_dev_driver.hip.h); declared here so that every failure that is
+// neither clears both: a refused read or byte range is an ordinary outcome there, and its text must not answer for a later, unrelated failure
+static thread_local const gdiet_ctx *gd_fx_failed_on = nullptr;
+static void gd_ds_clear_mark() { gd_ds_failed_on = nullptr, gd_fx_failed_on = nullptr; }
 static const char *gd_ds_err_of(const gdiet_ctx *ctx) { return ctx && gd_ds_failed_on == ctx ? ctx->ds_err.c_str() : nullptr; }
 
 // (like gd_grow, on the difference strings' own stream; the caller holds ds_mu)
@@ -52,7 +55,7 @@ static int gd_diffstr_run(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_rea
 	for (int i = 0; i < n_reads; ++i)
 		for (int j = 0; j < n_regs[i]; ++j) ++n_rec, n_cig += regs[i][j].n_cigar;
 	int64_t *h_off = (int64_t *)calloc((size_t)n_rec + 1, sizeof(int64_t));
-	auto fail = [&](int rc, const std::string &what) { free(h_off); if (!what.empty()) ctx->ds_err = what; gd_ds_failed_on = ctx; return rc; }; // (empty: ds_err is set)
+	auto fail = [&](int rc, const std::string &what) { free(h_off); if (!what.empty()) ctx->ds_err = what; gd_ds_failed_on = ctx, gd_fx_failed_on = nullptr; return rc; }; // (empty: ds_err is set)
 	if (!h_off) return fail(GDIET_E_NOMEM, "out of host memory");
 	if (mode < 0 || n_rec == 0) {
 		char *t = (char *)calloc(1, 1);

@@ -1,4 +1,4 @@
-"""ctypes mirror of the read-input entry points of include/gdiet_hip.h (gdiet_hip_fastx_*): FASTA / FASTQ, plain or gzip,
+"""ctypes mirror of the read-input entry points of include/gdiet_hip.h (gdiet_hip_fastx_*): FASTA / FASTQ, plain, gzip or BGZF,
 mini-batch by mini-batch with the reference's record grammar and batching rule (LR/bseq.c:80-121, LR/kseq.h:191-232)."""
 import ctypes as C
 
@@ -10,7 +10,9 @@ W_TRUNCATED = 1
 class FastxReader:
     """ctx: a Context; the reader is then attached to it (gdiet_hip_fastx_attach): the strict four-line FASTQ records at the front of
     every block are parsed on its device, and read_raw(..., resident=True) returns the resident batch next to the host arrays.  The
-    records, batches and truncation flags do not depend on it.  Close the reader before the context."""
+    records, batches and truncation flags do not depend on it.  Close the reader before the context.
+    A BGZF file (a regular file with the BGZF end-of-file member; GDIET_BGZF=0 turns it off) is inflated member by member: on `threads`
+    threads, or, with ctx, on the device; bgzf_stats() says by whom."""
 
     def __init__(self, path, threads=1, ctx=None):
         self.lib = load_library()
@@ -32,6 +34,10 @@ class FastxReader:
         L.gdiet_hip_fastx_read_resident.argtypes = L.gdiet_hip_fastx_read.argtypes + [C.POINTER(C.c_void_p)]
         i64p = C.POINTER(C.c_int64)
         L.gdiet_hip_fastx_stats.argtypes = [C.c_void_p, i64p, i64p, i64p, i64p]
+        L.gdiet_hip_fastx_bgzf_stats.argtypes = [C.c_void_p, i64p, i64p, i64p, i64p]
+        L.gdiet_hip_debug_bgzf_seconds.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.gdiet_hip_fastx_strerror.argtypes = [C.c_void_p]
+        L.gdiet_hip_fastx_strerror.restype = C.c_char_p
         self.ctx = ctx
         if ctx is not None and L.gdiet_hip_fastx_attach(self._h, ctx._h) != 0:
             raise GdietError("gdiet_hip_fastx_attach failed")
@@ -44,7 +50,7 @@ class FastxReader:
         rc = self.lib.gdiet_hip_fastx_read(self._h, chunk_size, int(with_qual), int(with_comment), int(frag_mode), C.byref(n), C.byref(names),
                                            C.byref(comments), C.byref(seqs), C.byref(quals), C.byref(lens))
         if rc < 0:
-            raise GdietError("read error" + (": " + self.lib.gdiet_hip_strerror(self.ctx._h).decode() if self.ctx is not None else ""))
+            raise self._read_error()
         self.truncated_now = rc == W_TRUNCATED  # this batch was closed by a malformed record
         self.truncated = self.truncated or self.truncated_now
         out = []
@@ -72,7 +78,7 @@ class FastxReader:
             rc = self.lib.gdiet_hip_fastx_read(self._h, chunk_size, int(with_qual), int(with_comment), int(frag_mode), C.byref(n), C.byref(names),
                                                C.byref(comments), C.byref(seqs), C.byref(quals), C.byref(lens))
         if rc < 0:
-            raise GdietError("read error" + (": " + self.lib.gdiet_hip_strerror(self.ctx._h).decode() if self.ctx is not None else ""))
+            raise self._read_error()
         self.truncated_now = rc == W_TRUNCATED
         self.truncated = self.truncated or self.truncated_now
         token = None
@@ -89,6 +95,21 @@ class FastxReader:
         v = [C.c_int64() for _ in range(4)]
         self.lib.gdiet_hip_fastx_stats(self._h, *[C.byref(x) for x in v])
         return dict(zip(("records_device", "records_host", "blocks", "blocks_handed_over"), (x.value for x in v)))
+
+    def bgzf_stats(self):
+        """gdiet_hip_fastx_bgzf_stats (all zero for a file that did not take the BGZF route), and the I/O thread's seconds per stage"""
+        v = [C.c_int64() for _ in range(4)]
+        self.lib.gdiet_hip_fastx_bgzf_stats(self._h, *[C.byref(x) for x in v])
+        t = (C.c_double * 6)()
+        self.lib.gdiet_hip_debug_bgzf_seconds(self._h, t)
+        out = dict(zip(("members_device", "members_host", "bytes_in", "bytes_out"), (x.value for x in v)))
+        # (h2d / kernel / d2h: the device's side of inflate_s, summed over the context's life, not the reader's)
+        out.update(zip(("raw_read_s", "inflate_s", "check_s", "h2d_s", "kernel_s", "d2h_s"), (round(x, 4) for x in t)))
+        return out
+
+    def _read_error(self):
+        return GdietError("read error: " + self.lib.gdiet_hip_fastx_strerror(self._h).decode() +
+                          (" (" + self.lib.gdiet_hip_strerror(self.ctx._h).decode() + ")" if self.ctx is not None else ""))
 
     def release(self, token):
         if token:

@@ -75,6 +75,7 @@ def load_library():
     lib.gdiet_hip_ksw_exts2_batch.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, u8p, C.POINTER(C.c_int8), C.c_int8, C.c_int8, C.c_int8, C.c_int8, C.c_int32,
                                               C.c_int8, C.c_int32, i32p, i32p, u32p, i64p]
     lib.gdiet_hip_ksw_extz2_batch_ex.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, i32p, C.POINTER(KswScore), C.c_int32, C.c_int32, i32p, i32p, u32p, i64p]
+    lib.gdiet_hip_bgzf_inflate.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = lib
     return lib
 
@@ -115,6 +116,15 @@ class Context:
     def _check(self, rc):
         if rc != 0:
             raise GdietError("gdiet_hip error %d: %s" % (rc, self.lib.gdiet_hip_strerror(self._h).decode()))
+
+    def bgzf_inflate(self, raw):
+        """gdiet_hip_bgzf_inflate: the bytes of whole BGZF members, inflated on the device and checked against their trailers"""
+        raw = bytes(raw)
+        n = C.c_size_t()
+        self._check(self.lib.gdiet_hip_bgzf_inflate(self._h, raw, len(raw), None, 0, C.byref(n)))
+        out = C.create_string_buffer(max(1, n.value))
+        self._check(self.lib.gdiet_hip_bgzf_inflate(self._h, raw, len(raw), C.cast(out, C.c_void_p), n.value, C.byref(n)))
+        return out.raw[:n.value]
 
     @property
     def device_name(self):

@@ -468,7 +468,7 @@ size_t gdiet_hip_paf_batch_comments(gdiet_ctx *ctx, const gdiet_index *idx, int 
                                     const char *const *comments, const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs,
                                     int64_t opt_flag, char **out);
 
-/* Read input, step 0 of worker_pipeline (LR/map.c:2095-2131): FASTA / FASTQ, plain or gzip ("-" = stdin), one mini-batch per
+/* Read input, step 0 of worker_pipeline (LR/map.c:2095-2131): FASTA / FASTQ, plain, gzip or BGZF ("-" = stdin), one mini-batch per
  * call.  Replaces mm_bseq_open / mm_bseq_read3 / mm_bseq_close (LR/bseq.c:38-58, 80-121) with the same record grammar
  * (kseq_read, LR/kseq.h:191-232: multi-line records, names up to the first white space, the rest of the header as comment,
  * "\r\n" line ends, U -> T) and the same batching rule (records until their lengths sum to chunk_size; in fragment mode the mates
@@ -517,6 +517,30 @@ int gdiet_hip_fastx_stats(const gdiet_fastx *fx, int64_t *records_device, int64_
 /* A resident batch as arrays, for tests and for a maintainer checking one: *n reads, roff[n + 1], and the roff[n] encoded bytes of the
  * host copy (enc_host) and of the device copy, downloaded (enc_device).  Sizes first: every array argument may be NULL. */
 int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n, int64_t *roff, uint8_t *enc_host, uint8_t *enc_device);
+
+/* BGZF input (the blocked gzip of htslib's bgzip).  No call selects it: gdiet_hip_fastx_open reads a file raw, member by member, when it
+ * is a regular file whose first gzip member carries the BC extra subfield and whose last 28 bytes are the BGZF end-of-file member, and
+ * GDIET_BGZF is not 0 in the environment at that time.  The members of one read are then inflated side by side: by zlib's raw inflate on
+ * the reader's threads (gdiet_hip_fastx_set_threads), or, once the reader is attached, on the device, one wavefront per member
+ * (csrc/bgzf_inflate.hip.h).  The records, batches and truncation flags are those of the same bytes uncompressed.  After inflation every
+ * member's length must be its ISIZE and its CRC32 its trailer's, on either route: otherwise the read fails with GDIET_E_PARAM
+ * (GDIET_E_HIP when the device itself failed; nothing continues on the host for that file), and gdiet_hip_fastx_strerror, or
+ * gdiet_hip_strerror of the attached context, says which member.  How many reads of earlier blocks were handed out before such an
+ * error is not what gzread's stream would have given.
+ * Still read through zlib's gzread, as before: single-stream gzip, stdin, and a BGZF file without its end marker.  A member without a BC
+ * subfield inside a file that took the BGZF route is a read error whose message names GDIET_BGZF=0; mixed streams are not read.
+ * Out of scope: the CRC on the device, keeping the inflated block resident for the device's parse pass (it is uploaded again),
+ * compressed SAM output, and the reference FASTA of the index build. */
+/* members inflated on the device and by zlib, compressed bytes taken and bytes produced since the reader was opened: all zero for a file
+ * that did not take the BGZF route.  Any pointer may be NULL. */
+int gdiet_hip_fastx_bgzf_stats(const gdiet_fastx *fx, int64_t *members_device, int64_t *members_host, int64_t *bytes_in, int64_t *bytes_out);
+/* the text of the reader's last read error ("" if there was none); valid until the reader is closed */
+const char *gdiet_hip_fastx_strerror(const gdiet_fastx *fx);
+/* The kernel-level boundary of the inflater: raw[0, raw_len) must be whole BGZF members; they are located (no inflating), inflated on the
+ * device, and checked (length against ISIZE, CRC32 against the trailer, on the host).  *out_len is the sum of ISIZE; with out == NULL
+ * only that is computed.  GDIET_E_PARAM with a message in gdiet_hip_strerror for a malformed range, a range that ends inside a member,
+ * out_cap too small, or a member's error; the context stays usable. */
+int gdiet_hip_bgzf_inflate(gdiet_ctx *ctx, const uint8_t *raw, size_t raw_len, uint8_t *out, size_t out_cap, size_t *out_len);
 
 #ifdef __cplusplus
 }

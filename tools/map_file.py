@@ -159,6 +159,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
         stop.set()  # (nothing is left to do: a reader that has not reached the end of the file stops here)
         th_r.join()
         map_file.last_reader_stats = fx.stats()
+        map_file.last_bgzf_stats = fx.bgzf_stats()
         fx.close()
     if errors:
         raise errors[0]
@@ -230,7 +231,7 @@ def main():
         sys.exit(1)
     print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), "mini_batch_bases": chunk,
                       "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "eqx": a.eqx, "out": a.out, "caller_seconds": map_file.last_stage_seconds,
-                      **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {})}))
+                      **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats}))
     m.close()
     ctx.close()
 
