@@ -381,6 +381,22 @@ static int gd_check_opt(gdiet_ctx *ctx, const GdMapOpt &O)
 	return GDIET_OK;
 }
 
+// The scoring of a mapping call: what the reference's mm_check_opt refuses (LR/options.c:208-223) is refused here too, and so is a value the
+// DP's int8_t parameters cannot hold (gd_stage_dp narrows them).  The DP-level entry points keep their own checks (gd_consts): they
+// take the larger gap model first as well.
+static int gd_check_scoring(gdiet_ctx *ctx, const GdMapOpt &O)
+{
+	for (int v : {O.a, O.b, O.q, O.e, O.q2, O.e2})
+		if (v < -128 || v > 127) { ctx->err = "scoring: a, b, q, e, q2 and e2 must each fit an int8_t"; return GDIET_E_PARAM; }
+	if (O.q <= 0 || O.e <= 0) { ctx->err = "scoring: q and e (-O, -E) must be positive"; return GDIET_E_PARAM; }
+	if ((O.q != O.q2 || O.e != O.e2) && !(O.e > O.e2 && O.q + O.e < O.q2 + O.e2)) {
+		ctx->err = "scoring: dual gap penalties violating e > e2 and q + e < q2 + e2";
+		return GDIET_E_PARAM;
+	}
+	if ((O.q + O.e) + (O.q2 + O.e2) > 127) { ctx->err = "scoring: (q+e)+(q2+e2) > 127"; return GDIET_E_PARAM; }
+	return GDIET_OK;
+}
+
 // a contiguous slice of a resident read batch
 struct GdBatchView {
 	int n;
@@ -1034,6 +1050,7 @@ extern "C" int gdiet_hip_map_uploaded(gdiet_ctx *ctx, const gdiet_index *ix, con
 	GdMapOpt O;
 	gd_opt_from_c(copt, ix, O);
 	{ const int rc = gd_check_opt(ctx, O); if (rc) return rc; }
+	{ const int rc = gd_check_scoring(ctx, O); if (rc) return rc; }
 	ctx->last_was_async = false;
 	for (int i = 0; i < GD_MAX_INFLIGHT; ++i)
 		if (ctx->async_busy[i]) { ctx->err = "batches submitted with gdiet_hip_map_submit are still in flight"; return GDIET_E_PARAM; }
@@ -1044,6 +1061,7 @@ extern "C" int gdiet_hip_map_uploaded(gdiet_ctx *ctx, const gdiet_index *ix, con
 		for (gdiet_ctx *c : ctx->children) gdiet_hip_destroy(c);
 		ctx->children.clear();
 		ctx->lane_threads = ctx->host_threads;
+		ctx->last_mask = 0; // (a batch without a box launches no DP kernel: not the mask of an earlier call)
 		GdBatchView V = {n, B->roff.data(), B->enc.data(), (const uint8_t *)B->d_reads, (const int64_t *)B->d_roff};
 		return gd_map_range(ctx, ix, O, V, n_regs, regs);
 	}
@@ -1071,14 +1089,18 @@ extern "C" int gdiet_hip_map_uploaded(gdiet_ctx *ctx, const gdiet_index *ix, con
 			c->kernel_mode = ctx->kernel_mode;
 			c->lane_threads = std::max(1, ctx->host_threads / lanes);
 			double acc[6] = {0, 0, 0, 0, 0, 0};
+			int mask = 0; // the union over this lane's slices of THIS call (a lane may take several, or none: then not what an earlier call left)
 			for (;;) {
 				const int sl = next.fetch_add(1);
 				if (sl >= n_slices || rcs[l]) break;
 				const int lo = (int)((int64_t)n * sl / n_slices), hi = (int)((int64_t)n * (sl + 1) / n_slices);
 				GdBatchView V = {hi - lo, B->roff.data() + lo, B->enc.data(), (const uint8_t *)B->d_reads, (const int64_t *)B->d_roff + lo};
+				c->last_mask = 0;
 				rcs[l] = gd_map_range(c, ix, O, V, n_regs + lo, regs + lo);
+				mask |= c->last_mask;
 				for (int i = 0; i < 6; ++i) acc[i] += c->stage_s[i];
 			}
+			c->last_mask = mask;
 			for (int i = 0; i < 6; ++i) c->stage_s[i] = acc[i];
 		});
 	for (auto &t : th) t.join();
@@ -1144,6 +1166,7 @@ extern "C" int gdiet_hip_map_submit(gdiet_ctx *ctx, const gdiet_index *ix, const
 	gdiet_map_ticket *t = new gdiet_map_ticket();
 	gd_opt_from_c(copt, ix, t->O);
 	int rc = gd_check_opt(ctx, t->O);
+	if (!rc) rc = gd_check_scoring(ctx, t->O);
 	if (rc) { delete t; return rc; }
 	const int l = ctx->async_next % ctx->async_depth;
 	if (ctx->async_busy[l]) { delete t; ctx->err = "too many batches in flight: wait for the oldest ticket first"; return GDIET_E_PARAM; }
@@ -1161,6 +1184,7 @@ extern "C" int gdiet_hip_map_submit(gdiet_ctx *ctx, const gdiet_index *ix, const
 	gd_copy_lane_opts(c, ctx);
 	c->lane_threads = c->host_threads = ctx->host_threads; // all lanes draw from the parent's pool
 	ctx->async_busy[l] = true, ctx->async_next++;
+	c->last_mask = 0; // (as in gdiet_hip_map_uploaded: a batch without a box reports no kernel)
 	t->lane = l;
 	ctx->open_tickets.push_back(t);
 	t->th = std::thread([=]() {

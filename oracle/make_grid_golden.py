@@ -15,7 +15,8 @@ Per row of grid.json (n_reads reads of the row's kind from first_read on, the ki
 What keeps a row from passing vacuously is asserted here (and again by tests/test_map_host.py on the committed files): the reference
 maps at least the row's min_mapped share of the reads; --for-only / --rev-only rows hold mapped and unmapped reads; leaving out any one of
 the row's option groups ("sensitive": every option of "extra") changes the reference's SAM or trace, so no option rides along inert; for a
-"scalar" row the two builds of the reference really print different traces.
+"scalar" row the two builds of the reference really print different traces; a "score" row holds what fixture_io.assert_score_row_conditions
+asks of it (records on both sides of the pre-filter's bound, Ns inside alignments at e2 = 2, a wave / generic tag that is true).
 Nothing of the product is involved in what is written."""
 import argparse
 import gzip
@@ -29,7 +30,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
-from fixture_io import OPTS, SETS, TRACE_PREFIXES, digest_sd, grid_cmd, grid_reads, grid_rows, mapped_share, star_seq_qual  # noqa: E402
+from fixture_io import OPTS, SETS, TRACE_PREFIXES, assert_score_row_conditions, digest_sd, grid_cmd, grid_reads, grid_rows, mapped_share, star_seq_qual  # noqa: E402
 from make_golden import _gunzip_to, _write_gz  # noqa: E402
 
 
@@ -73,6 +74,8 @@ def check_row(row, sam, trace, tmp):
     if "strand" in row["tags"]:
         assert 0 < mapped < n, (row["name"], mapped, n)
     assert trace.count("Final shift") == n and trace.count("SDX\t") > 0
+    if "score" in row["tags"]:
+        assert_score_row_conditions(row, lines)
     for group in row["sensitive"]:  # every option the row names changes what the reference itself prints
         assert reference_run(row, tmp, without=group) != (sam, trace), "%s: the reference prints the same without %s" % (row["name"], group)
     if row["build"] == "scalar":

@@ -20,11 +20,14 @@ OPTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "opts"
 # keys above mid_occ and above max_max_occ = 4095, microsatellites) and reads drawn across and inside the repeats: the drop branch of
 # mm_seed_mz_flt, mm_seed_select's rescue heap, the max_max_occ cut, multi-occurrence position lists in the index and strands with
 # far more than 4096 hits all fire (oracle/make_golden.py prints the counts; tests/test_map_host.py asserts them)
+# "hifi_n" / "sr_n": the first 12 reads of hifi.fq / 200 reads of sr.fq with 1 to 3 bases each replaced by N (tools/synth_n.py): Ns inside
+# alignments, which the DP scores as -e2 -- the option grid maps them at e2 = 2
 # "sr_rep_f60": the sr_rep reads with -f 60 (mid_occ = 60): at the preset's mid_occ = 1000 the query-side filter cannot fire in the
 # ShortReads variant, whose mm_sketch3 stops at 800 minimizers (SR/map.c:621-622)
 SETS = {"hifi_rep": (REP, "hifi_rep", "hifi"), "ont_rep": (REP, "ont_rep", "ont"), "sr_rep": (REP, "sr_rep", "sr"), "sr_rep_f60": (REP, "sr_rep_f60", "sr"),
         "hifi_sv": (LR, "hifi_sv", "hifi"), "ont_sv": (LR, "ont_sv", "ont"), "hifi_edge": (LR, "edge_hifi", "hifi"), "ont_edge": (LR, "edge_ont", "ont"), "sr_edge": (SR, "edge", "sr"),
-        "hifi_w1": (LR, "w1", "hifi"), "hifi": (LR, "hifi", "hifi"), "ont": (LR, "ont", "ont"), "sr": (SR, "sr", "sr"), "sr_var": (SR, "var", "sr")}
+        "hifi_w1": (LR, "w1", "hifi"), "hifi": (LR, "hifi", "hifi"), "ont": (LR, "ont", "ont"), "sr": (SR, "sr", "sr"), "sr_var": (SR, "var", "sr"),
+        "hifi_n": (LR, "hifi_n", "hifi"), "sr_n": (SR, "sr_n", "sr")}
 # options of var.cmd that differ from the sr preset (README command): -N 5 -n 0.3,0.1 -s 40 --AF_max_loc 20
 OVERRIDES = {"hifi_w1": dict(k=15, w=1), "ont_sv": dict(min_dp_max=4000),  # ont_sv.cmd: -s 4000 (reads of ~14 kbp)
              "ont_rep": dict(min_dp_max=4000), "sr_rep_f60": dict(mid_occ=60),
@@ -128,7 +131,7 @@ def reads_of(kind):
 
 def cmd_of(kind):
     d, stem, _ = SETS[kind]
-    name = {"hifi_edge": "hifi", "ont_edge": "ont", "sr_edge": "sr"}.get(kind, stem)
+    name = {"hifi_edge": "hifi", "ont_edge": "ont", "sr_edge": "sr", "hifi_n": "hifi", "sr_n": "sr"}.get(kind, stem)
     return open(os.path.join(d, name + ".cmd")).read().split()
 
 
@@ -211,6 +214,78 @@ def mapped_share(sam_lines):
         if f[2] != "*":
             mapped.add(f[0])
     return len(mapped), len(names)
+
+
+# ---- the scoring rows of the grid (tag "score"): what each must hold to test its point --------------------------------------------
+# tags of a "score" row: "wave" / "generic" (whether the register-resident DP kernels take the row's scoring: gdo.wave_scoring_ok -- a
+# refused scoring sends every box of the mapping batch to the generic kernel), "single" (q == q2, e == e2), "prefilter" (short reads at
+# a scoring whose widened pre-filter answers m <= 1 mismatches instead of the presets' m <= 3), "n_e2" (Ns inside alignments at e2 = 2)
+def grid_scoring(row):
+    """(a, b, q, e, q2, e2) a row maps with: its preset's scoring with the row's overrides"""
+    import gdo
+    s = dict(zip(("a", "b", "q", "e", "q2", "e2"), gdo.PRESETS[SETS[row["kind"]][2]]))
+    s.update({k: v for k, v in row["overrides"].items() if k in s})
+    return tuple(s[k] for k in ("a", "b", "q", "e", "q2", "e2"))
+
+
+def grid_wave_scoring_ok(row):
+    import gdo
+    return gdo.wave_scoring_ok(*grid_scoring(row))
+
+
+def prefilter_split(row, sam_lines):
+    """the mapped records of a SAM body whose CIGAR is one M run and whose NM:i: is m > 0, counted by the side of the widened pre-filter's
+    bound they fall on: (m (a + b) <= a + 2 (q + e): answered without the DP, above it: through the DP)"""
+    import re
+    a, b, q, e, _, _ = grid_scoring(row)
+    lo = hi = 0
+    for l in sam_lines:
+        f = l.split("\t")
+        nm = [int(x[5:]) for x in f[11:] if x.startswith("NM:i:")]
+        if f[2] == "*" or not re.fullmatch(r"\d+M", f[5]) or not nm or nm[0] <= 0:
+            continue
+        if nm[0] * (a + b) <= a + 2 * (q + e):
+            lo += 1
+        else:
+            hi += 1
+    return lo, hi
+
+
+def records_with_n_inside(row, sam_lines):
+    """mapped records with at least one non-ACGT base of SEQ (the row's reads: the goldens star SEQ) inside the aligned query span, as
+    read from the CIGAR's clips"""
+    import re
+    reads = {r[0]: r[1] for r in grid_reads(row)}
+    comp = str.maketrans("ACGTacgt", "TGCAtgca")
+    n = 0
+    for l in sam_lines:
+        f = l.split("\t")
+        if f[2] == "*":
+            continue
+        seq = reads[f[0]]
+        if int(f[1]) & 16:
+            seq = seq.translate(comp)[::-1]
+        left, right = re.match(r"(\d+)[SH]", f[5]), re.search(r"(\d+)[SH]$", f[5])
+        span = seq[int(left.group(1)) if left else 0:len(seq) - (int(right.group(1)) if right else 0)]
+        n += re.search(r"[^ACGTacgt]", span) is not None
+    return n
+
+
+def assert_score_row_conditions(row, sam_lines):
+    """what a "score" row of the grid must hold, from the reference's own SAM: its wave / generic tag is what gdo.wave_scoring_ok says of
+    its scoring; a "prefilter" row has at least 10 single-M records on either side of the pre-filter's bound; an "n_e2" row maps with
+    e2 = 2 and has at least 3 records with an N inside the alignment"""
+    tags = row["tags"]
+    assert ("wave" in tags) != ("generic" in tags) and ("wave" in tags) == grid_wave_scoring_ok(row), row["name"]
+    a, b, q, e, q2, e2 = grid_scoring(row)
+    assert ("single" in tags) == (q == q2 and e == e2), row["name"]
+    if "prefilter" in tags:
+        lo, hi = prefilter_split(row, sam_lines)
+        assert row["variant"] == "sr" and a + b > (a + 2 * (q + e)) // 2, row["name"]  # m = 2 is past the bound already
+        assert lo >= 10 and hi >= 10, (row["name"], lo, hi)
+    if "n_e2" in tags:
+        n = records_with_n_inside(row, sam_lines)
+        assert e2 == 2 and n >= 3, (row["name"], n)
 
 
 # ---- B4: the output of gdiet_hip_seed_batch against a --print-seeds trace ---------------------------------------------------------

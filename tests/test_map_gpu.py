@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("kind", ["hifi", "ont", "sr", "sr_var", "hifi_w1", "hifi_edge", "ont_edge", "sr_edge", "hifi_sv", "ont_sv",
-                                  "hifi_rep", "ont_rep", "sr_rep", "sr_rep_f60"])
+                                  "hifi_rep", "ont_rep", "sr_rep", "sr_rep_f60", "hifi_n", "sr_n"])
 def test_map_batch_matches_golden_sam(gpu_ctx, pkg, kind):
     base, stem, preset = SETS[kind]
     names, seqs = read_fasta(os.path.join(base, "ref.fa.gz"))
@@ -257,9 +257,18 @@ def host_emulator(tmp_path_factory):
     return exe, str(d)
 
 
-@pytest.mark.parametrize("kind,n,length", [("hifi", 160, 3000), ("ont", 20, 24000), ("sr", 4000, 150)])
-def test_fresh_reads_match_host_emulator(gpu_ctx, pkg, host_emulator, kind, n, length):
-    """a few thousand alignments per preset on reads drawn at test time (fixed seed): GPU path == host emulator, byte for byte"""
+# (kind, reads, length, entry of gdo.SCORINGS or None for the preset's, do the wave kernels take it)
+FRESH = [("hifi", 160, 3000, None, True), ("ont", 20, 24000, None, True), ("sr", 4000, 150, None, True),
+         ("hifi", 40, 3000, "single_affine", True), ("hifi", 40, 3000, "bound120_first", False),
+         ("sr", 1000, 150, "a16", True), ("sr", 1000, 150, "k3_2_16_24_1", False)]
+
+
+@pytest.mark.parametrize("kind,n,length,scoring,wave", FRESH, ids=["-".join(str(x) for x in f[:3 if f[3] is None else 4]) for f in FRESH])
+def test_fresh_reads_match_host_emulator(gpu_ctx, pkg, host_emulator, kind, n, length, scoring, wave):
+    """a few thousand alignments per preset on reads drawn at test time (fixed seed): GPU path == host emulator, byte for byte -- at the
+    preset's scoring, and for HiFi and short reads at one scoring of the oracle's table the wave kernels take and one they refuse (both
+    sides get it from the same tuple: -A -B -O -E there, Mapper overrides here): kernel dispatch, pre-filter bound and post kernels on
+    data no fixture was chosen for"""
     import gzip
     import subprocess
     import numpy as np
@@ -291,11 +300,21 @@ def test_fresh_reads_match_host_emulator(gpu_ctx, pkg, host_emulator, kind, n, l
     with open(fq, "w") as f:
         for nm, q, ql in reads:
             f.write("@%s\n%s\n+\n%s\n" % (nm, q, ql))
-    want = subprocess.run([exe] + cmd_of(kind) + [ref_fa, fq], capture_output=True, text=True, check=True).stdout
-    m = pkg.Mapper(gpu_ctx, names, seqs, preset=preset, **OVERRIDES.get(kind, {}))
+    extra, ov = [], dict(OVERRIDES.get(kind, {}))
+    if scoring is not None:
+        import gdo
+        a, b, q, e, q2, e2, ambi = gdo.SCORINGS[scoring]
+        assert ambi == 0 and gdo.wave_scoring_ok(a, b, q, e, q2, e2) == wave
+        assert q > 0 and e > 0 and ((q == q2 and e == e2) or (e > e2 and q + e < q2 + e2)) and q + e + q2 + e2 <= 127  # mm_check_opt takes it
+        extra = ["-A", str(a), "-B", str(b), "-O", "%d,%d" % (q, q2), "-E", "%d,%d" % (e, e2)]
+        ov.update(a=a, b=b, q=q, e=e, q2=q2, e2=e2)
+    want = subprocess.run([exe] + cmd_of(kind) + extra + [ref_fa, fq], capture_output=True, text=True, check=True).stdout
+    m = pkg.Mapper(gpu_ctx, names, seqs, preset=preset, **ov)
     try:
         res = m.map([r[1] for r in reads])
+        mask = gpu_ctx.last_kernel_mask()
         assert m.sam_batch(res, reads) == want
+        assert mask == 2 if not wave else mask & (1 | 4 | 8 | 16)
         mapped = sum(1 for i in range(n) if res.n_regs[i] > 0)
         assert mapped > 0.5 * n
     finally:

@@ -10,7 +10,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-from fixture_io import (LR, PAF_KINDS, REP, SD_DIGESTED, SETS, SR, TRACE_PREFIXES, cmd_of, digest_sd, golden_paf, golden_sam, grid_cmd, grid_golden_sam, grid_ids,
+from fixture_io import (LR, PAF_KINDS, REP, SD_DIGESTED, SETS, SR, TRACE_PREFIXES, assert_score_row_conditions, cmd_of, digest_sd, golden_paf, golden_sam, grid_cmd, grid_golden_sam, grid_ids,
                         grid_reads, grid_row, grid_rows, grid_trace, mapped_share, paf_cmd_of, reads_of, star_seq_qual, trace_of)
 
 
@@ -48,7 +48,7 @@ def _rep_run(host_driver, kind, tmp_path):
     return _rep_cache[kind]
 
 
-@pytest.mark.parametrize("kind", ["hifi", "ont", "sr", "sr_var", "hifi_w1", "hifi_edge", "ont_edge", "sr_edge", "hifi_sv", "ont_sv", "hifi_rep", "ont_rep", "sr_rep", "sr_rep_f60"])
+@pytest.mark.parametrize("kind", ["hifi", "ont", "sr", "sr_var", "hifi_w1", "hifi_edge", "ont_edge", "sr_edge", "hifi_sv", "ont_sv", "hifi_rep", "ont_rep", "sr_rep", "sr_rep_f60", "hifi_n", "sr_n"])
 def test_host_path_matches_golden_sam(host_driver, kind, tmp_path):
     exe, d = host_driver
     base = SETS[kind][0]
@@ -327,13 +327,15 @@ def test_grid_options_are_not_inert(host_driver, tmp_path, name):
 def test_grid_rows_cannot_pass_vacuously():
     """what oracle/make_grid_golden.py asserts when it writes the fixtures, again on the committed files: the reference maps at least
     min_mapped of every row's reads (0.9 for LongReads rows; 0.4 where the row is built to starve seeds or keeps one strand of a
-    two-strand read set; 0.5 for ShortReads rows on var.fq), strand rows hold mapped and unmapped reads, the *_sv rows reach the
-    second voting round's concatenations, every read has a trace"""
+    two-strand read set; 0.5 for ShortReads rows on var.fq; 0.25 for the scoring rows, whose scorings the reference itself maps fewer reads
+    at), strand rows hold mapped and unmapped reads, the *_sv rows reach the second voting round's concatenations, every read has a trace,
+    and a scoring row holds the records it was chosen for (fixture_io.assert_score_row_conditions: both sides of the widened pre-filter's
+    bound, Ns inside alignments at e2 = 2, a wave / generic tag that gdo.wave_scoring_ok confirms)"""
     for row in grid_rows():
         sam, trace = grid_golden_sam(row), grid_trace(row)
         mapped, n = mapped_share(sam)
         assert n == row["n_reads"] and mapped >= row["min_mapped"] * n, (row["name"], mapped, n)
-        floor = 0.25 if row["kind"] in ("sr", "sr_rep") else 0.5 if row["variant"] == "sr" else 0.4 if ("strand" in row["tags"] or row["overrides"].get("k") == 28) else 0.9
+        floor = 0.25 if row["kind"] in ("sr", "sr_rep") or "score" in row["tags"] else 0.5 if row["variant"] == "sr" else 0.4 if ("strand" in row["tags"] or row["overrides"].get("k") == 28) else 0.9
         assert row["min_mapped"] >= floor, row["name"]
         if "strand" in row["tags"]:
             assert 0 < mapped < n, row["name"]
@@ -341,6 +343,8 @@ def test_grid_rows_cannot_pass_vacuously():
             assert flags == ({0} if "--for-only" in row["extra"] else {16}), row["name"]
         if "sv" in row["tags"]:
             assert sum(1 for l in trace if l.startswith("CONQ")) >= 5, row["name"]
+        if "score" in row["tags"]:
+            assert_score_row_conditions(row, sam)
         if "vote_cap" in row["tags"]:  # reads of the repeat-rich reference with more candidates than any preset's vt_nb_loc + 2 = 7 keeps
             per_read = [len(r["VT"]) for r in _split_trace(trace)]
             assert sum(1 for c in per_read if c > 7) >= 10, (row["name"], per_read)
@@ -372,6 +376,26 @@ def test_grid_covers_what_it_was_built_for():
         assert [o["w"] for o in ov if o["variant"] == var and o["build"] == "scalar"] == [4]
     assert all(not (2 <= o.get("w", 10) <= 7) for o in ov if o["build"] == "avx")
     assert sum(1 for o in ov if "q2" in o) >= 2 and len(grid_rows("mmi")) == 3
+    # the scoring rows: every kind of scoring the DP dispatch, the pre-filter and the post kernels treat differently, per variant
+    from fixture_io import grid_scoring, grid_wave_scoring_ok
+    import gdo
+    score = grid_rows("score")
+    assert all("post" in r["tags"] and ("wave" in r["tags"]) == grid_wave_scoring_ok(r) != ("generic" in r["tags"]) for r in score)
+    sc_of = {r["name"]: grid_scoring(r) + (0,) for r in score}
+    lr_sc = {n: v for n, v in sc_of.items() if grid_row(n)["variant"] == "lr"}
+    sr_sc = {n: v for n, v in sc_of.items() if grid_row(n)["variant"] == "sr"}
+    table = gdo.SCORINGS
+    for want in ("bound120_last", "bound120_first", "k3_2_16_24_1"):  # long reads at the table's own entries
+        assert table[want] in lr_sc.values(), want
+    assert gdo.wave_scoring_ok(*table["bound120_last"]) and not gdo.wave_scoring_ok(*table["bound120_first"]) and not gdo.wave_scoring_ok(*table["k3_2_16_24_1"])
+    assert any(v[:6] == (1, 4, 6, 2, 6, 2) for v in lr_sc.values())  # single affine at the HiFi preset's a, b
+    assert any(v == table["a16"] and grid_row(n)["kind"] == "ont_sv" for n, v in lr_sc.items())
+    assert any(v[5] == 2 and v[3] > 2 for v in lr_sc.values()) and any("n_e2" in grid_row(n)["tags"] for n in lr_sc)
+    for want in ("a16", "skey_corner", "single_affine"):  # short reads
+        assert table[want] in sr_sc.values(), want
+    assert all("prefilter" in grid_row(n)["tags"] for n, v in sr_sc.items() if v in (table["a16"], table["skey_corner"]))
+    assert any(not gdo.wave_scoring_ok(*v) and v[4] == 48 for v in sr_sc.values())
+    assert any(v[5] == 2 and grid_row(n)["kind"] == "sr_edge" for n, v in sr_sc.items()) and any("n_e2" in grid_row(n)["tags"] for n in sr_sc)
     for r in rows:  # every option of a row is one of its sensitive groups
         assert " ".join(r["sensitive"]).split() == r["extra"].split(), r["name"]
     for r in rows:  # the two forms of a row agree on the options both can be read from
