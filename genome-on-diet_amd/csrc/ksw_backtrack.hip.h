@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ksw_common.h"
+#include "ksw_walk_core.h"
 
 // position of cell (r, i) inside a backtrace row, for the two layouts the DP kernels write
 //   generic: the reference's own layout, column i - off[r] with off[r] = st0(r)/16*16 (SR/ksw2.h:142)
@@ -21,13 +22,6 @@ __device__ __forceinline__ size_t gd_bt_index(const KswTask &T, int r, int i, in
 	// alignment at once: no ring); two-blocks-per-lane kernel: the reference's window-relative block position
 	const int bpos = T.kind == GD_KIND_WAVE128 ? (i >> 4) - (off >> 4) : (lanes & (lanes - 1)) ? (i >> 4) : ((i >> 4) & (lanes - 1));
 	return (size_t)r * T.row_bytes + (size_t)(bpos << 4) + (g << 2) + h;
-}
-
-// byte of the register-resident kernels -> the reference's backtrace byte
-static inline __host__ __device__ uint32_t gd_bt_decode(uint32_t b)
-{
-	const uint32_t nb = ~b;
-	return (4u - (b & 7u)) | ((nb >> 4) & 0x08u) | ((nb >> 2) & 0x10u) | (nb & 0x20u) | ((nb << 2) & 0x40u);
 }
 
 // Pre-filter (exact_match_sse, LR/map.c:1748-1806), widened by what can be PROVEN about the DP without running it.  For an N-free pair
@@ -207,11 +201,39 @@ __global__ __launch_bounds__(64) void ksw_backtrack_kernel(const KswTask *__rest
 }
 
 // K2 for long alignments: one WAVEFRONT per walk.  All 64 lanes fetch the next 64 cells of the current diagonal at once (one
-// round trip instead of one per cell), then the walk itself -- wave-uniform by construction -- runs as scalar code that pulls the
-// prefetched bytes out of the vector registers with v_readlane.  Same visited cells, same state machine as ksw_backtrack
-// (SR/ksw2.h:131-163); only the latency is hidden differently than in the one-walk-per-thread kernel above, which stays the
-// better choice for short reads (hundreds of thousands of 300-step walks).
-// the walk of one alignment by one whole wavefront (all 64 lanes must call it together); writes the CIGAR and n_cigar[tid]
+// round trip instead of one per cell) and decode their own byte; ten ballots turn the window into the wave-uniform masks of
+// gd_walk_window (ksw_walk_core.h), which consumes it as scalar code: a run of diagonal cells in one step, any other cell by the
+// reference's state machine.  Same visited cells, same ops as ksw_backtrack (SR/ksw2.h:131-163); the one-walk-per-thread kernel
+// above stays the better choice for short reads (hundreds of thousands of 300-step walks).
+// One fetched window: `inside` = this lane's cell (i0 - lane, j0 - lane) exists and belongs to the rows at hand, fs its force_state,
+// tmp the reference's byte (0 where the state is forced or the cell is not inside).  All 64 lanes must call it together.
+__device__ __forceinline__ void gd_walk_consume(GdWalk &W, uint32_t *cg, int cap, int lane, bool inside, int fs, uint32_t tmp)
+{
+	GdWalkMasks M;
+	M.valid = __builtin_amdgcn_ballot_w64(inside);
+	M.f1 = __builtin_amdgcn_ballot_w64(fs == 1), M.f2 = __builtin_amdgcn_ballot_w64(fs == 2);
+	M.d0 = __builtin_amdgcn_ballot_w64((tmp & 1u) != 0), M.d1 = __builtin_amdgcn_ballot_w64((tmp & 2u) != 0), M.d2 = __builtin_amdgcn_ballot_w64((tmp & 4u) != 0);
+	M.c1 = __builtin_amdgcn_ballot_w64((tmp & 0x08u) != 0), M.c2 = __builtin_amdgcn_ballot_w64((tmp & 0x10u) != 0);
+	M.c3 = __builtin_amdgcn_ballot_w64((tmp & 0x20u) != 0), M.c4 = __builtin_amdgcn_ballot_w64((tmp & 0x40u) != 0);
+	gd_walk_window(W, cg, cap, lane == 0, M);
+}
+// the end of a walk: the run along the matrix's edge, n_cigar[tid], and the ops into forward order
+__device__ __forceinline__ void gd_walk_finish(GdWalk &W, const KswTask &T, int tid, int32_t *__restrict__ n_cigar, uint32_t *__restrict__ cigar, int lane)
+{
+	uint32_t *cg = cigar + T.cig_off;
+	const int cap = __builtin_amdgcn_readfirstlane(T.cig_cap);
+	const int nc = gd_walk_tail(W, cg, cap, lane == 0);
+	if (lane == 0) n_cigar[tid] = nc;
+	if (nc <= cap) { // reverse in place, 64 swaps at a time (the stores above are this wavefront's own: program order suffices)
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); // lane 0 wrote the ops, all lanes read them
+		for (int k = lane; k < nc >> 1; k += 64) {
+			const uint32_t t0 = cg[k];
+			cg[k] = cg[nc - 1 - k], cg[nc - 1 - k] = t0;
+		}
+	}
+}
+// the walk of one alignment by one whole wavefront (all 64 lanes must call it together) over a whole backtrace in the layout of its
+// kind (gd_bt_index); writes the CIGAR and n_cigar[tid]
 __device__ __forceinline__ void gd_bt_wave_walk(const KswTask &T, int tid, const uint8_t *__restrict__ bt, int32_t *__restrict__ n_cigar,
                                                 uint32_t *__restrict__ cigar, int lane)
 {
@@ -222,73 +244,33 @@ __device__ __forceinline__ void gd_bt_wave_walk(const KswTask &T, int tid, const
 	const uint8_t *p = bt + T.bt_off;
 	uint32_t *cg = cigar + T.cig_off;
 	const int cap = __builtin_amdgcn_readfirstlane(T.cig_cap);
-	int nc = 0, i = tlen - 1, j = qlen - 1, state = 0, have = 0;
-	uint32_t last = 0;
-#define GD_PUSHW(op_, len_)                                                      \
-	do {                                                                         \
-		if (have && (last & 0xf) == (uint32_t)(op_)) last += (uint32_t)(len_) << 4; \
-		else {                                                                   \
-			if (have) { if (nc < cap && lane == 0) cg[nc] = last; ++nc; }        \
-			last = (uint32_t)(len_) << 4 | (uint32_t)(op_), have = 1;            \
-		}                                                                        \
-	} while (0)
-	while (i >= 0 && j >= 0) {
-		const int i0 = i, j0 = j;
-		const int ik = i0 - lane, jk = j0 - lane;
+	GdWalk W;
+	gd_walk_init(W, qlen, tlen);
+	while (W.i >= 0 && W.j >= 0) {
+		const int ik = W.i - lane, jk = W.j - lane;
+		const bool inside = ik >= 0 && jk >= 0;
 		int fs = -1;
-		uint32_t pf = 0;
-		if (ik >= 0 && jk >= 0) {
+		uint32_t tmp = 0;
+		if (inside) {
 			const int r = ik + jk;
 			int st0, en0;
 			gd_band(r, qlen, tlen, w, st0, en0);
 			const int off = st0 & ~15, off_end = en0 | 15;
 			if (ik < off) fs = 2;
 			if (ik > off_end) fs = 1;
-			if (fs < 0) pf = p[gd_bt_index(T, r, ik, off)];
-		}
-		for (int k = 0; k < 64; ++k) {
-			if (i != i0 - k || j != j0 - k || i < 0 || j < 0) break; // left the fetched diagonal (or finished)
-			const int force_state = __builtin_amdgcn_readlane(fs, k);
-			uint32_t tmp = (uint32_t)__builtin_amdgcn_readlane((int)pf, k);
-			if (force_state < 0 && kind != GD_KIND_GENERIC) { // wave-kernel byte -> the reference's byte (see ksw_backtrack_kernel)
-				tmp = gd_bt_decode(tmp);
+			if (fs < 0) {
+				tmp = p[gd_bt_index(T, r, ik, off)];
+				if (kind != GD_KIND_GENERIC) tmp = gd_bt_decode(tmp); // wave-kernel byte -> the reference's byte
 			}
-			if (state == 0) state = tmp & 7;
-			else if (!(tmp >> (state + 2) & 1)) state = 0;
-			if (state == 0) state = tmp & 7;
-			if (force_state >= 0) state = force_state;
-			if (state == 0) { GD_PUSHW(0, 1); --i, --j; }
-			else if (state == 1 || state == 3) { GD_PUSHW(2, 1); --i; }
-			else { GD_PUSHW(1, 1); --j; }
 		}
+		gd_walk_consume(W, cg, cap, lane, inside, fs, tmp);
 	}
-	if (i >= 0) GD_PUSHW(2, i + 1);
-	if (j >= 0) GD_PUSHW(1, j + 1);
-	if (have) { if (nc < cap && lane == 0) cg[nc] = last; ++nc; }
-#undef GD_PUSHW
-	if (lane == 0) n_cigar[tid] = nc;
-	if (nc <= cap) { // reverse in place, 64 swaps at a time (the stores above are this wavefront's own: program order suffices)
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); // lane 0 wrote the ops, all lanes read them
-		for (int k = lane; k < nc >> 1; k += 64) {
-			const uint32_t t0 = cg[k];
-			cg[k] = cg[nc - 1 - k], cg[nc - 1 - k] = t0;
-		}
-	}
+	gd_walk_finish(W, T, tid, n_cigar, cigar, lane);
 }
 
-// The same walk in resumable form, for a backtrace that exists one chunk of anti-diagonals at a time (ksw_extd2_wave128c_kernel):
-// gd_walk_rows consumes cells while their anti-diagonal is >= r0 (rows of `chunk`, row r at (r - r0) * row_bytes, the layout of
-// the two-blocks-per-lane kernel or of the cone) and returns with its state, to be called again on the chunk below.
-struct GdWalk { int i, j, state, have, nc; uint32_t last; };
-__device__ __forceinline__ void gd_walk_init(GdWalk &W, int qlen, int tlen) { W.i = tlen - 1, W.j = qlen - 1, W.state = 0, W.have = 0, W.nc = 0, W.last = 0; }
-__device__ __forceinline__ void gd_walk_push(GdWalk &W, uint32_t *cg, int cap, int lane, uint32_t op, uint32_t len)
-{
-	if (W.have && (W.last & 0xf) == op) W.last += len << 4;
-	else {
-		if (W.have) { if (W.nc < cap && lane == 0) cg[W.nc] = W.last; ++W.nc; }
-		W.last = len << 4 | op, W.have = 1;
-	}
-}
+// The same walk in resumable form, for a backtrace that exists one chunk of anti-diagonals at a time (ksw_extd2_wave128c_kernel) or in
+// one of the row formats of the 64-lane kernel's narrow rungs: gd_walk_rows consumes cells while their anti-diagonal is >= r0 (rows of
+// `chunk`, row r at (r - r0) * row_bytes) and returns with its state, to be called again on the chunk below.
 // cone_stride > 0: rows of `chunk` hold the 64 blocks [cone_b0, cone_b0 + 63] (gdw_cone_row) instead of the blocks of the band
 // half_ring (with cone_half): the 64 half blocks of a row are a ring, half block h at position h mod 64 (gdw_narrow_rows)
 // quarter_ring: rows of 64 quarter blocks as a ring, quarter block q at position q mod 64, byte c of a quarter = cell c (gdw_quarter_rows):
@@ -301,11 +283,11 @@ __device__ __forceinline__ void gd_walk_rows(GdWalk &W, const KswTask &T, const 
 	const int cap = __builtin_amdgcn_readfirstlane(T.cig_cap);
 	const size_t row_bytes = cone_stride > 0 ? (size_t)cone_stride : (size_t)__builtin_amdgcn_readfirstlane(T.row_bytes);
 	while (W.i >= 0 && W.j >= 0 && W.i + W.j >= r0) {
-		const int i0 = W.i, j0 = W.j;
-		const int ik = i0 - lane, jk = j0 - lane;
+		const int ik = W.i - lane, jk = W.j - lane;
+		const bool inside = ik >= 0 && jk >= 0 && ik + jk >= r0;
 		int fs = -1;
-		uint32_t pf = 0;
-		if (ik >= 0 && jk >= 0 && ik + jk >= r0) {
+		uint32_t tmp = 0;
+		if (inside) {
 			const int r = ik + jk;
 			int st0, en0;
 			gd_band(r, qlen, tlen, w, st0, en0);
@@ -313,47 +295,20 @@ __device__ __forceinline__ void gd_walk_rows(GdWalk &W, const KswTask &T, const 
 			if (ik < off) fs = 2;
 			if (ik > off_end) fs = 1;
 			if (fs < 0) {
-				if (quarter_ring) pf = chunk[(size_t)(r - r0) * row_bytes + (size_t)(ik & 255)];
+				if (quarter_ring) tmp = chunk[(size_t)(r - r0) * row_bytes + (size_t)(ik & 255)];
 				else if (cone_half) { // rows of 64 half blocks (gdw_cone_row_half): cone_b0 is a half-block index, byte 4g + h = cell 2g + (h & 1) + 4 (h >> 1)
 					const int c = ik & 7, g = (c & 3) >> 1, h = (c & 1) | ((c >> 2) << 1);
 					const int hpos = half_ring ? ((ik >> 3) & 63) : (ik >> 3) - cone_b0;
-					pf = chunk[(size_t)(r - r0) * row_bytes + (size_t)(hpos << 3) + (g << 2) + h];
+					tmp = chunk[(size_t)(r - r0) * row_bytes + (size_t)(hpos << 3) + (g << 2) + h];
 				} else {
 					const int c = ik & 15, g = (c & 7) >> 1, h = (c & 1) | ((c >> 3) << 1);
 					const int b = (ik >> 4) - (cone_stride > 0 ? cone_b0 : off >> 4);
-					pf = chunk[(size_t)(r - r0) * row_bytes + (size_t)(b << 4) + (g << 2) + h];
+					tmp = chunk[(size_t)(r - r0) * row_bytes + (size_t)(b << 4) + (g << 2) + h];
 				}
+				tmp = gd_bt_decode(tmp);
 			}
 		}
-		for (int k = 0; k < 64; ++k) {
-			if (W.i != i0 - k || W.j != j0 - k || W.i < 0 || W.j < 0 || W.i + W.j < r0) break; // left the fetched diagonal, the chunk, or finished
-			const int force_state = __builtin_amdgcn_readlane(fs, k);
-			uint32_t tmp = (uint32_t)__builtin_amdgcn_readlane((int)pf, k);
-			if (force_state < 0) tmp = gd_bt_decode(tmp);
-			if (W.state == 0) W.state = tmp & 7;
-			else if (!(tmp >> (W.state + 2) & 1)) W.state = 0;
-			if (W.state == 0) W.state = tmp & 7;
-			if (force_state >= 0) W.state = force_state;
-			if (W.state == 0) { gd_walk_push(W, cg, cap, lane, 0, 1); --W.i, --W.j; }
-			else if (W.state == 1 || W.state == 3) { gd_walk_push(W, cg, cap, lane, 2, 1); --W.i; }
-			else { gd_walk_push(W, cg, cap, lane, 1, 1); --W.j; }
-		}
-	}
-}
-__device__ __forceinline__ void gd_walk_finish(GdWalk &W, const KswTask &T, int tid, int32_t *__restrict__ n_cigar, uint32_t *__restrict__ cigar, int lane)
-{
-	uint32_t *cg = cigar + T.cig_off;
-	const int cap = __builtin_amdgcn_readfirstlane(T.cig_cap);
-	if (W.i >= 0) gd_walk_push(W, cg, cap, lane, 2, (uint32_t)(W.i + 1));
-	if (W.j >= 0) gd_walk_push(W, cg, cap, lane, 1, (uint32_t)(W.j + 1));
-	if (W.have) { if (W.nc < cap && lane == 0) cg[W.nc] = W.last; ++W.nc; }
-	if (lane == 0) n_cigar[tid] = W.nc;
-	if (W.nc <= cap) {
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-		for (int k = lane; k < W.nc >> 1; k += 64) {
-			const uint32_t t0 = cg[k];
-			cg[k] = cg[W.nc - 1 - k], cg[W.nc - 1 - k] = t0;
-		}
+		gd_walk_consume(W, cg, cap, lane, inside, fs, tmp);
 	}
 }
 
