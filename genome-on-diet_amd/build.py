@@ -25,7 +25,10 @@ BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           "_Z19fastx_record_kernel": dict(vgprs=32, scratch=0),
           "_Z19fastx_encode_kernel": dict(vgprs=32, scratch=0),
           # BGZF members inflated beside the DP of the batches in flight (bgzf_inflate.hip.h): nothing of the symbol loop in scratch memory
-          "_Z19bgzf_inflate_kernel": dict(vgprs=64, scratch=0)}
+          "_Z19bgzf_inflate_kernel": dict(vgprs=64, scratch=0),
+          # BGZF members written on the device (bgzf_deflate.hip.h): its local memory bounds it to one wavefront per SIMD at most, so
+          # registers up to 128 cost no occupancy; nothing in scratch memory
+          "_Z19bgzf_deflate_kernel": dict(vgprs=128, scratch=0)}
 
 
 def _newest_source():

@@ -11,6 +11,9 @@
 #include <hipcub/hipcub.hpp>
 #include "fastx_dev.hip.h"
 #include "bgzf_inflate.hip.h"
+#include "bgzf_deflate.hip.h"
+#include "bgzf_out.h"
+#include <fcntl.h>
 
 static const char *gd_fx_err_of(const gdiet_ctx *ctx) { return ctx && gd_fx_failed_on == ctx ? ctx->fx_err.c_str() : nullptr; }
 static int gd_fx_fail(gdiet_ctx *ctx, int rc, const std::string &what) // (the caller holds fx_mu)
@@ -103,6 +106,84 @@ static int gd_bz_inflate_device(gdiet_ctx *ctx, const unsigned char *raw, size_t
 			return -2;
 		}
 	}
+	return 0;
+}
+
+// BGZF members written on the device (bgzf_deflate.hip.h): in[0, in_len) up, one wavefront per member of 65280 input bytes into a slot
+// of 65536 bytes, the members' lengths down, their prefix sum (on the host) up, the pack kernel, and one copy brings the file bytes
+// out[0, *out_len) back.  A stream and a lock of its own (gdiet_ctx::bzd_stream, bzd_mu): a writer thread compresses the text of batch i
+// while batch i + 1 maps and the reader inflates.  Stream-ordered allocations.  The stream is synchronised twice: once for the 8 bytes
+// per member that the host's prefix sum needs (it also sizes the copy down), once before the host touches the bytes.  out_cap must be
+// at least 65536 bytes per member.  Returns 0 or -1 (the device failed) with the reason in why.
+static int gd_bz_deflate_device(gdiet_ctx *ctx, const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why)
+{
+	*out_len = 0;
+	const size_t n = (in_len + GDD_MAX_IN - 1) / GDD_MAX_IN;
+	if (n == 0) return 0;
+	if (n > ((size_t)1 << 30) || out_cap / GDD_SLOT < n) { why = "device deflate: the output holds fewer than 65536 bytes per member"; return -1; }
+	std::lock_guard<std::mutex> lk(ctx->bzd_mu);
+	(void)hipSetDevice(ctx->device);
+	hipError_t e = hipSuccess;
+	if (!ctx->bzd_stream && (e = hipStreamCreateWithFlags(&ctx->bzd_stream, hipStreamNonBlocking)) != hipSuccess) {
+		why = std::string("device deflate: stream: ") + hipGetErrorString(e);
+		return -1;
+	}
+	hipStream_t s = ctx->bzd_stream;
+	for (hipEvent_t &ev : ctx->bzd_ev)
+		if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) { ev = nullptr; why = std::string("device deflate: event: ") + hipGetErrorString(e); return -1; }
+	uint8_t *d_in = nullptr, *d_slots = nullptr, *d_out = nullptr;
+	GddResult *d_res = nullptr;
+	uint64_t *d_off = nullptr; // off[n], then len[n] as 32-bit words
+	auto fail = [&](hipError_t err, const char *what) {
+		(void)hipStreamSynchronize(s);
+		if (d_in) (void)hipFreeAsync(d_in, s);
+		if (d_slots) (void)hipFreeAsync(d_slots, s);
+		if (d_out) (void)hipFreeAsync(d_out, s);
+		if (d_res) (void)hipFreeAsync(d_res, s);
+		if (d_off) (void)hipFreeAsync(d_off, s);
+		why = std::string("device deflate: ") + what + ": " + hipGetErrorString(err);
+		return -1;
+	};
+	std::vector<GddResult> res(n);
+	if ((e = hipMallocAsync((void **)&d_in, in_len + 16, s)) != hipSuccess) return fail(e, "input");
+	if ((e = hipMallocAsync((void **)&d_slots, n * GDD_SLOT, s)) != hipSuccess) return fail(e, "slots");
+	if ((e = hipMallocAsync((void **)&d_res, sizeof(GddResult) * n, s)) != hipSuccess) return fail(e, "results");
+	(void)hipEventRecord(ctx->bzd_ev[0], s);
+	if ((e = hipMemcpyAsync(d_in, in, in_len, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "input copy");
+	if ((e = hipMemsetAsync(d_res, 0xff, sizeof(GddResult) * n, s)) != hipSuccess) return fail(e, "results");
+	(void)hipEventRecord(ctx->bzd_ev[1], s);
+	hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint8_t *)d_in, (uint64_t)in_len, (uint32_t)n, d_slots, d_res);
+	if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
+	(void)hipEventRecord(ctx->bzd_ev[2], s);
+	if ((e = hipMemcpyAsync(res.data(), d_res, sizeof(GddResult) * n, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "results copy");
+	if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "kernel");
+	std::vector<uint64_t> tab(n + (n + 1) / 2);
+	uint32_t *len = (uint32_t *)(tab.data() + n);
+	size_t total = 0;
+	for (size_t i = 0; i < n; ++i) { // the pack kernel takes every range from this table: none may leave its buffer
+		if (res[i].rc != GDD_OK || res[i].member_len < 28 || res[i].member_len > GDD_SLOT) return fail(hipErrorInvalidValue, "a member's result");
+		tab[i] = total, len[i] = res[i].member_len, total += res[i].member_len;
+	}
+	if (total > out_cap) return fail(hipErrorInvalidValue, "members larger than the output");
+	if ((e = hipMallocAsync((void **)&d_off, sizeof(uint64_t) * tab.size(), s)) != hipSuccess) return fail(e, "offsets");
+	if ((e = hipMallocAsync((void **)&d_out, total + 16, s)) != hipSuccess) return fail(e, "output");
+	if ((e = hipMemcpyAsync(d_off, tab.data(), sizeof(uint64_t) * tab.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "offsets copy");
+	(void)hipEventRecord(ctx->bzd_ev[3], s);
+	hipLaunchKernelGGL(bgzf_pack_kernel, dim3((unsigned)n), dim3(256), 0, s, (const uint8_t *)d_slots, (const uint64_t *)d_off, (const uint32_t *)(d_off + n), (uint32_t)n, d_out);
+	if ((e = hipGetLastError()) != hipSuccess) return fail(e, "pack launch");
+	(void)hipEventRecord(ctx->bzd_ev[4], s);
+	if ((e = hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "output copy");
+	(void)hipEventRecord(ctx->bzd_ev[5], s);
+	if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "pack kernel");
+	{ // (for measurements: gdiet_hip_debug_bgzf_deflate_seconds)
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, ctx->bzd_ev[0], ctx->bzd_ev[1]) == hipSuccess) ctx->bzd_ms[0] += ms;
+		if (hipEventElapsedTime(&ms, ctx->bzd_ev[1], ctx->bzd_ev[2]) == hipSuccess) ctx->bzd_ms[1] += ms;
+		if (hipEventElapsedTime(&ms, ctx->bzd_ev[3], ctx->bzd_ev[4]) == hipSuccess) ctx->bzd_ms[1] += ms;
+		if (hipEventElapsedTime(&ms, ctx->bzd_ev[4], ctx->bzd_ev[5]) == hipSuccess) ctx->bzd_ms[2] += ms;
+	}
+	(void)hipFreeAsync(d_in, s), (void)hipFreeAsync(d_slots, s), (void)hipFreeAsync(d_out, s), (void)hipFreeAsync(d_res, s), (void)hipFreeAsync(d_off, s);
+	*out_len = total;
 	return 0;
 }
 

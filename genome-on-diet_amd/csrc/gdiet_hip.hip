@@ -138,6 +138,12 @@ struct gdiet_ctx {
 	hipStream_t bz_stream = nullptr;
 	hipEvent_t bz_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three steps of a read: copy up, kernel, copy down
 	double bz_ms[3] = {0, 0, 0};                                // ... and their sums since the context was created (under bz_mu)
+	// BGZF members written on the device (bgzf_deflate.hip.h): a stream and a mutex of their own once more, because a writer thread
+	// compresses the SAM text of batch i while batch i + 1 maps
+	std::mutex bzd_mu;
+	hipStream_t bzd_stream = nullptr;
+	hipEvent_t bzd_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // copy up | deflate kernel || pack kernel | copy down
+	double bzd_ms[3] = {0, 0, 0};      // sums since the context was created: copy up, the two kernels, copy down (under bzd_mu)
 	std::string rg_line, rg_id;        // -R: the escaped @RG header line and its ID (gdiet_hip_set_read_group; read by the SAM formatters)
 };
 
@@ -289,8 +295,10 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 	if (ctx->ds_stream) (void)hipStreamSynchronize(ctx->ds_stream);
 	if (ctx->fx_stream) (void)hipStreamSynchronize(ctx->fx_stream);
 	if (ctx->bz_stream) (void)hipStreamSynchronize(ctx->bz_stream);
-	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev, ctx->bz_ev[0], ctx->bz_ev[1], ctx->bz_ev[2], ctx->bz_ev[3]};
-	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream, ctx->fx_stream, ctx->bz_stream};
+	if (ctx->bzd_stream) (void)hipStreamSynchronize(ctx->bzd_stream);
+	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev, ctx->bz_ev[0], ctx->bz_ev[1], ctx->bz_ev[2], ctx->bz_ev[3],
+	                            ctx->bzd_ev[0], ctx->bzd_ev[1], ctx->bzd_ev[2], ctx->bzd_ev[3], ctx->bzd_ev[4], ctx->bzd_ev[5]};
+	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream, ctx->fx_stream, ctx->bz_stream, ctx->bzd_stream};
 	delete ctx; // every DevBuf of the context releases itself here: before the streams and events go
 	for (hipEvent_t e : events)
 		if (e) (void)hipEventDestroy(e);
@@ -330,8 +338,10 @@ extern "C" int gdiet_hip_last_dp_clock(gdiet_ctx *ctx, double *sclk_mhz_median, 
 
 static const char *gd_ds_err_of(const gdiet_ctx *ctx); // map_diffstr_driver.hip.h
 static const char *gd_fx_err_of(const gdiet_ctx *ctx); // the reader's device mode, at the end of this file
+static const char *gd_bzd_err_of(const gdiet_ctx *ctx); // map_diffstr_driver.hip.h: the BGZF writing side (ctx may be NULL there)
 extern "C" const char *gdiet_hip_strerror(const gdiet_ctx *ctx)
 {
+	if (const char *bz = gd_bzd_err_of(ctx)) return bz; // this thread's last failure was a BGZF compression or the writer's write()
 	if (const char *ds = gd_ds_err_of(ctx)) return ds; // this thread's last failure on the context was a difference-string pass
 	if (const char *fx = gd_fx_err_of(ctx)) return fx; // ... or a device parse of the reader
 	return ctx ? ctx->err.c_str() : "no context";
@@ -1165,6 +1175,92 @@ extern "C" int gdiet_hip_bgzf_inflate(gdiet_ctx *ctx, const uint8_t *raw, size_t
 	gd_parallel_for(ctx, ctx->host_threads, (int)tab.size(), [&](int k) { ok[(size_t)k] = gd_bgzf_check(tab[(size_t)k], (size_t)k, out + tab[(size_t)k].out_off, lens[(size_t)k], &msg[(size_t)k]); });
 	for (size_t k = 0; k < tab.size(); ++k)
 		if (!ok[k]) return fail(GDIET_E_PARAM, msg[k]);
+	return GDIET_OK;
+}
+
+// ---- BGZF output -------------------------------------------------------------------------------------------------------------------
+extern "C" int gdiet_hip_bgzf_deflate(gdiet_ctx *ctx, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *out_len, int flags)
+{
+	if (!ctx || !out_len) return GDIET_E_PARAM;
+	*out_len = 0;
+	gd_ds_clear_mark();
+	if (!in && in_len) return gd_bzd_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_deflate: no input for " + std::to_string(in_len) + " bytes");
+	const size_t n = (in_len + GDD_MAX_IN - 1) / GDD_MAX_IN, bound = n * GDD_SLOT + GD_BGZF_EOF_LEN;
+	if (!out) { *out_len = bound; return GDIET_OK; } // sizes first
+	if (out_cap < bound) return gd_bzd_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_deflate: out holds " + std::to_string(out_cap) + " bytes, the bound is " + std::to_string(bound));
+	size_t got = 0;
+	std::string why;
+	const int rc = gd_bz_deflate_device(ctx, in, in_len, out, out_cap, &got, why);
+	if (rc < 0) return gd_bzd_fail(ctx, GDIET_E_HIP, "gdiet_hip_bgzf_deflate: " + why);
+	if (flags & 1) memcpy(out + got, GD_BGZF_EOF, GD_BGZF_EOF_LEN), got += GD_BGZF_EOF_LEN;
+	*out_len = got;
+	return GDIET_OK;
+}
+
+struct GdBzdExecutor : GdBgzfDeflater {
+	gdiet_ctx *ctx;
+	explicit GdBzdExecutor(gdiet_ctx *c) : ctx(c) {}
+	int deflate(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why) override
+	{
+		return gd_bz_deflate_device(ctx, in, in_len, out, out_cap, out_len, why);
+	}
+};
+struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; };
+
+extern "C" int gdiet_hip_bgzf_out_open(gdiet_ctx *ctx, const char *path, int level, int threads, gdiet_bgzf_out **out)
+{
+	if (!path || !out || level < -1 || level > 9) return GDIET_E_PARAM;
+	*out = nullptr;
+	gd_ds_clear_mark();
+	const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+	if (fd < 0) return gd_bzd_fail(ctx, GDIET_E_PARAM, std::string("gdiet_hip_bgzf_out_open: ") + path + ": " + strerror(errno));
+	gdiet_bgzf_out *h = new gdiet_bgzf_out();
+	h->ctx = ctx, h->w.fd = fd, h->w.level = level, h->w.threads = threads < 1 ? 1 : threads;
+	if (ctx) h->w.dev = std::make_shared<GdBzdExecutor>(ctx);
+	*out = h;
+	return GDIET_OK;
+}
+static int gd_bzo_done(gdiet_bgzf_out *h, int rc)
+{
+	if (!rc) return GDIET_OK;
+	return gd_bzd_fail(h->ctx, h->w.dev_error ? GDIET_E_HIP : GDIET_E_PARAM, "BGZF writer: " + (h->w.msg.empty() ? std::string("used after an error or after close") : h->w.msg));
+}
+extern "C" int gdiet_hip_bgzf_out_write(gdiet_bgzf_out *h, const void *bytes, size_t n)
+{
+	if (!h || (!bytes && n)) return GDIET_E_PARAM;
+	gd_ds_clear_mark();
+	return gd_bzo_done(h, h->w.write((const unsigned char *)bytes, n));
+}
+extern "C" int gdiet_hip_bgzf_out_flush(gdiet_bgzf_out *h)
+{
+	if (!h) return GDIET_E_PARAM;
+	gd_ds_clear_mark();
+	return gd_bzo_done(h, h->w.flush());
+}
+extern "C" int gdiet_hip_bgzf_out_close(gdiet_bgzf_out *h)
+{
+	if (!h) return GDIET_E_PARAM;
+	gd_ds_clear_mark();
+	const int rc = gd_bzo_done(h, h->w.close());
+	delete h;
+	return rc;
+}
+extern "C" int gdiet_hip_bgzf_out_stats(const gdiet_bgzf_out *h, int64_t *members_device, int64_t *members_host, int64_t *bytes_in, int64_t *bytes_out)
+{
+	if (!h) return GDIET_E_PARAM;
+	if (members_device) *members_device = h->w.members_device;
+	if (members_host) *members_host = h->w.members_host;
+	if (bytes_in) *bytes_in = h->w.bytes_in;
+	if (bytes_out) *bytes_out = h->w.bytes_out;
+	return GDIET_OK;
+}
+// measurement only (tools/map_file.py; not declared in include/gdiet_hip.h): the device's side of compressing since the context was
+// created, in seconds: copy up, the deflate and pack kernels, copy down (HIP events)
+extern "C" int gdiet_hip_debug_bgzf_deflate_seconds(gdiet_ctx *ctx, double *out3)
+{
+	if (!ctx || !out3) return GDIET_E_PARAM;
+	std::lock_guard<std::mutex> lk(ctx->bzd_mu);
+	for (int i = 0; i < 3; ++i) out3[i] = 1e-3 * ctx->bzd_ms[i];
 	return GDIET_OK;
 }
 

@@ -12,7 +12,18 @@ static thread_local const gdiet_ctx *gd_ds_failed_on = nullptr;
 // the same mark of the reader's device mode and of the BGZF inflater (fastx_dev_driver.hip.h); declared here so that every failure that is
 // neither clears both: a refused read or byte range is an ordinary outcome there, and its text must not answer for a later, unrelated failure
 static thread_local const gdiet_ctx *gd_fx_failed_on = nullptr;
-static void gd_ds_clear_mark() { gd_ds_failed_on = nullptr, gd_fx_failed_on = nullptr; }
+// ... and of the BGZF writing side (gdiet_hip_bgzf_deflate, the stream writer), which also works without a context: the text is the thread's own
+static thread_local bool gd_bzd_failed = false;
+static thread_local const gdiet_ctx *gd_bzd_failed_on = nullptr;
+static thread_local std::string gd_bzd_text;
+static void gd_ds_clear_mark() { gd_ds_failed_on = nullptr, gd_fx_failed_on = nullptr, gd_bzd_failed = false; }
+static const char *gd_bzd_err_of(const gdiet_ctx *ctx) { return gd_bzd_failed && gd_bzd_failed_on == ctx ? gd_bzd_text.c_str() : nullptr; }
+static int gd_bzd_fail(const gdiet_ctx *ctx, int rc, const std::string &what)
+{
+	gd_ds_clear_mark();
+	gd_bzd_text = what, gd_bzd_failed_on = ctx, gd_bzd_failed = true;
+	return rc;
+}
 static const char *gd_ds_err_of(const gdiet_ctx *ctx) { return ctx && gd_ds_failed_on == ctx ? ctx->ds_err.c_str() : nullptr; }
 
 // (like gd_grow, on the difference strings' own stream; the caller holds ds_mu)

@@ -76,6 +76,13 @@ def load_library():
                                               C.c_int8, C.c_int32, i32p, i32p, u32p, i64p]
     lib.gdiet_hip_ksw_extz2_batch_ex.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, i32p, C.POINTER(KswScore), C.c_int32, C.c_int32, i32p, i32p, u32p, i64p]
     lib.gdiet_hip_bgzf_inflate.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gdiet_hip_bgzf_deflate.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    lib.gdiet_hip_bgzf_out_open.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
+    lib.gdiet_hip_bgzf_out_write.argtypes = [vp, vp, C.c_size_t]
+    lib.gdiet_hip_bgzf_out_flush.argtypes = [vp]
+    lib.gdiet_hip_bgzf_out_close.argtypes = [vp]
+    lib.gdiet_hip_bgzf_out_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
+    lib.gdiet_hip_debug_bgzf_deflate_seconds.argtypes = [vp, C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -125,6 +132,22 @@ class Context:
         out = C.create_string_buffer(max(1, n.value))
         self._check(self.lib.gdiet_hip_bgzf_inflate(self._h, raw, len(raw), C.cast(out, C.c_void_p), n.value, C.byref(n)))
         return out.raw[:n.value]
+
+    def bgzf_deflate(self, data, eof=True):
+        """gdiet_hip_bgzf_deflate: data cut into members of 65280 bytes, each compressed by one wavefront of the device into a complete
+        BGZF member; eof appends the end-of-file member"""
+        data = bytes(data)
+        n = C.c_size_t()
+        self._check(self.lib.gdiet_hip_bgzf_deflate(self._h, data, len(data), None, 0, C.byref(n), int(bool(eof))))
+        out = C.create_string_buffer(max(1, n.value))
+        self._check(self.lib.gdiet_hip_bgzf_deflate(self._h, data, len(data), C.cast(out, C.c_void_p), n.value, C.byref(n), int(bool(eof))))
+        return out.raw[:n.value]
+
+    def bgzf_deflate_seconds(self):
+        """measurement only: seconds the device spent compressing since the context was created (copy up, kernels, copy down)"""
+        v = (C.c_double * 3)()
+        self._check(self.lib.gdiet_hip_debug_bgzf_deflate_seconds(self._h, v))
+        return list(v)
 
     @property
     def device_name(self):

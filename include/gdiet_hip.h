@@ -529,8 +529,8 @@ int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n
  * error is not what gzread's stream would have given.
  * Still read through zlib's gzread, as before: single-stream gzip, stdin, and a BGZF file without its end marker.  A member without a BC
  * subfield inside a file that took the BGZF route is a read error whose message names GDIET_BGZF=0; mixed streams are not read.
- * Out of scope: the CRC on the device, keeping the inflated block resident for the device's parse pass (it is uploaded again),
- * compressed SAM output, and the reference FASTA of the index build. */
+ * Out of scope: the reader's CRC on the device, keeping the inflated block resident for the device's parse pass (it is uploaded again),
+ * and the reference FASTA of the index build. */
 /* members inflated on the device and by zlib, compressed bytes taken and bytes produced since the reader was opened: all zero for a file
  * that did not take the BGZF route.  Any pointer may be NULL. */
 int gdiet_hip_fastx_bgzf_stats(const gdiet_fastx *fx, int64_t *members_device, int64_t *members_host, int64_t *bytes_in, int64_t *bytes_out);
@@ -541,6 +541,33 @@ const char *gdiet_hip_fastx_strerror(const gdiet_fastx *fx);
  * only that is computed.  GDIET_E_PARAM with a message in gdiet_hip_strerror for a malformed range, a range that ends inside a member,
  * out_cap too small, or a member's error; the context stays usable. */
 int gdiet_hip_bgzf_inflate(gdiet_ctx *ctx, const uint8_t *raw, size_t raw_len, uint8_t *out, size_t out_cap, size_t *out_len);
+
+/* BGZF output.  The kernel-level boundary of the compressor: in[0, in_len) is cut into members of 65280 input bytes (the last one
+ * shorter), every member is compressed by one wavefront of the device (csrc/bgzf_deflate.hip.h: LZ77 match search, dynamic, fixed or
+ * stored DEFLATE blocks, CRC32) and the complete members -- header with BC subfield and BSIZE, stream, CRC32, ISIZE -- are written one
+ * behind the other to out; flags & 1 appends the 28-byte end-of-file member.  A member's bytes depend on its input bytes alone.
+ * *out_len is what was written; with out == NULL it is the bound ceil(in_len / 65280) * 65536 + 28 that out_cap must reach, and nothing
+ * runs.  in_len == 0 writes nothing but the optional end-of-file member.  GDIET_E_PARAM, before any launch and with a message in
+ * gdiet_hip_strerror, for in == NULL with a length or out_cap below the bound; GDIET_E_HIP if the device fails. */
+int gdiet_hip_bgzf_deflate(gdiet_ctx *ctx, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *out_len, int flags);
+
+/* A BGZF stream writer: path is created or truncated.  With a context the members of a write go through the kernel above (on a stream
+ * and behind a lock of the context's own: a writer thread may compress while other threads map and read); with ctx == NULL they go
+ * through zlib's raw deflate at `level` (-1: zlib's default, 0..9) on `threads` host threads, plus zlib's crc32.  level and threads
+ * mean nothing with a context. */
+typedef struct gdiet_bgzf_out gdiet_bgzf_out;
+int gdiet_hip_bgzf_out_open(gdiet_ctx *ctx_or_null, const char *path, int level, int threads, gdiet_bgzf_out **out);
+/* n bytes more.  Whole members of 65280 bytes are compressed and written; what is left below that waits for the next call, so members
+ * are full except where a flush or the close ends one.  An error of the device (GDIET_E_HIP), of zlib or of write() -- a short write
+ * is one -- (GDIET_E_PARAM) leaves its message in gdiet_hip_strerror(ctx_or_null) for the calling thread; the writer then refuses
+ * everything but its close. */
+int gdiet_hip_bgzf_out_write(gdiet_bgzf_out *h, const void *bytes, size_t n);
+/* what is waiting becomes a (shorter) member now */
+int gdiet_hip_bgzf_out_flush(gdiet_bgzf_out *h);
+/* flushes, writes the end-of-file member, closes the file and frees the writer, whatever it returns */
+int gdiet_hip_bgzf_out_close(gdiet_bgzf_out *h);
+/* members compressed by the device and by zlib, bytes taken and bytes written to the file so far.  Any pointer may be NULL. */
+int gdiet_hip_bgzf_out_stats(const gdiet_bgzf_out *h, int64_t *members_device, int64_t *members_host, int64_t *bytes_in, int64_t *bytes_out);
 
 #ifdef __cplusplus
 }

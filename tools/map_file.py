@@ -4,6 +4,7 @@ No Python object is made per read: the C arrays of the reader go straight into t
 
     python tools/map_file.py --preset sr ref.fa reads.fq[.gz] -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
                              [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
+                             [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N]
 
 Writes the SAM body (the records).  --header puts the header lines of the reference's CLI in front (gdiet_hip_sam_header: @SQ per
 contig, the @RG line of -R, @PG with this tool's version and command line); it is opt-in, so that the default output stays the body alone.
@@ -11,7 +12,9 @@ contig, the @RG line of -R, @PG with this tool's version and command line); it i
 whole reads on supplementary records, long CIGARs in the CG tag, the FASTQ comment as the last field (read with with_comment), no
 qualities (not even read: with_qual off), no record for an unmapped read.
 --device-reader attaches the reader to the context (gdiet_hip_fastx_attach): four-line FASTQ is parsed and encoded on the device, the
-reader hands out resident batches, and the upload stage disappears; the output is the same, and the JSON line gains reader_stats."""
+reader hands out resident batches, and the upload stage disappears; the output is the same, and the JSON line gains reader_stats.
+--bgzf writes -o, the --header text included, as BGZF (BgzfWriter): `device` compresses every member of 65280 bytes on one wavefront of
+the GPU, `host` with zlib at --bgzf-level on --bgzf-threads threads; the JSON line gains bgzf_out.  Without it nothing changes."""
 import argparse
 import json
 import os
@@ -186,6 +189,9 @@ def main():
     ap.add_argument("-y", dest="copy_comment", action="store_true", help="copy the FASTA/FASTQ comment to the end of each record (MM_F_COPY_COMMENT)")
     ap.add_argument("-Q", dest="no_qual", action="store_true", help="no base qualities: QUAL is * (MM_F_NO_QUAL)")
     ap.add_argument("--sam-hit-only", action="store_true", help="no record for a read without an alignment (MM_F_SAM_HIT_ONLY)")
+    ap.add_argument("--bgzf", choices=["host", "device"], help="write -o as BGZF: members compressed by zlib on host threads, or on the device (one wavefront per member)")
+    ap.add_argument("--bgzf-level", type=int, default=-1, help="zlib level of --bgzf host (-1: zlib's default)")
+    ap.add_argument("--bgzf-threads", type=int, default=4, help="host threads of --bgzf host")
     ap.add_argument("--device-reader", action="store_true", help="parse and encode four-line FASTQ on the device (gdiet_hip_fastx_attach); the reader hands out resident batches")
     a = ap.parse_args()
     if a.eqx and a.preset != "sr":
@@ -219,7 +225,9 @@ def main():
     t_idx = time.perf_counter() - t0
     chunk = a.K or (39321600 if a.preset == "sr" else 80_000_000)
     try:
-        with open(a.out, "wb") as out:
+        bgzf_out = None
+        with (pkg.BgzfWriter(a.out, ctx=ctx if a.bgzf == "device" else None, level=a.bgzf_level, threads=a.bgzf_threads) if a.bgzf else open(a.out, "wb")) as out:
+            bgzf_out = out if a.bgzf else None
             if a.header:
                 out.write(m.sam_header(VERSION, sys.argv).encode())
             n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment,
@@ -231,7 +239,8 @@ def main():
         sys.exit(1)
     print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), "mini_batch_bases": chunk,
                       "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "eqx": a.eqx, "out": a.out, "caller_seconds": map_file.last_stage_seconds,
-                      **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats}))
+                      **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats,
+                      **({"bgzf_out": dict(bgzf_out.stats(), route=a.bgzf, device_seconds=[round(x, 4) for x in ctx.bgzf_deflate_seconds()])} if a.bgzf else {})}))
     m.close()
     ctx.close()
 
