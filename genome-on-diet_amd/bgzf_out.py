@@ -40,6 +40,13 @@ class BgzfWriter:
             self._check(self.lib.gdiet_hip_bgzf_out_write(self._h, (C.c_char * n).from_buffer(mv.cast("B")), n))
         return n
 
+    def write_bam(self, mapper, res, n, names, seqs, quals, lens, comments=None):
+        """The BAM records of a mapped batch appended to the stream (``gdiet_hip_bgzf_out_write_bam``; the arguments of
+        ``Mapper.bam_batch_raw``, which this is with the writer as sink).  With a context the records are encoded on the device behind the
+        writer's waiting tail and compressed there: the uncompressed records never reach the host.  Write ``mapper.bam_header()`` first."""
+        self._open()
+        mapper.bam_batch_raw(res, n, names, seqs, quals, lens, sink=self, comments=comments)
+
     def flush(self):
         self._open()
         self._check(self.lib.gdiet_hip_bgzf_out_flush(self._h))

@@ -28,7 +28,9 @@ BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           "_Z19bgzf_inflate_kernel": dict(vgprs=64, scratch=0),
           # BGZF members written on the device (bgzf_deflate.hip.h): its local memory bounds it to one wavefront per SIMD at most, so
           # registers up to 128 cost no occupancy; nothing in scratch memory
-          "_Z19bgzf_deflate_kernel": dict(vgprs=128, scratch=0)}
+          "_Z19bgzf_deflate_kernel": dict(vgprs=128, scratch=0),
+          # BAM records encoded on the device (bam_encode.hip.h): batch i is encoded beside the DP of batch i + 1, like the difference strings
+          "_Z17bam_encode_kernel": dict(vgprs=32, scratch=0)}
 
 
 def _newest_source():

@@ -27,6 +27,13 @@ struct GdBgzfDeflater {
 	// in[0, in_len) cut every 65280 bytes -> the members, one behind the other, in out[0, *out_len); out_cap is at least
 	// ceil(in_len / 65280) * 65536.  Returns 0 or a negative code with the reason in why.
 	virtual int deflate(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why) = 0;
+	// the same for an input the deflater's device already holds (d_in: a device pointer); only a device deflater can
+	virtual int deflate_resident(const void *d_in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why)
+	{
+		(void)d_in, (void)in_len, (void)out, (void)out_cap, (void)out_len;
+		why = "this deflater takes no resident input";
+		return -1;
+	}
 };
 
 // one member through zlib: header with the BC subfield, raw deflate at `level`, CRC32 and ISIZE; a stored block if the level's stream
@@ -110,6 +117,20 @@ struct GdBgzfOut {
 			members_host += (int64_t)k;
 		}
 		bytes_in += (int64_t)n;
+		return put(obuf.data(), out_len);
+	}
+	// whole members of an input resident on the deflater's device: d_in[0, n), n a multiple of 65280.  (The BAM route: the caller has put
+	// the waiting tail in front of what it encoded there, takes the tail away and sets the new one: gdiet_hip_bgzf_out_write_bam.)
+	int members_resident(const void *d_in, size_t n)
+	{
+		if (failed || fd < 0 || !dev || n % GD_BGZF_MEMBER_IN) return -1;
+		if (n == 0) return 0;
+		const size_t k = n / GD_BGZF_MEMBER_IN;
+		if (obuf.size() < k * GD_BGZF_SLOT) obuf.resize(k * GD_BGZF_SLOT);
+		size_t out_len = 0;
+		std::string why;
+		if (dev->deflate_resident(d_in, n, obuf.data(), obuf.size(), &out_len, why) != 0) { dev_error = true; return fail(why); }
+		members_device += (int64_t)k, bytes_in += (int64_t)n;
 		return put(obuf.data(), out_len);
 	}
 	int write(const unsigned char *p, size_t n)

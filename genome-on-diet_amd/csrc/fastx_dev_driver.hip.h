@@ -115,28 +115,31 @@ static int gd_bz_inflate_device(gdiet_ctx *ctx, const unsigned char *raw, size_t
 // while batch i + 1 maps and the reader inflates.  Stream-ordered allocations.  The stream is synchronised twice: once for the 8 bytes
 // per member that the host's prefix sum needs (it also sizes the copy down), once before the host touches the bytes.  out_cap must be
 // at least 65536 bytes per member.  Returns 0 or -1 (the device failed) with the reason in why.
-static int gd_bz_deflate_device(gdiet_ctx *ctx, const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why)
+// The middle of it: members from an input that is already resident, d_in[0, in_len) in device memory (the BAM route encodes its records
+// there: bam_driver.hip.h).  The caller holds bzd_mu, has made the stream and the events (gd_bzd_ready) and recorded bzd_ev[0] and [1]
+// around whatever brought the input up; d_in stays the caller's.  On failure the stream has been synchronised.
+static int gd_bzd_ready(gdiet_ctx *ctx, std::string &why)
 {
-	*out_len = 0;
-	const size_t n = (in_len + GDD_MAX_IN - 1) / GDD_MAX_IN;
-	if (n == 0) return 0;
-	if (n > ((size_t)1 << 30) || out_cap / GDD_SLOT < n) { why = "device deflate: the output holds fewer than 65536 bytes per member"; return -1; }
-	std::lock_guard<std::mutex> lk(ctx->bzd_mu);
 	(void)hipSetDevice(ctx->device);
 	hipError_t e = hipSuccess;
 	if (!ctx->bzd_stream && (e = hipStreamCreateWithFlags(&ctx->bzd_stream, hipStreamNonBlocking)) != hipSuccess) {
 		why = std::string("device deflate: stream: ") + hipGetErrorString(e);
 		return -1;
 	}
-	hipStream_t s = ctx->bzd_stream;
 	for (hipEvent_t &ev : ctx->bzd_ev)
 		if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) { ev = nullptr; why = std::string("device deflate: event: ") + hipGetErrorString(e); return -1; }
-	uint8_t *d_in = nullptr, *d_slots = nullptr, *d_out = nullptr;
+	return 0;
+}
+static int gd_bz_deflate_resident(gdiet_ctx *ctx, const uint8_t *d_in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why)
+{
+	const size_t n = (in_len + GDD_MAX_IN - 1) / GDD_MAX_IN;
+	hipStream_t s = ctx->bzd_stream;
+	hipError_t e = hipSuccess;
+	uint8_t *d_slots = nullptr, *d_out = nullptr;
 	GddResult *d_res = nullptr;
 	uint64_t *d_off = nullptr; // off[n], then len[n] as 32-bit words
 	auto fail = [&](hipError_t err, const char *what) {
 		(void)hipStreamSynchronize(s);
-		if (d_in) (void)hipFreeAsync(d_in, s);
 		if (d_slots) (void)hipFreeAsync(d_slots, s);
 		if (d_out) (void)hipFreeAsync(d_out, s);
 		if (d_res) (void)hipFreeAsync(d_res, s);
@@ -145,14 +148,11 @@ static int gd_bz_deflate_device(gdiet_ctx *ctx, const unsigned char *in, size_t 
 		return -1;
 	};
 	std::vector<GddResult> res(n);
-	if ((e = hipMallocAsync((void **)&d_in, in_len + 16, s)) != hipSuccess) return fail(e, "input");
 	if ((e = hipMallocAsync((void **)&d_slots, n * GDD_SLOT, s)) != hipSuccess) return fail(e, "slots");
 	if ((e = hipMallocAsync((void **)&d_res, sizeof(GddResult) * n, s)) != hipSuccess) return fail(e, "results");
-	(void)hipEventRecord(ctx->bzd_ev[0], s);
-	if ((e = hipMemcpyAsync(d_in, in, in_len, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "input copy");
 	if ((e = hipMemsetAsync(d_res, 0xff, sizeof(GddResult) * n, s)) != hipSuccess) return fail(e, "results");
 	(void)hipEventRecord(ctx->bzd_ev[1], s);
-	hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)n), dim3(64), 0, s, (const uint8_t *)d_in, (uint64_t)in_len, (uint32_t)n, d_slots, d_res);
+	hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)n), dim3(64), 0, s, d_in, (uint64_t)in_len, (uint32_t)n, d_slots, d_res);
 	if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
 	(void)hipEventRecord(ctx->bzd_ev[2], s);
 	if ((e = hipMemcpyAsync(res.data(), d_res, sizeof(GddResult) * n, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "results copy");
@@ -182,9 +182,34 @@ static int gd_bz_deflate_device(gdiet_ctx *ctx, const unsigned char *in, size_t 
 		if (hipEventElapsedTime(&ms, ctx->bzd_ev[3], ctx->bzd_ev[4]) == hipSuccess) ctx->bzd_ms[1] += ms;
 		if (hipEventElapsedTime(&ms, ctx->bzd_ev[4], ctx->bzd_ev[5]) == hipSuccess) ctx->bzd_ms[2] += ms;
 	}
-	(void)hipFreeAsync(d_in, s), (void)hipFreeAsync(d_slots, s), (void)hipFreeAsync(d_out, s), (void)hipFreeAsync(d_res, s), (void)hipFreeAsync(d_off, s);
+	(void)hipFreeAsync(d_slots, s), (void)hipFreeAsync(d_out, s), (void)hipFreeAsync(d_res, s), (void)hipFreeAsync(d_off, s);
 	*out_len = total;
 	return 0;
+}
+
+static int gd_bz_deflate_device(gdiet_ctx *ctx, const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why)
+{
+	*out_len = 0;
+	const size_t n = (in_len + GDD_MAX_IN - 1) / GDD_MAX_IN;
+	if (n == 0) return 0;
+	if (n > ((size_t)1 << 30) || out_cap / GDD_SLOT < n) { why = "device deflate: the output holds fewer than 65536 bytes per member"; return -1; }
+	std::lock_guard<std::mutex> lk(ctx->bzd_mu);
+	if (gd_bzd_ready(ctx, why)) return -1;
+	hipStream_t s = ctx->bzd_stream;
+	hipError_t e = hipSuccess;
+	uint8_t *d_in = nullptr;
+	auto fail = [&](hipError_t err, const char *what) {
+		(void)hipStreamSynchronize(s);
+		if (d_in) (void)hipFreeAsync(d_in, s);
+		why = std::string("device deflate: ") + what + ": " + hipGetErrorString(err);
+		return -1;
+	};
+	if ((e = hipMallocAsync((void **)&d_in, in_len + 16, s)) != hipSuccess) return fail(e, "input");
+	(void)hipEventRecord(ctx->bzd_ev[0], s);
+	if ((e = hipMemcpyAsync(d_in, in, in_len, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "input copy");
+	const int rc = gd_bz_deflate_resident(ctx, d_in, in_len, out, out_cap, out_len, why);
+	(void)hipFreeAsync(d_in, s);
+	return rc;
 }
 
 struct GdFxExecutor : GdFastxDevice {

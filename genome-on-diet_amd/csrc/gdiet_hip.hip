@@ -144,6 +144,12 @@ struct gdiet_ctx {
 	hipStream_t bzd_stream = nullptr;
 	hipEvent_t bzd_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // copy up | deflate kernel || pack kernel | copy down
 	double bzd_ms[3] = {0, 0, 0};      // sums since the context was created: copy up, the two kernels, copy down (under bzd_mu)
+	// BAM records encoded on the device (bam_encode.hip.h, bam_driver.hip.h): a stream and a mutex of their own, for the same writer thread
+	std::mutex bam_mu;
+	hipStream_t bam_stream = nullptr;
+	hipEvent_t bam_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // copy up | encode kernel | copy down
+	double bam_ms[3] = {0, 0, 0};      // their sums since the context was created (under bam_mu)
+	std::shared_ptr<void> bam_pool;    // GdbPool (bam_driver.hip.h): the flattened chunks of a batch and their merged table, kept from call to call (under bam_mu)
 	std::string rg_line, rg_id;        // -R: the escaped @RG header line and its ID (gdiet_hip_set_read_group; read by the SAM formatters)
 };
 
@@ -296,9 +302,10 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 	if (ctx->fx_stream) (void)hipStreamSynchronize(ctx->fx_stream);
 	if (ctx->bz_stream) (void)hipStreamSynchronize(ctx->bz_stream);
 	if (ctx->bzd_stream) (void)hipStreamSynchronize(ctx->bzd_stream);
+	if (ctx->bam_stream) (void)hipStreamSynchronize(ctx->bam_stream);
 	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev, ctx->bz_ev[0], ctx->bz_ev[1], ctx->bz_ev[2], ctx->bz_ev[3],
-	                            ctx->bzd_ev[0], ctx->bzd_ev[1], ctx->bzd_ev[2], ctx->bzd_ev[3], ctx->bzd_ev[4], ctx->bzd_ev[5]};
-	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream, ctx->fx_stream, ctx->bz_stream, ctx->bzd_stream};
+	                            ctx->bzd_ev[0], ctx->bzd_ev[1], ctx->bzd_ev[2], ctx->bzd_ev[3], ctx->bzd_ev[4], ctx->bzd_ev[5], ctx->bam_ev[0], ctx->bam_ev[1], ctx->bam_ev[2], ctx->bam_ev[3]};
+	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream, ctx->fx_stream, ctx->bz_stream, ctx->bzd_stream, ctx->bam_stream};
 	delete ctx; // every DevBuf of the context releases itself here: before the streams and events go
 	for (hipEvent_t e : events)
 		if (e) (void)hipEventDestroy(e);
@@ -1204,6 +1211,17 @@ struct GdBzdExecutor : GdBgzfDeflater {
 	{
 		return gd_bz_deflate_device(ctx, in, in_len, out, out_cap, out_len, why);
 	}
+	int deflate_resident(const void *d_in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why) override
+	{
+		*out_len = 0;
+		const size_t n = (in_len + GDD_MAX_IN - 1) / GDD_MAX_IN;
+		if (n == 0) return 0;
+		if (n > ((size_t)1 << 30) || out_cap / GDD_SLOT < n) { why = "device deflate: the output holds fewer than 65536 bytes per member"; return -1; }
+		std::lock_guard<std::mutex> lk(ctx->bzd_mu);
+		if (gd_bzd_ready(ctx, why)) return -1;
+		(void)hipEventRecord(ctx->bzd_ev[0], ctx->bzd_stream); // nothing goes up: the input is there
+		return gd_bz_deflate_resident(ctx, (const uint8_t *)d_in, in_len, out, out_cap, out_len, why);
+	}
 };
 struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; };
 
@@ -1263,6 +1281,8 @@ extern "C" int gdiet_hip_debug_bgzf_deflate_seconds(gdiet_ctx *ctx, double *out3
 	for (int i = 0; i < 3; ++i) out3[i] = 1e-3 * ctx->bzd_ms[i];
 	return GDIET_OK;
 }
+
+#include "bam_driver.hip.h" // BAM: the record encoder's driver, gdiet_hip_bam_header / _bam_batch_into / _bgzf_out_write_bam
 
 extern "C" int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n, int64_t *roff, uint8_t *enc_host, uint8_t *enc_device)
 {

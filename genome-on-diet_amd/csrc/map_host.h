@@ -667,6 +667,34 @@ static inline void gd_write_paf(std::string &s, const GdRefView &R, const char *
 	if ((opt_flag & GD_F_COPY_COMMENT) && comment) { s += '\t'; s += comment; } // :357, mapped lines only (the r == 0 branch returns at :332)
 }
 
+// the SA tag of a primary line when the read has other records that are no secondary ones ("\tSA:Z:...", LR/format.c:565-590); nothing otherwise
+static inline void gd_write_sa_tag(std::string &s, const GdRefView &R, const std::vector<GdReg> &regs, int reg_idx, int l_seq)
+{
+	const GdReg *r = &regs[reg_idx];
+	if (r->parent == r->id && r->has_p && regs.size() > 1) {
+		int n_sa = 0;
+		for (size_t i = 0; i < regs.size(); ++i) if ((int)i != reg_idx && regs[i].parent == regs[i].id && regs[i].has_p) ++n_sa;
+		if (n_sa > 0) {
+			s += "\tSA:Z:";
+			for (size_t i = 0; i < regs.size(); ++i) {
+				const GdReg *q = &regs[i];
+				if ((int)i == reg_idx || q->parent != q->id || !q->has_p) continue;
+				int l_M, l_I = 0, l_D = 0;
+				if (q->qe - q->qs < q->re - q->rs) l_M = q->qe - q->qs, l_D = (q->re - q->rs) - l_M;
+				else l_M = q->re - q->rs, l_I = (q->qe - q->qs) - l_M;
+				const int clip5 = q->rev ? l_seq - q->qe : q->qs, clip3 = q->rev ? q->qs : l_seq - q->qe;
+				s += R.seq[q->rid].name; s += ','; gd_fmt_int(s, q->rs + 1); s += ','; s += "+-"[q->rev]; s += ',';
+				if (clip5) { gd_fmt_int(s, clip5); s += 'S'; }
+				if (l_M) { gd_fmt_int(s, l_M); s += 'M'; }
+				if (l_I) { gd_fmt_int(s, l_I); s += 'I'; }
+				if (l_D) { gd_fmt_int(s, l_D); s += 'D'; }
+				if (clip3) { gd_fmt_int(s, clip3); s += 'S'; }
+				s += ','; gd_fmt_int(s, q->mapq); s += ','; gd_fmt_int(s, q->blen - q->mlen + (int)q->n_ambi); s += ';';
+			}
+		}
+	}
+}
+
 // mm_write_sam3 (LR/format.c:412-602).  opt_flag bits read: MM_F_SOFTCLIP (clips stay 'S' and SEQ / QUAL the whole read on 0x100 and 0x800 records, :402,:542),
 // MM_F_LONG_CIGAR (a CIGAR of more than 65 535 BAM operations moves into a CG:B:I tag, :476-490), MM_F_NO_QUAL (QUAL is '*': the
 // reference does not read the qualities at all, LR/map.c:2099), MM_F_COPY_COMMENT (the read's comment is the last field, :599) and the
@@ -736,29 +764,7 @@ static inline void gd_write_sam(std::string &s, const GdRefView &R, const char *
 		}
 		if (rg_id && rg_id[0]) { s += "\tRG:Z:"; s += rg_id; }
 		gd_write_tags(s, *r);
-		// SA tag for the primary line when supplementary alignments exist, :565-590
-		if (r->parent == r->id && r->has_p && regs.size() > 1) {
-			int n_sa = 0;
-			for (size_t i = 0; i < regs.size(); ++i) if ((int)i != reg_idx && regs[i].parent == regs[i].id && regs[i].has_p) ++n_sa;
-			if (n_sa > 0) {
-				s += "\tSA:Z:";
-				for (size_t i = 0; i < regs.size(); ++i) {
-					const GdReg *q = &regs[i];
-					if ((int)i == reg_idx || q->parent != q->id || !q->has_p) continue;
-					int l_M, l_I = 0, l_D = 0;
-					if (q->qe - q->qs < q->re - q->rs) l_M = q->qe - q->qs, l_D = (q->re - q->rs) - l_M;
-					else l_M = q->re - q->rs, l_I = (q->qe - q->qs) - l_M;
-					const int clip5 = q->rev ? l_seq - q->qe : q->qs, clip3 = q->rev ? q->qs : l_seq - q->qe;
-					s += R.seq[q->rid].name; s += ','; gd_fmt_int(s, q->rs + 1); s += ','; s += "+-"[q->rev]; s += ',';
-					if (clip5) { gd_fmt_int(s, clip5); s += 'S'; }
-					if (l_M) { gd_fmt_int(s, l_M); s += 'M'; }
-					if (l_I) { gd_fmt_int(s, l_I); s += 'I'; }
-					if (l_D) { gd_fmt_int(s, l_D); s += 'D'; }
-					if (clip3) { gd_fmt_int(s, clip3); s += 'S'; }
-					s += ','; gd_fmt_int(s, q->mapq); s += ','; gd_fmt_int(s, q->blen - q->mlen + (int)q->n_ambi); s += ';';
-				}
-			}
-		}
+		gd_write_sa_tag(s, R, regs, reg_idx, l_seq);
 	}
 	if (r && r->has_p && !r->cigar.empty()) gd_write_ds_tag(s, opt_flag, ds, ds_len); // :593-594, behind the SA tag
 	if (cigar_in_tag) { // write_sam_cigar with in_tag, :394-400

@@ -113,6 +113,12 @@ def _bind(lib):
     lib.gdiet_hip_sam_header.restype = C.c_size_t
     lib.gdiet_hip_diffstr_batch.argtypes = [vp, vp, vp, C.c_int, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp),
                                             C.POINTER(vp)]
+    lib.gdiet_hip_bam_header.argtypes = [vp, vp, C.c_char_p, C.c_int, cpp, C.POINTER(vp)]
+    lib.gdiet_hip_bam_header.restype = C.c_size_t
+    lib.gdiet_hip_bam_batch_into.argtypes = [vp, vp, C.c_int, cpp, cpp, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp),
+                                             C.POINTER(C.c_size_t)]
+    lib.gdiet_hip_bam_batch_into.restype = C.c_int64
+    lib.gdiet_hip_bgzf_out_write_bam.argtypes = [vp, vp, vp, C.c_int, cpp, cpp, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64]
     lib._map_bound = True
 
 
@@ -296,6 +302,9 @@ class Mapper:
         if getattr(self, "_sam_buf", None) is not None and self._sam_buf.value:
             C.CDLL(None).free(self._sam_buf)
             self._sam_buf = C.c_void_p()
+        if getattr(self, "_bam_buf", None) is not None and self._bam_buf.value:
+            C.CDLL(None).free(self._bam_buf)
+            self._bam_buf = C.c_void_p()
         if self._idx:
             self.lib.gdiet_hip_index_destroy(self.ctx._h, self._idx)
             self._idx = C.c_void_p()
@@ -403,6 +412,67 @@ class Mapper:
             return C.string_at(out.value, m).decode()
         finally:
             C.CDLL(None).free(C.c_void_p(out.value))
+
+    def bam_header(self, version=None, argv=()):
+        """gdiet_hip_bam_header: the bytes a BAM file starts with before compression -- magic, the text of sam_header(version, argv), the
+        reference dictionary"""
+        enc = lambda x: x if isinstance(x, bytes) else x.encode()
+        av = (C.c_char_p * max(1, len(argv)))(*[enc(x) for x in argv])
+        out = C.c_void_p()
+        m = self.lib.gdiet_hip_bam_header(self.ctx._h, self._idx, None if version is None else enc(version), len(argv), av, C.byref(out))
+        if not out.value:
+            raise GdietError("gdiet_hip_bam_header failed")
+        try:
+            return C.string_at(out.value, m)
+        finally:
+            C.CDLL(None).free(C.c_void_p(out.value))
+
+    def bam_batch_raw(self, res, n, names, seqs, quals, lens, sink=None, comments=None):
+        """The uncompressed BAM records of a batch, encoded on the device; the arguments of sam_batch_raw (C arrays; quals / comments may
+        be None).  Without a sink the bytes are returned (gdiet_hip_bam_batch_into).  With a BgzfWriter as sink the records go into its
+        stream (gdiet_hip_bgzf_out_write_bam: on a writer with a context they are compressed where they were encoded and never reach the
+        host) and None is returned; with any other sink the bytes are written to it and their number returned.  Write bam_header() first."""
+        cpp = C.POINTER(C.c_char_p)
+        args = (self.ctx._h, self._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp), C.cast(comments, cpp), lens, res.n_regs, res.regs, self.opt.flag)
+        if sink is not None and hasattr(sink, "_h") and hasattr(sink, "write_bam"):
+            rc = self.lib.gdiet_hip_bgzf_out_write_bam(sink._h, *args)
+            if rc:
+                raise GdietError("gdiet_hip_bgzf_out_write_bam: %s" % self.lib.gdiet_hip_strerror(self.ctx._h).decode())
+            return None
+        if sink is not None and not hasattr(self, "_bam_buf"):
+            self._bam_buf, self._bam_cap = C.c_void_p(), C.c_size_t(0)
+        buf, cap = (self._bam_buf, self._bam_cap) if sink is not None else (C.c_void_p(), C.c_size_t(0))
+        try:
+            m = self.lib.gdiet_hip_bam_batch_into(*args, C.byref(buf), C.byref(cap))
+            if m < 0:
+                raise GdietError("gdiet_hip_bam_batch_into: %s" % self.lib.gdiet_hip_strerror(self.ctx._h).decode())
+            if sink is None:
+                return C.string_at(buf.value, m) if m else b""
+            if m:
+                sink.write(memoryview((C.c_char * m).from_address(buf.value)))
+            return m
+        finally:
+            if sink is None and buf.value:
+                C.CDLL(None).free(C.c_void_p(buf.value))
+
+    def bam_device_seconds(self):
+        """measurement only: seconds the BAM encoder of this mapper's context spent on the device since the context was made -- copy up, the
+        encode kernel, and what followed on its stream (the copy down; on the resident route the members' compression as well)"""
+        out = (C.c_double * 3)()
+        self.lib.gdiet_hip_debug_bam_seconds.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self.lib.gdiet_hip_debug_bam_seconds(self.ctx._h, out)
+        return list(out)
+
+    def bam_batch(self, res, reads):
+        """bam_batch_raw on Python objects: reads = [(qname, seq, qual or None[, comment or None]), ...]; returns bytes"""
+        n = len(reads)
+        enc = lambda x: x if isinstance(x, bytes) else x.encode()
+        qn = (C.c_char_p * n)(*[enc(r[0]) for r in reads])
+        sq = (C.c_char_p * n)(*[enc(r[1]) for r in reads])
+        ql = (C.c_char_p * n)(*[None if len(r) < 3 or r[2] is None else enc(r[2]) for r in reads])
+        cm = (C.c_char_p * n)(*[None if len(r) < 4 or r[3] is None else enc(r[3]) for r in reads])
+        lens = np.array([len(r[1]) for r in reads], np.int32)
+        return self.bam_batch_raw(res, n, qn, sq, ql, lens.ctypes.data_as(C.POINTER(C.c_int32)), comments=cm)
 
     def _format_failed(self, what):
         """a batch formatter returned no text for a batch with reads: the difference-string pass refused a record, or memory ran out"""

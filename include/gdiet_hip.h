@@ -569,6 +569,53 @@ int gdiet_hip_bgzf_out_close(gdiet_bgzf_out *h);
 /* members compressed by the device and by zlib, bytes taken and bytes written to the file so far.  Any pointer may be NULL. */
 int gdiet_hip_bgzf_out_stats(const gdiet_bgzf_out *h, int64_t *members_device, int64_t *members_host, int64_t *bytes_in, int64_t *bytes_out);
 
+/* ---- BAM output ----------------------------------------------------------------------------------------------------------------------
+ * The reference writes no BAM.  A BAM alignment record (SAM specification 4.2; all integers little-endian) is defined here as a fixed
+ * function of the SAM line gdiet_hip_sam_batch_comments_into prints for the same arguments, so the SAM text, which is pinned to the
+ * reference, stays the oracle (tests/bam_ref.py restates the function):
+ *   RNAME -> refID (its index in the index; -1 for "*"), POS - 1 -> pos, MAPQ, FLAG; next_refID = next_pos = -1, tlen = 0;
+ *   CIGAR -> n_cigar_op words len << 4 | op (MIDNSHP=X = 0..8), clips included, "*" -> none.  More than 65 535 operations, clips
+ *            included: the two operations <l_seq>S<reference length>N and the real ones in a CG:B:I tag, placed where MM_F_LONG_CIGAR
+ *            puts it in the SAM line (behind cs / MD, in front of rl) -- whether or not that bit is set: BAM has no other way;
+ *   bin    = reg2bin(pos, pos + reference length of the real CIGAR, or pos + 1 if that is 0); 4680 for an unmapped record;
+ *   SEQ    -> 4-bit codes, the index of the upper-cased letter in "=ACMGRSVTWYHKDBN", 15 for any other byte; high nibble first.  SEQ is
+ *            taken from the read's text (seqs[i]), so IUPAC letters keep their codes.  "*" -> l_seq = 0 and no qualities;
+ *   QUAL   -> byte - 33; "*" -> l_seq bytes of 0xff;
+ *   tags in the order of the line: integers as the smallest type that holds the value (c s i for negative values, C S I otherwise),
+ *            A one byte, Z / H text and NUL, de:f: the float32 nearest to the decimal text printed, B:I the CG array;
+ *   the comment (MM_F_COPY_COMMENT): every tab-separated field must itself be a tag XX:T:value, T in A i f Z H B (B subtypes cCsSiIf),
+ *            and is stored as that tag.  A comment that is no list of tags cannot be stored: the batch call fails with GDIET_E_PARAM
+ *            and a message that names the read.  So does a read name of more than 254 bytes.
+ * Which records exist is decided exactly as in the SAM batch calls (MM_F_NO_PRINT_2ND, MM_F_SAM_HIT_ONLY, MM_F_SOFTCLIP, MM_F_NO_QUAL,
+ * MM_F_COPY_COMMENT, the cs / MD bits with their pass on the GPU, the context's read group, = / X operations as they come in regs).
+ * The records are written on the GPU, one wavefront per record (csrc/bam_encode.hip.h), from a table the context's host threads
+ * flatten; a stream and a lock of the context's own, so a writer thread may encode while other threads map.  Failures of these calls
+ * leave their text in gdiet_hip_strerror(ctx) for the calling thread.  Paired-end fields, sorting and indexes are out of scope. */
+
+/* The BAM header: "BAM\1", l_text and the text gdiet_hip_sam_header returns for the same arguments (no NUL), n_ref, and per index sequence
+ * l_name (with NUL), the name and its NUL, l_ref.  *out is malloc'd (free() it); returns its length, 0 with *out == NULL on failure. */
+size_t gdiet_hip_bam_header(gdiet_ctx *ctx, const gdiet_index *idx, const char *version, int argc, const char *const *argv, char **out);
+/* The uncompressed BAM records of a batch, in input order, one behind the other (each with its block_size), into a buffer the caller
+ * keeps from mini-batch to mini-batch: the argument shape of gdiet_hip_sam_batch_comments_into (*buf / *cap start as NULL / 0, are
+ * realloc'd when too small, and are free()d by the caller; quals, comments and their entries may be NULL).  This is the kernel-level
+ * boundary of the encoder: the records are encoded on the device and copied back.  Returns the number of bytes -- 0 for a batch that
+ * yields no record, which is no failure --, or a negative GDIET_E_* code: GDIET_E_PARAM for a comment that is no tag list, a name of
+ * more than 254 bytes, a record whose rid / qs / qe lie outside the index or the read, or a record the difference-string pass refuses;
+ * GDIET_E_HIP if the device fails. */
+int64_t gdiet_hip_bam_batch_into(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
+                                 const char *const *quals, const char *const *comments, const int32_t *lens, const int32_t *n_regs,
+                                 gdiet_reg_t *const *regs, int64_t opt_flag, char **buf, size_t *cap);
+/* The same records appended to a BGZF stream writer (write the header with gdiet_hip_bgzf_out_write first).  On a writer opened with a
+ * context -- it must be ctx -- the uncompressed records never reach the host: the writer's waiting tail (under 65280 bytes) is uploaded
+ * in front of a resident buffer, the records are encoded behind it, every whole member of 65280 bytes is compressed from that buffer by
+ * the deflate kernel, the members come down and are written, and what is left below a member comes down as the next tail.  The file's
+ * bytes are those of gdiet_hip_bam_batch_into followed by gdiet_hip_bgzf_out_write, which is what the call does on a writer without a
+ * context (the records are still encoded on ctx's device).  gdiet_hip_bgzf_out_stats counts these members like any others.  Returns
+ * GDIET_OK or the codes of gdiet_hip_bam_batch_into and gdiet_hip_bgzf_out_write. */
+int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames,
+                                 const char *const *seqs, const char *const *quals, const char *const *comments, const int32_t *lens,
+                                 const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag);
+
 #ifdef __cplusplus
 }
 #endif
