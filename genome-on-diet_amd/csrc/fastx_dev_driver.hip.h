@@ -1,6 +1,7 @@
 // Driver of the device mode of the reader (fastx_dev.hip.h); included by gdiet_hip.hip behind fastx_reader.h and map_pipeline.hip.h
 // (needs gdiet_ctx, gdiet_read_batch, gd_parallel_for, GdFastx).  Two pieces:
 //   GdFxExecutor::parse   a block of the file -> the record table of its strict prefix (count, scan, write, record pass);
+//   (bam_in_driver.hip.h  a BAM block's records -> their text, on the device and in the chunk's arena: GdFxExecutor::bam_unpack)
 //   gd_fx_build_batch     the reads read_batch selected -> a gdiet_read_batch, what gdiet_hip_batch_upload would have built of their
 //                         strings: reads of device-parsed chunks are encoded by the encode kernel from the blocks that are already on
 //                         the device, reads of host-parsed chunks by gd_nt4_encode and a copy, as before.
@@ -212,9 +213,17 @@ static int gd_bz_deflate_device(gdiet_ctx *ctx, const unsigned char *in, size_t 
 	return rc;
 }
 
+// BAM records unpacked on the device (bam_in_driver.hip.h, included behind this file)
+static int gd_bam_in_unpack_device(gdiet_ctx *ctx, const unsigned char *b, size_t n, const GdiRow *rows, size_t n_rows, uint64_t text_len, char *text, std::shared_ptr<void> *keep,
+                                   std::string &why);
+
 struct GdFxExecutor : GdFastxDevice {
 	gdiet_ctx *ctx;
 	explicit GdFxExecutor(gdiet_ctx *c) : ctx(c) {}
+	int bam_unpack(const unsigned char *b, size_t n, const GdiRow *rows, size_t n_rows, uint64_t text_len, char *text, std::shared_ptr<void> &dev, std::string &why) override
+	{
+		return gd_bam_in_unpack_device(ctx, b, n, rows, n_rows, text_len, text, &dev, why);
+	}
 	int inflate(const unsigned char *raw, size_t raw_len, const GdBgzfMember *m, size_t n, unsigned char *dst, size_t dst_len, uint32_t *out_len, std::string &why) override
 	{
 		return gd_bz_inflate_device(ctx, raw, raw_len, m, n, dst, dst_len, out_len, why);

@@ -18,6 +18,11 @@
 // without a BC subfield in the middle of such a file (mixed streams are not read: GDIET_BGZF=0, read at open, sends every file through
 // gzread, as do stdin, single-stream gzip and a BGZF file without its end marker).  A read error surfaces when the block that holds it is
 // taken, so the number of reads of earlier blocks handed out before it is not gzread's count, which stops at the failing byte.
+//
+// BAM input (bam_in.h) is a second grammar behind the same three sources: a stream whose first four bytes are "BAM\1" is walked record by
+// record (parse_bam) in place of parse_range / find_seam, and every kept record's SEQ and QUAL are unpacked into the chunk's arena -- by the
+// reader's threads, records side by side, or, attached, by GdFastxDevice::bam_unpack.  Chunks, batches and detaching are the same.  A
+// malformed record is a read error that surfaces behind the records in front of it (GdFastxChunk::fail).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -39,6 +44,7 @@
 #include <sys/stat.h>
 #include "fastx_dev.h"
 #include "bgzf.h"
+#include "bam_in.h"
 
 // Record parser over a byte range held in memory (kseq_read's grammar); the reader below feeds it blocks of the file.
 struct GdFastxParser {
@@ -158,6 +164,7 @@ struct GdFastxChunk {
 	std::vector<uint8_t> err;     // per record: a malformed record (kseq_read < -1) FOLLOWED this one ...
 	bool err_first = false;       // ... or preceded the first one
 	size_t next = 0;              // records handed out so far
+	std::string fail;             // BAM: a malformed record followed the last one of this chunk: the read error once they are handed out
 };
 
 // What parses the strict prefix of a block (fastx_dev.h) somewhere else.  parse() fills rec with the records [0, n_acc) of b[0, n) and
@@ -172,6 +179,14 @@ struct GdFastxDevice {
 	{
 		(void)raw, (void)raw_len, (void)m, (void)n, (void)dst, (void)dst_len, (void)out_len;
 		why = "this device does not inflate";
+		return -1;
+	}
+	// BAM: the text of the rows (bam_in.h; already checked against the block b[0, n)) into text[0, text_len); dev keeps the device's copy
+	// of the text and a GdxRec table over it for the batches.  0; -1 with the reason in why when the device failed (dev_error).
+	virtual int bam_unpack(const unsigned char *b, size_t n, const GdiRow *rows, size_t n_rows, uint64_t text_len, char *text, std::shared_ptr<void> &dev, std::string &why)
+	{
+		(void)b, (void)n, (void)rows, (void)n_rows, (void)text_len, (void)text, (void)dev;
+		why = "this device does not unpack BAM";
 		return -1;
 	}
 };
@@ -210,6 +225,10 @@ struct GdFastx {
 	std::vector<std::shared_ptr<GdFastxChunk>> pool; // used chunks, kept for their memory (fresh pages cost several times the parsing)
 	std::mutex pool_mu;
 	bool with_qual = true, with_comment = false, flags_set = false;
+	// BAM (bam_in.h): format is decided on the first four bytes of the stream (-1: not yet; 0: FASTA / FASTQ; 1: BAM)
+	int format = -1;
+	bool bam_header_done = false;
+	uint64_t bam_base = 0, bam_ordinal = 0; // stream offset of bp[0]; records walked so far
 	std::vector<const char *> v_name, v_comment, v_seq, v_qual;
 	std::vector<int32_t> v_len;
 	std::vector<int32_t> v_chunk, v_rec; // where read i of the batch came from: lent[v_chunk[i]], its record v_rec[i]
@@ -422,7 +441,7 @@ struct GdFastx {
 			if (!pool.empty()) c = std::move(pool.back()), pool.pop_back();
 		}
 		if (!c) c.reset(new GdFastxChunk());
-		c->arena.clear(), c->off.clear(), c->len.clear(), c->err.clear(), c->err_first = false, c->next = 0;
+		c->arena.clear(), c->off.clear(), c->len.clear(), c->err.clear(), c->err_first = false, c->next = 0, c->fail.clear();
 		c->rec.clear(), c->dev.reset(), c->on_device = false, c->text = nullptr; // (buf keeps its memory for the next block it takes over)
 		return c;
 	}
@@ -463,6 +482,86 @@ struct GdFastx {
 		parts.push_back(std::move(c));
 		return from;
 	}
+	// BAM: the records of the current block become one chunk; returns where the block's tail starts.  The walk is sequential and stays on
+	// the host; the rows it yields are independent, so their text is written side by side: by the device (one D2H copy becomes the front
+	// of the arena, and the device's copy stays with the chunk for the resident batch), or by n_threads host threads.  Names and comments
+	// are the host's on both routes: they go behind the text.  The end of the file inside a record (or inside the header) is the
+	// malformed record of the FASTQ grammar (GDIET_W_TRUNCATED); a record that contradicts itself ends the file with a read error.
+	size_t parse_bam(std::vector<std::shared_ptr<GdFastxChunk>> &parts)
+	{
+		std::shared_ptr<GdFastxChunk> c = fresh_chunk();
+		auto done = [&](size_t pos) {
+			if (!c->fail.empty()) file_end = true, pos = fill; // nothing behind a malformed record is read
+			parts.push_back(std::move(c));
+			return pos;
+		};
+		if (fill >= ((size_t)1 << 31)) { c->fail = "BAM: a record, or the header, of 2 GiB or more"; return done(fill); } // (the tables hold 32-bit offsets)
+		uint64_t from = 0;
+		if (!bam_header_done) {
+			const int h = gdi_header(bp, fill, &from, c->fail);
+			if (h > 0) {
+				if (file_end) c->err_first = true;
+				return done(file_end ? fill : 0);
+			}
+			if (h < 0) return done(fill);
+			bam_header_done = true;
+		}
+		GdiWalk W;
+		gdi_walk(bp, (size_t)from, fill, with_qual, with_comment, bam_ordinal, bam_base, W);
+		bam_ordinal += W.n_seen;
+		const size_t n = W.rows.size(), nt = (size_t)std::max(1, n_threads);
+		const bool on_dev = dev && !dev_error && n > 0 && W.text_len < ((uint64_t)1 << 32);
+		if (n) {
+			std::string &A = c->arena;
+			A.resize((size_t)(W.text_len + W.names_len));
+			if (on_dev) {
+				std::string why;
+				if (!gdi_rows_inside(W.rows.data(), n, fill, W.text_len)) why = "BAM: a table row outside its block";
+				if (!why.empty() || dev->bam_unpack(bp, fill, W.rows.data(), n, W.text_len, &A[0], c->dev, why) < 0) {
+					dev_error = true, io_msg = why, c->fail = why; // (nothing continues on the host for this file)
+					c->dev.reset(), c->arena.clear();
+					return done(fill);
+				}
+			}
+			// ranges of rows for the threads: the text (host route), the names, and the comments, which each range collects for itself
+			const size_t n_rng = std::min(n, nt * 4);
+			std::vector<std::string> cm(with_comment ? n_rng : 0);
+			std::vector<int64_t> cm_off(with_comment ? n : 0, -1);
+			uint8_t *text = (uint8_t *)&A[0];
+			bz_parallel(nt, n_rng, [&](size_t g, size_t) {
+				for (size_t k = n * g / n_rng; k < n * (g + 1) / n_rng; ++k) {
+					const GdiHostRow &H = W.host[k];
+					if (!on_dev) gdi_unpack(W.rows[k], bp, text, 0, 1);
+					memcpy(text + W.text_len + H.name_dst, bp + H.name_off, H.l_name);
+					if (with_comment && H.aux_len) {
+						cm_off[k] = (int64_t)cm[g].size();
+						gdi_aux_text(bp + H.aux_off, H.aux_len, cm[g]);
+						cm[g].push_back('\0');
+					}
+				}
+			});
+			c->off.resize(4 * n), c->len.resize(n), c->err.assign(n, 0);
+			for (size_t g = 0; g < cm.size(); ++g) {
+				for (size_t k = n * g / n_rng; k < n * (g + 1) / n_rng; ++k) if (cm_off[k] >= 0) cm_off[k] += (int64_t)A.size();
+				A += cm[g];
+			}
+			for (size_t k = 0; k < n; ++k) {
+				const GdiRow &R = W.rows[k];
+				int64_t *o = c->off.data() + 4 * k;
+				o[0] = (int64_t)(W.text_len + W.host[k].name_dst), o[1] = with_comment ? cm_off[k] : -1;
+				o[2] = (int64_t)R.dst, o[3] = (R.flags & GDI_NOQUAL) ? -1 : (int64_t)(R.dst + R.l_seq + 1);
+				c->len[k] = (int32_t)R.l_seq;
+			}
+			if (on_dev) c->text = A.data(), c->on_device = true, n_rec_device += (int64_t)n; // (the arena does not change any more)
+			else n_rec_host += (int64_t)n;
+		}
+		if (W.bad) c->fail = W.msg;
+		else if (file_end && W.pos < fill) { // the input ends inside a record
+			if (n) c->err[n - 1] = 1; else c->err_first = true;
+			W.pos = fill;
+		}
+		return done(W.pos);
+	}
 	// read and parse one more block; false when the input is exhausted
 	bool parse_more()
 	{
@@ -478,55 +577,74 @@ struct GdFastx {
 				if (io_dev_err) dev_error = true;
 			} else take_prefetched();
 			if (fill == 0) return false;
-			// split points: record starts verified by look-ahead; whether they ARE boundaries of the sequential grammar is checked
-			// afterwards (every stretch must end exactly where the next one began) -- if not, the rest is parsed again in sequence
-			std::vector<size_t> cut(1, 0);
-			std::vector<std::shared_ptr<GdFastxChunk>> dparts;
-			if (dev && !dev_error) cut[0] = parse_on_device(dparts); // the rest goes through parse_range in sequence, as behind a wrong seam
-			else if (n_threads > 1 && fill >= std::min<size_t>((size_t)1 << 20, block_size))
-				for (int k = 1; k < n_threads; ++k) {
-					const size_t c = find_seam(std::max(cut.back() + 1, fill / (size_t)n_threads * (size_t)k));
-					if (c >= fill) break;
-					cut.push_back(c);
-				}
-			const size_t nr = cut.size();
-			std::vector<std::shared_ptr<GdFastxChunk>> parts(nr);
-			std::vector<size_t> endpos(nr, 0);
-			auto work = [&](size_t k) {
-				parts[k] = fresh_chunk();
-				endpos[k] = parse_range(*parts[k], cut[k], k + 1 < nr ? cut[k + 1] : fill, file_end);
-			};
-			if (nr > 1) {
-				std::vector<std::thread> th;
-				for (size_t k = 1; k < nr; ++k) th.emplace_back(work, k);
-				work(0);
-				for (auto &t : th) t.join();
-			} else work(0);
-			size_t good = 1; // stretches [0, good) are what a sequential parse would have produced
-			while (good < nr && endpos[good - 1] == cut[good]) ++good;
-			size_t pos = endpos[good - 1];
-			if (getenv("GDIET_FASTX_TRACE")) fprintf(stderr, "[fastx] block %zu bytes, %zu stretches, %zu good, file_end %d\n", fill, nr, good, (int)file_end);
-			if (good < nr) { // a seam was no boundary: everything after the last good stretch again, in sequence
-				parts.resize(good + 1);
-				parts[good] = fresh_chunk();
-				pos = parse_range(*parts[good], endpos[good - 1], fill, file_end);
+			if (format < 0) { // the first bytes of the stream decide; fewer than four of them with more to come: read on
+				const bool is_bam = fill >= 4 && !memcmp(bp, "BAM\1", 4);
+				if (fill >= 4 || file_end || memcmp(bp, "BAM\1", fill)) format = is_bam ? 1 : 0;
 			}
-			size_t n_rec = 0;
-			for (auto &c : parts) if (c) n_rec_host += (int64_t)c->len.size();
+			std::vector<std::shared_ptr<GdFastxChunk>> parts;
+			size_t pos = 0;
+			if (format == 1) pos = parse_bam(parts);
+			else if (format == 0) pos = parse_fastx(parts);
 			++n_blocks;
-			if (!dparts.empty()) {
-				for (auto &c : parts) if (c && (!c->len.empty() || c->err_first)) { ++n_blocks_handed; break; }
-				parts.insert(parts.begin(), dparts.begin(), dparts.end());
+			size_t n_rec = 0;
+			for (auto &c : parts) if (c) {
+				const bool any = !c->len.empty() || c->err_first || !c->fail.empty();
+				n_rec += c->len.size() + (c->err_first ? 1 : 0) + (c->fail.empty() ? 0 : 1);
+				if (any) ready.push_back(std::move(c)); else if (pool.size() < 64) pool.push_back(std::move(c));
 			}
-			for (auto &c : parts) if (c) { n_rec += c->len.size() + (c->err_first ? 1 : 0); if (!c->len.empty() || c->err_first) ready.push_back(std::move(c)); else if (pool.size() < 64) pool.push_back(std::move(c)); }
 			// the unparsed tail (a record cut off by the block end) goes in front of the next stretch of the file, which is read while
 			// the caller works on what was parsed
 			if (file_end && pos >= fill) { fill = 0, io_pending = false; return n_rec > 0; }
 			if (!n_rec && !file_end) want *= 2; // a record longer than the block: read on, in bigger steps
 			if (!n_rec && file_end) { fill = 0, io_pending = false; return false; } // (only separators / a malformed rest were left)
+			if (format == 1) bam_base += pos;
 			prefetch(pos, want);
 			if (n_rec) return true;
 		}
+	}
+	// FASTA / FASTQ: the records of the current block as chunks in file order; returns where the block's tail starts
+	size_t parse_fastx(std::vector<std::shared_ptr<GdFastxChunk>> &out)
+	{
+		// split points: record starts verified by look-ahead; whether they ARE boundaries of the sequential grammar is checked
+		// afterwards (every stretch must end exactly where the next one began) -- if not, the rest is parsed again in sequence
+		std::vector<size_t> cut(1, 0);
+		std::vector<std::shared_ptr<GdFastxChunk>> dparts;
+		if (dev && !dev_error) cut[0] = parse_on_device(dparts); // the rest goes through parse_range in sequence, as behind a wrong seam
+		else if (n_threads > 1 && fill >= std::min<size_t>((size_t)1 << 20, block_size))
+			for (int k = 1; k < n_threads; ++k) {
+				const size_t c = find_seam(std::max(cut.back() + 1, fill / (size_t)n_threads * (size_t)k));
+				if (c >= fill) break;
+				cut.push_back(c);
+			}
+		const size_t nr = cut.size();
+		std::vector<std::shared_ptr<GdFastxChunk>> parts(nr);
+		std::vector<size_t> endpos(nr, 0);
+		auto work = [&](size_t k) {
+			parts[k] = fresh_chunk();
+			endpos[k] = parse_range(*parts[k], cut[k], k + 1 < nr ? cut[k + 1] : fill, file_end);
+		};
+		if (nr > 1) {
+			std::vector<std::thread> th;
+			for (size_t k = 1; k < nr; ++k) th.emplace_back(work, k);
+			work(0);
+			for (auto &t : th) t.join();
+		} else work(0);
+		size_t good = 1; // stretches [0, good) are what a sequential parse would have produced
+		while (good < nr && endpos[good - 1] == cut[good]) ++good;
+		size_t pos = endpos[good - 1];
+		if (getenv("GDIET_FASTX_TRACE")) fprintf(stderr, "[fastx] block %zu bytes, %zu stretches, %zu good, file_end %d\n", fill, nr, good, (int)file_end);
+		if (good < nr) { // a seam was no boundary: everything after the last good stretch again, in sequence
+			parts.resize(good + 1);
+			parts[good] = fresh_chunk();
+			pos = parse_range(*parts[good], endpos[good - 1], fill, file_end);
+		}
+		for (auto &c : parts) if (c) n_rec_host += (int64_t)c->len.size();
+		if (!dparts.empty()) {
+			for (auto &c : parts) if (c && (!c->len.empty() || c->err_first)) { ++n_blocks_handed; break; }
+			parts.insert(parts.begin(), dparts.begin(), dparts.end());
+		}
+		out.swap(parts);
+		return pos;
 	}
 	// U -> T in the host strings of the last batch's reads from device-parsed chunks (kseq2bseq, LR/bseq.c:71-73; read_record does it
 	// for the host's own).  For a caller that takes no resident batch: the encode kernel flags the reads that need it otherwise.
@@ -549,11 +667,15 @@ struct GdFastx {
 		int64_t size = 0;
 		bool closing = false; // the batch is full: only mates of its last read may still join (fragment mode)
 		for (;;) {
-			while (!ready.empty() && ready.front()->next >= ready.front()->len.size() && !ready.front()->err_first) ready.pop_front();
+			while (!ready.empty() && ready.front()->next >= ready.front()->len.size() && !ready.front()->err_first && ready.front()->fail.empty()) ready.pop_front();
 			if (ready.empty() && !parse_more()) break;
 			if (ready.empty()) continue;
 			GdFastxChunk &C = *ready.front();
 			if (C.err_first) { C.err_first = false; if (parse_error) *parse_error = true; break; } // the reference warns and returns what it has
+			if (C.next >= C.len.size() && !C.fail.empty()) { // BAM: the malformed record is next: the reads in front of it go out first
+				if (v_len.empty()) io_error = true, io_msg = C.fail;
+				break;
+			}
 			if (C.next >= C.len.size()) continue;
 			const size_t i = C.next;
 			const char *const base = C.base();

@@ -1048,6 +1048,7 @@ extern "C" int gdiet_hip_debug_seed_prof(unsigned long long *out8) { return (int
 // ---- read input (input half) ---------------------------------------------------------------------------
 #include "fastx_reader.h"
 #include "fastx_dev_driver.hip.h" // struct gdiet_fastx; the device mode of the reader
+#include "bam_in_driver.hip.h"    // BAM input: the unpack kernel's driver, gdiet_hip_bam_in_unpack
 static int gd_fx_read_failed(gdiet_fastx *fx);
 
 extern "C" int gdiet_hip_fastx_open(gdiet_fastx **fx, const char *path)
@@ -1118,6 +1119,8 @@ extern "C" int gdiet_hip_fastx_stats(const gdiet_fastx *fx, int64_t *records_dev
 	if (blocks_handed_over) *blocks_handed_over = fx->r->n_blocks_handed;
 	return GDIET_OK;
 }
+
+extern "C" int gdiet_hip_fastx_format(const gdiet_fastx *fx) { return fx && fx->r && fx->r->format == 1 ? 1 : 0; }
 
 // a read error of the reader, kept where gdiet_hip_strerror finds it
 static int gd_fx_read_failed(gdiet_fastx *fx)

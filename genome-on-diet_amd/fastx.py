@@ -11,6 +11,8 @@ class FastxReader:
     """ctx: a Context; the reader is then attached to it (gdiet_hip_fastx_attach): the strict four-line FASTQ records at the front of
     every block are parsed on its device, and read_raw(..., resident=True) returns the resident batch next to the host arrays.  The
     records, batches and truncation flags do not depend on it.  Close the reader before the context.
+    A BAM stream (its first four bytes, decompressed, are BAM\\1) is read record by record in place of the FASTQ grammar: SEQ and QUAL are
+    unpacked on `threads` threads or, with ctx, on the device; format() says which grammar reads the file.
     A BGZF file (a regular file with the BGZF end-of-file member; GDIET_BGZF=0 turns it off) is inflated member by member: on `threads`
     threads, or, with ctx, on the device; bgzf_stats() says by whom."""
 
@@ -38,6 +40,7 @@ class FastxReader:
         L.gdiet_hip_debug_bgzf_seconds.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.gdiet_hip_fastx_strerror.argtypes = [C.c_void_p]
         L.gdiet_hip_fastx_strerror.restype = C.c_char_p
+        L.gdiet_hip_fastx_format.argtypes = [C.c_void_p]
         self.ctx = ctx
         if ctx is not None and L.gdiet_hip_fastx_attach(self._h, ctx._h) != 0:
             raise GdietError("gdiet_hip_fastx_attach failed")
@@ -95,6 +98,10 @@ class FastxReader:
         v = [C.c_int64() for _ in range(4)]
         self.lib.gdiet_hip_fastx_stats(self._h, *[C.byref(x) for x in v])
         return dict(zip(("records_device", "records_host", "blocks", "blocks_handed_over"), (x.value for x in v)))
+
+    def format(self):
+        """gdiet_hip_fastx_format: "bam" when the stream is BAM, else "fastx"; valid after the first read"""
+        return "bam" if self.lib.gdiet_hip_fastx_format(self._h) == 1 else "fastx"
 
     def bgzf_stats(self):
         """gdiet_hip_fastx_bgzf_stats (all zero for a file that did not take the BGZF route), and the I/O thread's seconds per stage"""

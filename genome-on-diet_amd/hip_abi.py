@@ -76,6 +76,8 @@ def load_library():
                                               C.c_int8, C.c_int32, i32p, i32p, u32p, i64p]
     lib.gdiet_hip_ksw_extz2_batch_ex.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, i32p, C.POINTER(KswScore), C.c_int32, C.c_int32, i32p, i32p, u32p, i64p]
     lib.gdiet_hip_bgzf_inflate.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gdiet_hip_bam_in_unpack.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), i64p, i32p, i32p]
+    lib.gdiet_hip_fastx_format.argtypes = [vp]
     lib.gdiet_hip_bgzf_deflate.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     lib.gdiet_hip_bgzf_out_open.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
     lib.gdiet_hip_bgzf_out_write.argtypes = [vp, vp, C.c_size_t]
@@ -132,6 +134,18 @@ class Context:
         out = C.create_string_buffer(max(1, n.value))
         self._check(self.lib.gdiet_hip_bgzf_inflate(self._h, raw, len(raw), C.cast(out, C.c_void_p), n.value, C.byref(n)))
         return out.raw[:n.value]
+
+    def bam_in_unpack(self, records, with_qual=True):
+        """gdiet_hip_bam_in_unpack: whole uncompressed BAM records, unpacked by the device: (text, off, lens) -- off holds four offsets per
+        kept record: name and aux fields (-1: none) in `records`, seq and qual (-1: none) in text"""
+        records = bytes(records)
+        tl, n = C.c_size_t(), C.c_int32()
+        self._check(self.lib.gdiet_hip_bam_in_unpack(self._h, records, len(records), int(with_qual), None, 0, C.byref(tl), None, None, C.byref(n)))
+        text = C.create_string_buffer(max(1, tl.value))
+        off, lens = np.zeros(4 * max(1, n.value), np.int64), np.zeros(max(1, n.value), np.int32)
+        self._check(self.lib.gdiet_hip_bam_in_unpack(self._h, records, len(records), int(with_qual), C.cast(text, C.c_void_p), tl.value, C.byref(tl), _ptr(off, C.c_int64),
+                                                     _ptr(lens, C.c_int32), C.byref(n)))
+        return text.raw[:tl.value], off[:4 * n.value].reshape(-1, 4), lens[:n.value]
 
     def bgzf_deflate(self, data, eof=True):
         """gdiet_hip_bgzf_deflate: data cut into members of 65280 bytes, each compressed by one wavefront of the device into a complete

@@ -542,6 +542,44 @@ const char *gdiet_hip_fastx_strerror(const gdiet_fastx *fx);
  * out_cap too small, or a member's error; the context stays usable. */
 int gdiet_hip_bgzf_inflate(gdiet_ctx *ctx, const uint8_t *raw, size_t raw_len, uint8_t *out, size_t out_cap, size_t *out_len);
 
+/* BAM input.  No call selects it and no switch: a source whose first four bytes, after decompression, are "BAM\1" is BAM -- on the BGZF
+ * route, through gzread (BGZF without its end marker, stdin) and as a raw uncompressed stream alike; GDIET_BGZF=0 still only selects the
+ * inflater.  The reads are DEFINED as the records gdiet_hip_fastx_read returns for the FASTQ equivalent of the file:
+ *   header    consumed, not returned: l_text, the text, n_ref, and l_name, name, l_ref per reference; it may be longer than a reader block.
+ *   records   every alignment record is one read, in file order, except records with FLAG 0x100 or 0x800 (secondary, supplementary),
+ *             which are skipped as `samtools fastq` skips them.  CIGAR and reference fields are passed over.
+ *   name      read_name up to its NUL.      len   l_seq; 0 gives an empty string.
+ *   seq       the l_seq letters of "=ACMGRSVTWYHKDBN".
+ *   qual      (qual[i] + 33) mod 256 per base; NULL when the first quality byte is 0xFF, when l_seq is 0 and when the reader was opened
+ *             with with_qual == 0.
+ *   FLAG 0x10 the sequence is reverse-complemented and the quality reversed: the read is the one the instrument produced.  The complement
+ *             is the BAM writer's (csrc/bam_record.h), which is the 4-bit reversal of the code (csrc/bam_in.h proves it at compile time),
+ *             so this library's own BAM output, read back, gives the reads that went in.
+ *   comment   only with with_comment: the record's aux fields as SAM text, in record order, joined by tabs; NULL when there are none.
+ *             Every integer type prints as i; f as the shortest decimal text, without exponent, whose float32 it is ("nan", "inf",
+ *             "-inf"); A, Z, H verbatim; B as its subtype and comma-separated values.  A comment is thus a list of SAM tags, which is
+ *             what -y into SAM or BAM output needs.  Made on host threads.
+ * Batching is that of FASTQ input (mates in fragment mode are consecutive records with equal names).  Input that ends inside the header
+ * or inside a record gives GDIET_W_TRUNCATED with the records before it.  A record that contradicts itself is a read error
+ * (GDIET_E_PARAM) that surfaces behind the reads in front of it: a block_size below 32; fields that do not fit their record
+ * (32 + l_read_name + 4 n_cigar_op + ceil(l_seq / 2) + l_seq > block_size); l_read_name == 0; a name without its NUL; a negative l_seq;
+ * a negative count in the header; and, only when comments are asked for, an aux field that runs past the record or has no known type.
+ * A record is judged once all of its block_size bytes are there.  gdiet_hip_fastx_strerror then reads "BAM record <k> at offset <o>: ..."
+ * with k counting every record of the file from 0 and o the offset of its block_size field in the decompressed stream.
+ * Unattached, SEQ and QUAL are unpacked on the reader's threads, records side by side; attached, by bam_unpack_kernel, one wavefront per
+ * record (csrc/bam_in.hip.h), and gdiet_hip_fastx_read_resident builds the resident batch from the text that is already on the device.
+ * gdiet_hip_fastx_stats counts the records of either route as records_device / records_host.  Out of scope: CRAM, SAM text input,
+ * index-driven region reads, and keeping the inflated block resident between inflate and unpack. */
+/* 0: the reader reads FASTA / FASTQ; 1: BAM.  Valid after the first read. */
+int gdiet_hip_fastx_format(const gdiet_fastx *fx);
+/* The kernel-level boundary of the unpack step: recs[0, len) must be whole uncompressed alignment records (no header).  They are walked
+ * on the host, unpacked on the device and copied back: text holds seq NUL [qual NUL] per kept record, off four offsets per kept record
+ * -- name and aux fields in recs (-1: no aux field), seq and qual in text (-1: no quality) -- and lens its l_seq.  *text_len and *n_reads
+ * are always set; with text, off and lens all NULL nothing else happens (sizes first).  GDIET_E_PARAM with a message in
+ * gdiet_hip_strerror for a malformed record, a range that ends inside a record or text_cap too small; GDIET_E_HIP if the device fails. */
+int gdiet_hip_bam_in_unpack(gdiet_ctx *ctx, const uint8_t *recs, size_t len, int with_qual, char *text, size_t text_cap, size_t *text_len, int64_t *off, int32_t *lens,
+                            int32_t *n_reads);
+
 /* BGZF output.  The kernel-level boundary of the compressor: in[0, in_len) is cut into members of 65280 input bytes (the last one
  * shorter), every member is compressed by one wavefront of the device (csrc/bgzf_deflate.hip.h: LZ77 match search, dynamic, fixed or
  * stored DEFLATE blocks, CRC32) and the complete members -- header with BC subfield and BSIZE, stream, CRC32, ISIZE -- are written one

@@ -1,8 +1,8 @@
-"""Steps 0-2 of the reference's worker_pipeline through the library: FASTA/FASTQ file -> mini-batches (gdiet_hip_fastx_read) ->
+"""Steps 0-2 of the reference's worker_pipeline through the library: FASTA/FASTQ or unaligned BAM file -> mini-batches (gdiet_hip_fastx_read) ->
 map with several batches in flight (gdiet_hip_map_submit / _wait) -> SAM records (gdiet_hip_sam_batch) -> output file.
 No Python object is made per read: the C arrays of the reader go straight into the upload and the SAM formatter.
 
-    python tools/map_file.py --preset sr ref.fa reads.fq[.gz] -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
+    python tools/map_file.py --preset sr ref.fa reads.fq[.gz] | reads.bam -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
                              [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
                              [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam]
 
@@ -13,6 +13,8 @@ whole reads on supplementary records, long CIGARs in the CG tag, the FASTQ comme
 qualities (not even read: with_qual off), no record for an unmapped read.
 --device-reader attaches the reader to the context (gdiet_hip_fastx_attach): four-line FASTQ is parsed and encoded on the device, the
 reader hands out resident batches, and the upload stage disappears; the output is the same, and the JSON line gains reader_stats.
+A BAM file is read like FASTQ, with no option: the reader sees BAM\1 at the start of the decompressed stream (reads_format in the JSON
+line says "bam").  Its records' aux fields are the comment -y copies; with --device-reader SEQ and QUAL are unpacked by the device.
 --bgzf writes -o, the --header text included, as BGZF (BgzfWriter): `device` compresses every member of 65280 bytes on one wavefront of
 the GPU, `host` with zlib at --bgzf-level on --bgzf-threads threads; the JSON line gains bgzf_out.  Without it nothing changes.
 --bam writes -o as BAM: the header always (gdiet_hip_bam_header), then the records of every batch, encoded on the device
@@ -167,6 +169,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
         th_r.join()
         map_file.last_reader_stats = fx.stats()
         map_file.last_bgzf_stats = fx.bgzf_stats()
+        map_file.last_format = fx.format()
         fx.close()
     if errors:
         raise errors[0]
@@ -248,7 +251,7 @@ def main():
         sys.exit(1)
     print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), "mini_batch_bases": chunk,
                       "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "eqx": a.eqx, "out": a.out, "caller_seconds": map_file.last_stage_seconds,
-                      **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats,
+                      **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats, "reads_format": map_file.last_format,
                       **({"bgzf_out": dict(bgzf_out.stats(), route=a.bgzf, device_seconds=[round(x, 4) for x in ctx.bgzf_deflate_seconds()])} if a.bgzf else {}),
                       **({"bam": True, "bam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.bam else {})}))
     m.close()
