@@ -5,9 +5,9 @@
 // A batch is flattened on the context's host threads (bam_flatten.h: chunks of reads side by side, every chunk with pools of its own,
 // merged by a prefix sum of their sizes), the table and the pools go up, ONE kernel writes every record at its final offset of a resident
 // stream, and then either the stream comes down (gdiet_hip_bam_batch_into) or the BGZF deflate kernel reads it where it is
-// (gdiet_hip_bgzf_out_write_bam on a writer with a context) and only compressed members and the next tail come down.  A stream, events
-// and a lock of the context's own (bam_stream, bam_mu), like the deflate driver: a writer thread encodes batch i while batch i + 1 maps.
-// Failures leave their text with the calling thread (gd_bzd_fail), as the BGZF writing side does.
+// (gdiet_hip_bgzf_out_write_bam on a writer with a context) and only compressed members and the next tail come down.  A lane of the
+// context's own (gdiet_ctx::bam), like the deflate driver: a writer thread encodes batch i while batch i + 1 maps.
+// Failures leave their text with the calling thread (gd_err_fail), as the BGZF writing side does.
 #pragma once
 #include "bam_encode.hip.h"
 #include "bam_flatten.h"
@@ -15,7 +15,7 @@
 // the chunks' pools and the merged table of a batch: the context's (gdiet_ctx::bam_pool), so that they keep their pages from mini-batch to
 // mini-batch -- a mini-batch is some 130 MB of table and text, and a fresh allocation of that size is paid for page by page every time
 struct GdbPool { std::vector<GdbPart> parts; GdbPart all; };
-static GdbPool &gd_bam_pool(gdiet_ctx *ctx) // the caller holds bam_mu
+static GdbPool &gd_bam_pool(gdiet_ctx *ctx) // the caller holds bam.mu
 {
 	if (!ctx->bam_pool) ctx->bam_pool = std::make_shared<GdbPool>();
 	return *static_cast<GdbPool *>(ctx->bam_pool.get());
@@ -32,7 +32,7 @@ static int gd_bam_flatten(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, co
 		if (rc) { why.clear(); return rc; }
 	}
 	const int CH = gd_fmt_chunk(ctx, n_reads), n_ch = (n_reads + CH - 1) / CH;
-	std::vector<GdbPart> &part = gd_bam_pool(ctx).parts; // (the caller holds bam_mu)
+	std::vector<GdbPart> &part = gd_bam_pool(ctx).parts; // (the caller holds bam.mu)
 	if (part.size() < (size_t)n_ch) part.resize((size_t)n_ch);
 	for (int c = 0; c < n_ch; ++c) part[c].clear();
 	std::vector<std::string> err((size_t)n_ch);
@@ -78,64 +78,48 @@ static int gd_bam_flatten(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, co
 template <class Use>
 static int gd_bam_encode_device(gdiet_ctx *ctx, const GdbPart &P, const unsigned char *front, size_t front_len, std::string &why, Use use)
 {
-	(void)hipSetDevice(ctx->device); // (the caller holds bam_mu, from the flattening on: the table it made is the context's)
+	GdLane &L = ctx->bam; // (the caller holds bam.mu, from the flattening on: the table it made is the context's)
+	if (L.ready(ctx->device, 4, "device BAM encoder", why)) return -1;
+	hipStream_t s = L.stream;
 	hipError_t e = hipSuccess;
-	if (!ctx->bam_stream && (e = hipStreamCreateWithFlags(&ctx->bam_stream, hipStreamNonBlocking)) != hipSuccess) {
-		why = std::string("device BAM encoder: stream: ") + hipGetErrorString(e);
-		return -1;
-	}
-	hipStream_t s = ctx->bam_stream;
-	for (hipEvent_t &ev : ctx->bam_ev)
-		if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) { ev = nullptr; why = std::string("device BAM encoder: event: ") + hipGetErrorString(e); return -1; }
-	uint8_t *d_stream = nullptr, *d_text = nullptr, *d_blob = nullptr;
-	uint32_t *d_cig = nullptr;
-	GdbRec *d_rec = nullptr;
-	auto release = [&]() {
-		if (d_stream) (void)hipFreeAsync(d_stream, s);
-		if (d_text) (void)hipFreeAsync(d_text, s);
-		if (d_blob) (void)hipFreeAsync(d_blob, s);
-		if (d_cig) (void)hipFreeAsync(d_cig, s);
-		if (d_rec) (void)hipFreeAsync(d_rec, s);
-	};
+	GdStreamMem mem(s);
+	uint8_t *d_stream, *d_text, *d_blob;
+	uint32_t *d_cig;
+	GdbRec *d_rec;
 	auto fail = [&](hipError_t err, const char *what) {
-		(void)hipStreamSynchronize(s);
-		release();
+		mem.fail();
 		why = std::string("device BAM encoder: ") + what + ": " + hipGetErrorString(err);
 		return -1;
 	};
 	const size_t n = P.rec.size(), total = front_len + (size_t)P.bytes;
 	if ((n + 3) / 4 > 0x7fffffffull) { why = "device BAM encoder: too many records for one launch"; return -1; }
-	if ((e = hipMallocAsync((void **)&d_stream, total + 16, s)) != hipSuccess) return fail(e, "stream buffer");
-	if ((e = hipMallocAsync((void **)&d_text, P.text.size() + 16, s)) != hipSuccess) return fail(e, "read text");
-	if ((e = hipMallocAsync((void **)&d_blob, P.blob.size() + 16, s)) != hipSuccess) return fail(e, "tag blobs");
-	if ((e = hipMallocAsync((void **)&d_cig, sizeof(uint32_t) * P.cig.size() + 16, s)) != hipSuccess) return fail(e, "CIGAR pool");
-	if ((e = hipMallocAsync((void **)&d_rec, sizeof(GdbRec) * n + 16, s)) != hipSuccess) return fail(e, "record table");
-	(void)hipEventRecord(ctx->bam_ev[0], s);
+	if ((e = mem.alloc(&d_stream, total + 16)) != hipSuccess) return fail(e, "stream buffer");
+	if ((e = mem.alloc(&d_text, P.text.size() + 16)) != hipSuccess) return fail(e, "read text");
+	if ((e = mem.alloc(&d_blob, P.blob.size() + 16)) != hipSuccess) return fail(e, "tag blobs");
+	if ((e = mem.alloc(&d_cig, sizeof(uint32_t) * P.cig.size() + 16)) != hipSuccess) return fail(e, "CIGAR pool");
+	if ((e = mem.alloc(&d_rec, sizeof(GdbRec) * n + 16)) != hipSuccess) return fail(e, "record table");
+	(void)hipEventRecord(L.ev[0], s);
 	if (front_len && (e = hipMemcpyAsync(d_stream, front, front_len, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "tail copy");
 	if (!P.text.empty() && (e = hipMemcpyAsync(d_text, P.text.data(), P.text.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "read text copy");
 	if (!P.blob.empty() && (e = hipMemcpyAsync(d_blob, P.blob.data(), P.blob.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "tag blobs copy");
 	if (!P.cig.empty() && (e = hipMemcpyAsync(d_cig, P.cig.data(), sizeof(uint32_t) * P.cig.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "CIGAR pool copy");
 	if (n && (e = hipMemcpyAsync(d_rec, P.rec.data(), sizeof(GdbRec) * n, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "record table copy");
-	(void)hipEventRecord(ctx->bam_ev[1], s);
+	(void)hipEventRecord(L.ev[1], s);
 	if (n) {
 		hipLaunchKernelGGL(bam_encode_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, (const GdbRec *)d_rec, (uint64_t)n, (const uint8_t *)d_text, (const uint32_t *)d_cig,
 		                   (const uint8_t *)d_blob, d_stream + front_len, (uint64_t)P.bytes);
 		if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
 	}
-	(void)hipEventRecord(ctx->bam_ev[2], s);
+	(void)hipEventRecord(L.ev[2], s);
 	if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "kernel");
 	const int rc = use(d_stream, total, s);
-	(void)hipEventRecord(ctx->bam_ev[3], s);
-	if (rc || (e = hipStreamSynchronize(s)) != hipSuccess) {
-		if (!rc) return fail(e, "copy down");
-		(void)hipStreamSynchronize(s), release();
-		return -1;
-	}
+	(void)hipEventRecord(L.ev[3], s);
+	if (rc) { mem.fail(); return -1; } // (why is use()'s)
+	if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "copy down");
 	for (int i = 0; i < 3; ++i) { // (for measurements: gdiet_hip_debug_bam_seconds)
 		float ms = 0;
-		if (hipEventElapsedTime(&ms, ctx->bam_ev[i], ctx->bam_ev[i + 1]) == hipSuccess) ctx->bam_ms[i] += ms;
+		if (hipEventElapsedTime(&ms, L.ev[i], L.ev[i + 1]) == hipSuccess) L.ms[i] += ms;
 	}
-	release();
 	return 0;
 }
 
@@ -164,18 +148,18 @@ extern "C" int64_t gdiet_hip_bam_batch_into(gdiet_ctx *ctx, const gdiet_index *i
                                             size_t *cap)
 {
 	if (!gd_bam_args_ok(ctx, ix, n_reads, qnames, seqs, lens, n_regs, regs) || !buf || !cap) return GDIET_E_PARAM;
-	gd_ds_clear_mark();
-	std::lock_guard<std::mutex> lk(ctx->bam_mu);
+	gd_err_clear();
+	std::lock_guard<std::mutex> lk(ctx->bam.mu);
 	GdbPart &P = gd_bam_pool(ctx).all;
 	std::string why;
 	int rc = gd_bam_flatten(ctx, ix, n_reads, qnames, seqs, quals, comments, lens, n_regs, regs, opt_flag, P, why);
-	if (rc) return why.empty() ? rc : gd_bzd_fail(ctx, rc, "gdiet_hip_bam_batch_into: " + why);
+	if (rc) return why.empty() ? rc : gd_err_fail(ctx, rc, "gdiet_hip_bam_batch_into: " + why);
 	const size_t tot = (size_t)P.bytes;
 	if (tot == 0) return 0;
 	if (!*buf || *cap < tot + 1) {
 		const size_t want = tot + 1 + (tot >> 3);
 		char *nb = (char *)realloc(*buf, want);
-		if (!nb) return gd_bzd_fail(ctx, GDIET_E_NOMEM, "gdiet_hip_bam_batch_into: out of host memory");
+		if (!nb) return gd_err_fail(ctx, GDIET_E_NOMEM, "gdiet_hip_bam_batch_into: out of host memory");
 		*buf = nb, *cap = want;
 	}
 	char *dst = *buf;
@@ -184,7 +168,7 @@ extern "C" int64_t gdiet_hip_bam_batch_into(gdiet_ctx *ctx, const gdiet_index *i
 		if (e != hipSuccess) { why = std::string("device BAM encoder: copy down: ") + hipGetErrorString(e); return -1; }
 		return 0;
 	});
-	if (rc) return gd_bzd_fail(ctx, GDIET_E_HIP, "gdiet_hip_bam_batch_into: " + why);
+	if (rc) return gd_err_fail(ctx, GDIET_E_HIP, "gdiet_hip_bam_batch_into: " + why);
 	dst[tot] = 0;
 	return (int64_t)tot;
 }
@@ -194,7 +178,7 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
                                             int64_t opt_flag)
 {
 	if (!h || !gd_bam_args_ok(ctx, ix, n_reads, qnames, seqs, lens, n_regs, regs) || (h->ctx && h->ctx != ctx)) return GDIET_E_PARAM;
-	gd_ds_clear_mark();
+	gd_err_clear();
 	if (!h->ctx) { // a host writer: the records come down and go through write()
 		char *buf = nullptr;
 		size_t cap = 0;
@@ -205,11 +189,11 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 		return rc;
 	}
 	if (h->w.failed || h->w.fd < 0) return gd_bzo_done(h, -1);
-	std::lock_guard<std::mutex> lk(ctx->bam_mu);
+	std::lock_guard<std::mutex> lk(ctx->bam.mu);
 	GdbPart &P = gd_bam_pool(ctx).all;
 	std::string why;
 	int rc = gd_bam_flatten(ctx, ix, n_reads, qnames, seqs, quals, comments, lens, n_regs, regs, opt_flag, P, why);
-	if (rc) return why.empty() ? rc : gd_bzd_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why);
+	if (rc) return why.empty() ? rc : gd_err_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why);
 	if (P.bytes == 0) return GDIET_OK;
 	// the waiting tail in front, the records behind it; every whole member is compressed from there, the rest comes down as the next tail
 	GdBgzfOut &w = h->w;
@@ -236,7 +220,7 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 extern "C" int gdiet_hip_debug_bam_seconds(gdiet_ctx *ctx, double *out3)
 {
 	if (!ctx || !out3) return GDIET_E_PARAM;
-	std::lock_guard<std::mutex> lk(ctx->bam_mu);
-	for (int i = 0; i < 3; ++i) out3[i] = 1e-3 * ctx->bam_ms[i];
+	std::lock_guard<std::mutex> lk(ctx->bam.mu);
+	for (int i = 0; i < 3; ++i) out3[i] = 1e-3 * ctx->bam.ms[i];
 	return GDIET_OK;
 }

@@ -18,6 +18,7 @@
 #include <sched.h>
 
 #include "../../include/gdiet_hip.h"
+#include "err_mark.h"
 #include "ksw_common.h"
 #include "ksw_generic.hip.h"
 #include "ksw_backtrack.hip.h"
@@ -46,6 +47,56 @@ struct DevBuf {
 		p = nullptr, cap = 0;
 		return e;
 	}
+};
+
+// A side lane of a context: a pass that runs beside the mapping path (difference strings, the reader's device mode, BGZF inflate and
+// deflate, the BAM encoder) on a stream of its own behind a mutex of its own, so that its caller's thread never waits for a map call or an
+// open ticket.  The stream and the events are made on first use and go with the context (gdiet_hip_destroy walks the lanes).
+struct GdLane {
+	std::mutex mu;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // around the steps of a call; a lane uses the first n_events
+	double ms[3] = {0, 0, 0};                                                   // sums of their intervals since the context was created (under mu)
+	// the caller holds mu.  0, or -1 with why = "<prefix>: stream: ..." / "<prefix>: event: ..."
+	int ready(int device, int n_events, const char *prefix, std::string &why)
+	{
+		(void)hipSetDevice(device);
+		hipError_t e = hipSuccess;
+		if (!stream && (e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) != hipSuccess) {
+			why = std::string(prefix) + ": stream: " + hipGetErrorString(e);
+			return -1;
+		}
+		for (int i = 0; i < n_events; ++i)
+			if (!ev[i] && (e = hipEventCreate(&ev[i])) != hipSuccess) { ev[i] = nullptr; why = std::string(prefix) + ": event: " + hipGetErrorString(e); return -1; }
+		return 0;
+	}
+};
+
+// The stream-ordered allocations of one call on one stream (a plain hipMalloc / hipFree would synchronise every batch in flight).  What
+// the call has not released or freed by its end is freed behind whatever it enqueued.  A call that fails with copies still in flight
+// into its host vectors calls fail() first: the stream is synchronised before those vectors go out of scope.
+struct GdStreamMem {
+	hipStream_t s;
+	std::vector<void *> held;
+	explicit GdStreamMem(hipStream_t stream) : s(stream) {}
+	GdStreamMem(const GdStreamMem &) = delete;
+	GdStreamMem &operator=(const GdStreamMem &) = delete;
+	~GdStreamMem() { drop(); }
+	template <class T> hipError_t alloc(T **p, size_t bytes)
+	{
+		const hipError_t e = hipMallocAsync((void **)p, bytes, s);
+		if (e == hipSuccess) held.push_back((void *)*p);
+		else *p = nullptr;
+		return e;
+	}
+	void release(const void *p) { held.erase(std::remove(held.begin(), held.end(), p), held.end()); } // p outlives the call: its new owner frees it
+	void free_now(const void *p) { release(p), (void)hipFreeAsync(const_cast<void *>(p), s); }
+	void drop()
+	{
+		for (void *p : held) (void)hipFreeAsync(p, s);
+		held.clear();
+	}
+	void fail() { (void)hipStreamSynchronize(s), drop(); }
 };
 
 #define GD_MAX_INFLIGHT 8 // batches in flight per context (gdiet_hip_set_inflight)
@@ -119,37 +170,22 @@ struct gdiet_ctx {
 	// with n_regs = 0 while the rest of the batch is mapped.  failed_total: since the context was created.
 	int64_t failed_last = 0, failed_total = 0;
 	std::string warn;                  // what the last such read was (gdiet_hip_map_failed_reads)
-	// cs / MD difference strings (map_diffstr_driver.hip.h): a stream and buffers of their own behind a mutex of their own, because the
-	// formatters call it from a writer thread while map tickets are open on the other streams
-	std::mutex ds_mu;
-	std::string ds_err;                // text of the last failing difference-string pass (written under ds_mu; gdiet_hip_strerror)
-	hipStream_t ds_stream = nullptr;
-	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff;
-	std::vector<uint8_t> ds_enc;       // host copy of the reads a call without a resident batch encodes
-	// FASTQ blocks parsed on the device (fastx_dev.hip.h; the driver is at the end of this file): like the difference strings, a stream,
-	// a scan buffer and a mutex of their own, because the reader thread of a file route calls it while map tickets are open
-	std::mutex fx_mu;
-	std::string fx_err;                // text of the last failing device parse (written under fx_mu; gdiet_hip_strerror)
-	hipStream_t fx_stream = nullptr;
-	DevBuf fx_scan;
-	// BGZF members inflated on the device (bgzf_inflate.hip.h): a stream and a mutex of their own again, because the reader's I/O thread
-	// inflates the next block while its reader thread parses the current one under fx_mu
-	std::mutex bz_mu;
-	hipStream_t bz_stream = nullptr;
-	hipEvent_t bz_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three steps of a read: copy up, kernel, copy down
-	double bz_ms[3] = {0, 0, 0};                                // ... and their sums since the context was created (under bz_mu)
-	// BGZF members written on the device (bgzf_deflate.hip.h): a stream and a mutex of their own once more, because a writer thread
-	// compresses the SAM text of batch i while batch i + 1 maps
-	std::mutex bzd_mu;
-	hipStream_t bzd_stream = nullptr;
-	hipEvent_t bzd_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // copy up | deflate kernel || pack kernel | copy down
-	double bzd_ms[3] = {0, 0, 0};      // sums since the context was created: copy up, the two kernels, copy down (under bzd_mu)
-	// BAM records encoded on the device (bam_encode.hip.h, bam_driver.hip.h): a stream and a mutex of their own, for the same writer thread
-	std::mutex bam_mu;
-	hipStream_t bam_stream = nullptr;
-	hipEvent_t bam_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // copy up | encode kernel | copy down
-	double bam_ms[3] = {0, 0, 0};      // their sums since the context was created (under bam_mu)
-	std::shared_ptr<void> bam_pool;    // GdbPool (bam_driver.hip.h): the flattened chunks of a batch and their merged table, kept from call to call (under bam_mu)
+	// The side lanes (GdLane), each one apart from the mapping path's streams and from the others because:
+	//   ds   cs / MD difference strings (map_diffstr_driver.hip.h): the formatters call it from a writer thread while map tickets are open
+	//   fx   FASTQ blocks parsed and BAM blocks unpacked on the device (fastx_dev_driver.hip.h, bam_in_driver.hip.h): the reader thread of a
+	//        file route calls it while map tickets are open
+	//   bz   BGZF members inflated on the device (bgzf_driver.hip.h): the reader's I/O thread inflates the next block while its reader
+	//        thread parses the current one under fx.mu.  ev[0..3]: copy up | kernel | copy down
+	//   bzd  BGZF members written on the device (bgzf_driver.hip.h): a writer thread compresses the text of batch i while batch i + 1 maps
+	//        and the reader inflates.  ev[0..5]: copy up | deflate kernel || pack kernel | copy down; ms: copy up, the two kernels, copy down
+	//   bam  BAM records encoded on the device (bam_driver.hip.h): the same writer thread encodes batch i while batch i + 1 maps; it takes
+	//        bam.mu, then bzd.mu when the deflate kernel reads the records where they are.  ev[0..3]: copy up | encode kernel | copy down
+	GdLane ds, fx, bz, bzd, bam;
+	template <class F> void each_lane(F f) { f(ds), f(fx), f(bz), f(bzd), f(bam); }
+	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff; // (under ds.mu)
+	std::vector<uint8_t> ds_enc;       // host copy of the reads a difference-string call without a resident batch encodes
+	DevBuf fx_scan;                    // the scan's scratch of the FASTQ parser (under fx.mu)
+	std::shared_ptr<void> bam_pool;    // GdbPool (bam_driver.hip.h): the flattened chunks of a batch and their merged table, kept from call to call (under bam.mu)
 	std::string rg_line, rg_id;        // -R: the escaped @RG header line and its ID (gdiet_hip_set_read_group; read by the SAM formatters)
 };
 
@@ -298,14 +334,13 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 		if (ctx->async_lane[i]) gdiet_hip_destroy(ctx->async_lane[i]), ctx->async_lane[i] = nullptr;
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-	if (ctx->ds_stream) (void)hipStreamSynchronize(ctx->ds_stream);
-	if (ctx->fx_stream) (void)hipStreamSynchronize(ctx->fx_stream);
-	if (ctx->bz_stream) (void)hipStreamSynchronize(ctx->bz_stream);
-	if (ctx->bzd_stream) (void)hipStreamSynchronize(ctx->bzd_stream);
-	if (ctx->bam_stream) (void)hipStreamSynchronize(ctx->bam_stream);
-	const hipEvent_t events[] = {ctx->ev[0], ctx->ev[1], ctx->ev[2], ctx->ev[3], ctx->arena_ev, ctx->wait_ev, ctx->gather_ev, ctx->bz_ev[0], ctx->bz_ev[1], ctx->bz_ev[2], ctx->bz_ev[3],
-	                            ctx->bzd_ev[0], ctx->bzd_ev[1], ctx->bzd_ev[2], ctx->bzd_ev[3], ctx->bzd_ev[4], ctx->bzd_ev[5], ctx->bam_ev[0], ctx->bam_ev[1], ctx->bam_ev[2], ctx->bam_ev[3]};
-	const hipStream_t streams[] = {ctx->stream_dp, ctx->stream, ctx->ds_stream, ctx->fx_stream, ctx->bz_stream, ctx->bzd_stream, ctx->bam_stream};
+	std::vector<hipEvent_t> events(ctx->ev, ctx->ev + 4);
+	events.insert(events.end(), {ctx->arena_ev, ctx->wait_ev, ctx->gather_ev});
+	std::vector<hipStream_t> streams{ctx->stream_dp, ctx->stream};
+	ctx->each_lane([&](GdLane &l) { // (a lane that was never used has neither)
+		if (l.stream) (void)hipStreamSynchronize(l.stream);
+		events.insert(events.end(), l.ev, l.ev + 6), streams.push_back(l.stream);
+	});
 	delete ctx; // every DevBuf of the context releases itself here: before the streams and events go
 	for (hipEvent_t e : events)
 		if (e) (void)hipEventDestroy(e);
@@ -343,14 +378,9 @@ extern "C" int gdiet_hip_last_dp_clock(gdiet_ctx *ctx, double *sclk_mhz_median, 
 }
 
 
-static const char *gd_ds_err_of(const gdiet_ctx *ctx); // map_diffstr_driver.hip.h
-static const char *gd_fx_err_of(const gdiet_ctx *ctx); // the reader's device mode, at the end of this file
-static const char *gd_bzd_err_of(const gdiet_ctx *ctx); // map_diffstr_driver.hip.h: the BGZF writing side (ctx may be NULL there)
 extern "C" const char *gdiet_hip_strerror(const gdiet_ctx *ctx)
 {
-	if (const char *bz = gd_bzd_err_of(ctx)) return bz; // this thread's last failure was a BGZF compression or the writer's write()
-	if (const char *ds = gd_ds_err_of(ctx)) return ds; // this thread's last failure on the context was a difference-string pass
-	if (const char *fx = gd_fx_err_of(ctx)) return fx; // ... or a device parse of the reader
+	if (const char *mine = gd_err_text(ctx)) return mine; // this thread's last failure on the context (or without one) was on a side lane (err_mark.h)
 	return ctx ? ctx->err.c_str() : "no context";
 }
 
@@ -1047,7 +1077,7 @@ extern "C" int gdiet_hip_debug_seed_prof(unsigned long long *out8) { return (int
 #endif
 // ---- read input (input half) ---------------------------------------------------------------------------
 #include "fastx_reader.h"
-#include "fastx_dev_driver.hip.h" // struct gdiet_fastx; the device mode of the reader
+#include "fastx_dev_driver.hip.h" // struct gdiet_fastx; the device mode of the reader.  It includes bgzf_driver.hip.h: the BGZF drivers, gdiet_bgzf_out, gdiet_hip_bgzf_*
 #include "bam_in_driver.hip.h"    // BAM input: the unpack kernel's driver, gdiet_hip_bam_in_unpack
 static int gd_fx_read_failed(gdiet_fastx *fx);
 
@@ -1126,10 +1156,7 @@ extern "C" int gdiet_hip_fastx_format(const gdiet_fastx *fx) { return fx && fx->
 static int gd_fx_read_failed(gdiet_fastx *fx)
 {
 	const int rc = fx->r->dev_error ? GDIET_E_HIP : GDIET_E_PARAM;
-	if (fx->ctx && !fx->r->io_msg.empty()) {
-		std::lock_guard<std::mutex> lk(fx->ctx->fx_mu);
-		return gd_fx_fail(fx->ctx, rc, "read error: " + fx->r->io_msg);
-	}
+	if (fx->ctx && !fx->r->io_msg.empty()) return gd_err_fail(fx->ctx, rc, "read error: " + fx->r->io_msg);
 	return rc;
 }
 
@@ -1153,135 +1180,9 @@ extern "C" int gdiet_hip_debug_bgzf_seconds(const gdiet_fastx *fx, double *out6)
 	if (!fx || !fx->r || !out6) return GDIET_E_PARAM;
 	for (int i = 0; i < 3; ++i) out6[i] = 1e-9 * (double)fx->r->bz_ns[i], out6[3 + i] = 0;
 	if (fx->ctx) {
-		std::lock_guard<std::mutex> lk(fx->ctx->bz_mu);
-		for (int i = 0; i < 3; ++i) out6[3 + i] = 1e-3 * fx->ctx->bz_ms[i];
+		std::lock_guard<std::mutex> lk(fx->ctx->bz.mu);
+		for (int i = 0; i < 3; ++i) out6[3 + i] = 1e-3 * fx->ctx->bz.ms[i];
 	}
-	return GDIET_OK;
-}
-
-extern "C" int gdiet_hip_bgzf_inflate(gdiet_ctx *ctx, const uint8_t *raw, size_t raw_len, uint8_t *out, size_t out_cap, size_t *out_len)
-{
-	if (!ctx || (!raw && raw_len) || !out_len) return GDIET_E_PARAM;
-	*out_len = 0;
-	gd_ds_clear_mark(); // (an earlier refusal on this thread is not this call's text)
-	auto fail = [&](int rc, const std::string &what) {
-		std::lock_guard<std::mutex> lk(ctx->fx_mu);
-		return gd_fx_fail(ctx, rc, "gdiet_hip_bgzf_inflate: " + what);
-	};
-	std::vector<GdBgzfMember> tab;
-	size_t inc = 0, bad_at = 0;
-	std::string why;
-	if (gd_bgzf_scan(raw, raw_len, tab, &inc, &bad_at, &why) != GD_BGZF_OK) return fail(GDIET_E_PARAM, "offset " + std::to_string(bad_at) + ": " + why);
-	if (inc != raw_len) return fail(GDIET_E_PARAM, "offset " + std::to_string(inc) + ": the range ends inside a member");
-	const size_t total = tab.empty() ? 0 : (size_t)(tab.back().out_off + tab.back().isize);
-	*out_len = total;
-	if (!out) return GDIET_OK; // sizes first
-	if (total > out_cap) return fail(GDIET_E_PARAM, "the members inflate to " + std::to_string(total) + " bytes, out holds " + std::to_string(out_cap));
-	std::vector<uint32_t> lens(tab.size(), 0);
-	const int rc = gd_bz_inflate_device(ctx, raw, raw_len, tab.data(), tab.size(), out, total, lens.data(), why);
-	if (rc < 0) return fail(rc == -1 ? GDIET_E_HIP : GDIET_E_PARAM, why);
-	std::vector<std::string> msg(tab.size());
-	std::vector<uint8_t> ok(tab.size(), 1);
-	gd_parallel_for(ctx, ctx->host_threads, (int)tab.size(), [&](int k) { ok[(size_t)k] = gd_bgzf_check(tab[(size_t)k], (size_t)k, out + tab[(size_t)k].out_off, lens[(size_t)k], &msg[(size_t)k]); });
-	for (size_t k = 0; k < tab.size(); ++k)
-		if (!ok[k]) return fail(GDIET_E_PARAM, msg[k]);
-	return GDIET_OK;
-}
-
-// ---- BGZF output -------------------------------------------------------------------------------------------------------------------
-extern "C" int gdiet_hip_bgzf_deflate(gdiet_ctx *ctx, const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, size_t *out_len, int flags)
-{
-	if (!ctx || !out_len) return GDIET_E_PARAM;
-	*out_len = 0;
-	gd_ds_clear_mark();
-	if (!in && in_len) return gd_bzd_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_deflate: no input for " + std::to_string(in_len) + " bytes");
-	const size_t n = (in_len + GDD_MAX_IN - 1) / GDD_MAX_IN, bound = n * GDD_SLOT + GD_BGZF_EOF_LEN;
-	if (!out) { *out_len = bound; return GDIET_OK; } // sizes first
-	if (out_cap < bound) return gd_bzd_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_deflate: out holds " + std::to_string(out_cap) + " bytes, the bound is " + std::to_string(bound));
-	size_t got = 0;
-	std::string why;
-	const int rc = gd_bz_deflate_device(ctx, in, in_len, out, out_cap, &got, why);
-	if (rc < 0) return gd_bzd_fail(ctx, GDIET_E_HIP, "gdiet_hip_bgzf_deflate: " + why);
-	if (flags & 1) memcpy(out + got, GD_BGZF_EOF, GD_BGZF_EOF_LEN), got += GD_BGZF_EOF_LEN;
-	*out_len = got;
-	return GDIET_OK;
-}
-
-struct GdBzdExecutor : GdBgzfDeflater {
-	gdiet_ctx *ctx;
-	explicit GdBzdExecutor(gdiet_ctx *c) : ctx(c) {}
-	int deflate(const unsigned char *in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why) override
-	{
-		return gd_bz_deflate_device(ctx, in, in_len, out, out_cap, out_len, why);
-	}
-	int deflate_resident(const void *d_in, size_t in_len, unsigned char *out, size_t out_cap, size_t *out_len, std::string &why) override
-	{
-		*out_len = 0;
-		const size_t n = (in_len + GDD_MAX_IN - 1) / GDD_MAX_IN;
-		if (n == 0) return 0;
-		if (n > ((size_t)1 << 30) || out_cap / GDD_SLOT < n) { why = "device deflate: the output holds fewer than 65536 bytes per member"; return -1; }
-		std::lock_guard<std::mutex> lk(ctx->bzd_mu);
-		if (gd_bzd_ready(ctx, why)) return -1;
-		(void)hipEventRecord(ctx->bzd_ev[0], ctx->bzd_stream); // nothing goes up: the input is there
-		return gd_bz_deflate_resident(ctx, (const uint8_t *)d_in, in_len, out, out_cap, out_len, why);
-	}
-};
-struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; };
-
-extern "C" int gdiet_hip_bgzf_out_open(gdiet_ctx *ctx, const char *path, int level, int threads, gdiet_bgzf_out **out)
-{
-	if (!path || !out || level < -1 || level > 9) return GDIET_E_PARAM;
-	*out = nullptr;
-	gd_ds_clear_mark();
-	const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-	if (fd < 0) return gd_bzd_fail(ctx, GDIET_E_PARAM, std::string("gdiet_hip_bgzf_out_open: ") + path + ": " + strerror(errno));
-	gdiet_bgzf_out *h = new gdiet_bgzf_out();
-	h->ctx = ctx, h->w.fd = fd, h->w.level = level, h->w.threads = threads < 1 ? 1 : threads;
-	if (ctx) h->w.dev = std::make_shared<GdBzdExecutor>(ctx);
-	*out = h;
-	return GDIET_OK;
-}
-static int gd_bzo_done(gdiet_bgzf_out *h, int rc)
-{
-	if (!rc) return GDIET_OK;
-	return gd_bzd_fail(h->ctx, h->w.dev_error ? GDIET_E_HIP : GDIET_E_PARAM, "BGZF writer: " + (h->w.msg.empty() ? std::string("used after an error or after close") : h->w.msg));
-}
-extern "C" int gdiet_hip_bgzf_out_write(gdiet_bgzf_out *h, const void *bytes, size_t n)
-{
-	if (!h || (!bytes && n)) return GDIET_E_PARAM;
-	gd_ds_clear_mark();
-	return gd_bzo_done(h, h->w.write((const unsigned char *)bytes, n));
-}
-extern "C" int gdiet_hip_bgzf_out_flush(gdiet_bgzf_out *h)
-{
-	if (!h) return GDIET_E_PARAM;
-	gd_ds_clear_mark();
-	return gd_bzo_done(h, h->w.flush());
-}
-extern "C" int gdiet_hip_bgzf_out_close(gdiet_bgzf_out *h)
-{
-	if (!h) return GDIET_E_PARAM;
-	gd_ds_clear_mark();
-	const int rc = gd_bzo_done(h, h->w.close());
-	delete h;
-	return rc;
-}
-extern "C" int gdiet_hip_bgzf_out_stats(const gdiet_bgzf_out *h, int64_t *members_device, int64_t *members_host, int64_t *bytes_in, int64_t *bytes_out)
-{
-	if (!h) return GDIET_E_PARAM;
-	if (members_device) *members_device = h->w.members_device;
-	if (members_host) *members_host = h->w.members_host;
-	if (bytes_in) *bytes_in = h->w.bytes_in;
-	if (bytes_out) *bytes_out = h->w.bytes_out;
-	return GDIET_OK;
-}
-// measurement only (tools/map_file.py; not declared in include/gdiet_hip.h): the device's side of compressing since the context was
-// created, in seconds: copy up, the deflate and pack kernels, copy down (HIP events)
-extern "C" int gdiet_hip_debug_bgzf_deflate_seconds(gdiet_ctx *ctx, double *out3)
-{
-	if (!ctx || !out3) return GDIET_E_PARAM;
-	std::lock_guard<std::mutex> lk(ctx->bzd_mu);
-	for (int i = 0; i < 3; ++i) out3[i] = 1e-3 * ctx->bzd_ms[i];
 	return GDIET_OK;
 }
 

@@ -1,44 +1,25 @@
 // Driver of the difference-string kernel (map_diffstr.hip.h); included by map_pipeline.hip.h (needs gdiet_ctx, gdiet_index,
 // gdiet_read_batch, gd_parallel_for, gd_index_seq_table).  mm_gen_cs_or_MD (LR/format.c:270-281) for every record of a mini-batch.
-// The call works on a stream, device buffers and a mutex of its own (gdiet_ctx::ds_*): it touches nothing a map call or an open ticket
-// uses, so it is safe from another caller thread while batches are in flight -- the position gdiet_hip_sam_batch is called from.
+// The call works on a lane and device buffers of its own (gdiet_ctx::ds, ds_*): it touches nothing a map call or an open ticket uses, so
+// it is safe from another caller thread while batches are in flight -- the position gdiet_hip_sam_batch is called from.  The text of a
+// failing pass is kept apart from gdiet_ctx::err, with the thread whose call failed (err_mark.h): the pass is designed to refuse bad
+// records on a writer thread while a mapping thread may be writing err.
 #pragma once
 #include "map_diffstr.hip.h"
 
-// The text of a failing difference-string pass is kept apart from gdiet_ctx::err (gdiet_ctx::ds_err, written under ds_mu only): the pass is
-// designed to refuse bad records on a writer thread while a mapping thread may be writing err.  gdiet_hip_strerror hands it to the thread
-// whose call failed (gd_ds_err_of below), until that thread's next difference-string, upload or map call on any context.
-static thread_local const gdiet_ctx *gd_ds_failed_on = nullptr;
-// the same mark of the reader's device mode and of the BGZF inflater (fastx_dev_driver.hip.h); declared here so that every failure that is
-// neither clears both: a refused read or byte range is an ordinary outcome there, and its text must not answer for a later, unrelated failure
-static thread_local const gdiet_ctx *gd_fx_failed_on = nullptr;
-// ... and of the BGZF writing side (gdiet_hip_bgzf_deflate, the stream writer), which also works without a context: the text is the thread's own
-static thread_local bool gd_bzd_failed = false;
-static thread_local const gdiet_ctx *gd_bzd_failed_on = nullptr;
-static thread_local std::string gd_bzd_text;
-static void gd_ds_clear_mark() { gd_ds_failed_on = nullptr, gd_fx_failed_on = nullptr, gd_bzd_failed = false; }
-static const char *gd_bzd_err_of(const gdiet_ctx *ctx) { return gd_bzd_failed && gd_bzd_failed_on == ctx ? gd_bzd_text.c_str() : nullptr; }
-static int gd_bzd_fail(const gdiet_ctx *ctx, int rc, const std::string &what)
-{
-	gd_ds_clear_mark();
-	gd_bzd_text = what, gd_bzd_failed_on = ctx, gd_bzd_failed = true;
-	return rc;
-}
-static const char *gd_ds_err_of(const gdiet_ctx *ctx) { return ctx && gd_ds_failed_on == ctx ? ctx->ds_err.c_str() : nullptr; }
-
-// (like gd_grow, on the difference strings' own stream; the caller holds ds_mu)
-static int gd_ds_grow(gdiet_ctx *ctx, DevBuf &b, size_t bytes)
+// (like gd_grow, on the difference strings' own stream; the caller holds ds.mu)
+static int gd_ds_grow(gdiet_ctx *ctx, DevBuf &b, size_t bytes, std::string &why)
 {
 	if (bytes <= b.cap) return GDIET_OK;
-	hipError_t e0 = hipStreamSynchronize(ctx->ds_stream);
+	hipError_t e0 = hipStreamSynchronize(ctx->ds.stream);
 	if (e0 == hipSuccess) e0 = b.release();
-	if (e0 != hipSuccess) { ctx->ds_err = std::string("difference strings: buffer: ") + hipGetErrorString(e0); return GDIET_E_HIP; }
+	if (e0 != hipSuccess) { why = std::string("difference strings: buffer: ") + hipGetErrorString(e0); return GDIET_E_HIP; }
 	b.kind = DevBuf::DEVICE;
 	const size_t want = bytes + (bytes >> 3) + 4096;
 	const hipError_t e = hipMalloc(&b.p, want);
 	if (e != hipSuccess) {
 		(void)hipGetLastError();
-		ctx->ds_err = "hipMalloc of " + std::to_string(want) + " bytes failed: " + hipGetErrorString(e);
+		why = "hipMalloc of " + std::to_string(want) + " bytes failed: " + hipGetErrorString(e);
 		b.p = nullptr;
 		return GDIET_E_NOMEM;
 	}
@@ -59,14 +40,14 @@ static int gd_diffstr_run(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_rea
                           const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag, char **text, int64_t **off)
 {
 	*text = nullptr, *off = nullptr;
-	gd_ds_clear_mark();
-	std::lock_guard<std::mutex> lk(ctx->ds_mu); // (from the first check on: ds_err and the buffers belong to one call at a time)
+	gd_err_clear();
+	std::lock_guard<std::mutex> lk(ctx->ds.mu); // (from the first check on: the buffers belong to one call at a time)
 	const int mode = gd_ds_mode(opt_flag);
 	int64_t n_rec = 0, n_cig = 0;
 	for (int i = 0; i < n_reads; ++i)
 		for (int j = 0; j < n_regs[i]; ++j) ++n_rec, n_cig += regs[i][j].n_cigar;
 	int64_t *h_off = (int64_t *)calloc((size_t)n_rec + 1, sizeof(int64_t));
-	auto fail = [&](int rc, const std::string &what) { free(h_off); if (!what.empty()) ctx->ds_err = what; gd_ds_failed_on = ctx, gd_fx_failed_on = nullptr; return rc; }; // (empty: ds_err is set)
+	auto fail = [&](int rc, const std::string &what) { free(h_off); return gd_err_fail(ctx, rc, what); };
 	if (!h_off) return fail(GDIET_E_NOMEM, "out of host memory");
 	if (mode < 0 || n_rec == 0) {
 		char *t = (char *)calloc(1, 1);
@@ -105,8 +86,9 @@ static int gd_diffstr_run(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_rea
 	if (rc) return fail(rc, "difference strings: the contig table could not be uploaded");
 	auto hip_fail = [&](hipError_t e, const char *what) { return fail(GDIET_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
 	hipError_t e;
-	if (!ctx->ds_stream && (e = hipStreamCreateWithFlags(&ctx->ds_stream, hipStreamNonBlocking)) != hipSuccess) return hip_fail(e, "difference strings: stream");
-	hipStream_t s = ctx->ds_stream;
+	std::string why; // of ready() and gd_ds_grow
+	if (ctx->ds.ready(ctx->device, 0, "difference strings", why)) return fail(GDIET_E_HIP, why);
+	hipStream_t s = ctx->ds.stream;
 	const uint8_t *d_reads;
 	const int64_t *d_roff;
 	if (batch) d_reads = (const uint8_t *)batch->d_reads, d_roff = (const int64_t *)batch->d_roff;
@@ -119,15 +101,15 @@ static int gd_diffstr_run(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_rea
 		gd_parallel_for(ctx, ctx->host_threads, n_reads, [&](int i) {
 			if (lens[i] > 0 && n_regs[i] > 0) gd_nt4_encode(seqs[i], enc + roff[i], (size_t)lens[i]); // (reads without records are never read)
 		});
-		if ((rc = gd_ds_grow(ctx, ctx->ds_reads, bytes)) || (rc = gd_ds_grow(ctx, ctx->ds_roff, sizeof(int64_t) * ((size_t)n_reads + 1)))) return fail(rc, "");
+		if ((rc = gd_ds_grow(ctx, ctx->ds_reads, bytes, why)) || (rc = gd_ds_grow(ctx, ctx->ds_roff, sizeof(int64_t) * ((size_t)n_reads + 1), why))) return fail(rc, why);
 		if ((e = hipMemcpyAsync(ctx->ds_reads.p, enc, bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e, "difference strings: reads");
 		if ((e = hipMemcpyAsync(ctx->ds_roff.p, roff.data(), sizeof(int64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e, "difference strings: reads");
 		if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "difference strings: reads"); // (roff is a local)
 		d_reads = (const uint8_t *)ctx->ds_reads.p, d_roff = (const int64_t *)ctx->ds_roff.p;
 	}
-	if ((rc = gd_ds_grow(ctx, ctx->ds_rec, sizeof(GddRec) * (size_t)n_rec)) || (rc = gd_ds_grow(ctx, ctx->ds_cig, sizeof(uint32_t) * cig.size())) ||
-	    (rc = gd_ds_grow(ctx, ctx->ds_len, sizeof(int64_t) * ((size_t)n_rec + 1))) || (rc = gd_ds_grow(ctx, ctx->ds_off, sizeof(int64_t) * ((size_t)n_rec + 1))))
-		return fail(rc, "");
+	if ((rc = gd_ds_grow(ctx, ctx->ds_rec, sizeof(GddRec) * (size_t)n_rec, why)) || (rc = gd_ds_grow(ctx, ctx->ds_cig, sizeof(uint32_t) * cig.size(), why)) ||
+	    (rc = gd_ds_grow(ctx, ctx->ds_len, sizeof(int64_t) * ((size_t)n_rec + 1), why)) || (rc = gd_ds_grow(ctx, ctx->ds_off, sizeof(int64_t) * ((size_t)n_rec + 1), why)))
+		return fail(rc, why);
 	if ((e = hipMemcpyAsync(ctx->ds_rec.p, rec.data(), sizeof(GddRec) * (size_t)n_rec, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e, "difference strings: records");
 	if ((e = hipMemcpyAsync(ctx->ds_cig.p, cig.data(), sizeof(uint32_t) * cig.size(), hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e, "difference strings: records");
 	if ((e = hipMemsetAsync((int64_t *)ctx->ds_len.p + n_rec, 0, sizeof(int64_t), s)) != hipSuccess) return hip_fail(e, "difference strings: lengths");
@@ -139,7 +121,7 @@ static int gd_diffstr_run(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_rea
 	map_diffstr_launch<false>(mode, s, n_rec, in, d_len, nullptr, nullptr);
 	size_t sb = 0;
 	if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, sb, d_len, d_off, (int)(n_rec + 1), s)) != hipSuccess) return hip_fail(e, "difference strings: scan");
-	if ((rc = gd_ds_grow(ctx, ctx->ds_scan, sb + 64))) return fail(rc, "");
+	if ((rc = gd_ds_grow(ctx, ctx->ds_scan, sb + 64, why))) return fail(rc, why);
 	sb = ctx->ds_scan.cap;
 	if ((e = hipcub::DeviceScan::ExclusiveSum(ctx->ds_scan.p, sb, d_len, d_off, (int)(n_rec + 1), s)) != hipSuccess) return hip_fail(e, "difference strings: scan");
 	if ((e = hipMemcpyAsync(h_off, d_off, sizeof(int64_t) * ((size_t)n_rec + 1), hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e, "difference strings: offsets");
@@ -149,7 +131,7 @@ static int gd_diffstr_run(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_rea
 	if (!t) return fail(GDIET_E_NOMEM, "out of host memory");
 	t[total] = 0;
 	if (total > 0) {
-		if ((rc = gd_ds_grow(ctx, ctx->ds_text, (size_t)total))) { free(t); return fail(rc, ""); }
+		if ((rc = gd_ds_grow(ctx, ctx->ds_text, (size_t)total, why))) { free(t); return fail(rc, why); }
 		map_diffstr_launch<true>(mode, s, n_rec, in, nullptr, d_off, (char *)ctx->ds_text.p);
 		if ((e = hipMemcpyAsync(t, ctx->ds_text.p, (size_t)total, hipMemcpyDeviceToHost, s)) != hipSuccess) { free(t); return hip_fail(e, "difference strings: text"); }
 		if ((e = hipStreamSynchronize(s)) != hipSuccess) { free(t); return hip_fail(e, "difference strings: write pass"); }

@@ -42,8 +42,6 @@ struct gdiet_read_batch {
 #include "host_pool.h"
 #include "nt4_encode.h"
 
-static void gd_ds_clear_mark(); // map_diffstr_driver.hip.h: this thread's "my last failure was a difference-string pass" mark
-
 static void gd_pool_free(void *pool) { delete (GdPool *)pool; }
 
 static GdPool *gd_pool(gdiet_ctx *ctx)
@@ -220,7 +218,7 @@ extern "C" int gdiet_hip_map_stage_seconds(const gdiet_ctx *ctx, double out[6])
 
 extern "C" int gdiet_hip_batch_upload(gdiet_ctx *ctx, gdiet_read_batch **out, int n, const char *const *seqs, const int32_t *lens)
 {
-	gd_ds_clear_mark();
+	gd_err_clear();
 	if (!ctx || !out || n < 0 || (n && (!seqs || !lens))) return GDIET_E_PARAM;
 	(void)hipSetDevice(ctx->device);
 	const bool trace = gd_trace_stages();
@@ -243,15 +241,17 @@ extern "C" int gdiet_hip_batch_upload(gdiet_ctx *ctx, gdiet_read_batch **out, in
 	});
 	t_[2] = gd_now();
 	// stream-ordered allocation: a plain hipMalloc / hipFree per mini-batch synchronises the whole device, i.e. every batch in flight
-	hipError_t e = hipMallocAsync(&b->d_reads, enc_len + 64, ctx->stream); // (slack: the seed kernel reads aligned 8-byte words)
-	if (e == hipSuccess) e = hipMallocAsync(&b->d_roff, sizeof(int64_t) * (n + 1), ctx->stream);
+	GdStreamMem mem(ctx->stream);
+	hipError_t e = mem.alloc(&b->d_reads, enc_len + 64); // (slack: the seed kernel reads aligned 8-byte words)
+	if (e == hipSuccess) e = mem.alloc(&b->d_roff, sizeof(int64_t) * (n + 1));
 	if (e == hipSuccess) e = hipMemcpyAsync(b->d_reads, b->enc.data(), enc_len, hipMemcpyHostToDevice, ctx->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(b->d_roff, b->roff.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream);
 	t_[3] = gd_now();
 	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
 	t_[4] = gd_now();
 	if (trace) fprintf(stderr, "[gdiet upload, ms] n=%d alloc %.2f encode %.2f enqueue %.2f sync %.2f\n", n, 1e3 * (t_[1] - t_[0]), 1e3 * (t_[2] - t_[1]), 1e3 * (t_[3] - t_[2]), 1e3 * (t_[4] - t_[3]));
-	if (e != hipSuccess) { ctx->err = std::string("batch upload: ") + hipGetErrorString(e); delete b; return GDIET_E_HIP; }
+	if (e != hipSuccess) { mem.fail(); ctx->err = std::string("batch upload: ") + hipGetErrorString(e); delete b; return GDIET_E_HIP; } // (a copy may still read b->enc)
+	mem.release(b->d_reads), mem.release(b->d_roff); // the batch's from here on (gdiet_hip_batch_destroy)
 	*out = b;
 	return GDIET_OK;
 }
@@ -1041,7 +1041,7 @@ extern "C" int gdiet_hip_set_map_lanes(gdiet_ctx *ctx, int n)
 extern "C" int gdiet_hip_map_uploaded(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_mapopt_t *copt, gdiet_read_batch *B,
                                       int32_t *n_regs, gdiet_reg_t **regs)
 {
-	gd_ds_clear_mark();
+	gd_err_clear();
 	if (!ctx || !ix || !copt || !B || !n_regs || !regs) return GDIET_E_PARAM;
 	(void)hipSetDevice(ctx->device);
 	const int n = B->n;
@@ -1159,7 +1159,7 @@ extern "C" int gdiet_hip_set_inflight(gdiet_ctx *ctx, int n)
 extern "C" int gdiet_hip_map_submit(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_mapopt_t *copt, gdiet_read_batch *B, int32_t *n_regs,
                                     gdiet_reg_t **regs, gdiet_map_ticket **out)
 {
-	gd_ds_clear_mark();
+	gd_err_clear();
 	if (!ctx || !ix || !copt || !B || !n_regs || !regs || !out) return GDIET_E_PARAM;
 	(void)hipSetDevice(ctx->device);
 	std::lock_guard<std::mutex> guard(ctx->async_mu); // (submit and wait may come from different threads of the caller's pipeline)
@@ -1197,7 +1197,7 @@ extern "C" int gdiet_hip_map_submit(gdiet_ctx *ctx, const gdiet_index *ix, const
 
 extern "C" int gdiet_hip_map_wait(gdiet_ctx *ctx, gdiet_map_ticket *t)
 {
-	gd_ds_clear_mark();
+	gd_err_clear();
 	if (!ctx || !t) return GDIET_E_PARAM;
 	if (t->th.joinable()) t->th.join();
 	bool rung_offered = false;
@@ -1260,7 +1260,7 @@ extern "C" int gdiet_hip_seed_batch(gdiet_ctx *ctx, const gdiet_index *ix, const
                                     int32_t *shift, uint32_t *tmp_extracted_len, uint32_t *n_mv, int64_t *seed_off, int64_t *occ_off, gdiet_seed_t **seeds,
                                     uint64_t **occ)
 {
-	gd_ds_clear_mark();
+	gd_err_clear();
 	if (!ctx || !ix || !copt || n < 0 || (n && (!seqs || !lens)) || !shift || !tmp_extracted_len || !n_mv || !seed_off || !occ_off || !seeds || !occ) return GDIET_E_PARAM;
 	*seeds = nullptr, *occ = nullptr;
 	seed_off[0] = occ_off[0] = 0;
@@ -1514,7 +1514,7 @@ extern "C" int gdiet_hip_set_read_group(gdiet_ctx *ctx, const char *rg_line)
 	if (!rg_line) return GDIET_OK;
 	std::string err;
 	if (!gd_parse_rg_line(rg_line, ctx->rg_line, ctx->rg_id, err)) {
-		gd_ds_clear_mark(); // (gdiet_hip_strerror is to return this text, not that of an earlier difference-string pass)
+		gd_err_clear(); // (gdiet_hip_strerror is to return this text, not that of an earlier difference-string pass)
 		ctx->err = err;
 		return GDIET_E_PARAM;
 	}

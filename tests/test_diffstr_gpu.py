@@ -220,3 +220,42 @@ def test_a_bad_record_is_refused_and_the_context_goes_on(pkg, synth, mapped):
     keep = [i for i, l in enumerate(golden_sam("hifi_sv")) if l.split("\t")[0] in names]
     plain, rows = golden_sam("hifi_sv"), dr.tag_rows("hifi_sv.md")
     check_lines(got, [plain[i] for i in keep], [rows[i] for i in keep], 4, lambda f, i: f[i + 1] == "rl:i:0", "MD:Z:")
+
+
+def test_each_thread_reads_the_text_of_its_own_refusal(pkg, synth):
+    """two writer threads on one context, each refused by the host check (nothing is launched) at another record: gdiet_hip_strerror
+    answers every thread with the text of its own failure, and a thread that did not fail with neither"""
+    import threading
+    m, reads = synth["m"], synth["reads"]
+    m.diffstr(synth["res"], reads, dr.MODE_FLAG["cs"])  # (the main thread's last call on the context succeeded)
+    step = threading.Barrier(2)
+    seen, raised = {}, {}
+
+    def writer(name, k, first):
+        recs = [dict(r) for r in synth["recs"]]
+        recs[k]["qe"] -= 1
+        res = HandRes(pkg, len(reads), recs)
+        if not first:
+            step.wait()  # B fails after A has
+        try:
+            m.diffstr(res, reads, dr.MODE_FLAG["cs"])
+        except pkg.GdietError as e:
+            raised[name] = str(e)
+        if first:
+            step.wait()
+        step.wait()  # both have failed
+        if not first:
+            step.wait()  # B reads after A has
+        seen[name] = m.lib.gdiet_hip_strerror(m.ctx._h).decode()
+        if first:
+            step.wait()
+
+    ta, tb = threading.Thread(target=writer, args=("a", 7, True)), threading.Thread(target=writer, args=("b", 3, False))
+    ta.start(), tb.start()
+    ta.join(60), tb.join(60)
+    assert not ta.is_alive() and not tb.is_alive()
+    assert "read 7 record 0" in raised["a"] and "read 3 record 0" in raised["b"]
+    assert "read 7 record 0" in seen["a"] and "read 3 record 0" not in seen["a"], seen
+    assert "read 3 record 0" in seen["b"] and "read 7 record 0" not in seen["b"], seen
+    mine = m.lib.gdiet_hip_strerror(m.ctx._h).decode()
+    assert "read 7 record 0" not in mine and "read 3 record 0" not in mine, mine
