@@ -162,7 +162,8 @@ struct gdiet_ctx {
 	int narrow_band = 1;               // GDIET_NARROW_BAND=0: the 64-lane DP kernel runs every alignment at its full band (ksw_wave.hip.h, "NARROW BAND FIRST")
 	DevBuf narrow_cnt;                 // six counters of the most recent 64-lane DP launch: alignments that tried a narrow band, certified ones; the same per rung (239, 495)
 	bool narrow_launched = false;      // that launch had a 64-lane kernel at all
-	uint64_t async_narrow[6] = {0, 0, 0, 0, 0, 0}; // the lane's counters, copied at gdiet_hip_map_wait
+	uint64_t async_narrow[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // the lane's counters, copied at gdiet_hip_map_wait
+	size_t last_arena_bytes = 0;       // backtrace arena of the most recent planned batch (a lane's: copied to the root at gdiet_hip_map_wait)
 	int narrow_quarter = -1;           // GDIET_NARROW_QUARTER: 0 never offers the quarter rung (band 239), 1 always, unset (-1): auto
 	GdQuarterAuto quarter_auto;        // (root) auto mode: whether the next launches offer the rung (ksw_plan.h; read and written under dp_mu)
 	bool quarter_offered = false;      // this context's most recent DP launch offered the rung
@@ -420,6 +421,10 @@ extern "C" int gdiet_hip_reserve(gdiet_ctx *ctx, size_t bytes)
 static const int gd_group_lanes = getenv("GDIET_GROUP_LANES") ? atoi(getenv("GDIET_GROUP_LANES")) : 0; // 16: always four alignments per wavefront
 // GDIET_SR_PIPE=0: no skewed pipelines (ksw_pipe.hip.h), short alignments on the grouped kernels only
 static const bool gd_use_pipe = !(getenv("GDIET_SR_PIPE") && atoi(getenv("GDIET_SR_PIPE")) == 0);
+// GDIET_BT_COMPACT=0: every backtrace slot is sized for the full-band rows, no overflow pool, no drain launches (ksw_plan.h)
+static const bool gd_bt_compact = !(getenv("GDIET_BT_COMPACT") && atoi(getenv("GDIET_BT_COMPACT")) == 0);
+// GDIET_BT_OVERFLOW_MB: size of the overflow pool of the compact arena (default: a sixteenth of the slots)
+static const int64_t gd_bt_overflow_bytes = getenv("GDIET_BT_OVERFLOW_MB") ? (int64_t)(atof(getenv("GDIET_BT_OVERFLOW_MB")) * 1048576.0) : -1;
 
 extern "C" size_t gdiet_hip_ksw_workspace_bytes(int n, const int64_t *qoff, const int64_t *toff, const int32_t *w)
 {
@@ -523,12 +528,20 @@ static int gd_dp_launch(gdiet_ctx *ctx, const GdPlan &P, int n, const KswConst &
 	ctx->narrow_launched = false;
 	ctx->last_was_async = false; // this context's own launch is now its most recent one (a lane's flag is never set; gdiet_hip_map_wait sets the root's after the lane's batch)
 	if (n64 > 0) {
-		if ((rc = gd_grow(ctx, ctx->narrow_cnt, 6 * sizeof(uint32_t)))) return rc;
-		GD_HIP(hipMemsetAsync(ctx->narrow_cnt.p, 0, 6 * sizeof(uint32_t), stream));
+		const size_t n_cnt = (size_t)GD_CNT_CLAIM + 1 + (size_t)P.n_drain; // (ksw_wave_core.h: the ladder's six, the compact arena's, one claim counter per launch)
+		if ((rc = gd_grow(ctx, ctx->narrow_cnt, n_cnt * sizeof(uint32_t)))) return rc;
+		GD_HIP(hipMemsetAsync(ctx->narrow_cnt.p, 0, n_cnt * sizeof(uint32_t), stream));
 		ctx->narrow_launched = true;
+		const int dp_waves = ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves;
 		gd_launch_wave64(d_tasks, d_ids + P.id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
-		                 ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves, (ctx->parent ? ctx->parent->narrow_band : ctx->narrow_band) ? GD_W_NARROW : 0,
-		                 (uint32_t *)ctx->narrow_cnt.p, ctx->quarter_offered ? GD_W_QUARTER : 0);
+		                 dp_waves, (ctx->parent ? ctx->parent->narrow_band : ctx->narrow_band) ? GD_W_NARROW : 0,
+		                 (uint32_t *)ctx->narrow_cnt.p, ctx->quarter_offered ? GD_W_QUARTER : 0, 0, P.n_drain == 0, (int64_t)P.pool_off, P.n_compact ? (int64_t)P.pool_bytes : -1);
+		// The compact arena: boxes that found no room in the overflow pool are still pending.  The drain launches take them up behind the main
+		// launch and BEFORE the kernels of the other kinds, whose slots they may overwrite: the main launch's rows are dead (its walks are
+		// done), those kernels write theirs afterwards.  Almost always every wavefront of them returns at once.
+		for (int k = 1; k <= P.n_drain; ++k)
+			gd_launch_wave64(d_tasks, d_ids + P.id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
+			                 dp_waves, 0, (uint32_t *)ctx->narrow_cnt.p, 0, k, k == P.n_drain, 0, (int64_t)P.bt);
 	}
 	if (P.n_kind[GD_KIND_WAVE16]) {
 		// The short-alignment kernels CAN walk their own alignments back (every group's first lane, gd_bt_thread_walk), but it does not pay:
@@ -624,10 +637,14 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 	GdPlanOpt O;
 	O.kernel_mode = ctx->kernel_mode, O.wave_scoring_ok = gd_wave_scoring_ok(K), O.single_affine = ctx->single_affine && K.q == K.q2 && K.e == K.e2;
 	O.wide_ckpt = ctx->wide_ckpt, O.wave_slots = ctx->wave_slots, O.lane = ctx->parent != nullptr, O.group_lanes = gd_group_lanes, O.use_pipe = gd_use_pipe;
+	// the compact arena, where the launch offers the narrow band (gd_dp_launch passes the same switch to the kernel; the CIGAR buffers are always given here)
+	O.compact = gd_bt_compact && (ctx->parent ? ctx->parent->narrow_band : ctx->narrow_band), O.overflow_bytes = gd_bt_overflow_bytes;
 	GdPlan &P = ctx->plan;
 	gd_plan_batch(P, O, n, h_qoff, h_toff, h_w, h_cigar_off, d_exact_score ? h_exact_score : nullptr, h_tasks,
 	              [&](int n_sl, auto f) { gd_parallel_for(ctx, ctx->lane_threads, n_sl, f); }, mark);
 	ctx->last_mask = P.mask;
+	if (!P.err && P.n_drain < 0) { ctx->err = "DP planner: the arena is smaller than the largest full-band slot"; return GDIET_E_PARAM; }
+	if (!P.err) ctx->last_arena_bytes = P.bt;
 	if (P.err == 1) { ctx->err = "empty sequence in batch (the reference returns without aligning)"; return GDIET_E_PARAM; }
 	if (P.err == 2) { ctx->err = "alignment does not fit the wave kernel"; return GDIET_E_PARAM; }
 	if (P.err == 4) { ctx->err = "band wider than the LDS window of the generic kernel"; return GDIET_E_PARAM; }
@@ -713,25 +730,33 @@ extern "C" int gdiet_hip_last_dp_work(const gdiet_ctx *ctx, uint64_t *cells, uin
 	return GDIET_OK;
 }
 
-static int gd_narrow_counters(gdiet_ctx *ctx, uint64_t v[6])
+// v[0..6): the ladder's counters; v[GD_CNT_POOL], v[GD_CNT_DRAINED], v[GD_CNT_LEFT]: the compact arena's (ksw_wave.hip.h)
+static int gd_narrow_counters(gdiet_ctx *ctx, uint64_t v[10])
 {
-	for (int i = 0; i < 6; ++i) v[i] = 0;
+	for (int i = 0; i < 10; ++i) v[i] = 0;
 	if (ctx->last_was_async) {
-		for (int i = 0; i < 6; ++i) v[i] = ctx->async_narrow[i];
+		for (int i = 0; i < 10; ++i) v[i] = ctx->async_narrow[i];
 	} else if (ctx->narrow_launched && ctx->narrow_cnt.p) {
-		uint32_t h[6] = {0, 0, 0, 0, 0, 0};
+		uint32_t h[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		(void)hipSetDevice(ctx->device);
 		GD_HIP(hipMemcpy(h, ctx->narrow_cnt.p, sizeof(h), hipMemcpyDeviceToHost));
-		for (int i = 0; i < 6; ++i) v[i] = h[i];
+		for (int i = 0; i < 10; ++i) v[i] = h[i];
 	}
 	return GDIET_OK;
+}
+// after a batch has completed: a box the last drain launch could not serve has no alignment (gd_drain_launches rules it out)
+static int gd_check_drained(gdiet_ctx *ctx, const uint64_t v[10])
+{
+	if (v[GD_CNT_LEFT] == 0) return GDIET_OK;
+	ctx->err = "DP planner bug: " + std::to_string(v[GD_CNT_LEFT]) + " alignments found no full-band rows after the last drain launch";
+	return GDIET_E_HIP;
 }
 
 // the narrow-band counters of the most recent DP launch (call after the batch has completed)
 extern "C" int gdiet_hip_last_narrow_band(gdiet_ctx *ctx, uint64_t *tried, uint64_t *certified)
 {
 	if (!ctx) return GDIET_E_PARAM;
-	uint64_t v[6];
+	uint64_t v[10];
 	int rc;
 	if ((rc = gd_narrow_counters(ctx, v))) return rc;
 	if (tried) *tried = v[0];
@@ -744,11 +769,23 @@ extern "C" int gdiet_hip_last_narrow_band(gdiet_ctx *ctx, uint64_t *tried, uint6
 extern "C" int gdiet_hip_last_narrow_rungs(gdiet_ctx *ctx, uint64_t out[4])
 {
 	if (!ctx || !out) return GDIET_E_PARAM;
-	uint64_t v[6];
+	uint64_t v[10];
 	int rc;
 	if ((rc = gd_narrow_counters(ctx, v))) return rc;
 	for (int i = 0; i < 4; ++i) out[i] = v[2 + i];
 	return GDIET_OK;
+}
+
+// the compact arena of the most recent DP launch (call after the batch has completed): out[0] boxes that claimed full-band rows from the
+// overflow pool, out[1] boxes served by a drain launch, out[2] bytes of backtrace arena the batch was planned with
+extern "C" int gdiet_hip_last_arena(gdiet_ctx *ctx, uint64_t out[3])
+{
+	if (!ctx || !out) return GDIET_E_PARAM;
+	uint64_t v[10];
+	int rc;
+	if ((rc = gd_narrow_counters(ctx, v))) return rc;
+	out[0] = v[GD_CNT_POOL], out[1] = v[GD_CNT_DRAINED], out[2] = ctx->last_arena_bytes;
+	return gd_check_drained(ctx, v);
 }
 
 extern "C" int gdiet_hip_last_kernel_ms(gdiet_ctx *ctx, float *dp_ms, float *bt_ms)
@@ -854,6 +891,10 @@ extern "C" int gdiet_hip_ksw_extd2_batch(gdiet_ctx *ctx, int n, const uint8_t *q
 	GD_HIP(hipMemcpyAsync(n_cigar, ctx->ncig.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
 	GD_HIP(hipMemcpyAsync(cigar, ctx->cigar.p, sizeof(uint32_t) * cb, hipMemcpyDeviceToHost, s));
 	GD_HIP(hipStreamSynchronize(s));
+	if (ctx->plan.n_drain > 0) { // (a batch with a compact arena: one more small copy)
+		uint64_t v[10];
+		if ((rc = gd_narrow_counters(ctx, v)) || (rc = gd_check_drained(ctx, v))) return rc;
+	}
 	return gd_check_cigar_caps(ctx, n, n_cigar, cigar_off);
 }
 

@@ -233,15 +233,15 @@ __device__ __forceinline__ void gd_walk_finish(GdWalk &W, const KswTask &T, int 
 	}
 }
 // the walk of one alignment by one whole wavefront (all 64 lanes must call it together) over a whole backtrace in the layout of its
-// kind (gd_bt_index); writes the CIGAR and n_cigar[tid]
-__device__ __forceinline__ void gd_bt_wave_walk(const KswTask &T, int tid, const uint8_t *__restrict__ bt, int32_t *__restrict__ n_cigar,
+// kind (gd_bt_index), at byte bt_off of the arena (T.bt_off, or the rows a box of the 64-lane kernel claimed); writes the CIGAR and n_cigar[tid]
+__device__ __forceinline__ void gd_bt_wave_walk(const KswTask &T, int tid, const uint8_t *__restrict__ bt, int64_t bt_off, int32_t *__restrict__ n_cigar,
                                                 uint32_t *__restrict__ cigar, int lane)
 {
 	const int qlen = __builtin_amdgcn_readfirstlane(T.qlen), tlen = __builtin_amdgcn_readfirstlane(T.tlen);
 	const int w0 = __builtin_amdgcn_readfirstlane(T.w);
 	const int w = w0 < 0 ? (tlen > qlen ? tlen : qlen) : w0;
 	const int kind = __builtin_amdgcn_readfirstlane(T.kind);
-	const uint8_t *p = bt + T.bt_off;
+	const uint8_t *p = bt + bt_off;
 	uint32_t *cg = cigar + T.cig_off;
 	const int cap = __builtin_amdgcn_readfirstlane(T.cig_cap);
 	GdWalk W;
@@ -331,5 +331,5 @@ __global__ __launch_bounds__(256) void ksw_backtrack_wave_kernel(const KswTask *
 		}
 		return;
 	}
-	gd_bt_wave_walk(tasks[tid], tid, bt, n_cigar, cigar, lane);
+	gd_bt_wave_walk(tasks[tid], tid, bt, tasks[tid].bt_off, n_cigar, cigar, lane);
 }

@@ -33,7 +33,18 @@ struct GdPlanOpt {
 	bool lane = false;            // the context is a lane of one with batches in flight: longer pipelines (see np below)
 	int group_lanes = 0;          // 16: always four alignments per wavefront
 	bool use_pipe = true;         // false: no skewed pipelines, short alignments on the grouped kernels only
+	// The compact arena.  true: the launch offers the narrow band with the fused walk (the condition under which the 64-lane kernel looks at
+	// the mark), so a GD_NARROW_TRY box gets a slot for the half-block rows only and claims full-band rows if its certificate fails at both
+	// rungs (GDIET_BT_COMPACT=0 and a context with the narrow band off: false, every slot is sized for the full-band rows)
+	bool compact = false;
+	int64_t overflow_bytes = -1;  // size of the overflow pool behind the last slot; < 0: GD_POOL_SHARE of the slots' total (GDIET_BT_OVERFLOW_MB)
 };
+// the overflow pool's default share of the compact total: about 16 of the 9 400 boxes of a HiFi batch of 5 120 reads need their full-band
+// rows (profiles/r06_quarter_band.md); a sixteenth of the arena holds a few hundred such boxes
+#define GD_POOL_DIV 16
+#define GD_POOL_MIN (64 << 20) // ... but at least 64 MiB, or all the full-size slots together if that is less
+// bytes per anti-diagonal a GD_NARROW_TRY box's slot holds in the compact layout: the half-block rows (the quarter-block rows use its first half)
+#define GD_COMPACT_ROW 512
 
 // decide kernel + backtrace geometry of one alignment
 static void gd_plan_one(const GdPlanOpt &O, int qlen, int tlen, int w, int32_t &kind, int32_t &row_bytes)
@@ -62,7 +73,12 @@ struct GdPlan {
 	uint64_t cells = 0, alg_bytes = 0; // roofline accounting
 	int max_cap = 0;               // largest gd_generic_cap of the generic kernel's alignments
 	size_t bt = 0;                 // bytes of backtrace arena
-	bool wide_ck = false;          // the wide-band alignments run checkpointed ...
+	// the compact layout (GdPlanOpt::compact, and the batch has GD_NARROW_TRY boxes; else pool_bytes = n_drain = 0 and n_compact = 0):
+	// [pool_off, pool_off + pool_bytes) behind the last slot is the overflow pool, bt their sum; n_drain launches of the 64-lane kernel
+	// behind the main one serve every box that found no room there, whatever the order of the claims (gd_drain_launches)
+	size_t pool_off = 0, pool_bytes = 0, n_compact = 0, full_total = 0, full_max = 0; // n_compact boxes with a half-size slot; their full-size slots in all, the largest
+	int n_drain = 0;
+	bool wide_ck = false;         // the wide-band alignments run checkpointed ...
 	size_t n_ring96 = 0;           // ... and the first n_ring96 of their list on the 96-block ring
 	// the id lists of the four kinds back to back, ids[id_off[k]] the first of kind k (n_kind[k] alignments).  Inside the short-alignment
 	// kind: three lists of groups of 4 / 6 / 8 ids (16 / 10 / 8 lanes; n_group[g] entries from group_off[g], -1 pads a group), then the
@@ -72,6 +88,19 @@ struct GdPlan {
 	std::vector<PipeWave> pipes;
 	std::vector<PipeRun> pipe_runs;
 };
+
+// How many launches whose claims go to `arena` bytes serve n_boxes boxes that need full_total bytes of full-size slots in all (each a
+// multiple of 256, the largest full_max), in whatever order the claims arrive.  A claim is one atomic add on the launch's counter and is
+// served iff the counter, before and after, is inside the arena: a launch serves the claims in the order of their arrival up to the first
+// that does not fit -- at least one box (arena >= full_max), and more than arena - full_max bytes unless it serves all that are left.
+// -1: the arena is smaller than the largest slot.
+static inline int gd_drain_launches(size_t n_boxes, size_t full_total, size_t full_max, size_t arena)
+{
+	if (n_boxes == 0) return 0;
+	if (arena < full_max) return -1;
+	const size_t per = arena - full_max + 256;
+	return (int)std::min(n_boxes, (full_total + per - 1) / per);
+}
 
 // Fills tasks[0..n) and P.  run_slices(n_sl, f) calls f(sl) for every sl in [0, n_sl), in any order and on any threads; mark(name) is
 // told when a step is done (the caller's stage trace).  With P.err set, only err, mask and the tasks' own fields are defined.
@@ -113,7 +142,7 @@ static void gd_plan_batch(GdPlan &P, const GdPlanOpt &O, int n, const int64_t *h
 				else {
 					gd_plan_one(O, T.qlen, T.tlen, T.w, T.kind, T.row_bytes);
 					// the 64-lane kernel's boxes that try the band GD_W_NARROW first, or run their own narrow band on the half-block rows (the
-					// kernel's argument decides whether it looks at the mark; the slot is sized for the full-band rows either way)
+					// kernel's argument decides whether it looks at the mark; O.compact says so here, and sizes the slot below)
 					T.pad = T.kind == GD_KIND_WAVE64 && !O.single_affine ? gd_narrow_mode(T.qlen, T.tlen, T.w) : GD_NARROW_NO;
 					memo.qlen = T.qlen, memo.tlen = T.tlen, memo.w = T.w, memo.kind = T.kind, memo.row_bytes = T.row_bytes, memo.narrow = T.pad;
 				}
@@ -161,11 +190,25 @@ static void gd_plan_batch(GdPlan &P, const GdPlanOpt &O, int n, const int64_t *h
 		for (int32_t id : ids[GD_KIND_WAVE128]) full += (size_t)(h_tasks[id].qlen + h_tasks[id].tlen - 1) * (size_t)h_tasks[id].row_bytes;
 		wide_ck = O.wide_ckpt == 1 || (O.wide_ckpt < 0 && ((int)ids[GD_KIND_WAVE128].size() >= O.wave_slots / 5 || full > ((size_t)100 << 30)));
 	}
+	P.pool_off = P.pool_bytes = P.n_compact = P.full_total = P.full_max = 0, P.n_drain = 0;
 	for (int i = 0; i < n; ++i) {
 		KswTask &T = h_tasks[i];
 		T.bt_off = (int64_t)bt;
+		const size_t full = gd_align256((size_t)(T.qlen + T.tlen - 1) * (size_t)T.row_bytes + 64);
 		if (wide_ck && T.kind == GD_KIND_WAVE128) bt += gd_align256(gd_ck_bytes(T.qlen, T.tlen, T.row_bytes) + 64);
-		else bt += gd_align256((size_t)(T.qlen + T.tlen - 1) * (size_t)T.row_bytes + 64);
+		else if (O.compact && T.kind == GD_KIND_WAVE64 && T.pad == GD_NARROW_TRY) {
+			bt += gd_align256((size_t)(T.qlen + T.tlen - 1) * GD_COMPACT_ROW + 64);
+			++P.n_compact, P.full_total += full, P.full_max = std::max(P.full_max, full);
+		} else bt += full;
+	}
+	if (P.n_compact) {
+		P.pool_off = bt;
+		// (the floor: in a batch of a few dozen boxes a sixteenth of the slots holds not one full-size box, and a lone fall-back served by
+		// a drain launch is a second serial alignment behind the first -- nothing the arena of such a batch needs to save)
+		P.pool_bytes = O.overflow_bytes >= 0 ? gd_align256((size_t)O.overflow_bytes) : std::max(gd_align256(bt / GD_POOL_DIV), std::min(P.full_total, (size_t)GD_POOL_MIN));
+		if (P.pool_off + P.pool_bytes < P.full_max) P.pool_bytes = P.full_max - P.pool_off; // (a batch of one or two boxes: the drain launches need room for the largest)
+		bt += P.pool_bytes;
+		P.n_drain = gd_drain_launches(P.n_compact, P.full_total, P.full_max, bt);
 	}
 	mark("bt_off");
 	// longest alignments first inside each class: the tail of the grid is then made of short jobs (a class whose members all have

@@ -52,6 +52,12 @@ __device__ __forceinline__ const uint8_t *gdw_uniform_ptr(const uint8_t *p, int 
 	const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)a, src_lane), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(a >> 32), src_lane);
 	return (const uint8_t *)((uintptr_t)hi << 32 | lo);
 }
+// a wave-uniform 64-bit value the compiler cannot prove uniform, as a scalar
+__device__ __forceinline__ int64_t gdw_uniform_i64(int64_t v)
+{
+	const u32 lo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(uint64_t)v), hi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)((uint64_t)v >> 32));
+	return (int64_t)((uint64_t)hi << 32 | lo);
+}
 
 // ---- the narrow form of the 64-lane kernel: one HALF block per lane (ksw_wave_core.h, "the narrow form") ---------------------------
 // The DP rows of one alignment at band w <= GD_W_NARROW on a ring of 64 half blocks: the row loop of ksw_extd2_wave_kernel<64> -- general
@@ -310,6 +316,13 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 // that is admitted runs the quarter-block rows at its own band.  All in the same backtrace slot.
 // narrow_cnt[0] / [1]: GD_NARROW_TRY alignments that tried a narrow band / that finished in one; [2] / [3]: alignments that evaluated the
 // certificate at NA.wq / for which it held; [4] / [5]: the same at NA.w.  Added to by every such wavefront.
+// THE COMPACT ARENA (NA.claim_units >= 0): the slot of a GD_NARROW_TRY box holds the half-block rows only (ksw_plan.h).  A box whose
+// certificate fails at both rungs claims its full-band rows from the overflow pool behind the slots and goes on in them, in the same
+// wavefront; if the pool is used up it returns and stays GD_ST_PENDING, and one of the drain launches that follow on the same stream
+// (NA.drain = 1, 2, ...: the same kernel over the same ids, narrow band off, every wavefront whose box is not pending returns at once)
+// gives it rows from the start of the arena.  narrow_cnt[GD_CNT_POOL] / [GD_CNT_DRAINED]: boxes served by the pool / by a drain launch;
+// [GD_CNT_LEFT]: boxes the last launch could not serve (the planner's number of drain launches rules that out; the host reports it);
+// [GD_CNT_CLAIM + k]: the claim counter of launch k.
 #define GD_CLOCK_SLOTS 16384
 __device__ unsigned long long gd_clock_stamps[GD_CLOCK_SLOTS * 4];
 template <int LANES, int TAG = 0, bool DUAL = true>
@@ -357,7 +370,9 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 	// The 16 backtrace bytes of a lane.  64-lane form: the alignment's backtrace is a buffer resource (base in SGPRs), the row a scalar
 	// offset and the lane a constant 32-bit vector offset, so the row loop carries no 64-bit vector address (2-3 VGPRs of the 96).
 	typedef u32 gdw_u32x4 __attribute__((ext_vector_type(4)));
-	__amdgpu_buffer_rsrc_t bt_rsrc = __builtin_amdgcn_make_buffer_rsrc(bt + (LANES == 64 ? Tp->bt_off : 0), 0, (int)0xffffffffu, 0x00020000);
+	// (64-lane form: where the rows in use start, wave-uniform -- the box's slot, or the full-band rows it claimed, see the ladder)
+	int64_t bt_base = LANES == 64 ? gdw_uniform_i64(Tp->bt_off) : 0;
+	__amdgpu_buffer_rsrc_t bt_rsrc = __builtin_amdgcn_make_buffer_rsrc(bt + bt_base, 0, (int)0xffffffffu, 0x00020000);
 	auto store_row = [&](const int r, const u32 out[4]) __attribute__((always_inline)) {
 		if (LANES == 64) {
 			const gdw_u32x4 d = {out[0], out[1], out[2], out[3]};
@@ -366,6 +381,8 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 	};
 	if constexpr (LANES == 64 && DUAL) {
 		const int mode = NA.w > 0 && cigar != nullptr ? __builtin_amdgcn_readfirstlane(Tp->pad) : GD_NARROW_NO;
+		// a drain launch (narrow band off): whatever is still pending is a box of the main launch that found no room for its full-band rows
+		bool claim = NA.drain > 0;
 		if (mode != GD_NARROW_NO) {
 			// the ladder: quarter-block rows at NA.wq (or the box's own band up to it), half-block rows at NA.w (or its own band), full band
 			int s8 = 0, wn = 0, stride = 0;
@@ -408,6 +425,23 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 				gd_walk_finish(Wk, *Tp, tid, n_cigar, cigar, lane);
 				return;
 			}
+			claim = mode == GD_NARROW_TRY && NA.claim_units >= 0; // the compact arena: this box's slot holds the half-block rows only
+		}
+		if (claim) {
+			// THE CLAIM: full-band rows from the overflow pool (a drain launch: from the arena, whose slots are all dead by then) -- one atomic
+			// add on the launch's counter, in units of 256 bytes.  No room: the box stays GD_ST_PENDING for the next launch over the same id
+			// list; the wavefront never waits for another.
+			const u32 need = gd_full_units(qlen, tlen);
+			u32 at = 0;
+			if (lane == 0) at = atomicAdd(narrow_cnt + GD_CNT_CLAIM + NA.drain, need);
+			at = (u32)__builtin_amdgcn_readfirstlane((int)at);
+			if ((int64_t)at + (int64_t)need > NA.claim_units) {
+				if (NA.last && lane == 0) atomicAdd(narrow_cnt + GD_CNT_LEFT, 1u);
+				return;
+			}
+			if (lane == 0) atomicAdd(narrow_cnt + (NA.drain > 0 ? GD_CNT_DRAINED : GD_CNT_POOL), 1u);
+			bt_base = NA.claim_off + ((int64_t)at << 8);
+			bt_rsrc = __builtin_amdgcn_make_buffer_rsrc(bt + bt_base, 0, (int)0xffffffffu, 0x00020000);
 		}
 	}
 	WaveLane L;
@@ -556,7 +590,7 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 	}
 	if (fuse) {
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); // this wavefront's own backtrace stores: complete, and not served from a stale L1 line
-		if (LANES == 64) gd_bt_wave_walk(*Tp, tid, bt, n_cigar, cigar, lane_w);
+		if (LANES == 64) gd_bt_wave_walk(*Tp, tid, bt, bt_base, n_cigar, cigar, lane_w);
 		else if (live && sub == 0) {
 			// short alignments, several per wavefront: one walk per group on its first lane -- a few hundred dependent steps through bytes
 			// the wavefront has just written, while the SIMD's other wavefronts are in their DP rows; no separate backtrack pass after
@@ -571,11 +605,13 @@ static inline void gd_launch_wave64(const KswTask *tasks, const int32_t *ids, in
                                     uint8_t *bt, int32_t *status, int32_t *score, KswConst C, hipStream_t s, bool single,
                                     int32_t *n_cigar, uint32_t *cigar /* fused backtrack */, int waves_per_simd /* 4: see gdiet_hip_set_dp_waves */,
                                     int narrow_w /* GD_W_NARROW, or 0: every alignment at its full band */, uint32_t *narrow_cnt /* six counters, see the kernel */,
-                                    int quarter_w /* GD_W_QUARTER, or 0: the quarter rung is not offered */)
+                                    int quarter_w /* GD_W_QUARTER, or 0: the quarter rung is not offered */,
+                                    int drain = 0, bool last = true, int64_t claim_off = 0, int64_t claim_bytes = -1 /* the compact arena: GdNarrowArg */)
 {
 	WaveK K;
 	gdw_make_consts(C, K);
-	const GdNarrowArg NA = gd_narrow_arg(C, narrow_cnt ? narrow_w : 0, quarter_w);
+	GdNarrowArg NA = gd_narrow_arg(C, narrow_cnt ? narrow_w : 0, quarter_w);
+	NA.drain = drain, NA.last = last, NA.claim_off = claim_off, NA.claim_units = claim_bytes < 0 ? -1 : claim_bytes >> 8;
 	// one wavefront per workgroup: a finished wavefront frees its slot at once instead of waiting for its three block mates
 	const dim3 grid(n), block(64);
 	// Four wavefronts per SIMD instead of five: the kernel uses no LDS, so an (unused) dynamic allocation of a sixteenth of the CU's 160 KB
@@ -720,7 +756,7 @@ __global__ __launch_bounds__(128) void ksw_extd2_wave128_kernel(const KswTask *_
 	}
 	if (fuse) {
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-		gd_bt_wave_walk(*Tp, tid, bt, n_cigar, cigar, lane);
+		gd_bt_wave_walk(*Tp, tid, bt, Tp->bt_off, n_cigar, cigar, lane);
 	}
 }
 
@@ -1344,7 +1380,7 @@ __global__ __launch_bounds__(128) void ksw_extd2_wave2x64_kernel(const KswTask *
 	if (fuse) { // one of the two wavefronts walks the alignment back, once both have stored their last rows
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
 		__syncthreads();
-		if (wv == 0) gd_bt_wave_walk(*Tp, tid, bt, n_cigar, cigar, lane);
+		if (wv == 0) gd_bt_wave_walk(*Tp, tid, bt, Tp->bt_off, n_cigar, cigar, lane);
 	}
 }
 

@@ -818,8 +818,8 @@ static int gd_stage_dp(GdMapCall &c)
 	const size_t nbp = c.nbp;
 	hipStream_t s = ctx->stream;
 	int rc;
-	// an async lane shares its parent's backtrace arena (two whole-batch arenas do not fit in HBM, and concurrent DP kernels of
-	// smaller batches measured slower): the DP stages take turns
+	// an async lane whose batch does not fit a private arena (gd_ksw_batch_dev: own_arena) shares its parent's backtrace arena, and the
+	// DP stages take turns; one whose batch fits -- a HiFi batch of 5 120 reads does, with the compact arena -- is not chained behind the others
 	std::unique_lock<std::mutex> dp_lock;
 	gdiet_ksw_score_t ks;
 	ks.match = (int8_t)O.a, ks.mismatch = (int8_t)(O.b < 0 ? O.b : -O.b), ks.sc_ambi = 0, ks.q = (int8_t)O.q, ks.e = (int8_t)O.e, ks.q2 = (int8_t)O.q2, ks.e2 = (int8_t)O.e2;
@@ -1220,7 +1220,9 @@ extern "C" int gdiet_hip_map_wait(gdiet_ctx *ctx, gdiet_map_ticket *t)
 			    gd_narrow_counters(c, ctx->async_narrow) == GDIET_OK) {
 				ctx->last_was_async = true;
 				rung_offered = c->narrow_launched && c->quarter_offered, rung[0] = ctx->async_narrow[2], rung[1] = ctx->async_narrow[3];
+				if ((rc = gd_check_drained(ctx, ctx->async_narrow))) t->rc = rc;
 			}
+			ctx->last_arena_bytes = c->last_arena_bytes;
 		}
 		ctx->async_busy[t->lane] = false;
 		delete t;

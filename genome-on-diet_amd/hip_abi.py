@@ -65,6 +65,7 @@ def load_library():
     lib.gdiet_hip_last_dp_work.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.gdiet_hip_last_narrow_band.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.gdiet_hip_last_narrow_rungs.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.gdiet_hip_last_arena.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.gdiet_hip_ksw_extd2_batch.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, i32p, i32p, C.POINTER(KswScore),
                                               i32p, i32p, u32p, i64p]
     lib.gdiet_hip_ksw_extd2_batch_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(KswScore),
@@ -206,6 +207,13 @@ class Context:
         """(tried at 239, certified at 239, tried at 495, certified at 495) of the most recent DP launch (gdiet_hip_last_narrow_rungs)"""
         v = (C.c_uint64 * 4)()
         self._check(self.lib.gdiet_hip_last_narrow_rungs(self._h, v))
+        return tuple(int(x) for x in v)
+
+    def last_arena(self):
+        """(boxes that claimed full-band rows from the overflow pool, boxes served by a drain launch, bytes of backtrace arena) of the most
+        recent DP launch (gdiet_hip_last_arena)"""
+        v = (C.c_uint64 * 3)()
+        self._check(self.lib.gdiet_hip_last_arena(self._h, v))
         return tuple(int(x) for x in v)
 
     def reserve(self, nbytes):

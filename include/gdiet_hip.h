@@ -200,6 +200,13 @@ int gdiet_hip_last_narrow_band(gdiet_ctx *ctx, uint64_t *tried, uint64_t *certif
  * same at 495.  GDIET_NARROW_QUARTER (read at gdiet_hip_init): 0 never offers the 239 rung, 1 always does; unset, a context stops
  * offering it for 15 launches after one in which fewer than four fifths of at least 64 boxes certified there.  Results never depend on it. */
 int gdiet_hip_last_narrow_rungs(gdiet_ctx *ctx, uint64_t out[4]);
+/* The backtrace arena of the most recent DP launch.  Where the narrow band is offered, the slot of a box that tries it holds the 512-byte
+ * rows only; a box whose certificate fails at both rungs claims its full-band rows from an overflow pool behind the slots (default: a
+ * sixteenth of them, at least 64 MiB; GDIET_BT_OVERFLOW_MB), and one that finds the pool used up is served by a drain launch of the same kernel behind
+ * the main one, from the start of the arena.  out[0]: boxes that claimed from the pool; out[1]: boxes served by a drain launch; out[2]:
+ * bytes of arena the batch was planned with.  GDIET_BT_COMPACT=0 (read when the library is loaded): every slot is sized for the full-band
+ * rows.  Results never depend on either.  GDIET_E_HIP if a box was left without rows (a planner bug, never a wrong alignment). */
+int gdiet_hip_last_arena(gdiet_ctx *ctx, uint64_t out[3]);
 
 /* ---- B1: the per-read mapping path for a whole batch of reads (LongReads variant; ShortReads variant with MM_F_SR) ----
  * Replaces step 1 of worker_pipeline -- kt_for(n_threads, worker_for, ...) -> mm_map_frag() per read

@@ -54,9 +54,12 @@ def main():
                 # every launch of the process was counted by the profiler; the bench line carries the cells of all of them
                 cells, n_l = r["dp_cells_all_launches"], r["dp_launches"]
                 res["dp_cells_all_launches"], res["dp_launches"] = cells, n_l
+                # (a batch with a compact arena is the main launch plus its drain launches, DESIGN.md section 3: the same number for every batch)
                 for c in ("SQ_INSTS_VALU", "SQ_INSTS_SALU"):
                     if c in tot:
-                        assert calls[c] == n_l, "the profile saw %d launches, the bench made %d" % (calls[c], n_l)
+                        assert calls[c] % n_l == 0, "the profile saw %d launches, the bench made %d batches" % (calls[c], n_l)
+                res["kernel_launches_per_batch"] = {c: calls[c] // n_l for c in calls}
+                res["per_batch_raw"] = {c: tot[c] / n_l for c in tot}
                 if "SQ_INSTS_VALU" in tot:
                     res["valu_insts_per_cell"] = tot["SQ_INSTS_VALU"] / cells
                     res["valu_insts_per_1024_cell_row"] = 1024 * tot["SQ_INSTS_VALU"] / cells
