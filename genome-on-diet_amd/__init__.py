@@ -11,4 +11,5 @@ from .hip_abi import Context, GdietError, KswScore, library_path, load_library, 
 from .map_api import Mapper, MapOpt, PRESETS as MAP_PRESETS, map_multi, read_ranges_by_cost_c  # noqa: F401,E402
 from .fastx import FastxReader  # noqa: F401,E402
 from .bgzf_out import BgzfWriter  # noqa: F401,E402
+from .bam_sort import BamSorter  # noqa: F401,E402
 from .shard import JobClock, effective_cpus, rank_seed, read_range, read_ranges_by_cost  # noqa: F401,E402

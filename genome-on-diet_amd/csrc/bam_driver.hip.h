@@ -137,6 +137,22 @@ extern "C" size_t gdiet_hip_bam_header(gdiet_ctx *ctx, const gdiet_index *ix, co
 	return s.size();
 }
 
+// the same with an @HD line in front of the text
+extern "C" size_t gdiet_hip_bam_header_so(gdiet_ctx *ctx, const gdiet_index *ix, const char *version, int argc, const char *const *argv, const char *sort_order, char **out)
+{
+	if (!ctx || !ix || !out || !sort_order || !*sort_order || argc < 0 || (argc > 1 && !argv)) return 0;
+	*out = nullptr;
+	for (const char *p = sort_order; *p; ++p)
+		if (!((*p >= 'a' && *p <= 'z') || (*p >= 'A' && *p <= 'Z'))) return 0;
+	const GdRefView R = ix->h.ref();
+	const std::string s = gdb_header(R, std::string("@HD\tVN:1.6\tSO:") + sort_order + "\n" + gd_sam_header(R, ctx->rg_line, version, argc, argv));
+	char *buf = (char *)malloc(s.size() + 1);
+	if (!buf) return 0;
+	memcpy(buf, s.data(), s.size()), buf[s.size()] = 0;
+	*out = buf;
+	return s.size();
+}
+
 static int gd_bam_args_ok(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs, const int32_t *lens, const int32_t *n_regs,
                           gdiet_reg_t *const *regs)
 {

@@ -240,7 +240,8 @@ static inline void gdi_aux_text(const uint8_t *a, uint64_t n, std::string &out)
 // The records of b[from, fill), a stretch of the decompressed stream whose byte 0 stands at stream offset `base`; `ordinal` is the
 // number of records in front of it (skipped ones count).  Walks whole records only: pos is where the first record starts that the
 // stretch does not hold completely (the block's tail), or fill.  A malformed record ends the walk with bad = true and its message; the
-// rows in front of it stand.  Records with FLAG 0x100 or 0x800 are checked like the others and give no row.
+// rows in front of it stand.  Records with FLAG 0x100 or 0x800 are checked like the others and give no row.  starts != NULL takes the
+// start offset (in b) of every record the walk passed, those without a row included (the sort pass of bam_sort_driver.hip.h).
 struct GdiWalk {
 	std::vector<GdiRow> rows;
 	std::vector<GdiHostRow> host;
@@ -249,7 +250,8 @@ struct GdiWalk {
 	bool bad = false;
 	std::string msg;
 };
-static inline void gdi_walk(const uint8_t *b, size_t from, size_t fill, bool with_qual, bool want_aux, uint64_t ordinal, uint64_t base, GdiWalk &W)
+static inline void gdi_walk(const uint8_t *b, size_t from, size_t fill, bool with_qual, bool want_aux, uint64_t ordinal, uint64_t base, GdiWalk &W,
+                            std::vector<uint64_t> *starts = nullptr)
 {
 	size_t pos = from;
 	auto fail = [&](const std::string &what) {
@@ -272,6 +274,7 @@ static inline void gdi_walk(const uint8_t *b, size_t from, size_t fill, bool wit
 		if (r[32 + l_name - 1] != 0) { fail("a name without its NUL"); break; }
 		if (want_aux && !gdi_aux_scan(r + need, bs - need)) { fail("an aux field runs past the record or has an unknown type"); break; }
 		++W.n_seen;
+		if (starts) starts->push_back(pos);
 		const size_t at = pos + 4;
 		pos += 4 + (size_t)bs;
 		if (flag & 0x900u) continue; // secondary, supplementary

@@ -16,6 +16,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 #include <zlib.h>
 #include "bgzf.h"
@@ -71,6 +72,17 @@ struct GdBgzfOut {
 	int64_t members_device = 0, members_host = 0, bytes_in = 0, bytes_out = 0;
 	bool failed = false, dev_error = false;
 	std::string msg;
+	// internal hook of the sorted-BAM writer (bam_sorter.h): {input bytes, file bytes} of every member written, in file order, from which
+	// the index builder makes virtual offsets.  Not set by anything else.
+	std::vector<std::pair<uint64_t, uint64_t>> *member_log = nullptr;
+	void log_members(const unsigned char *out, size_t out_len, size_t in_len)
+	{
+		for (size_t at = 0; member_log && at + 18 <= out_len;) { // BSIZE, the member's size - 1, sits at offset 16
+			const size_t m = ((size_t)out[at + 16] | (size_t)out[at + 17] << 8) + 1, in = std::min<size_t>(in_len, GD_BGZF_MEMBER_IN);
+			member_log->push_back(std::make_pair((uint64_t)in, (uint64_t)m));
+			at += m, in_len -= in;
+		}
+	}
 
 	int fail(const std::string &what) { failed = true, msg = what; return -1; }
 	int put(const unsigned char *p, size_t n)
@@ -117,6 +129,7 @@ struct GdBgzfOut {
 			members_host += (int64_t)k;
 		}
 		bytes_in += (int64_t)n;
+		log_members(obuf.data(), out_len, n);
 		return put(obuf.data(), out_len);
 	}
 	// whole members of an input resident on the deflater's device: d_in[0, n), n a multiple of 65280.  (The BAM route: the caller has put
@@ -131,6 +144,7 @@ struct GdBgzfOut {
 		std::string why;
 		if (dev->deflate_resident(d_in, n, obuf.data(), obuf.size(), &out_len, why) != 0) { dev_error = true; return fail(why); }
 		members_device += (int64_t)k, bytes_in += (int64_t)n;
+		log_members(obuf.data(), out_len, n);
 		return put(obuf.data(), out_len);
 	}
 	int write(const unsigned char *p, size_t n)
@@ -159,7 +173,7 @@ struct GdBgzfOut {
 	{
 		if (fd < 0) return failed ? -1 : 0;
 		int rc = failed ? -1 : flush();
-		if (!rc) rc = put(GD_BGZF_EOF, GD_BGZF_EOF_LEN);
+		if (!rc) log_members(GD_BGZF_EOF, GD_BGZF_EOF_LEN, 0), rc = put(GD_BGZF_EOF, GD_BGZF_EOF_LEN);
 		if (::close(fd) != 0 && !rc) rc = fail(std::string("close: ") + strerror(errno));
 		fd = -1;
 		return rc;

@@ -181,8 +181,10 @@ struct gdiet_ctx {
 	//        and the reader inflates.  ev[0..5]: copy up | deflate kernel || pack kernel | copy down; ms: copy up, the two kernels, copy down
 	//   bam  BAM records encoded on the device (bam_driver.hip.h): the same writer thread encodes batch i while batch i + 1 maps; it takes
 	//        bam.mu, then bzd.mu when the deflate kernel reads the records where they are.  ev[0..3]: copy up | encode kernel | copy down
-	GdLane ds, fx, bz, bzd, bam;
-	template <class F> void each_lane(F f) { f(ds), f(fx), f(bz), f(bzd), f(bam); }
+	//   bsort BAM records put into coordinate order on the device (bam_sort_driver.hip.h): apart from bam, so that a caller that sorts a buffer
+	//        never holds the encoder's mutex.  ev[0..2]: key, sort and scan | gather
+	GdLane ds, fx, bz, bzd, bam, bsort;
+	template <class F> void each_lane(F f) { f(ds), f(fx), f(bz), f(bzd), f(bam), f(bsort); }
 	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff; // (under ds.mu)
 	std::vector<uint8_t> ds_enc;       // host copy of the reads a difference-string call without a resident batch encodes
 	DevBuf fx_scan;                    // the scan's scratch of the FASTQ parser (under fx.mu)
@@ -1228,6 +1230,7 @@ extern "C" int gdiet_hip_debug_bgzf_seconds(const gdiet_fastx *fx, double *out6)
 }
 
 #include "bam_driver.hip.h" // BAM: the record encoder's driver, gdiet_hip_bam_header / _bam_batch_into / _bgzf_out_write_bam
+#include "bam_sort_driver.hip.h" // BAM records in coordinate order: the sort pass's driver, gdiet_hip_bam_sort_records
 
 extern "C" int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n, int64_t *roff, uint8_t *enc_host, uint8_t *enc_device)
 {

@@ -78,6 +78,8 @@ def load_library():
     lib.gdiet_hip_ksw_extz2_batch_ex.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, i32p, C.POINTER(KswScore), C.c_int32, C.c_int32, i32p, i32p, u32p, i64p]
     lib.gdiet_hip_bgzf_inflate.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.gdiet_hip_bam_in_unpack.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), i64p, i32p, i32p]
+    lib.gdiet_hip_bam_sort_records.argtypes = [vp, C.c_char_p, C.c_size_t, vp, vp, C.c_size_t, i64p]
+    lib.gdiet_hip_bam_sort_records.restype = C.c_int64
     lib.gdiet_hip_fastx_format.argtypes = [vp]
     lib.gdiet_hip_bgzf_deflate.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     lib.gdiet_hip_bgzf_out_open.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
@@ -147,6 +149,23 @@ class Context:
         self._check(self.lib.gdiet_hip_bam_in_unpack(self._h, records, len(records), int(with_qual), C.cast(text, C.c_void_p), tl.value, C.byref(tl), _ptr(off, C.c_int64),
                                                      _ptr(lens, C.c_int32), C.byref(n)))
         return text.raw[:tl.value], off[:4 * n.value].reshape(-1, 4), lens[:n.value]
+
+    BAM_ROW = np.dtype([("key", "<u8"), ("out", "<u8"), ("refID", "<i4"), ("pos", "<i4"), ("end", "<i4"), ("bin", "<u2"), ("flag", "<u2")])
+
+    def bam_sort_records(self, records):
+        """gdiet_hip_bam_sort_records: whole uncompressed BAM records put into coordinate order by the device: (sorted bytes, rows) -- one
+        row (BAM_ROW: key, offset in the sorted bytes, refID, pos, end, bin, flag) per record, in sorted order"""
+        records = bytes(records)
+        n = C.c_int64()
+        rc = self.lib.gdiet_hip_bam_sort_records(self._h, records, len(records), None, None, 0, C.byref(n))
+        if rc < 0:
+            self._check(int(rc))
+        out = C.create_string_buffer(max(1, len(records)))
+        rows = np.zeros(max(1, n.value), self.BAM_ROW)
+        rc = self.lib.gdiet_hip_bam_sort_records(self._h, records, len(records), C.cast(out, C.c_void_p), rows.ctypes.data_as(C.c_void_p), rows.nbytes, C.byref(n))
+        if rc < 0:
+            self._check(int(rc))
+        return out.raw[:len(records)], rows[:n.value]
 
     def bgzf_deflate(self, data, eof=True):
         """gdiet_hip_bgzf_deflate: data cut into members of 65280 bytes, each compressed by one wavefront of the device into a complete

@@ -115,6 +115,8 @@ def _bind(lib):
                                             C.POINTER(vp)]
     lib.gdiet_hip_bam_header.argtypes = [vp, vp, C.c_char_p, C.c_int, cpp, C.POINTER(vp)]
     lib.gdiet_hip_bam_header.restype = C.c_size_t
+    lib.gdiet_hip_bam_header_so.argtypes = [vp, vp, C.c_char_p, C.c_int, cpp, C.c_char_p, C.POINTER(vp)]
+    lib.gdiet_hip_bam_header_so.restype = C.c_size_t
     lib.gdiet_hip_bam_batch_into.argtypes = [vp, vp, C.c_int, cpp, cpp, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64, C.POINTER(vp),
                                              C.POINTER(C.c_size_t)]
     lib.gdiet_hip_bam_batch_into.restype = C.c_int64
@@ -413,13 +415,16 @@ class Mapper:
         finally:
             C.CDLL(None).free(C.c_void_p(out.value))
 
-    def bam_header(self, version=None, argv=()):
+    def bam_header(self, version=None, argv=(), sort_order=None):
         """gdiet_hip_bam_header: the bytes a BAM file starts with before compression -- magic, the text of sam_header(version, argv), the
-        reference dictionary"""
+        reference dictionary.  sort_order ("coordinate"): gdiet_hip_bam_header_so, the same with @HD VN:1.6 SO:<sort_order> as first line"""
         enc = lambda x: x if isinstance(x, bytes) else x.encode()
         av = (C.c_char_p * max(1, len(argv)))(*[enc(x) for x in argv])
         out = C.c_void_p()
-        m = self.lib.gdiet_hip_bam_header(self.ctx._h, self._idx, None if version is None else enc(version), len(argv), av, C.byref(out))
+        if sort_order is None:
+            m = self.lib.gdiet_hip_bam_header(self.ctx._h, self._idx, None if version is None else enc(version), len(argv), av, C.byref(out))
+        else:
+            m = self.lib.gdiet_hip_bam_header_so(self.ctx._h, self._idx, None if version is None else enc(version), len(argv), av, enc(sort_order), C.byref(out))
         if not out.value:
             raise GdietError("gdiet_hip_bam_header failed")
         try:

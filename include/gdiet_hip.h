@@ -635,7 +635,7 @@ int gdiet_hip_bgzf_out_stats(const gdiet_bgzf_out *h, int64_t *members_device, i
  * MM_F_COPY_COMMENT, the cs / MD bits with their pass on the GPU, the context's read group, = / X operations as they come in regs).
  * The records are written on the GPU, one wavefront per record (csrc/bam_encode.hip.h), from a table the context's host threads
  * flatten; a stream and a lock of the context's own, so a writer thread may encode while other threads map.  Failures of these calls
- * leave their text in gdiet_hip_strerror(ctx) for the calling thread.  Paired-end fields, sorting and indexes are out of scope. */
+ * leave their text in gdiet_hip_strerror(ctx) for the calling thread.  Paired-end fields are out of scope; coordinate order and the index: "Sorted BAM output" below. */
 
 /* The BAM header: "BAM\1", l_text and the text gdiet_hip_sam_header returns for the same arguments (no NUL), n_ref, and per index sequence
  * l_name (with NUL), the name and its NUL, l_ref.  *out is malloc'd (free() it); returns its length, 0 with *out == NULL on failure. */
@@ -660,6 +660,80 @@ int64_t gdiet_hip_bam_batch_into(gdiet_ctx *ctx, const gdiet_index *idx, int n_r
 int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames,
                                  const char *const *seqs, const char *const *quals, const char *const *comments, const int32_t *lens,
                                  const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag);
+
+/* ---- Sorted BAM output ---------------------------------------------------------------------------------------------------------------
+ * Coordinate order, and the BAI index of a file in that order.  Definitions (tests/bam_sort_ref.py restates them):
+ *   ORDER   records are sorted by key = (uint32)refID << 32 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1), the low word computed in 32 bits.
+ *           refID -1 becomes 0xFFFFFFFF: unplaced records come last.  pos -1 comes first within its contig.  On equal position the
+ *           forward strand comes before the reverse strand.  Records with equal keys keep their input order: the sort is stable, so the
+ *           output is a function of the input records alone.
+ *   HEADER  gdiet_hip_bam_header_so: gdiet_hip_bam_header with "@HD\tVN:1.6\tSO:<sort_order>\n" as the first line of the text.
+ *   INDEX   <path>.bai, SAM specification 5.2: "BAI\1", n_ref, per reference the bins with their chunks and the linear index, n_no_coor.
+ *           - A record covers [pos, pos + max(ref_len, 1)); ref_len is the sum of the M / D / N / = / X operations of the record's own
+ *             CIGAR field (a record with the <l_seq>S<ref_len>N placeholder is covered by this rule without reading CG).  The windows
+ *             of the linear index run from max(pos, 0) >> 14 to (max(pos + max(ref_len, 1), 1) - 1) >> 14.
+ *           - The record's bin is the bin field it carries.
+ *           - A chunk is a maximal stretch of consecutive records of one reference with one bin; it runs from the first record's start
+ *             virtual offset to the last record's end virtual offset.  Bins are written in ascending bin number, a bin's chunks in file
+ *             order.
+ *           - Pseudo-bin 37450 comes last for every reference that has a record: {first start, last end}, {mapped, unmapped-but-placed}.
+ *             A reference without a record has n_bin = 0 and n_intv = 0.
+ *           - ioffset[w] is the start virtual offset of the first record covering the 16 kbp window w; n_intv is the last covered
+ *             window + 1; an uncovered window takes the value of the next covered one to its right.
+ *           - Virtual offset = member_file_offset << 16 | offset_in_member.  A stream offset lies in the first member that ends behind
+ *             it; the end of the stream is the file offset of the end-of-file member << 16.
+ *           - n_no_coor counts the records whose refID is outside [0, n_ref).
+ *           No claim is made that the bytes equal those of `samtools index`.  A contig longer than 2^29 cannot be indexed (CSI is out of
+ *           scope).
+ * The device pass (csrc/bam_sort.hip.h) reads nothing but the records' own bytes, so it sorts any BAM records: bam_key_kernel (one thread
+ * per record: key and size from refID, pos, flag and block_size, assembled from byte loads), hipCUB's stable radix sort and exclusive
+ * scan, and bam_gather_kernel (one wavefront per output record: the copy to the sorted offset, the reference length of the CIGAR field, and
+ * one 32-byte index row).  It runs on a lane of the context's own.  The host side of the merge of several sorted runs (csrc/bam_sorter.h:
+ * gdq_plan_chunks) and of the index (csrc/bam_index.h: gdx_bai_build) is host-only code.  Out of scope: CSI / tabix indexes, name sort,
+ * merging existing BAM files, compressed spools, paired-end fields, sorted SAM text. */
+
+/* gdiet_hip_bam_header with "@HD\tVN:1.6\tSO:<sort_order>\n" in front of the text ("coordinate" for a sorted file; letters only, or the
+ * call fails).  *out is malloc'd (free() it); returns its length, 0 with *out == NULL on failure. */
+size_t gdiet_hip_bam_header_so(gdiet_ctx *ctx, const gdiet_index *idx, const char *version, int argc, const char *const *argv, const char *sort_order, char **out);
+
+/* One 32-byte row per record of a sorted buffer, in sorted order: what the index needs of a record.  end = pos + max(ref_len, 1). */
+typedef struct {
+	uint64_t key, out_offset;
+	int32_t refID, pos, end;
+	uint16_t bin, flag;
+} gdiet_bam_row_t;
+/* The kernel-level boundary of the sort pass: recs[0, len) holds whole uncompressed BAM records (any records, each with its block_size;
+ * under 2 GiB).  The host walks them for their starts, the device sorts them into out[0, len) and writes rows[k] for the record at place
+ * k (rows_cap: bytes rows holds; 32 per record are needed); both are copied back.  *n_rec takes the number of records.  With out and
+ * rows both NULL only *n_rec is set.  Returns len, or a negative code: GDIET_E_PARAM for a malformed record (the text of
+ * gdiet_hip_strerror(ctx) names it as the BAM reader does) or too small a rows, GDIET_E_HIP if the device fails. */
+int64_t gdiet_hip_bam_sort_records(gdiet_ctx *ctx, const void *recs, size_t len, void *out, void *rows, size_t rows_cap, int64_t *n_rec);
+
+/* The sorter: a coordinate-sorted BAM file, and its index, from mapped batches in any order.  open takes the uncompressed header
+ * (gdiet_hip_bam_header_so(..., "coordinate", ...)) and writes it; add encodes a batch -- the batch arguments of
+ * gdiet_hip_bam_batch_into -- into a resident run buffer; a run that would exceed run_bytes (0: 512 MiB) is sorted on the device and
+ * spooled, uncompressed, to a file in tmp_dir (NULL: the output's directory) that is created and unlinked at once; close merges the
+ * runs in chunks of at most chunk_bytes (0: 256 MiB) on the device -- or, if one run was all, writes its sorted buffer as it is --,
+ * ends the file and writes <path>.bai if want_index.  bgzf_device: the stream is compressed from the resident buffer by the deflate
+ * kernel; otherwise by zlib at `level` on `threads` host threads.  The output is a function of the input records alone.
+ * open fails with GDIET_E_PARAM for a header that is none, a tmp_dir that cannot be written (the text names it), an output that cannot
+ * be created, and, with want_index, a contig longer than 2^29 (the text names it).  *out still takes a handle then -- unless an
+ * argument was NULL --: it refuses add, and its close frees it and returns GDIET_OK, having created nothing.  After a failed add --
+ * GDIET_E_PARAM as gdiet_hip_bam_batch_into, or for the 2^31st record of a file (the merge sorts all keys in one call that counts them in
+ * an int; 2^32 is not reached); GDIET_E_HIP for the device, a short spool or output write -- the sorter refuses everything but close,
+ * which always frees the handle and the spools, removes a partial .bai, and returns the failure's code.  Texts are
+ * gdiet_hip_strerror(ctx)'s, for the calling thread.  One thread at a time per sorter. */
+typedef struct gdiet_bam_sorter gdiet_bam_sorter;
+typedef struct {
+	int64_t records, runs, spooled_bytes, chunks, members, n_no_coor;
+	double seconds[5]; /* device: key + sort, gather; wall: spool write, spool read, compress + write */
+} gdiet_bam_sort_stats_t;
+int gdiet_hip_bam_sort_open(gdiet_ctx *ctx, const char *path, const void *header, size_t header_len, int bgzf_device, int level, int threads,
+                            uint64_t run_bytes, uint64_t chunk_bytes, const char *tmp_dir, int want_index, gdiet_bam_sorter **out);
+int gdiet_hip_bam_sort_add(gdiet_bam_sorter *h, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
+                           const char *const *quals, const char *const *comments, const int32_t *lens, const int32_t *n_regs,
+                           gdiet_reg_t *const *regs, int64_t opt_flag);
+int gdiet_hip_bam_sort_close(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *stats);
 
 #ifdef __cplusplus
 }

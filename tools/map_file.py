@@ -4,7 +4,7 @@ No Python object is made per read: the C arrays of the reader go straight into t
 
     python tools/map_file.py --preset sr ref.fa reads.fq[.gz] | reads.bam -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
                              [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
-                             [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam]
+                             [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--sort-mem BYTES] [--tmp-dir DIR]]]
 
 Writes the SAM body (the records).  --header puts the header lines of the reference's CLI in front (gdiet_hip_sam_header: @SQ per
 contig, the @RG line of -R, @PG with this tool's version and command line); it is opt-in, so that the default output stays the body alone.
@@ -20,7 +20,11 @@ the GPU, `host` with zlib at --bgzf-level on --bgzf-threads threads; the JSON li
 --bam writes -o as BAM: the header always (gdiet_hip_bam_header), then the records of every batch, encoded on the device
 (gdiet_hip_bgzf_out_write_bam), in the BGZF container --bgzf picks (default `device`: the records are compressed where they were
 encoded and only compressed members come back; `host`: they come back and go through zlib).  Every output option keeps its meaning;
-a -y comment must be a list of SAM tags, or the run fails.  The JSON line gains bam_device_seconds."""
+a -y comment must be a list of SAM tags, or the run fails.  The JSON line gains bam_device_seconds.
+--bam --sort writes -o in coordinate order (BamSorter: every batch is encoded into a resident run buffer, a run of --sort-mem bytes is
+sorted on the device and spooled to an unnamed file in --tmp-dir, default the output's directory, and the runs are merged on the device
+at the end); the header then starts with @HD VN:1.6 SO:coordinate.  --index writes <out>.bai as well.  The JSON line gains bam_sort.
+Without --sort nothing changes."""
 import argparse
 import json
 import os
@@ -38,7 +42,7 @@ from __graft_entry__ import _load_pkg  # noqa: E402
 VERSION = "gdiet-hip-map_file"  # the VN: field of --header's @PG line
 
 
-def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False, bam=False):
+def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False, bam=False, sorter=None):
     """returns (reads, seconds).  Three stages on three threads, as the reference's kt_pipeline runs its three steps (LR/map.c:2094-2170):
     read -> upload + submit -> wait + format + write; the C calls release the interpreter lock, so the stages overlap.
     A failure in any stage stops all three: `stop` is set, the writer keeps draining q_done (every open ticket is still waited for and
@@ -106,7 +110,9 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
                 fail(e)
             open_tickets.release()
             try:
-                if res is not None and not stop.is_set():
+                if res is not None and not stop.is_set() and sorter is not None:
+                    timed("sam+write", sorter.add, res, n, names, seqs, quals, lens, comments if with_comment else None)
+                elif res is not None and not stop.is_set():
                     timed("sam+write", mapper.bam_batch_raw if bam else mapper.sam_batch_raw, res, n, names, seqs, quals, lens, out, comments if with_comment else None)
             except Exception as e:  # noqa: BLE001
                 fail(e)
@@ -200,12 +206,18 @@ def main():
     ap.add_argument("--bgzf-level", type=int, default=-1, help="zlib level of --bgzf host (-1: zlib's default)")
     ap.add_argument("--bgzf-threads", type=int, default=4, help="host threads of --bgzf host")
     ap.add_argument("--bam", action="store_true", help="write -o as BAM (header always; records encoded on the device); --bgzf picks the compressor, default device")
+    ap.add_argument("--sort", action="store_true", help="with --bam: write the records in coordinate order (sorted and merged on the device; header with @HD SO:coordinate)")
+    ap.add_argument("--index", action="store_true", help="with --bam --sort: write <out>.bai as well")
+    ap.add_argument("--sort-mem", type=int, default=1 << 29, metavar="BYTES", help="bytes of records per sorted run (default 512 MiB)")
+    ap.add_argument("--tmp-dir", metavar="DIR", help="where the runs are spooled (unnamed files; default: the directory of -o)")
     ap.add_argument("--device-reader", action="store_true", help="parse and encode four-line FASTQ on the device (gdiet_hip_fastx_attach); the reader hands out resident batches")
     a = ap.parse_args()
     if a.eqx and a.preset != "sr":
         ap.error("--eqx is interpreted for --preset sr only (the LongReads variant does not interpret MM_F_EQX)")
     if a.bam and not a.bgzf:
         a.bgzf = "device"
+    if (a.sort and not a.bam) or (a.index and not a.sort):
+        ap.error("--sort goes with --bam, --index with --sort")
     pkg = _load_pkg()
     from fixture_io import read_fasta
     ctx = pkg.Context(0)
@@ -234,16 +246,33 @@ def main():
     m.set_host_threads(pkg.effective_cpus())
     t_idx = time.perf_counter() - t0
     chunk = a.K or (39321600 if a.preset == "sr" else 80_000_000)
+    sort_stats = None
     try:
         bgzf_out = None
-        with (pkg.BgzfWriter(a.out, ctx=ctx if a.bgzf == "device" else None, level=a.bgzf_level, threads=a.bgzf_threads) if a.bgzf else open(a.out, "wb")) as out:
-            bgzf_out = out if a.bgzf else None
-            if a.bam:
-                out.write(m.bam_header(VERSION, sys.argv))
-            elif a.header:
-                out.write(m.sam_header(VERSION, sys.argv).encode())
-            n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment,
-                             device_reader=a.device_reader, bam=a.bam)
+        if a.sort:
+            sorter = pkg.BamSorter(a.out, m, bgzf=a.bgzf, level=a.bgzf_level, threads=a.bgzf_threads, run_bytes=a.sort_mem, tmp_dir=a.tmp_dir, index=a.index, version=VERSION, argv=sys.argv)
+            try:
+                n, dt = map_file(pkg, m, a.reads, None, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment, device_reader=a.device_reader,
+                                 bam=True, sorter=sorter)
+                t_close = time.perf_counter()
+                sort_stats = dict(sorter.close(), route=a.bgzf)
+                sort_stats["close_seconds"] = round(time.perf_counter() - t_close, 3)
+                dt += sort_stats["close_seconds"]
+            finally:
+                if sort_stats is None:
+                    try:
+                        sorter.close()
+                    except pkg.GdietError:
+                        pass
+        else:
+            with (pkg.BgzfWriter(a.out, ctx=ctx if a.bgzf == "device" else None, level=a.bgzf_level, threads=a.bgzf_threads) if a.bgzf else open(a.out, "wb")) as out:
+                bgzf_out = out if a.bgzf else None
+                if a.bam:
+                    out.write(m.bam_header(VERSION, sys.argv))
+                elif a.header:
+                    out.write(m.sam_header(VERSION, sys.argv).encode())
+                n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment,
+                                 device_reader=a.device_reader, bam=a.bam)
     except Exception as e:  # noqa: BLE001  (every ticket has been waited for by now: the context can be closed)
         print("map_file failed: %r" % (e,), file=sys.stderr)
         m.close()
@@ -252,7 +281,8 @@ def main():
     print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), "mini_batch_bases": chunk,
                       "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "eqx": a.eqx, "out": a.out, "caller_seconds": map_file.last_stage_seconds,
                       **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats, "reads_format": map_file.last_format,
-                      **({"bgzf_out": dict(bgzf_out.stats(), route=a.bgzf, device_seconds=[round(x, 4) for x in ctx.bgzf_deflate_seconds()])} if a.bgzf else {}),
+                      **({"bgzf_out": dict(bgzf_out.stats(), route=a.bgzf, device_seconds=[round(x, 4) for x in ctx.bgzf_deflate_seconds()])} if bgzf_out is not None else {}),
+                      **({"bam_sort": sort_stats} if sort_stats is not None else {}),
                       **({"bam": True, "bam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.bam else {})}))
     m.close()
     ctx.close()
