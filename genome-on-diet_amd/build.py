@@ -18,6 +18,10 @@ BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           "_Z21ksw_extd2_pipe_kernelILb1E": dict(vgprs=128, scratch=320),  # four wavefronts per SIMD; the spills sit in the once-per-alignment staging code, none in the steps
           "_Z20map_post_wave_kernel": dict(vgprs=32, scratch=0),
           "_Z21map_pack_cigar_kernel": dict(vgprs=32, scratch=0),
+          # the rest of a HiFi batch's tail: with two batches in flight every kernel between a batch's main DP launch and its results runs
+          # beside the other batch's DP launch (profiles/r13_batch_tail.md)
+          "_Z25ksw_backtrack_wave_kernel": dict(vgprs=32, scratch=0),
+          "_Z22ksw_exact_match_kernel": dict(vgprs=32, scratch=0),
           "_Z18map_diffstr_kernel": dict(vgprs=32, scratch=0),  # every instance: count / write pass x MD / cs / cs=long (map_diffstr.hip.h)
           # the reader's device mode (fastx_dev.hip.h) parses block i + 1 and encodes batch i + 1 beside the DP of batch i
           "_Z18fastx_count_kernel": dict(vgprs=32, scratch=0),

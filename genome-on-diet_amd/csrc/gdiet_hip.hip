@@ -163,6 +163,8 @@ struct gdiet_ctx {
 	DevBuf narrow_cnt;                 // six counters of the most recent 64-lane DP launch: alignments that tried a narrow band, certified ones; the same per rung (239, 495)
 	bool narrow_launched = false;      // that launch had a 64-lane kernel at all
 	uint64_t async_narrow[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // the lane's counters, copied at gdiet_hip_map_wait
+	DevBuf h_pending;                  // page-locked, one word: the length of the pending list, read back when the main launch has ended (gd_dp_launch)
+	int drain_enqueued = 0;            // drain launches the most recent DP launch enqueued (a lane's: copied to the root at gdiet_hip_map_wait)
 	size_t last_arena_bytes = 0;       // backtrace arena of the most recent planned batch (a lane's: copied to the root at gdiet_hip_map_wait)
 	int narrow_quarter = -1;           // GDIET_NARROW_QUARTER: 0 never offers the quarter rung (band 239), 1 always, unset (-1): auto
 	GdQuarterAuto quarter_auto;        // (root) auto mode: whether the next launches offer the rung (ksw_plan.h; read and written under dp_mu)
@@ -504,7 +506,8 @@ struct GdStageTrace {
 // The launches of a planned batch on `stream`, its descriptors uploaded: the exact-match pre-filter, the DP kernels of the four kinds over
 // their id lists, the walks they left, the score bias; ctx->ev[0..2] before the first, after the DP and after the last.
 static int gd_dp_launch(gdiet_ctx *ctx, const GdPlan &P, int n, const KswConst &K, const gdiet_ksw_score_t *sc, const uint8_t *d_qseq, const uint8_t *d_tseq,
-                        uint8_t *d_bt, int32_t *d_score, int32_t *d_n_cigar, uint32_t *d_cigar, hipStream_t stream, hipEvent_t arena_free)
+                        uint8_t *d_bt, int32_t *d_score, int32_t *d_n_cigar, uint32_t *d_cigar, hipStream_t stream, hipEvent_t arena_free,
+                        bool host_decides /* the caller waits for `stream` anyway and nothing of another batch is queued behind this stage: see the drain launches */)
 {
 	int rc;
 	const KswTask *d_tasks = (const KswTask *)ctx->tasks.p;
@@ -529,21 +532,43 @@ static int gd_dp_launch(gdiet_ctx *ctx, const GdPlan &P, int n, const KswConst &
 	const bool single = ctx->single_affine && K.q == K.q2 && K.e == K.e2;
 	ctx->narrow_launched = false;
 	ctx->last_was_async = false; // this context's own launch is now its most recent one (a lane's flag is never set; gdiet_hip_map_wait sets the root's after the lane's batch)
+	ctx->drain_enqueued = 0;
 	if (n64 > 0) {
-		const size_t n_cnt = (size_t)GD_CNT_CLAIM + 1 + (size_t)P.n_drain; // (ksw_wave_core.h: the ladder's six, the compact arena's, one claim counter per launch)
-		if ((rc = gd_grow(ctx, ctx->narrow_cnt, n_cnt * sizeof(uint32_t)))) return rc;
-		GD_HIP(hipMemsetAsync(ctx->narrow_cnt.p, 0, n_cnt * sizeof(uint32_t), stream));
+		// (ksw_wave_core.h: the ladder's six, the compact arena's, one claim counter per launch; behind them the pending list, a word per id)
+		const size_t n_cnt = (size_t)GD_CNT_CLAIM + 1 + (size_t)P.n_drain, n_list = P.n_drain > 0 ? (size_t)n64 : 0;
+		if ((rc = gd_grow(ctx, ctx->narrow_cnt, (n_cnt + n_list) * sizeof(uint32_t)))) return rc;
+		uint32_t *d_cnt = (uint32_t *)ctx->narrow_cnt.p;
+		GD_HIP(hipMemsetAsync(d_cnt, 0, n_cnt * sizeof(uint32_t), stream));
 		ctx->narrow_launched = true;
 		const int dp_waves = ctx->parent ? ctx->parent->dp_waves : ctx->dp_waves;
 		gd_launch_wave64(d_tasks, d_ids + P.id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
 		                 dp_waves, (ctx->parent ? ctx->parent->narrow_band : ctx->narrow_band) ? GD_W_NARROW : 0,
-		                 (uint32_t *)ctx->narrow_cnt.p, ctx->quarter_offered ? GD_W_QUARTER : 0, 0, P.n_drain == 0, (int64_t)P.pool_off, P.n_compact ? (int64_t)P.pool_bytes : -1);
-		// The compact arena: boxes that found no room in the overflow pool are still pending.  The drain launches take them up behind the main
-		// launch and BEFORE the kernels of the other kinds, whose slots they may overwrite: the main launch's rows are dead (its walks are
-		// done), those kernels write theirs afterwards.  Almost always every wavefront of them returns at once.
-		for (int k = 1; k <= P.n_drain; ++k)
-			gd_launch_wave64(d_tasks, d_ids + P.id_off[GD_KIND_WAVE64], n64, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
-			                 dp_waves, 0, (uint32_t *)ctx->narrow_cnt.p, 0, k, k == P.n_drain, 0, (int64_t)P.bt);
+		                 d_cnt, ctx->quarter_offered ? GD_W_QUARTER : 0, 0, P.n_drain == 0, (int64_t)P.pool_off, P.n_compact ? (int64_t)P.pool_bytes : -1, n_list ? (int)n_cnt : 0);
+		// The compact arena: boxes that found no room in the overflow pool are still pending, their ids in the pending list.  Drain launches
+		// take them up behind the main launch and BEFORE the kernels of the other kinds, whose slots they may overwrite: the main launch's
+		// rows are dead (its walks are done), those kernels write theirs afterwards.
+		// A drain launch is the 96-register kernel: every wavefront of it needs a DP wavefront slot, and with two batches in flight the other
+		// batch's main launch holds them all for 10 ms and more (profiles/r13_batch_tail.md).  So where the caller waits for this stream
+		// anyway (host_decides) the host waits HERE, reads the list's length, and enqueues drain launches only if it is not zero -- it
+		// almost always is zero -- and then over the pending boxes alone.  Elsewhere (a caller's stream that is never waited for; the shared
+		// arena, where the next lane's kernels are already queued behind this stage) they are enqueued up front, a wavefront per id.
+		int n_rounds = P.n_drain, n_slots = n64;
+		if (P.n_drain > 0 && host_decides) {
+			if (!ctx->h_pending.p) {
+				ctx->h_pending.kind = DevBuf::PINNED;
+				if (hipHostMalloc(&ctx->h_pending.p, 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ctx->h_pending.p = nullptr; ctx->err = "hipHostMalloc of the pending count failed"; return GDIET_E_NOMEM; }
+				ctx->h_pending.cap = 64;
+			}
+			GD_HIP(hipMemcpyAsync(ctx->h_pending.p, d_cnt + GD_CNT_PENDING, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+			GD_HIP(gd_stream_wait(ctx, stream));
+			const uint32_t n_pending = *(volatile uint32_t *)ctx->h_pending.p;
+			n_slots = (int)std::min<uint32_t>(n_pending, (uint32_t)n64);
+			n_rounds = gd_drain_rounds(GdDrainSet{(size_t)n_slots, P.full_total, P.full_max}, P.bt);
+		}
+		for (int k = 1; k <= n_rounds; ++k)
+			gd_launch_wave64(d_tasks, (const int32_t *)(d_cnt + n_cnt), n_slots, d_qseq, d_tseq, d_bt, d_status, d_score, K, stream, single, d_n_cigar, d_cigar,
+			                 dp_waves, 0, d_cnt, 0, k, k == n_rounds, 0, (int64_t)P.bt, (int)n_cnt);
+		ctx->drain_enqueued = n_rounds;
 	}
 	if (P.n_kind[GD_KIND_WAVE16]) {
 		// The short-alignment kernels CAN walk their own alignments back (every group's first lane, gd_bt_thread_walk), but it does not pay:
@@ -606,7 +631,8 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
                             const gdiet_ksw_score_t *sc, int32_t *d_score, int32_t *d_n_cigar, uint32_t *d_cigar, const int64_t *d_cigar_off,
                             const int64_t *h_qoff, const int64_t *h_toff, const int32_t *h_w, void *stream_, const int64_t *h_cigar_off,
                             const int32_t *h_exact_score, hipEvent_t arena_free = nullptr /* the kernels (not the descriptor copies) wait for it */,
-                            std::unique_lock<std::mutex> *arena_turn = nullptr /* locked here once the planning is done, left locked */)
+                            std::unique_lock<std::mutex> *arena_turn = nullptr /* locked here once the planning is done, left locked */,
+                            bool may_wait = false /* the caller waits for the stream behind this call anyway: the call may wait for the main DP launch (gd_dp_launch, host_decides) */)
 {
 	if (!ctx) return GDIET_E_PARAM;
 	if (n <= 0) return GDIET_OK;
@@ -707,7 +733,8 @@ static int gd_ksw_batch_dev(gdiet_ctx *ctx, int n, const uint8_t *d_qseq, const 
 		GD_HIP(hipMemcpyAsync(ctx->pipe_runs.p, P.pipe_runs.data(), sizeof(PipeRun) * P.pipe_runs.size(), hipMemcpyHostToDevice, stream));
 	}
 	mark("upload");
-	if ((rc = gd_dp_launch(ctx, P, n, K, sc, d_qseq, d_tseq, (uint8_t *)arena.p, d_score, d_n_cigar, d_cigar, stream, arena_free))) return rc;
+	if ((rc = gd_dp_launch(ctx, P, n, K, sc, d_qseq, d_tseq, (uint8_t *)arena.p, d_score, d_n_cigar, d_cigar, stream, arena_free,
+	                       may_wait && !(ctx->parent && !own) /* (in the shared arena the lanes take turns: the next lane's kernels queue behind this stage as it was enqueued) */))) return rc;
 	mark("launch");
 	if (mark.on) fprintf(stderr, "[gdiet dp planner, ms] n=%d%s\n", n, mark.s.c_str());
 	return GDIET_OK;
@@ -788,6 +815,15 @@ extern "C" int gdiet_hip_last_arena(gdiet_ctx *ctx, uint64_t out[3])
 	if ((rc = gd_narrow_counters(ctx, v))) return rc;
 	out[0] = v[GD_CNT_POOL], out[1] = v[GD_CNT_DRAINED], out[2] = ctx->last_arena_bytes;
 	return gd_check_drained(ctx, v);
+}
+
+// drain launches the most recent DP launch enqueued: 0 where the host saw an empty pending list (or the batch has no compact arena), the
+// planner's worst case where they are enqueued before the main launch has ended (gd_dp_launch)
+extern "C" int gdiet_hip_last_drain_launches(gdiet_ctx *ctx, int *enqueued)
+{
+	if (!ctx || !enqueued) return GDIET_E_PARAM;
+	*enqueued = ctx->drain_enqueued;
+	return GDIET_OK;
 }
 
 extern "C" int gdiet_hip_last_kernel_ms(gdiet_ctx *ctx, float *dp_ms, float *bt_ms)
@@ -885,9 +921,8 @@ extern "C" int gdiet_hip_ksw_extd2_batch(gdiet_ctx *ctx, int n, const uint8_t *q
 	GD_HIP(hipMemcpyAsync(d_t, tseq, tb, hipMemcpyHostToDevice, s));
 	GD_HIP(hipMemcpyAsync(d_cigoff, cigar_off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
 	if (exact_score) GD_HIP(hipMemcpyAsync(d_ex, exact_score, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-	rc = gdiet_hip_ksw_extd2_batch_dev(ctx, n, d_q, nullptr, d_t, nullptr, nullptr, exact_score ? d_ex : nullptr, sc,
-	                                   (int32_t *)ctx->score.p, (int32_t *)ctx->ncig.p, (uint32_t *)ctx->cigar.p, d_cigoff,
-	                                   qoff, toff, w, s);
+	rc = gd_ksw_batch_dev(ctx, n, d_q, d_t, exact_score ? d_ex : nullptr, sc, (int32_t *)ctx->score.p, (int32_t *)ctx->ncig.p, (uint32_t *)ctx->cigar.p, d_cigoff,
+	                      qoff, toff, w, s, nullptr, nullptr, nullptr, nullptr, true /* this call waits for s below */);
 	if (rc) return rc;
 	GD_HIP(hipMemcpyAsync(score, ctx->score.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
 	GD_HIP(hipMemcpyAsync(n_cigar, ctx->ncig.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));

@@ -75,7 +75,8 @@ struct GdPlan {
 	size_t bt = 0;                 // bytes of backtrace arena
 	// the compact layout (GdPlanOpt::compact, and the batch has GD_NARROW_TRY boxes; else pool_bytes = n_drain = 0 and n_compact = 0):
 	// [pool_off, pool_off + pool_bytes) behind the last slot is the overflow pool, bt their sum; n_drain launches of the 64-lane kernel
-	// behind the main one serve every box that found no room there, whatever the order of the claims (gd_drain_launches)
+	// behind the main one serve every box that found no room there, whatever the order of the claims (gd_drain_launches) -- the worst
+	// case, for which the claim counters are allocated; a caller that knows how many boxes are pending enqueues gd_drain_rounds of them
 	size_t pool_off = 0, pool_bytes = 0, n_compact = 0, full_total = 0, full_max = 0; // n_compact boxes with a half-size slot; their full-size slots in all, the largest
 	int n_drain = 0;
 	bool wide_ck = false;         // the wide-band alignments run checkpointed ...
@@ -100,6 +101,37 @@ static inline int gd_drain_launches(size_t n_boxes, size_t full_total, size_t fu
 	if (arena < full_max) return -1;
 	const size_t per = arena - full_max + 256;
 	return (int)std::min(n_boxes, (full_total + per - 1) / per);
+}
+
+// The drain launches over a PENDING LIST (ksw_wave.hip.h): n_pending boxes of the batch found no room in the overflow pool.  All the host
+// knows of them when it decides is how many they are and what the planner summed over every box that could have been among them
+// (full_total, full_max), so it bounds their bytes by both: n_pending boxes need at most min(full_total, n_pending * full_max).
+// gd_drain_launches of that set is the number of rounds -- 0 for an empty list, never more than the planner's n_drain for the whole
+// batch (the bound grows with the count and with the bytes), so the claim counters the batch allocated suffice.
+struct GdDrainSet { size_t n_pending, full_total, full_max; };
+static inline int gd_drain_rounds(const GdDrainSet &S, size_t arena)
+{
+	return gd_drain_launches(S.n_pending, std::min(S.full_total, S.n_pending * S.full_max), S.full_max, arena);
+}
+// The claims of those rounds, replayed: the boxes arrive in the order of `units` (their full-size slots in units of 256 bytes) in every
+// round, each adds its size to the round's counter, and the ones gd_claim_fits admits -- the kernel's own test -- have their rows at
+// the counter's old value; the others go on to the next round.  round[i] (1-based; 0: not served within n_rounds) and off_units[i] of
+// every box; returns the number of boxes left without rows, which gd_drain_rounds rules out.  tests/emul/drain_rounds_test.cpp checks
+// that against brute force for whatever order the boxes arrive in.
+static inline size_t gd_drain_replay(const std::vector<uint32_t> &units, size_t arena, int n_rounds, std::vector<int32_t> &round, std::vector<uint32_t> &off_units)
+{
+	round.assign(units.size(), 0), off_units.assign(units.size(), 0);
+	size_t left = units.size();
+	for (int k = 1; k <= n_rounds && left; ++k) {
+		uint32_t counter = 0; // (the device's is 32 bits wide as well: every box of a batch together stays below 2^32 units)
+		for (size_t i = 0; i < units.size(); ++i) {
+			if (round[i]) continue;
+			const uint32_t at = counter;
+			counter += units[i];
+			if (gd_claim_fits(at, units[i], (int64_t)(arena >> 8))) round[i] = k, off_units[i] = at, --left;
+		}
+	}
+	return left;
 }
 
 // Fills tasks[0..n) and P.  run_slices(n_sl, f) calls f(sl) for every sl in [0, n_sl), in any order and on any threads; mark(name) is

@@ -318,11 +318,14 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 // certificate at NA.wq / for which it held; [4] / [5]: the same at NA.w.  Added to by every such wavefront.
 // THE COMPACT ARENA (NA.claim_units >= 0): the slot of a GD_NARROW_TRY box holds the half-block rows only (ksw_plan.h).  A box whose
 // certificate fails at both rungs claims its full-band rows from the overflow pool behind the slots and goes on in them, in the same
-// wavefront; if the pool is used up it returns and stays GD_ST_PENDING, and one of the drain launches that follow on the same stream
-// (NA.drain = 1, 2, ...: the same kernel over the same ids, narrow band off, every wavefront whose box is not pending returns at once)
-// gives it rows from the start of the arena.  narrow_cnt[GD_CNT_POOL] / [GD_CNT_DRAINED]: boxes served by the pool / by a drain launch;
-// [GD_CNT_LEFT]: boxes the last launch could not serve (the planner's number of drain launches rules that out; the host reports it);
-// [GD_CNT_CLAIM + k]: the claim counter of launch k.
+// wavefront; if the pool is used up it appends its id to the PENDING LIST (narrow_cnt[NA.list ...], narrow_cnt[GD_CNT_PENDING] its
+// length), returns and stays GD_ST_PENDING.  Drain launches on the same stream (NA.drain = 1, 2, ...: the same kernel with the pending
+// list as its id list, narrow band off; a wavefront whose box an earlier drain launch served returns at once) give such boxes rows from
+// the start of the arena.  Where the host waits for the main launch anyway it reads the list's length first and enqueues the drain
+// launches only if there is something to drain, with one wavefront per pending box; elsewhere they are enqueued up front with a
+// wavefront for every id, and those past the list's end return (gd_dp_launch).  narrow_cnt[GD_CNT_POOL] / [GD_CNT_DRAINED]: boxes served
+// by the pool / by a drain launch; [GD_CNT_LEFT]: boxes the last launch could not serve (the number of drain launches rules that out,
+// gd_drain_rounds; the host reports it); [GD_CNT_CLAIM + k]: the claim counter of launch k.
 #define GD_CLOCK_SLOTS 16384
 __device__ unsigned long long gd_clock_stamps[GD_CLOCK_SLOTS * 4];
 template <int LANES, int TAG = 0, bool DUAL = true>
@@ -344,6 +347,8 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 	if (slot >= n_slots) return;
 	int tid, live = 1;
 	if (LANES == 64) {
+		// (a drain launch enqueued before the main launch had ended has a wavefront for every id: those past the pending list's end return)
+		if (DUAL && NA.drain > 0 && slot >= __builtin_amdgcn_readfirstlane((int)narrow_cnt[GD_CNT_PENDING])) return;
 		tid = __builtin_amdgcn_readfirstlane(task_ids[slot]);
 		if (__builtin_amdgcn_readfirstlane(status[tid]) != GD_ST_PENDING) return;
 	} else {
@@ -429,14 +434,18 @@ void ksw_extd2_wave_kernel(const KswTask *__restrict__ tasks,
 		}
 		if (claim) {
 			// THE CLAIM: full-band rows from the overflow pool (a drain launch: from the arena, whose slots are all dead by then) -- one atomic
-			// add on the launch's counter, in units of 256 bytes.  No room: the box stays GD_ST_PENDING for the next launch over the same id
-			// list; the wavefront never waits for another.
+			// add on the launch's counter, in units of 256 bytes.  No room: the box stays GD_ST_PENDING; the main launch appends its id to the
+			// pending list (one more atomic add, on the list's length), which is what the drain launches run over.  The wavefront never waits
+			// for another.
 			const u32 need = gd_full_units(qlen, tlen);
 			u32 at = 0;
 			if (lane == 0) at = atomicAdd(narrow_cnt + GD_CNT_CLAIM + NA.drain, need);
 			at = (u32)__builtin_amdgcn_readfirstlane((int)at);
-			if ((int64_t)at + (int64_t)need > NA.claim_units) {
-				if (NA.last && lane == 0) atomicAdd(narrow_cnt + GD_CNT_LEFT, 1u);
+			if (!gd_claim_fits(at, need, NA.claim_units)) {
+				if (lane == 0) {
+					if (NA.last) atomicAdd(narrow_cnt + GD_CNT_LEFT, 1u);
+					if (NA.drain == 0 && NA.list > 0) narrow_cnt[NA.list + atomicAdd(narrow_cnt + GD_CNT_PENDING, 1u)] = (u32)tid;
+				}
 				return;
 			}
 			if (lane == 0) atomicAdd(narrow_cnt + (NA.drain > 0 ? GD_CNT_DRAINED : GD_CNT_POOL), 1u);
@@ -606,12 +615,12 @@ static inline void gd_launch_wave64(const KswTask *tasks, const int32_t *ids, in
                                     int32_t *n_cigar, uint32_t *cigar /* fused backtrack */, int waves_per_simd /* 4: see gdiet_hip_set_dp_waves */,
                                     int narrow_w /* GD_W_NARROW, or 0: every alignment at its full band */, uint32_t *narrow_cnt /* six counters, see the kernel */,
                                     int quarter_w /* GD_W_QUARTER, or 0: the quarter rung is not offered */,
-                                    int drain = 0, bool last = true, int64_t claim_off = 0, int64_t claim_bytes = -1 /* the compact arena: GdNarrowArg */)
+                                    int drain = 0, bool last = true, int64_t claim_off = 0, int64_t claim_bytes = -1, int list = 0 /* the compact arena: GdNarrowArg */)
 {
 	WaveK K;
 	gdw_make_consts(C, K);
 	GdNarrowArg NA = gd_narrow_arg(C, narrow_cnt ? narrow_w : 0, quarter_w);
-	NA.drain = drain, NA.last = last, NA.claim_off = claim_off, NA.claim_units = claim_bytes < 0 ? -1 : claim_bytes >> 8;
+	NA.drain = drain, NA.last = last, NA.list = list, NA.claim_off = claim_off, NA.claim_units = claim_bytes < 0 ? -1 : claim_bytes >> 8;
 	// one wavefront per workgroup: a finished wavefront frees its slot at once instead of waiting for its three block mates
 	const dim3 grid(n), block(64);
 	// Four wavefronts per SIMD instead of five: the kernel uses no LDS, so an (unused) dynamic allocation of a sixteenth of the CU's 160 KB

@@ -783,19 +783,23 @@ struct GdNarrowArg {
 	int32_t wq;            // the band of the quarter-block rows, tried before it (GD_W_QUARTER; 0: that rung is not offered)
 	// the compact arena (ksw_plan.h): where a GD_NARROW_TRY box that needs its full-band rows after all claims them
 	int32_t drain;         // 0: the main launch, claims go to the overflow pool; k > 0: the k-th drain launch behind it, claims go to the whole arena
-	int32_t last;          // this is the last launch over the id list: a claim that finds no room is counted (a planner bug)
+	int32_t last;          // this is the last launch of the batch's 64-lane kernel: a claim that finds no room is counted (a planner bug)
+	int32_t list;          // where the pending list starts, in words of the counter array (0: the batch has none)
 	int64_t claim_off;     // the pool's byte offset in the arena (a drain launch: 0)
 	int64_t claim_units;   // ... and its size in units of 256 bytes; < 0: the slots are full-size, nothing is ever claimed
 };
 // the counters of a 64-lane launch behind the six of the ladder (see the kernel): boxes that claimed from the pool, boxes served by a
-// drain launch, unused, boxes left without rows after the last launch, then the claim counter (units of 256 bytes) of the main launch and
-// of every drain launch
-enum : int { GD_CNT_POOL = 6, GD_CNT_DRAINED = 7, GD_CNT_LEFT = 9, GD_CNT_CLAIM = 10 };
+// drain launch, boxes of the main launch that found no room in the pool (the length of the pending list), boxes left without rows after
+// the last launch, then the claim counter (units of 256 bytes) of the main launch and of every drain launch, then the pending list
+enum : int { GD_CNT_POOL = 6, GD_CNT_DRAINED = 7, GD_CNT_PENDING = 8, GD_CNT_LEFT = 9, GD_CNT_CLAIM = 10 };
 GDW_HD uint32_t gd_full_units(int qlen, int tlen) { return (uint32_t)(((size_t)(qlen + tlen - 1) * 1024 + 64 + 255) >> 8); } // the full-band slot of a box of the 64-lane kernel
+// THE CLAIM of a launch, for the kernel and for its replay on the host (ksw_plan.h, gd_drain_rounds): the launch's counter stood at `at`
+// units before the atomic add of `need`; the box has its rows at `at` iff they end inside the `units` the launch may hand out
+GDW_HD bool gd_claim_fits(uint32_t at, uint32_t need, int64_t units) { return (int64_t)at + (int64_t)need <= units; }
 static inline GdNarrowArg gd_narrow_arg(const KswConst &C, int w, int wq = 0)
 {
 	GdNarrowArg A;
-	A.drain = 0, A.last = 1, A.claim_off = 0, A.claim_units = -1;
+	A.drain = 0, A.last = 1, A.list = 0, A.claim_off = 0, A.claim_units = -1;
 	A.w = w, A.wq = w > 0 ? wq : 0, A.q = C.q, A.e = C.e, A.q2 = C.q2, A.e2 = C.e2;
 	A.a = C.sc_mch > C.sc_mis ? C.sc_mch : C.sc_mis;
 	if (C.sc_N > A.a) A.a = C.sc_N;

@@ -436,8 +436,8 @@ __global__ __launch_bounds__(64) void map_post_kernel(int nb, const MapBox *__re
 
 // ---- wave-parallel form of map_post_kernel: one 64-lane wavefront per alignment ---------------------------------------------------
 // One thread per alignment leaves a HiFi batch with 147 wavefronts, each lane in a 15 000-step loop of dependent loads: 22 ms per
-// 9 400 alignments, a quarter of a single batch's latency.  Here mm_fix_cigar is a kernel of its own (map_fix_cigar_kernel: a few hundred
-// operations per alignment), and the walk over the bases -- mlen / blen / n_ambi and the running score of mm_update_extra -- is done
+// 9 400 alignments, a quarter of a single batch's latency.  Here mm_fix_cigar (a few hundred operations per alignment) stays on one
+// lane, and the walk over the bases -- mlen / blen / n_ambi and the running score of mm_update_extra -- is done
 // by all 64 lanes of a wavefront per alignment.
 // The running score  s <- max(s + a_i, 0),  mx <- max(mx, s)  (LR/align.c:286-310; the reference updates mx only where s stays >= 0,
 // and not at gaps: the same thing, as s <= mx always holds and mx starts at 0) is a composition of maps  s -> max(s + A, B)  together
@@ -468,26 +468,8 @@ __device__ __forceinline__ GdpSeg gdp_seg_join(const GdpSeg &x, const GdpSeg &y)
 // next batch in flight holds 5 x 96 of a SIMD's 512 registers, so a wavefront of this size is the largest that can start BESIDE a full
 // house of DP wavefronts instead of waiting for one of them to retire (with 52 registers the kernel's 9 400 wavefronts took as long as
 // the DP kernel next to them, the batch's results arrived one DP kernel late and the pipelined step went from 88.8 to 97.6 ms).
-// first half of P1 for the wave-parallel form: mm_fix_cigar alone, one alignment per thread (a few hundred CIGAR operations each; the few
-// wavefronts this needs find room at once).  Leaves the fixed CIGAR and its length in place and the two shifts in post[b].
-__global__ __launch_bounds__(64) void map_fix_cigar_kernel(int nb, const MapBox *__restrict__ boxes, const uint8_t *__restrict__ qbuf, const uint8_t *__restrict__ tbuf,
-                                                           const int64_t *__restrict__ coff, uint32_t *__restrict__ cig, int32_t *__restrict__ n_cigar,
-                                                           const int32_t *__restrict__ score, GdPostOut *__restrict__ post)
-{
-	__builtin_amdgcn_s_setprio(3); // (see map_post_wave_kernel)
-	const int b = blockIdx.x * blockDim.x + threadIdx.x;
-	if (b >= nb) return;
-	GdPostOut P;
-	P.qshift = P.tshift = P.mlen = P.blen = P.dp_max = 0, P.n_ambi = 0;
-	const int32_t n0 = n_cigar[b];
-	if (score[b] != GD_NEG_INF_SCORE_DEV && n0 > 0 && (int64_t)n0 <= coff[b + 1] - coff[b]) {
-		uint32_t n = (uint32_t)n0;
-		gdp_fix_cigar(cig + coff[b], &n, qbuf + boxes[b].q_dst, tbuf + boxes[b].t_dst, &P.qshift, &P.tshift);
-		n_cigar[b] = (int32_t)n;
-	}
-	post[b] = P;
-}
-
+// mm_fix_cigar is the kernel's prologue, on lane 0 (below).  Every kernel of a batch's tail is held to this budget (build.py): with two
+// batches in flight each of them runs beside the other batch's main DP launch.
 __global__ __launch_bounds__(64) void map_post_wave_kernel(int nb, const MapBox *__restrict__ boxes, const uint8_t *__restrict__ qbuf, const uint8_t *__restrict__ tbuf,
                                                            const int64_t *__restrict__ coff, uint32_t *__restrict__ cig, int32_t *__restrict__ n_cigar,
                                                            const int32_t *__restrict__ score, MapPostOpt O, GdPostOut *__restrict__ post,
@@ -509,14 +491,25 @@ __global__ __launch_bounds__(64) void map_post_wave_kernel(int nb, const MapBox 
 	const int32_t sc_b = __builtin_amdgcn_readfirstlane(score[b]);
 	const int64_t c0 = coff[b], c1 = coff[b + 1];
 	const bool live = sc_b != GD_NEG_INF_SCORE_DEV && n0 > 0 && (int64_t)n0 <= c1 - c0;
-	const int32_t n_out = n0;
+	int32_t n_out = n0;
 	if (live) {
 		// (everything about the alignment as a whole is wave-uniform and is kept on the scalar unit: the per-lane state is a segment, two
 		// counters and the loaded bytes)
 		uint32_t *cg = (uint32_t *)gdw_uniform_ptr((const uint8_t *)(cig + c0), 0);
 		const uint8_t *qseq = gdw_uniform_ptr(qbuf + boxes[b].q_dst, 0), *tseq = gdw_uniform_ptr(tbuf + boxes[b].t_dst, 0);
-		const uint32_t n = (uint32_t)n0; // (mm_fix_cigar has run: map_fix_cigar_kernel)
-		P.qshift = __builtin_amdgcn_readfirstlane(post[b].qshift), P.tshift = __builtin_amdgcn_readfirstlane(post[b].tshift);
+		// mm_fix_cigar first, on lane 0 (a few hundred CIGAR operations): the fixed CIGAR stays in its slot, its length and the two shifts
+		// go to the scalar unit.  (It was a kernel of its own, one alignment per thread, with the shifts passed through post[b]: one more
+		// launch in every batch's tail, and at 33 registers the one kernel of the tail that could not start beside a full house.)
+		uint32_t n_fix = (uint32_t)n0;
+		int32_t qshift = 0, tshift = 0;
+		if (lane == 0) {
+			gdp_fix_cigar(cg, &n_fix, qseq, tseq, &qshift, &tshift);
+			n_cigar[b] = (int32_t)n_fix;
+		}
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); // lane 0's CIGAR words are written before any lane reads them below
+		const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_fix);
+		n_out = (int32_t)n;
+		P.qshift = __builtin_amdgcn_readfirstlane(qshift), P.tshift = __builtin_amdgcn_readfirstlane(tshift);
 		__syncthreads(); // (s_mat)
 		qseq += P.qshift, tseq += P.tshift;
 		// the running score S and its maximum MX as (integer part, fraction in units of 2^-GDP_FRAC, 0 <= fraction < 2^GDP_FRAC): base

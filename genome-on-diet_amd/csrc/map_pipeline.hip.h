@@ -836,7 +836,7 @@ static int gd_stage_dp(GdMapCall &c)
 	}
 	rc = gd_ksw_batch_dev(ctx, nb, (const uint8_t *)ctx->m_q.p, (const uint8_t *)ctx->m_t.p, c.d_ex, &ks, c.d_score, c.d_ncig, (uint32_t *)ctx->m_cig.p, c.d_coff,
 	                      T.qoff.data(), T.toff.data(), T.bw.data(), sd, T.coff.data(), T.ex.data(), ctx->parent ? ctx->parent->arena_ev : nullptr,
-	                      ctx->parent ? &dp_lock : nullptr);
+	                      ctx->parent ? &dp_lock : nullptr, true /* this stage waits for sd below */);
 	if (rc) { // kernels of this stage may already be queued in the shared arena: let them finish before the next lane takes its turn
 		(void)hipStreamSynchronize(sd);
 		return rc; // (the lock, if taken, is released by dp_lock's destructor)
@@ -879,12 +879,9 @@ static int gd_stage_dp(GdMapCall &c)
 		o_score = (int32_t *)ctx->h_pin.p, o_ncig = o_score + nbp, o_post = (GdPostOut *)(o_ncig + nbp);
 		c.h_score = o_score, c.h_ncig = o_ncig, c.h_post = o_post;
 	}
-	if (post_wave) {
-		hipLaunchKernelGGL(map_fix_cigar_kernel, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-		                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, o_post);
+	if (post_wave)
 		hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
 		                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
-	}
 	else if (eqx) hipLaunchKernelGGL(map_post_kernel<true>, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
 	                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
 	else hipLaunchKernelGGL(map_post_kernel<false>, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
@@ -1222,7 +1219,7 @@ extern "C" int gdiet_hip_map_wait(gdiet_ctx *ctx, gdiet_map_ticket *t)
 				rung_offered = c->narrow_launched && c->quarter_offered, rung[0] = ctx->async_narrow[2], rung[1] = ctx->async_narrow[3];
 				if ((rc = gd_check_drained(ctx, ctx->async_narrow))) t->rc = rc;
 			}
-			ctx->last_arena_bytes = c->last_arena_bytes;
+			ctx->last_arena_bytes = c->last_arena_bytes, ctx->drain_enqueued = c->drain_enqueued;
 		}
 		ctx->async_busy[t->lane] = false;
 		delete t;

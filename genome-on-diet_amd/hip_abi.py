@@ -66,6 +66,7 @@ def load_library():
     lib.gdiet_hip_last_narrow_band.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.gdiet_hip_last_narrow_rungs.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.gdiet_hip_last_arena.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.gdiet_hip_last_drain_launches.argtypes = [vp, C.POINTER(C.c_int)]
     lib.gdiet_hip_ksw_extd2_batch.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, i32p, i32p, C.POINTER(KswScore),
                                               i32p, i32p, u32p, i64p]
     lib.gdiet_hip_ksw_extd2_batch_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(KswScore),
@@ -234,6 +235,12 @@ class Context:
         v = (C.c_uint64 * 3)()
         self._check(self.lib.gdiet_hip_last_arena(self._h, v))
         return tuple(int(x) for x in v)
+
+    def last_drain_launches(self):
+        """drain launches the most recent DP launch enqueued (gdiet_hip_last_drain_launches)"""
+        n = C.c_int()
+        self._check(self.lib.gdiet_hip_last_drain_launches(self._h, C.byref(n)))
+        return n.value
 
     def reserve(self, nbytes):
         self._check(self.lib.gdiet_hip_reserve(self._h, nbytes))

@@ -207,6 +207,12 @@ int gdiet_hip_last_narrow_rungs(gdiet_ctx *ctx, uint64_t out[4]);
  * bytes of arena the batch was planned with.  GDIET_BT_COMPACT=0 (read when the library is loaded): every slot is sized for the full-band
  * rows.  Results never depend on either.  GDIET_E_HIP if a box was left without rows (a planner bug, never a wrong alignment). */
 int gdiet_hip_last_arena(gdiet_ctx *ctx, uint64_t out[3]);
+/* Drain launches the most recent DP launch enqueued.  A box that finds the pool used up appends its id to a pending list on the device.
+ * Where the call waits for its stream anyway (gdiet_hip_ksw_extd2_batch, the mapping path in an arena of its own) the host reads the
+ * list's length when the main launch has ended: 0 launches for an empty list, else as many as the pending boxes need, one wavefront per
+ * box.  gdiet_hip_ksw_extd2_batch_dev never waits, and lanes that take turns in a shared arena must not: there the planner's worst case
+ * for the whole batch is enqueued up front, and the wavefronts past the list's end return at once. */
+int gdiet_hip_last_drain_launches(gdiet_ctx *ctx, int *enqueued);
 
 /* ---- B1: the per-read mapping path for a whole batch of reads (LongReads variant; ShortReads variant with MM_F_SR) ----
  * Replaces step 1 of worker_pipeline -- kt_for(n_threads, worker_for, ...) -> mm_map_frag() per read
