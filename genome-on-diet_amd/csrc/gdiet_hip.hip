@@ -1157,6 +1157,7 @@ extern "C" int gdiet_hip_debug_seed_prof(unsigned long long *out8) { return (int
 #include "fastx_reader.h"
 #include "fastx_dev_driver.hip.h" // struct gdiet_fastx; the device mode of the reader.  It includes bgzf_driver.hip.h: the BGZF drivers, gdiet_bgzf_out, gdiet_hip_bgzf_*
 #include "bam_in_driver.hip.h"    // BAM input: the unpack kernel's driver, gdiet_hip_bam_in_unpack
+#include "ref_fasta_driver.hip.h" // reference input: FASTA blocks parsed on the device, gdiet_hip_index_open / _index_info / _index_open_stats / _ref_block
 static int gd_fx_read_failed(gdiet_fastx *fx);
 
 extern "C" int gdiet_hip_fastx_open(gdiet_fastx **fx, const char *path)

@@ -166,6 +166,39 @@ static inline void gd_index_build(GdIndex &I, const std::vector<std::string> &na
 	for (auto &t : th) t.join();
 }
 
+// Sequence table + 4-bit packing of S on host threads (the part of gd_index_build that is not sketching): what the device
+// build (map_index_dev.hip.h) starts from, and what ref_pack_kernel (ref_fasta.hip.h) must reproduce
+static inline void gd_index_pack_S(GdIndex &I, const std::vector<std::string> &names, const std::vector<GdSeqSpan> &seqs, int n_threads)
+{
+	const size_t n = seqs.size();
+	uint64_t sum = 0;
+	I.seq.resize(n);
+	for (size_t i = 0; i < n; ++i) I.seq[i].name = names[i], I.seq[i].offset = sum, I.seq[i].len = (uint32_t)seqs[i].size(), sum += seqs[i].size();
+	I.S.assign((sum + 7) / 8, 0);
+	// word-aligned chunks of 1 Mbases: a chunk never shares a word with another (contig boundaries inside a word are handled
+	// by walking the contigs that overlap the chunk)
+	const uint64_t CH = 1u << 20;
+	const uint64_t n_chunks = (sum + CH - 1) / CH;
+	std::atomic<uint64_t> next(0);
+	auto work = [&]() {
+		for (;;) {
+			const uint64_t c = next.fetch_add(1);
+			if (c >= n_chunks) break;
+			const uint64_t lo = c * CH, hi = std::min(sum, lo + CH);
+			// first contig overlapping lo
+			size_t ci = (size_t)(std::upper_bound(I.seq.begin(), I.seq.end(), lo, [](uint64_t v, const GdSeqInfo &s) { return v < s.offset; }) - I.seq.begin());
+			ci = ci ? ci - 1 : 0;
+			for (; ci < n && I.seq[ci].offset < hi; ++ci) {
+				const uint64_t off = I.seq[ci].offset, a = std::max(lo, off), b = std::min<uint64_t>(hi, off + I.seq[ci].len);
+				for (uint64_t o = a; o < b; ++o) I.S[o >> 3] |= (uint32_t)gd_nt4((unsigned char)seqs[ci][o - off]) << ((o & 7) << 2);
+			}
+		}
+	};
+	std::vector<std::thread> th;
+	for (int t = 0; t < std::max(1, n_threads); ++t) th.emplace_back(work);
+	for (auto &t : th) t.join();
+}
+
 // ---- flat form -> GdIndex (what gdiet_hip_index_import and the .mmi reader feed) -------------------------------------------------
 // keys[i] = minimizer hash (x >> 8), cnt[i] its number of occurrences, pos = the occurrence lists (y values, each ascending)
 // concatenated in key order.
@@ -358,9 +391,12 @@ static inline bool gd_index_write_mmi(const GdIndex &h, const char *path, int bu
 			if (kh.flag[k] == 0) kv.push_back(ekey[kh.vals[k]]), kv.push_back(eval[kh.vals[k]]);
 		const int32_t n = (int32_t)p.size();
 		const uint32_t size = (uint32_t)(kv.size() / 2);
-		fwrite(&n, 4, 1, fp), fwrite(p.data(), 8, p.size(), fp), fwrite(&size, 4, 1, fp), fwrite(kv.data(), 8, kv.size(), fp);
+		fwrite(&n, 4, 1, fp);
+		if (!p.empty()) fwrite(p.data(), 8, p.size(), fp); // (an empty vector's data() may be null, which fwrite must not be given)
+		fwrite(&size, 4, 1, fp);
+		if (!kv.empty()) fwrite(kv.data(), 8, kv.size(), fp);
 	}
-	fwrite(h.S.data(), 4, (sum_len + 7) / 8, fp);
+	if (sum_len) fwrite(h.S.data(), 4, (sum_len + 7) / 8, fp);
 	const bool ok = fflush(fp) == 0 && !ferror(fp);
 	fclose(fp);
 	if (!ok) err = std::string("write error on ") + path;

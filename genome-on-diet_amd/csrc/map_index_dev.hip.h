@@ -1,7 +1,7 @@
 // Index build on the device: mm_sketch over the reference (LR/sketch.c:156/1577 via the shared automaton
 // of map_stages.h, AVX-512 flush rule = GDiet_avx), sort of the (minimizer, position) pairs, run-length encoding into distinct keys
 // and the open-addressing table -- the same flat index gd_index_build (map_index.h) makes on the host, built where it will live.
-//   host    : contig table, 4-bit packing of S (the host post-processing needs S anyway)
+//   host    : contig table, 4-bit packing of S (gd_index_pack_S, map_index.h; the host post-processing needs S anyway)
 //   device  : unpack S -> nt4 bytes; one thread per slice of 4096 sparsified bases runs the winnowing automaton twice (count,
 //             then emit: exact slices, see gd_sketch_slice); two stable radix sorts (by y, then by hash: hipCUB); run-length
 //             encode; one thread per distinct key claims its table slot with a 64-bit compare-and-swap.
@@ -86,58 +86,20 @@ struct GdDevTmp { // frees everything it allocated when it goes out of scope
 
 #define GD_IDX_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e__); return false; } } while (0)
 
-// Sequence table + 4-bit packing of S on host threads (the part of gd_index_build that is not sketching)
-static inline void gd_index_pack_S(GdIndex &I, const std::vector<std::string> &names, const std::vector<GdSeqSpan> &seqs, int n_threads)
-{
-	const size_t n = seqs.size();
-	uint64_t sum = 0;
-	I.seq.resize(n);
-	for (size_t i = 0; i < n; ++i) I.seq[i].name = names[i], I.seq[i].offset = sum, I.seq[i].len = (uint32_t)seqs[i].size(), sum += seqs[i].size();
-	I.S.assign((sum + 7) / 8, 0);
-	// word-aligned chunks of 1 Mbases: a chunk never shares a word with another (contig boundaries inside a word are handled
-	// by walking the contigs that overlap the chunk)
-	const uint64_t CH = 1u << 20;
-	const uint64_t n_chunks = (sum + CH - 1) / CH;
-	std::atomic<uint64_t> next(0);
-	auto work = [&]() {
-		for (;;) {
-			const uint64_t c = next.fetch_add(1);
-			if (c >= n_chunks) break;
-			const uint64_t lo = c * CH, hi = std::min(sum, lo + CH);
-			// first contig overlapping lo
-			size_t ci = (size_t)(std::upper_bound(I.seq.begin(), I.seq.end(), lo, [](uint64_t v, const GdSeqInfo &s) { return v < s.offset; }) - I.seq.begin());
-			ci = ci ? ci - 1 : 0;
-			for (; ci < n && I.seq[ci].offset < hi; ++ci) {
-				const uint64_t off = I.seq[ci].offset, a = std::max(lo, off), b = std::min<uint64_t>(hi, off + I.seq[ci].len);
-				for (uint64_t o = a; o < b; ++o) I.S[o >> 3] |= (uint32_t)gd_nt4((unsigned char)seqs[ci][o - off]) << ((o & 7) << 2);
-			}
-		}
-	};
-	std::vector<std::thread> th;
-	for (int t = 0; t < std::max(1, n_threads); ++t) th.emplace_back(work);
-	for (auto &t : th) t.join();
-}
-
-// Builds ix->h's sequence part on the host and the table part on the device (d_tkey, d_tval, d_pos, d_S, d_cnt_sorted).
-static bool gd_index_build_device(gdiet_index *ix, const std::vector<std::string> &names, const std::vector<GdSeqSpan> &seqs, int k, int w,
-                                  const GdPattern &pat, int n_threads, hipStream_t st, std::string &err)
+// Slices, sketch, sorts and table from the point where the sequence table (I.seq), S (I.S on the host, d_S on the device) and the nt4
+// bytes of every base (d_nt4, one per base at its offset in S) are complete: the part of the device build that both routes share,
+// gd_index_build_device below (sequences in memory) and gd_ref_open_device (ref_fasta_driver.hip.h: a file, parsed on the device).
+// d_S and d_nt4 are T's; d_S is kept for the index.
+static bool gd_index_build_from_nt4(gdiet_index *ix, GdDevTmp &T, uint32_t *d_S, const uint64_t *d_nt4, int k, int w, const GdPattern &pat, hipStream_t st, std::string &err)
 {
 	GdIndex &I = ix->h;
 	I.k = k, I.w = w, I.pat = pat;
-	gd_index_pack_S(I, names, seqs, n_threads);
-	const uint64_t n_words = I.S.size();
-	GdDevTmp T;
-	uint32_t *d_S = nullptr;
-	GD_IDX_HIP(T.alloc(&d_S, n_words + 2));
-	GD_IDX_HIP(hipMemcpyAsync(d_S, I.S.data(), n_words * 4, hipMemcpyHostToDevice, st));
-	uint64_t *d_nt4 = nullptr;
-	GD_IDX_HIP(T.alloc(&d_nt4, n_words + 8));
-	if (n_words) hipLaunchKernelGGL(idx_unpack_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, d_S, d_nt4, n_words);
+	const std::vector<GdSeqInfo> &seqs = I.seq;
 	// slices
 	std::vector<GdIdxSlice> sl;
 	for (size_t c = 0; c < seqs.size(); ++c) {
-		if (seqs[c].empty()) continue;
-		const unsigned dl = gd_diet_len(pat, (unsigned)seqs[c].size(), 0);
+		if (seqs[c].len == 0) continue;
+		const unsigned dl = gd_diet_len(pat, (unsigned)seqs[c].len, 0);
 		for (unsigned a = 0; a < dl || a == 0; a += GD_IDX_SLICE) { // a contig with dl == 0 still gets its (empty) final flush
 			GdIdxSlice s = {I.seq[c].offset, (uint32_t)c, dl, a, std::min(dl, a + GD_IDX_SLICE)};
 			sl.push_back(s);
@@ -247,6 +209,23 @@ static bool gd_index_build_device(gdiet_index *ix, const std::vector<std::string
 	ix->dview.tkey = (const uint64_t *)ix->d_tkey, ix->dview.tval = (const uint64_t *)ix->d_tval, ix->dview.pos = (const uint64_t *)ix->d_pos;
 	ix->host_tables = false;
 	return true;
+}
+
+// Builds ix->h's sequence part on the host and the table part on the device (d_tkey, d_tval, d_pos, d_S, d_cnt_sorted).
+static bool gd_index_build_device(gdiet_index *ix, const std::vector<std::string> &names, const std::vector<GdSeqSpan> &seqs, int k, int w,
+                                  const GdPattern &pat, int n_threads, hipStream_t st, std::string &err)
+{
+	GdIndex &I = ix->h;
+	gd_index_pack_S(I, names, seqs, n_threads);
+	const uint64_t n_words = I.S.size();
+	GdDevTmp T;
+	uint32_t *d_S = nullptr;
+	GD_IDX_HIP(T.alloc(&d_S, n_words + 2));
+	GD_IDX_HIP(hipMemcpyAsync(d_S, I.S.data(), n_words * 4, hipMemcpyHostToDevice, st));
+	uint64_t *d_nt4 = nullptr;
+	GD_IDX_HIP(T.alloc(&d_nt4, n_words + 8));
+	if (n_words) hipLaunchKernelGGL(idx_unpack_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, d_S, d_nt4, n_words);
+	return gd_index_build_from_nt4(ix, T, d_S, d_nt4, k, w, pat, st, err);
 }
 
 // the host copies of a device-built table, fetched when someone needs them (export, .mmi dump)

@@ -28,6 +28,13 @@ struct gdiet_index {
 	uint32_t *d_seq_len = nullptr;
 	uint64_t *d_seq_off = nullptr;
 	std::mutex seq_mu;
+	// gdiet_hip_index_info: the sequence table as C arrays, made on first use (under seq_mu); gdiet_hip_index_open_stats: the counters of
+	// the gdiet_hip_index_open that made this index (ref_fasta_driver.hip.h), zero for any other
+	std::vector<const char *> info_names;
+	std::vector<uint32_t> info_lens;
+	int64_t open_counts[6] = {0, 0, 0, 0, 0, 0};
+	double open_seconds[5] = {0, 0, 0, 0, 0};
+	uint64_t open_peak = 0;
 };
 
 struct gdiet_read_batch {

@@ -89,6 +89,8 @@ def load_library():
     lib.gdiet_hip_bgzf_out_close.argtypes = [vp]
     lib.gdiet_hip_bgzf_out_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
     lib.gdiet_hip_debug_bgzf_deflate_seconds.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.gdiet_hip_ref_block.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t), u32p, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_size_t), C.POINTER(C.c_int), u32p]
     _lib = lib
     return lib
 
@@ -167,6 +169,21 @@ class Context:
         if rc < 0:
             self._check(int(rc))
         return out.raw[:len(records)], rows[:n.value]
+
+    REF_LS, REF_HD, REF_SQ = 0, 1, 2  # the parser's state at byte 0 of a block: at a line start, inside a header line, inside a sequence line
+
+    def ref_block(self, text, state_in=0):
+        """gdiet_hip_ref_block: the three passes of the reference input on one block of text.  Returns dict(claimed, state_out, run_nl,
+        nt4, rows): claimed is len(text) or 0 (then state_out is -1 and the rest empty); nt4 the codes of the block's bases; rows one
+        (offset of '>', offset of its newline or 0xffffffff, bases in front) per header line that starts in the block; run_nl the offset
+        of the newline that ends a header line running into the block, or 0xffffffff"""
+        text = bytes(text)
+        nb, nr, cl, so, rn = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int(), C.c_uint32()
+        nt4 = np.zeros(max(1, len(text)), np.uint8)
+        rows = np.zeros((max(1, len(text)), 3), np.uint32)
+        self._check(self.lib.gdiet_hip_ref_block(self._h, text, len(text), state_in, _ptr(nt4, C.c_uint8), nt4.size, C.byref(nb), _ptr(rows, C.c_uint32), rows.shape[0],
+                                                 C.byref(nr), C.byref(cl), C.byref(so), C.byref(rn)))
+        return dict(claimed=cl.value, state_out=so.value, run_nl=rn.value, nt4=nt4[:nb.value].copy(), rows=rows[:nr.value].copy())
 
     def bgzf_deflate(self, data, eof=True):
         """gdiet_hip_bgzf_deflate: data cut into members of 65280 bytes, each compressed by one wavefront of the device into a complete

@@ -5,6 +5,7 @@ Mirrors the reference's call shape: ``Mapper(ctx, ref_names, ref_seqs, preset_op
 (reference map.c, step 1 of worker_pipeline); ``Mapper.sam(...)`` for ``mm_write_sam3``.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -65,6 +66,9 @@ def _bind(lib):
     lib.gdiet_hip_index_export.argtypes = [vp, u64p, u64p, u64p, u64p, u32p, u64p, u32p, u64p]
     lib.gdiet_hip_index_load_mmi.argtypes = [vp, C.POINTER(vp), C.c_char_p, C.c_char_p, C.c_int]
     lib.gdiet_hip_index_dump_mmi.argtypes = [vp, vp, C.c_char_p, C.c_int]
+    lib.gdiet_hip_index_open.argtypes = [vp, C.POINTER(vp), C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int]
+    lib.gdiet_hip_index_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(cpp), C.POINTER(u32p)]
+    lib.gdiet_hip_index_open_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double), u64p]
     lib.gdiet_hip_index_destroy.argtypes = [vp, vp]
     lib.gdiet_hip_index_destroy.restype = None
     lib.gdiet_hip_index_cal_max_occ.argtypes = [vp, C.c_float]
@@ -268,6 +272,40 @@ class Mapper:
         ctx._check(self.lib.gdiet_hip_index_load_mmi(ctx._h, C.byref(self._idx), path.encode(), p["Z"].encode(), p["W"]))
         self._setup_opt()
         return self
+
+    @classmethod
+    def from_file(cls, ctx, path, preset="hifi", n_threads=0, **overrides):
+        """gdiet_hip_index_open: the reference from a FASTA / FASTQ file (plain, gzip, BGZF, "-") or an .mmi file, known by its magic.  Names
+        and lengths come from the index (gdiet_hip_index_info); for an .mmi so do k and w, whatever the preset says."""
+        self = cls.__new__(cls)
+        self.ctx, self.lib = ctx, load_library()
+        _bind(self.lib)
+        p = dict(PRESETS[preset])
+        p.update(overrides)
+        self._idx = C.c_void_p()
+        ctx._check(self.lib.gdiet_hip_index_open(ctx._h, C.byref(self._idx), os.fsencode(path), p["k"], p["w"], p["Z"].encode(), p["W"], n_threads))
+        info = self.index_info()
+        p["k"], p["w"] = info["k"], info["w"]
+        self.p = p
+        self.names, self.lens = info["names"], info["lens"]
+        self._setup_opt()
+        return self
+
+    def index_info(self):
+        """gdiet_hip_index_info: dict(k, w, names, lens) of the index in use"""
+        k, w, n = C.c_int(), C.c_int(), C.c_int()
+        names, lens = C.POINTER(C.c_char_p)(), C.POINTER(C.c_uint32)()
+        self.ctx._check(self.lib.gdiet_hip_index_info(self._idx, C.byref(k), C.byref(w), C.byref(n), C.byref(names), C.byref(lens)))
+        return dict(k=k.value, w=w.value, names=[names[i].decode() for i in range(n.value)], lens=np.array([lens[i] for i in range(n.value)], np.uint32))
+
+    def open_stats(self):
+        """gdiet_hip_index_open_stats: the counters of the from_file call that made this index (zeros for any other)"""
+        c, t, peak = (C.c_int64 * 6)(), (C.c_double * 5)(), C.c_uint64()
+        self.ctx._check(self.lib.gdiet_hip_index_open_stats(self._idx, c, t, C.byref(peak)))
+        out = dict(zip(("file_bytes", "text_bytes", "blocks", "blocks_host", "bases_device", "bases_host"), (int(x) for x in c)))
+        out.update(zip(("read_s", "inflate_s", "device_s", "host_s", "build_s"), (float(x) for x in t)))
+        out["device_peak_bytes"] = int(peak.value)
+        return out
 
     def dump_mmi(self, path, bucket_bits=14):
         self.ctx._check(self.lib.gdiet_hip_index_dump_mmi(self.ctx._h, self._idx, path.encode(), bucket_bits))

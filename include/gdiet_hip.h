@@ -261,6 +261,47 @@ void gdiet_hip_index_destroy(gdiet_ctx *ctx, gdiet_index *idx);
 int32_t gdiet_hip_index_cal_max_occ(const gdiet_index *idx, float frac);
 uint64_t gdiet_hip_index_n_keys(const gdiet_index *idx);
 
+/* ---- Reference input: an index from a file -----------------------------------------------------------------------------------------
+ * gdiet_hip_index_open takes the reference as the reference's command line does (mm_idx_reader_open, LR/index.c:595-613): a FASTA or
+ * FASTQ file -- plain, gzip, BGZF, or "-" for stdin -- or an .mmi index file.
+ *   WHAT IT RETURNS.  For a sequence file: the index gdiet_hip_index_build makes of the names and sequences that this library's sequential
+ *     reader grammar (kseq_read, LR/kseq.h:191-232, without qualities) returns for the file, in file order.  Nothing else defines it:
+ *     neither the route (device or host), nor the block size, nor the compression of the input changes a byte of it.
+ *   .mmi.  An index file is known by its magic alone, as mm_idx_is_idx knows it (LR/index.c:573-593: a regular file of four bytes or
+ *     more that starts with "MMI\2"); the file name is not looked at.  k and w are then the file's: other values in the arguments are
+ *     not an error (the reference overrides them with a warning); gdiet_hip_index_info reports the values in use.  pattern / pattern_len
+ *     are always the arguments' (the file does not store them, see gdiet_hip_index_load_mmi).
+ *   LIMITS.  Those of gdiet_hip_index_build, refused with the same texts.  One part only: the file is never split as -I splits it.  A
+ *     file without any sequence is GDIET_E_PARAM, as n_seq = 0 is there.
+ *   ERRORS.  A file that cannot be opened or read: GDIET_E_PARAM, and gdiet_hip_strerror names the file.
+ *   ROUTES.  By default the blocks of the file go to the device as the reader reads them (inflated, where compressed, on n_threads host
+ *     threads): three passes per block place the nt4 code of every base and find the header lines (csrc/ref_fasta.h says which blocks
+ *     the device claims, and why its result is kseq_read's there; every other block goes through that grammar on the host), a last pass
+ *     packs S, and sketch, sorts and table are gdiet_hip_index_build's.  GDIET_INDEX_BUILD=host keeps everything on the host: the reader
+ *     collects the records and the host builder runs.  GDIET_FASTX_BLOCK sizes the blocks, as for reads.
+ *   n_threads <= 0: the CPUs the process may use. */
+int gdiet_hip_index_open(gdiet_ctx *ctx, gdiet_index **idx, const char *path, int k, int w, const char *pattern, int pattern_len,
+                         int n_threads);
+/* The sequence table of any index, however it was made; every pointer may be NULL.  *names and *lens point at n_seq entries that stay
+ * valid while the index lives. */
+int gdiet_hip_index_info(const gdiet_index *idx, int *k, int *w, int *n_seq, const char *const **names, const uint32_t **lens);
+/* The counters of the gdiet_hip_index_open that made this index (all zero for an index made otherwise).
+ *   counts6:  file bytes | decompressed bytes | blocks | blocks handed to the host grammar | bases placed by the device | bases placed
+ *             by the host
+ *   seconds5: read | inflate (both on the reading thread, beside the passes; a gzip stream inflates inside its reads and reports them
+ *             here) | device passes (copy up, kernels, tables down) | host grammar | the rest of the build (pack, sketch, sorts, table)
+ *   device_peak_bytes: the most device memory the block passes, the bases and S held at one time (0 on the host route). */
+int gdiet_hip_index_open_stats(const gdiet_index *idx, int64_t *counts6, double *seconds5, uint64_t *device_peak_bytes);
+/* The kernel-level boundary, for tests: the three block passes on text[0, n) with the parser in state_in at byte 0 -- 0: at the start
+ * of a line, 1: inside a header line, 2: inside a sequence line.  *claimed is n where the device claims the block and 0 where it does
+ * not (then nothing else is returned and *state_out is -1).  For a claimed block: nt4[0, *n_bases) are the codes of its bases;
+ * rows[3 r ..] = {offset of the '>', offset of its '\n' or 0xffffffff where the header line does not end in the block, bases in front
+ * of it} for every header line that starts in the block (*n_rows of them); *run_nl is the offset of the '\n' that ends the header line
+ * running into the block (state_in == 1), or 0xffffffff; *state_out is the state behind the last byte.  nt4 / rows may be NULL to ask
+ * for the sizes only; too little room is GDIET_E_PARAM. */
+int gdiet_hip_ref_block(gdiet_ctx *ctx, const char *text, size_t n, int state_in, uint8_t *nt4, size_t nt4_cap, size_t *n_bases,
+                        uint32_t *rows, size_t row_cap, size_t *n_rows, size_t *claimed, int *state_out, uint32_t *run_nl);
+
 /* the fields of mm_mapopt_t (LR/minimap.h:145-214) this path reads; fill them from the reference's struct */
 typedef struct {
 	int64_t flag;                 /* MM_F_* bits; only NO_PRINT_2ND, SR (selects the variant), FRAG_MODE, FOR_ONLY, REV_ONLY and, with SR, EQX are

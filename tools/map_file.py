@@ -2,10 +2,13 @@
 map with several batches in flight (gdiet_hip_map_submit / _wait) -> SAM records (gdiet_hip_sam_batch) -> output file.
 No Python object is made per read: the C arrays of the reader go straight into the upload and the SAM formatter.
 
-    python tools/map_file.py --preset sr ref.fa reads.fq[.gz] | reads.bam -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
-                             [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
+    python tools/map_file.py --preset sr ref.fa[.gz] | ref.mmi reads.fq[.gz] | reads.bam -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
+                             [-d out.mmi] [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
                              [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--sort-mem BYTES] [--tmp-dir DIR]]]
 
+`ref` is a FASTA / FASTQ file (plain, gzip or BGZF) or an .mmi index file, known by its magic, not its name (Mapper.from_file:
+gdiet_hip_index_open -- FASTA blocks are parsed on the device); "synth:MBP" stands for bench.py's synthetic reference.  -d FILE dumps
+the index to FILE after the build, as the reference's -d does; FILE can be the `ref` of a later run.  The JSON line gains ref_open.
 Writes the SAM body (the records).  --header puts the header lines of the reference's CLI in front (gdiet_hip_sam_header: @SQ per
 contig, the @RG line of -R, @PG with this tool's version and command line); it is opt-in, so that the default output stays the body alone.
 -R, -Y, -L, -y, -Q and --sam-hit-only mean what they mean to the reference (LR/main.c): a read group on every record, soft clips and
@@ -35,7 +38,6 @@ import torch  # noqa: F401  (first: one HIP runtime for torch and libgdiet_hip.s
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from __graft_entry__ import _load_pkg  # noqa: E402
 
 
@@ -210,6 +212,7 @@ def main():
     ap.add_argument("--index", action="store_true", help="with --bam --sort: write <out>.bai as well")
     ap.add_argument("--sort-mem", type=int, default=1 << 29, metavar="BYTES", help="bytes of records per sorted run (default 512 MiB)")
     ap.add_argument("--tmp-dir", metavar="DIR", help="where the runs are spooled (unnamed files; default: the directory of -o)")
+    ap.add_argument("-d", dest="dump", metavar="FILE", help="dump the index to FILE (.mmi, as the reference's -d) after the build; FILE can be given as ref later")
     ap.add_argument("--device-reader", action="store_true", help="parse and encode four-line FASTQ on the device (gdiet_hip_fastx_attach); the reader hands out resident batches")
     a = ap.parse_args()
     if a.eqx and a.preset != "sr":
@@ -219,16 +222,23 @@ def main():
     if (a.sort and not a.bam) or (a.index and not a.sort):
         ap.error("--sort goes with --bam, --index with --sort")
     pkg = _load_pkg()
-    from fixture_io import read_fasta
     ctx = pkg.Context(0)
-    if a.ref.startswith("synth:"):  # "synth:3088": bench.py's synthetic reference of that many Mbp, made in-process (no 3 GB FASTA file to write and parse)
-        import bench
-        names, seqs = bench.synth_reference(float(a.ref.split(":")[1]), seed=2)
-    else:
-        names, seqs = read_fasta(a.ref)
-    t0 = time.perf_counter()
     tag_bits = (0x1000000 if a.MD else 0) | (0x40 if a.cs else 0) | (0x800 if a.cs == "long" else 0)
-    m = pkg.Mapper(ctx, names, seqs, preset=a.preset, n_threads=pkg.effective_cpus())
+    try:
+        if a.ref.startswith("synth:"):  # "synth:3088": bench.py's synthetic reference of that many Mbp, made in-process (no 3 GB FASTA file to write and parse)
+            import bench
+            names, seqs = bench.synth_reference(float(a.ref.split(":")[1]), seed=2)
+            t0 = time.perf_counter()
+            m = pkg.Mapper(ctx, names, seqs, preset=a.preset, n_threads=pkg.effective_cpus())
+        else:  # a FASTA / FASTQ file (plain, gzip, BGZF) or an .mmi, known by its magic: gdiet_hip_index_open
+            t0 = time.perf_counter()
+            m = pkg.Mapper.from_file(ctx, a.ref, preset=a.preset, n_threads=pkg.effective_cpus())
+        if a.dump:
+            m.dump_mmi(a.dump)
+    except pkg.GdietError as e:
+        print("map_file: %s: %s" % (a.ref, e), file=sys.stderr)
+        ctx.close()
+        sys.exit(1)
     m.opt.flag |= tag_bits  # read by the SAM formatter alone (gdiet_hip_sam_batch); the mapping path does not interpret them
     if a.eqx:
         m.opt.flag |= 0x4000000  # MM_F_EQX: read by the mapping path (the CIGARs are rewritten on the device)
@@ -278,7 +288,7 @@ def main():
         m.close()
         ctx.close()
         sys.exit(1)
-    print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), "mini_batch_bases": chunk,
+    print(json.dumps({"reads": n, "seconds": round(dt, 3), "reads_per_s": round(n / dt), "index_s": round(t_idx, 2), **({} if a.ref.startswith("synth:") else {"ref_open": m.open_stats()}), "mini_batch_bases": chunk,
                       "inflight": a.inflight, "reader_threads": a.reader_threads, "tags": "MD" if a.MD else ("cs=" + a.cs if a.cs else None), "eqx": a.eqx, "out": a.out, "caller_seconds": map_file.last_stage_seconds,
                       **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats, "reads_format": map_file.last_format,
                       **({"bgzf_out": dict(bgzf_out.stats(), route=a.bgzf, device_seconds=[round(x, 4) for x in ctx.bgzf_deflate_seconds()])} if bgzf_out is not None else {}),
