@@ -129,7 +129,8 @@ struct GddOut { // all of it wave-uniform
 // the Kraft sum is repaired on the histogram of lengths, one unit at a time: the deepest code below the limit moves one level down and
 // makes room for two at its new depth.  The lengths are handed out again in the order of the frequencies, so a rarer symbol never gets
 // a shorter code.  Every lane of the wavefront calls it with the same arguments; freq and lens are local memory (or the emulator's heap).
-GDD_HD void gdd_build_lengths(const uint32_t *freq, uint32_t n, uint32_t max_bits, uint8_t *lens, GddBuild &B)
+// cut (the emulator's; the kernel passes none): counted up when the plain Huffman code was deeper than the limit, so that lengths were cut.
+GDD_HD void gdd_build_lengths(const uint32_t *freq, uint32_t n, uint32_t max_bits, uint8_t *lens, GddBuild &B, uint32_t *cut = nullptr)
 {
 	GDD_WAVE_FENCE();
 	// rank sort by (frequency, symbol) over the symbols that occur: every symbol has a rank of its own
@@ -167,6 +168,7 @@ GDD_HD void gdd_build_lengths(const uint32_t *freq, uint32_t n, uint32_t max_bit
 			int32_t avail = 1, used = 0, r = (int32_t)m - 2, left = (int32_t)m;
 			GDD_ROLLED for (uint32_t depth = 0; avail > 0 && left > 0 && depth < GDD_LITS; ++depth) {
 				GDD_ROLLED while (r >= 0 && A[r] == depth) ++used, --r;
+				if (cut && avail > used && left > 0 && depth > max_bits) ++*cut, cut = nullptr;
 				GDD_ROLLED while (avail > used && left > 0) B.cnt[depth < max_bits ? depth : max_bits]++, --avail, --left;
 				avail = 2 * used, used = 0;
 			}
@@ -333,8 +335,9 @@ GDD_HD uint32_t gdd_crc32(GddLds &L, uint32_t n)
 
 // ---- one block ---------------------------------------------------------------------------------------------------------------------
 // The tokens tok[0, ntok) as one block, dynamic or fixed, whichever is smaller.  Returns false, with nothing written, if the stream
-// would then not be smaller than a stored member's 5 + in_len bytes (W2).
-GDD_HD bool gdd_block(GddLds &L, GddOut &O, uint32_t ntok, bool last, uint32_t in_len)
+// would then not be smaller than a stored member's 5 + in_len bytes (W2).  cuts (the emulator's; the kernel passes none): three counters
+// of gdd_build_lengths, for the literal/length code, the distance code and the code-length code.
+GDD_HD bool gdd_block(GddLds &L, GddOut &O, uint32_t ntok, bool last, uint32_t in_len, uint32_t *cuts = nullptr)
 {
 	GDD_WAVE_FENCE();
 	GDD_LANES(lane) {
@@ -353,8 +356,8 @@ GDD_HD bool gdd_block(GddLds &L, GddOut &O, uint32_t ntok, bool last, uint32_t i
 		}
 		if (lane == 0) GDD_ATOMIC_ADD(L.freq[256], 1u); // the end-of-block code
 	}
-	gdd_build_lengths(L.freq, GDD_NLIT, 15, L.lens, L.build);
-	gdd_build_lengths(L.freq + GDD_LITS, GDD_NDIST, 15, L.lens + GDD_LITS, L.build);
+	gdd_build_lengths(L.freq, GDD_NLIT, 15, L.lens, L.build, cuts);
+	gdd_build_lengths(L.freq + GDD_LITS, GDD_NDIST, 15, L.lens + GDD_LITS, L.build, cuts ? cuts + 1 : nullptr);
 	uint32_t hlit = GDD_NLIT, hdist = GDD_NDIST;
 	GDD_ROLLED while (hlit > 257 && GDD_UNI(L.lens[hlit - 1]) == 0) --hlit;
 	GDD_ROLLED while (hdist > 1 && GDD_UNI(L.lens[GDD_LITS + hdist - 1]) == 0) --hdist;
@@ -377,7 +380,7 @@ GDD_HD bool gdd_block(GddLds &L, GddOut &O, uint32_t ntok, bool last, uint32_t i
 		GDD_ROLLED for (uint32_t s = 0; s < GDD_NCL; ++s) nz += L.clfreq[s] != 0;
 		if (nz < 2) L.clfreq[L.clfreq[0] ? 1 : 0] = 1;
 	}
-	gdd_build_lengths(L.clfreq, GDD_NCL, 7, L.cllens, L.build);
+	gdd_build_lengths(L.clfreq, GDD_NCL, 7, L.cllens, L.build, cuts ? cuts + 2 : nullptr);
 	gdd_make_codes(L.cllens, GDD_NCL, L.clcode, L.build);
 	const char *const order = "\x10\x11\x12\x00\x08\x07\x09\x06\x0a\x05\x0b\x04\x0c\x03\x0d\x02\x0e\x01\x0f"; // RFC 1951, 3.2.7
 	uint32_t hclen = GDD_NCL;
@@ -456,8 +459,8 @@ GDD_HD void gdd_start(GddLds &L, GddOut &O)
 
 // in[0, in_len) -> the complete BGZF member at slot[0, *member_len) (slot: GDD_SLOT bytes, 16-byte aligned; the bytes of its last word
 // behind the member are zero).  Returns GDD_OK, or GDD_E_LEN for in_len above 65280 (nothing is written then).  Every lane of the
-// wavefront calls it with the same arguments.
-GDD_HD uint32_t gdd_deflate(GddLds &L, const uint8_t *in, uint32_t in_len, uint8_t *slot, uint32_t *member_len)
+// wavefront calls it with the same arguments.  cuts: see gdd_block.
+GDD_HD uint32_t gdd_deflate(GddLds &L, const uint8_t *in, uint32_t in_len, uint8_t *slot, uint32_t *member_len, uint32_t *cuts = nullptr)
 {
 	*member_len = 0;
 	if (in_len > GDD_MAX_IN) return GDD_E_LEN;
@@ -508,7 +511,7 @@ GDD_HD uint32_t gdd_deflate(GddLds &L, const uint8_t *in, uint32_t in_len, uint8
 		for (;;) { // (W4: every turn that does not end the loop moves cur on by at least one)
 			if (ntok == GDD_TOK || cur >= in_len) {
 				ended = cur >= in_len;
-				stored = !gdd_block(L, O, ntok, ended, in_len);
+				stored = !gdd_block(L, O, ntok, ended, in_len, cuts);
 				ntok = 0;
 			}
 			if (cur >= end || stored) break;

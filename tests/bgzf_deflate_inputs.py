@@ -44,6 +44,26 @@ def inputs():
     return out
 
 
+def limiter_inputs():
+    """[(name, bytes)]: inputs for which gdd_build_lengths has to cut a code to its limit inside a real block (the emulator counts the
+    blocks: "cut A B C" of its report).
+
+    clen_limit: 65280 bytes whose even positions are drawn from 60 values with p ~ 0.618^i and whose odd positions walk through 120 others,
+    so that few matches form and the literal/length code has a long tail of lengths: in one of its blocks the plain Huffman code over the
+    header's symbols is 8 deep, one more than the code-length code may be.
+
+    The limit of 15 was looked for and not found: 4290 inputs of this kind (ratios 0.5 .. 0.72 over 20 .. 120 values, alone or interleaved
+    with a walk through 3 .. 120 others; 60 s of emulator runs) gave plain Huffman codes at most 13 deep in both alphabets.  A block holds
+    4096 tokens, depth 16 needs at least 2584 of them in near-Fibonacci proportions, and bytes that skewed turn into matches.  The limit
+    of 15 stays with test_build_lengths (tests/test_bgzf_deflate.py), which calls the builder on frequencies directly."""
+    rng = np.random.default_rng(5)
+    p = 0.618 ** np.arange(60)
+    a = np.zeros(M, dtype=np.uint8)
+    a[0::2] = rng.choice(60, size=M // 2, p=p / p.sum())
+    a[1::2] = (130 + 7 * np.arange(M // 2)) % 120
+    return [("clen_limit", a.tobytes())]
+
+
 def member_sizes(z):
     """[(member bytes, ISIZE)] of a BGZF file, walked by BSIZE"""
     out, at = [], 0
@@ -53,3 +73,15 @@ def member_sizes(z):
         at += n
     assert at == len(z)
     return out
+
+
+def same_members(got, want, what):
+    """two BGZF files are the same bytes; where they are not, the failure names the member"""
+    if got != want:
+        a, b = member_sizes(got), member_sizes(want)
+        assert a == b, (what, [k for k, (x, y) in enumerate(zip(a, b)) if x != y][:5])
+        at = 0
+        for k, (n, _) in enumerate(a):
+            assert got[at:at + n] == want[at:at + n], (what, "member %d" % k)
+            at += n
+    assert got == want, what

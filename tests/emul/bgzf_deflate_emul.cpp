@@ -8,8 +8,10 @@
 //                                             stream gives the input back; the trailer's CRC32 is zlib's and ISIZE the length; BSIZE + 1
 //                                             is the member's length, at most 65536; gd_bgzf_scan finds exactly these members; the
 //                                             project's own decoder (gdz_inflate, emulated) returns GDZ_OK and the same bytes.  Prints
-//                                             "member K in N out M type T maxdist D" per member (T: the first block's BTYPE; D: the longest
-//                                             distance among the tokens of its last block) and
+//                                             "member K in N out M type T maxdist D cut A B C" per member (T: the first block's BTYPE; D:
+//                                             the longest distance among the tokens of its last block; A, B, C: the blocks in which
+//                                             gdd_build_lengths had to cut the literal/length code, the distance code, the code-length
+//                                             code to its limit, whether or not the block was then written with those codes) and
 //                                             "ok members K bytes_in N bytes_out M".
 //     bgzf_deflate_emul lengths MAXBITS F...  gdd_build_lengths on the frequencies F: prints the lengths
 //     bgzf_deflate_emul writer IN OUT LEVEL THREADS OP...
@@ -39,7 +41,7 @@ static std::vector<unsigned char> slurp(const char *path)
 
 static GddLds *g_lds = new GddLds();
 static GdzLds *g_zlds = new GdzLds();
-static uint32_t g_maxdist = 0;
+static uint32_t g_maxdist = 0, g_cuts[3];
 
 #define FAIL(...) do { printf("MISMATCH " __VA_ARGS__); printf("\n"); exit(1); } while (0)
 
@@ -53,7 +55,8 @@ static std::vector<unsigned char> emul_member(const unsigned char *in, uint32_t 
 	memset((void *)g_lds, 0xa5, sizeof(GddLds)); // (nothing may depend on what local memory held)
 	memset((void *)g_lds->tok, 0, sizeof(g_lds->tok)); // (... but the token buffer is read below, for the longest distance)
 	uint32_t len = 0;
-	const uint32_t rc = gdd_deflate(*g_lds, src, n, slot, &len);
+	g_cuts[0] = g_cuts[1] = g_cuts[2] = 0;
+	const uint32_t rc = gdd_deflate(*g_lds, src, n, slot, &len, g_cuts);
 	if (rc != GDD_OK) FAIL("gdd_deflate returns %u", rc);
 	if (len < 28 || len > GDD_SLOT) FAIL("member of %u bytes", len);
 	for (uint32_t k = (len + 3) / 4 * 4; k < GDD_SLOT; ++k) if (slot[k] != 0xee) FAIL("a write behind the member at %u", k);
@@ -109,7 +112,7 @@ int main(int argc, char **argv)
 			const uint32_t n = (uint32_t)std::min<size_t>(GDD_MAX_IN, in.size() - at);
 			const std::vector<unsigned char> m = emul_member(in.data() + at, n);
 			check_member(m, in.data() + at, n, k);
-			printf("member %zu in %u out %zu type %u maxdist %u\n", k, n, m.size(), (m[18] >> 1) & 3u, g_maxdist);
+			printf("member %zu in %u out %zu type %u maxdist %u cut %u %u %u\n", k, n, m.size(), (m[18] >> 1) & 3u, g_maxdist, g_cuts[0], g_cuts[1], g_cuts[2]);
 			fwrite(m.data(), 1, m.size(), f), total += m.size();
 		}
 		if (in.empty()) { // what gdiet_hip_bgzf_deflate does not write, but the kernel must handle: a member of no bytes

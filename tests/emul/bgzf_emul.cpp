@@ -8,6 +8,8 @@
 //     bgzf_emul decode FILE                   every member through the emulated kernel and through zlib's raw inflate: equal bytes and lengths
 //     bgzf_emul trunc FILE                    every member cut at every length: the decoder must return (and never succeed where zlib fails)
 //     bgzf_emul fuzz FILE SEED N              N single-bit and single-byte mutations of every member, likewise
+//     bgzf_emul agree FILE                    every member, valid or not, likewise; prints "member K code C (its text) out N" per member: what
+//                                             the decoder returned and the bytes it had produced by then
 //     bgzf_emul reader BGZF PLAIN BLOCK CHUNK attached|host THREADS
 //                                             the reader on BGZF (the emulated device inflating and parsing, or zlib on THREADS threads) hands
 //                                             out the batches of the unattached reader on PLAIN; prints the BGZF statistics and the
@@ -63,12 +65,15 @@ static int zlib_inflate(const unsigned char *in, uint32_t in_len, uint32_t cap, 
 	return rc;
 }
 
-// the decoder against zlib on one stream; strict: both must succeed.  Returns whether the stream was valid.
-static bool compare(const unsigned char *in, uint32_t in_len, uint32_t isize, bool strict, const char *what, long k)
+// the decoder against zlib on one stream; strict: both must succeed.  Returns whether the stream was valid; code, produced: what the
+// decoder returned and the bytes it had produced by then.
+static bool compare(const unsigned char *in, uint32_t in_len, uint32_t isize, bool strict, const char *what, long k, uint32_t *code = nullptr, uint32_t *produced = nullptr)
 {
 	std::vector<unsigned char> got, want;
 	uint32_t out_len = 0;
 	const uint32_t rc = emul_inflate(in, in_len, isize, got, &out_len);
+	if (code) *code = rc;
+	if (produced) *produced = out_len;
 	const int zrc = zlib_inflate(in, in_len, isize, want);
 	const bool ok = rc == GDZ_OK, zok = zrc == Z_STREAM_END;
 	if (out_len > isize) { printf("MISMATCH %s %ld: %u bytes into room for %u\n", what, k, out_len, isize); exit(1); }
@@ -155,13 +160,19 @@ int main(int argc, char **argv)
 		}
 		return 0;
 	}
-	if (cmd == "decode" || cmd == "trunc" || cmd == "fuzz") {
+	if (cmd == "decode" || cmd == "trunc" || cmd == "fuzz" || cmd == "agree") {
 		const std::vector<unsigned char> file = slurp(argv[2]);
 		const std::vector<GdBgzfMember> tab = scan_all(file);
 		long n_valid = 0, n_tried = 0;
 		size_t bytes = 0;
 		if (cmd == "decode")
 			for (size_t k = 0; k < tab.size(); ++k) compare(file.data() + tab[k].in_off, tab[k].in_len, tab[k].isize, true, "member", (long)k), bytes += tab[k].isize, ++n_tried, ++n_valid;
+		else if (cmd == "agree")
+			for (size_t k = 0; k < tab.size(); ++k) {
+				uint32_t code = 0, produced = 0;
+				n_valid += compare(file.data() + tab[k].in_off, tab[k].in_len, tab[k].isize, false, "member", (long)k, &code, &produced), ++n_tried;
+				printf("member %zu code %u (%s) out %u\n", k, code, gdz_strerror(code), produced);
+			}
 		else if (cmd == "trunc")
 			for (size_t k = 0; k < tab.size(); ++k)
 				for (uint32_t len = 0; len < tab[k].in_len; ++len) n_valid += compare(file.data() + tab[k].in_off, len, tab[k].isize, false, "truncation of member", (long)k), ++n_tried;

@@ -13,6 +13,7 @@ import pytest
 
 import bgzf_deflate_inputs as di
 import bgzf_inputs as bi
+from bgzf_deflate_inputs import same_members
 from conftest import ROOT
 from fixture_io import SR, golden_sam, read_fasta
 
@@ -33,17 +34,6 @@ def emul(tmp_path_factory):
         subprocess.run([exe, "deflate", src, dst], check=True, capture_output=True, timeout=120)
         return open(dst, "rb").read()
     return run
-
-
-def same_members(got, want, what):
-    if got != want:  # name the member
-        a, b = di.member_sizes(got), di.member_sizes(want)
-        assert a == b, (what, [k for k, (x, y) in enumerate(zip(a, b)) if x != y][:5])
-        at = 0
-        for k, (n, _) in enumerate(a):
-            assert got[at:at + n] == want[at:at + n], (what, "member %d" % k)
-            at += n
-    assert got == want, what
 
 
 def test_every_input_in_one_call(gpu_ctx, emul):
