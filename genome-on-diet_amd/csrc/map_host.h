@@ -203,6 +203,9 @@ static inline void gd_update_extra(GdReg &r, const uint8_t *qseq, const uint8_t 
 	if (!r.has_p) return;
 	uint32_t n = (uint32_t)r.cigar.size();
 	GdPostOut P;
+#ifdef GD_POST_DUMP_HOOK // (tests/emul/map_host_main.cpp --dump-post: what reaches P1, as it reaches it)
+	GD_POST_DUMP_HOOK(r.cigar, qseq, tseq, mat, q, e, log_gap);
+#endif
 	gdp_update_extra(r.cigar.data(), &n, qseq, tseq, mat, q, e, log_gap, &P);
 	r.cigar.resize(n);
 	if (is_eqx && n > 0) { // mm_update_cigar_eqx, SR/align.c:315-317: the vector stands for the device's qlen + tlen slot

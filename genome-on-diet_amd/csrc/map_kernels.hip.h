@@ -447,22 +447,8 @@ __global__ __launch_bounds__(64) void map_post_kernel(int nb, const MapBox *__re
 // lanes).  It is also EXACT: the scores of bases are integers and a gap's penalty q + e * mg_log2(1 + len) -- a float times a small
 // integer -- is a multiple of 2^-30, so every sum the reference forms in its double accumulator is exactly representable (|s| < 2^20,
 // 50 bits), no addition ever rounds, and the order of additions cannot matter.  The state is kept as integer part + fraction in units of 2^-30.
-#define GDP_FRAC 30
-struct GdpSeg { int32_t A, B, P, Q; }; // in units of 1 (base scores are integers); B / Q = GDP_NONE: no clamp inside the segment
-#define GDP_NONE (-0x20000000)
-__device__ __forceinline__ GdpSeg gdp_seg_join(const GdpSeg &x, const GdpSeg &y)
-{
-	GdpSeg r;
-	r.A = x.A + y.A;
-	const int32_t bx = x.B == GDP_NONE ? GDP_NONE : x.B + y.A;
-	r.B = bx > y.B ? bx : y.B;
-	const int32_t p2 = y.P == GDP_NONE ? GDP_NONE : x.A + y.P;
-	r.P = x.P > p2 ? x.P : p2;
-	const int32_t q2 = (x.B == GDP_NONE || y.P == GDP_NONE) ? GDP_NONE : x.B + y.P;
-	int32_t q = x.Q > y.Q ? x.Q : y.Q;
-	r.Q = q > q2 ? q : q2;
-	return r;
-}
+// The segment, its join, the fold into the running state, the gap step and the rounding are the gdp_ helpers of map_post.h, which a host
+// program runs as well (tests/emul/post_emul.cpp).
 
 // At most 32 VGPRs (checked at build time by __graft_entry__.build through the compiler's resource remarks): the 64-lane DP kernel of the
 // next batch in flight holds 5 x 96 of a SIMD's 512 registers, so a wavefront of this size is the largest that can start BESIDE a full
@@ -530,7 +516,7 @@ __global__ __launch_bounds__(64) void map_post_wave_kernel(int nb, const MapBox 
 						else if (ct != cq) cnt2 = 1 << 16;
 						const int idx = ct * 5 + cq;
 						const int32_t a = idx < 25 ? (int32_t)s_mat[idx] : 0;
-						g.A = a, g.B = 0, g.P = a, g.Q = 0; // s -> max(s + a, 0); the state after it is max(s + a, 0) as well
+						g = gdp_seg_base(a);
 					}
 #pragma unroll 1 // (not unrolled: the kernel must stay within 32 VGPRs, see above)
 					for (int d = 1; d < 64; d <<= 1) { // lane i: segment [i, i + 2d) = its own [i, i + d) followed by lane i + d's
@@ -542,10 +528,7 @@ __global__ __launch_bounds__(64) void map_post_wave_kernel(int nb, const MapBox 
 					const int32_t A = __builtin_amdgcn_readfirstlane(g.A), Bc = __builtin_amdgcn_readfirstlane(g.B), Pm = __builtin_amdgcn_readfirstlane(g.P),
 					              Qm = __builtin_amdgcn_readfirstlane(g.Q);
 					const int c2 = __builtin_amdgcn_readfirstlane(cnt2), na = c2 & 0xffff, nd = c2 >> 16;
-					if (Pm != GDP_NONE && (Si + Pm > MXi || (Si + Pm == MXi && Sf > MXf))) MXi = Si + Pm, MXf = Sf; // MX = max(MX, S + P)
-					if (Qm != GDP_NONE && (Qm > MXi)) MXi = Qm, MXf = 0;                                              // MX = max(MX, Q)
-					Si += A;
-					if (Bc != GDP_NONE && Si < Bc) Si = Bc, Sf = 0; // S = max(S + A, B): with 0 <= fraction < 1, S + A < B iff its integer part is
+					gdp_run_fold(A, Bc, Pm, Qm, Si, Sf, MXi, MXf);
 					const uint32_t cnt = len - base < 64 ? len - base : 64;
 					blen += (int32_t)cnt - na, mlen += (int32_t)cnt - (na + nd), n_ambi_tot += (uint32_t)na;
 				}
@@ -555,22 +538,15 @@ __global__ __launch_bounds__(64) void map_post_wave_kernel(int nb, const MapBox 
 				const uint8_t *src = op == 1 ? qseq + qoff : tseq + toff;
 				for (uint32_t l0 = 0; l0 < len; l0 += 64) na += __popcll(__ballot(l0 + lane < len && src[l0 + lane] > 3));
 				blen += (int32_t)len - na, n_ambi_tot += (uint32_t)na;
-				double tot;
-				if (O.log_gap) {
-					const double pen = (double)O.e * (double)gdp_mg_log2(1.0f + (float)len);
-					tot = (double)O.q + pen;
-				} else tot = (double)(O.q + O.e);
-				// tot >= 0 is a multiple of 2^-30 below 2^12: integer part and fraction, both exact
-				const int32_t Ti = __builtin_amdgcn_readfirstlane((int32_t)tot);
-				const int32_t Tf = __builtin_amdgcn_readfirstlane((int32_t)((tot - (double)Ti) * (double)(1 << GDP_FRAC)));
-				Sf -= Tf, Si -= Ti;
-				if (Sf < 0) Sf += 1 << GDP_FRAC, Si -= 1;
-				if (Si < 0) Si = 0, Sf = 0; // (s < 0 iff its integer part is)
+				const double tot = gdp_gap_cost(O.q, O.e, O.log_gap, len);
+				const int32_t Ti = __builtin_amdgcn_readfirstlane(gdp_gap_int(tot));
+				const int32_t Tf = __builtin_amdgcn_readfirstlane(gdp_gap_frac(tot, Ti));
+				gdp_run_gap(Ti, Tf, Si, Sf);
 				if (op == 1) qoff += len; else toff += len;
 			} else if (op == 3) toff += len;
 		}
 		P.mlen = mlen, P.blen = blen, P.n_ambi = n_ambi_tot;
-		P.dp_max = (int32_t)((double)MXi + (double)MXf / (double)(1 << GDP_FRAC) + .499);
+		P.dp_max = gdp_run_round(MXi, MXf);
 	}
 	if (lane == 0) {
 		post[b] = P;

@@ -815,6 +815,91 @@ static int gd_result_tables(GdMapCall &c)
 	return GDIET_OK;
 }
 
+// P1's launch in one of its three forms: what gd_stage_dp enqueues behind the backtrack, and all that gdiet_hip_post_batch runs
+static void gd_launch_post(bool wave, bool eqx, int nb, const MapBox *boxes, const uint8_t *q, const uint8_t *t, const int64_t *coff, uint32_t *cig, int32_t *ncig,
+                           const int32_t *score, const MapPostOpt &PO, GdPostOut *post, int32_t *x_score, int32_t *x_ncig, hipStream_t s)
+{
+	if (wave) hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, s, nb, boxes, q, t, coff, cig, ncig, score, PO, post, x_score, x_ncig);
+	else if (eqx) hipLaunchKernelGGL(map_post_kernel<true>, dim3((nb + 63) / 64), dim3(64), 0, s, nb, boxes, q, t, coff, cig, ncig, score, PO, post, x_score, x_ncig);
+	else hipLaunchKernelGGL(map_post_kernel<false>, dim3((nb + 63) / 64), dim3(64), 0, s, nb, boxes, q, t, coff, cig, ncig, score, PO, post, x_score, x_ncig);
+}
+
+// The kernel-level boundary of P1 (include/gdiet_hip.h): buffers of its own for this call, the launch above, the results back.  The
+// windows must hold what every live CIGAR consumes: checked here, on the raw CIGAR (mm_fix_cigar moves bases between operations, never
+// their sums), so that no input can make a kernel read outside them.
+extern "C" int gdiet_hip_post_batch(gdiet_ctx *ctx, int n, const uint8_t *qseq, const int64_t *qoff, const uint8_t *tseq, const int64_t *toff, uint32_t *cigar,
+                                    const int64_t *coff, int32_t *n_cigar, const int32_t *score, const int8_t *mat, int8_t q, int8_t e, int log_gap, int form,
+                                    int exported, int32_t *post)
+{
+	if (!ctx || n < 0 || (n && (!qoff || !toff || !coff || !n_cigar || !score || !mat || !post)) || (form != 0 && form != 1)) return GDIET_E_PARAM;
+	if (n == 0) return GDIET_OK;
+	gd_err_clear();
+	(void)hipSetDevice(ctx->device);
+	if (qoff[0] < 0 || toff[0] < 0 || coff[0] < 0) { ctx->err = "gdiet_hip_post_batch: negative offset"; return GDIET_E_PARAM; }
+	std::vector<MapBox> boxes((size_t)n);
+	for (int b = 0; b < n; ++b) {
+		if (qoff[b + 1] < qoff[b] || toff[b + 1] < toff[b] || coff[b + 1] < coff[b]) { ctx->err = "gdiet_hip_post_batch: offsets must not decrease"; return GDIET_E_PARAM; }
+		memset(&boxes[(size_t)b], 0, sizeof(MapBox));
+		boxes[(size_t)b].q_dst = qoff[b], boxes[(size_t)b].t_dst = toff[b];
+		if (score[b] == GD_NEG_INF_SCORE_DEV || n_cigar[b] <= 0 || (int64_t)n_cigar[b] > coff[b + 1] - coff[b]) continue; // dead: never read
+		int64_t ql = 0, tl = 0;
+		for (int32_t k = 0; k < n_cigar[b]; ++k) {
+			const uint32_t c = cigar[coff[b] + k], op = c & 0xf, len = c >> 4;
+			if (op == 0) ql += len, tl += len;
+			else if (op == 1) ql += len;
+			else if (op == 2 || op == 3) tl += len;
+		}
+		if (ql > qoff[b + 1] - qoff[b] || tl > toff[b + 1] - toff[b]) {
+			ctx->err = "gdiet_hip_post_batch: the CIGAR of alignment " + std::to_string(b) + " consumes more than its windows hold";
+			return GDIET_E_PARAM;
+		}
+	}
+	const size_t nq = (size_t)qoff[n], nt = (size_t)toff[n], nc = (size_t)coff[n], nbp = ((size_t)n + 63) & ~(size_t)63;
+	if ((nq && !qseq) || (nt && !tseq) || (nc && !cigar)) return GDIET_E_PARAM;
+	MapPostOpt PO;
+	memcpy(PO.mat, mat, 25);
+	PO.q = q, PO.e = e, PO.log_gap = log_gap != 0;
+	DevBuf d_box, d_q, d_t, d_coff, d_cig, d_nc, d_sc, d_post, h_pin;
+	int rc;
+	if ((rc = gd_grow(ctx, d_box, sizeof(MapBox) * (size_t)n)) || (rc = gd_grow(ctx, d_q, std::max<size_t>(nq, 1))) || (rc = gd_grow(ctx, d_t, std::max<size_t>(nt, 1))) ||
+	    (rc = gd_grow(ctx, d_coff, sizeof(int64_t) * ((size_t)n + 1))) || (rc = gd_grow(ctx, d_cig, sizeof(uint32_t) * std::max<size_t>(nc, 1))) ||
+	    (rc = gd_grow(ctx, d_nc, sizeof(int32_t) * (size_t)n)) || (rc = gd_grow(ctx, d_sc, sizeof(int32_t) * (size_t)n)) ||
+	    (rc = gd_grow(ctx, d_post, sizeof(GdPostOut) * (size_t)n)))
+		return rc;
+	hipStream_t s = ctx->stream;
+	GD_HIP(hipMemcpyAsync(d_box.p, boxes.data(), sizeof(MapBox) * (size_t)n, hipMemcpyHostToDevice, s));
+	if (nq) GD_HIP(hipMemcpyAsync(d_q.p, qseq, nq, hipMemcpyHostToDevice, s));
+	if (nt) GD_HIP(hipMemcpyAsync(d_t.p, tseq, nt, hipMemcpyHostToDevice, s));
+	GD_HIP(hipMemcpyAsync(d_coff.p, coff, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+	if (nc) GD_HIP(hipMemcpyAsync(d_cig.p, cigar, sizeof(uint32_t) * nc, hipMemcpyHostToDevice, s));
+	GD_HIP(hipMemcpyAsync(d_nc.p, n_cigar, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+	GD_HIP(hipMemcpyAsync(d_sc.p, score, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+	GdPostOut *o_post = (GdPostOut *)d_post.p;
+	int32_t *o_score = nullptr, *o_ncig = nullptr;
+	if (exported) { // laid out as gd_stage_dp lays its export buffer out: scores, CIGAR lengths, results
+		const size_t need = sizeof(GdPostOut) * (size_t)n + sizeof(int32_t) * 2 * nbp;
+		h_pin.kind = DevBuf::PINNED;
+		GD_HIP(hipHostMalloc(&h_pin.p, need, hipHostMallocDefault));
+		h_pin.cap = need;
+		memset(h_pin.p, 0xff, need);
+		o_score = (int32_t *)h_pin.p, o_ncig = o_score + nbp, o_post = (GdPostOut *)(o_ncig + nbp);
+	}
+	gd_launch_post(form == 1, false, n, (const MapBox *)d_box.p, (const uint8_t *)d_q.p, (const uint8_t *)d_t.p, (const int64_t *)d_coff.p, (uint32_t *)d_cig.p,
+	               (int32_t *)d_nc.p, (const int32_t *)d_sc.p, PO, o_post, o_score, o_ncig, s);
+	GD_HIP(hipGetLastError());
+	if (nc) GD_HIP(hipMemcpyAsync(cigar, d_cig.p, sizeof(uint32_t) * nc, hipMemcpyDeviceToHost, s));
+	if (!exported) {
+		GD_HIP(hipMemcpyAsync(n_cigar, d_nc.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+		GD_HIP(hipMemcpyAsync(post, d_post.p, sizeof(GdPostOut) * (size_t)n, hipMemcpyDeviceToHost, s));
+	}
+	GD_HIP(hipStreamSynchronize(s));
+	if (exported) {
+		if (memcmp(o_score, score, sizeof(int32_t) * (size_t)n)) { ctx->err = "gdiet_hip_post_batch: the exported scores differ from the ones given"; return GDIET_E_HIP; }
+		memcpy(n_cigar, o_ncig, sizeof(int32_t) * (size_t)n), memcpy(post, o_post, sizeof(GdPostOut) * (size_t)n);
+	}
+	return GDIET_OK;
+}
+
 // the DP batch over the gathered windows (gd_ksw_batch_dev), P1 on the device behind it, the results to the host
 static int gd_stage_dp(GdMapCall &c)
 {
@@ -886,13 +971,8 @@ static int gd_stage_dp(GdMapCall &c)
 		o_score = (int32_t *)ctx->h_pin.p, o_ncig = o_score + nbp, o_post = (GdPostOut *)(o_ncig + nbp);
 		c.h_score = o_score, c.h_ncig = o_ncig, c.h_post = o_post;
 	}
-	if (post_wave)
-		hipLaunchKernelGGL(map_post_wave_kernel, dim3(nb), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-		                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
-	else if (eqx) hipLaunchKernelGGL(map_post_kernel<true>, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-	                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
-	else hipLaunchKernelGGL(map_post_kernel<false>, dim3((nb + 63) / 64), dim3(64), 0, sd, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p,
-	                   (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff, (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig);
+	gd_launch_post(post_wave, eqx, nb, (const MapBox *)ctx->m_boxes.p, (const uint8_t *)ctx->m_q.p, (const uint8_t *)ctx->m_t.p, (const int64_t *)c.d_coff,
+	               (uint32_t *)ctx->m_cig.p, c.d_ncig, (const int32_t *)c.d_score, PO, o_post, o_score, o_ncig, sd);
 	if (!exported) {
 		GD_HIP(hipMemcpyAsync(ctx->h_post.p, ctx->m_post.p, sizeof(GdPostOut) * (size_t)nb, hipMemcpyDeviceToHost, sd));
 		GD_HIP(hipMemcpyAsync(c.h_score, c.d_score, sizeof(int32_t) * 2 * nbp, hipMemcpyDeviceToHost, sd));

@@ -204,6 +204,89 @@ GDP_HD void gdp_update_extra(uint32_t *cg, uint32_t *n_io, const uint8_t *qseq, 
 	out->dp_max = (int32_t)(mx + .499);
 }
 
+// ---- the arithmetic of the wave-parallel form (map_post_wave_kernel, map_kernels.hip.h, which explains it) ------------------------------
+// Written here so that a host program can run it lane by lane (tests/emul/post_emul.cpp); the kernel calls exactly these.
+// GDP_MISTAKE = n swaps one expression below for a wrong one: the seeded mistakes of tests/test_post.py, compiled by the emulator's
+// build alone.
+#if defined(GDP_MISTAKE) && !defined(GDP_POST_EMUL)
+#error "GDP_MISTAKE belongs to the build of tests/emul/post_emul.cpp alone"
+#endif
+#ifndef GDP_MISTAKE
+#define GDP_MISTAKE 0
+#endif
+#define GDP_MIS(n, right, wrong) (GDP_MISTAKE == (n) ? (wrong) : (right))
+
+#define GDP_FRAC 30
+struct GdpSeg { int32_t A, B, P, Q; }; // in units of 1 (base scores are integers); B / Q = GDP_NONE: no clamp inside the segment
+#define GDP_NONE (-0x20000000)
+GDP_HD GdpSeg gdp_seg_join(const GdpSeg &x, const GdpSeg &y)
+{
+	GdpSeg r;
+	r.A = x.A + y.A;
+	const int32_t bx = x.B == GDP_NONE ? GDP_NONE : GDP_MIS(1, x.B + y.A, x.B);
+	r.B = bx > y.B ? bx : y.B;
+	const int32_t p2 = y.P == GDP_NONE ? GDP_NONE : GDP_MIS(2, x.A + y.P, y.P);
+	r.P = x.P > p2 ? x.P : p2;
+	const int32_t q2 = (x.B == GDP_NONE || y.P == GDP_NONE) ? GDP_NONE : GDP_MIS(3, x.B + y.P, GDP_NONE);
+	int32_t q = x.Q > y.Q ? x.Q : y.Q;
+	r.Q = q > q2 ? q : q2;
+	return r;
+}
+
+// one base of score a:  s -> max(s + a, 0); the state after it is max(s + a, 0) as well
+GDP_HD GdpSeg gdp_seg_base(int32_t a)
+{
+	GdpSeg g;
+	g.A = a, g.B = 0, g.P = a, g.Q = 0;
+	return g;
+}
+
+// A chunk's segment (A, Bc, Pm, Qm) folded into the running score S and its maximum MX, each as (integer part, fraction in units of
+// 2^-GDP_FRAC, 0 <= fraction < 2^GDP_FRAC): base scores are integers, only gap penalties carry a fraction.
+GDP_HD void gdp_run_fold(int32_t A, int32_t Bc, int32_t Pm, int32_t Qm, int32_t &Si, int32_t &Sf, int32_t &MXi, int32_t &MXf)
+{
+	if (Pm != GDP_NONE && (Si + Pm > MXi || GDP_MIS(4, (Si + Pm == MXi && Sf > MXf), false))) MXi = Si + Pm, MXf = Sf; // MX = max(MX, S + P)
+	if (Qm != GDP_NONE && GDP_MIS(5, (Qm > MXi), (Qm >= MXi))) MXi = Qm, MXf = 0;                                      // MX = max(MX, Q)
+	Si += A;
+	if (Bc != GDP_NONE && Si < Bc) Si = Bc, Sf = GDP_MIS(6, 0, Sf); // S = max(S + A, B): with 0 <= fraction < 1, S + A < B iff its integer part is
+}
+
+// A gap's cost q + e * mg_log2(1 + len) (or q + e): >= 0, a multiple of 2^-GDP_FRAC below 2^12 -- integer part and fraction, both exact
+GDP_HD double gdp_gap_cost(int8_t q, int8_t e, int log_gap, uint32_t len)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+	double tot;
+	if (log_gap) {
+		const double pen = (double)e * (double)gdp_mg_log2(1.0f + (float)len);
+		tot = (double)q + pen;
+	} else tot = (double)(q + e);
+	return tot;
+}
+GDP_HD int32_t gdp_gap_int(double tot) { return (int32_t)tot; }
+GDP_HD int32_t gdp_gap_frac(double tot, int32_t Ti)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+	return (int32_t)((tot - (double)Ti) * (double)(1 << GDP_FRAC));
+}
+GDP_HD void gdp_run_gap(int32_t Ti, int32_t Tf, int32_t &Si, int32_t &Sf)
+{
+	Sf -= Tf, Si -= Ti;
+	if (Sf < 0) Sf += 1 << GDP_FRAC, Si -= GDP_MIS(7, 1, 0);
+	if (Si < 0) Si = 0, Sf = 0; // (s < 0 iff its integer part is)
+}
+
+GDP_HD int32_t gdp_run_round(int32_t MXi, int32_t MXf)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+	return (int32_t)((double)MXi + (double)MXf / (double)(1 << GDP_FRAC) + GDP_MIS(8, .499, .5));
+}
+
 // ---- mm_update_cigar_eqx (SR/align.c:174-257; --eqx of the ShortReads variant): every M becomes its runs of = (7) and X (8) -------------
 // Called where the reference calls it (SR/align.c:315-317): behind mm_update_extra, on the CIGAR as gdp_fix_cigar leaves it (no
 // zero-length operation) and on the sequences moved by the shifts that function returned.  "Equal" is equality of the two bytes, as in the

@@ -91,6 +91,7 @@ def load_library():
     lib.gdiet_hip_debug_bgzf_deflate_seconds.argtypes = [vp, C.POINTER(C.c_double)]
     lib.gdiet_hip_ref_block.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t), u32p, C.c_size_t, C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int), u32p]
+    lib.gdiet_hip_post_batch.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, u32p, i64p, i32p, i32p, C.POINTER(C.c_int8), C.c_int8, C.c_int8, C.c_int, C.c_int, C.c_int, i32p]
     _lib = lib
     return lib
 
@@ -184,6 +185,27 @@ class Context:
         self._check(self.lib.gdiet_hip_ref_block(self._h, text, len(text), state_in, _ptr(nt4, C.c_uint8), nt4.size, C.byref(nb), _ptr(rows, C.c_uint32), rows.shape[0],
                                                  C.byref(nr), C.byref(cl), C.byref(so), C.byref(rn)))
         return dict(claimed=cl.value, state_out=so.value, run_nl=rn.value, nt4=nt4[:nb.value].copy(), rows=rows[:nr.value].copy())
+
+    POST_FIELDS = ("qshift", "tshift", "mlen", "blen", "dp_max", "n_ambi")
+
+    def post_batch(self, qseq, qoff, tseq, toff, cigar, coff, n_cigar, score, mat, q, e, log_gap, form, exported=False):
+        """gdiet_hip_post_batch: mm_fix_cigar + mm_update_extra of n alignments by the mapping path's own kernels -- form 0: one alignment
+        per thread, 1: one per wavefront; exported: the kernel stores its results to page-locked host memory itself.  qseq / tseq: nt4
+        codes with n + 1 offsets each; cigar: the pool of coff[n] words, alignment b's raw CIGAR at coff[b]; returns (the pool as the
+        kernel left it, n_cigar int32[n], post int32[n, 6] in the order of POST_FIELDS)"""
+        n = len(n_cigar)
+        qseq, tseq = np.ascontiguousarray(qseq, np.uint8), np.ascontiguousarray(tseq, np.uint8)
+        qoff, toff, coff = (np.ascontiguousarray(a, np.int64) for a in (qoff, toff, coff))
+        pool = np.array(cigar, np.uint32)
+        nc, sc = np.array(n_cigar, np.int32), np.ascontiguousarray(score, np.int32)
+        mat = np.ascontiguousarray(mat, np.int8)
+        assert len(qoff) == len(toff) == len(coff) == n + 1 and len(sc) == n and mat.size == 25
+        assert qseq.size == qoff[-1] and tseq.size == toff[-1] and pool.size == coff[-1]
+        post = np.zeros((max(n, 1), 6), np.int32)
+        self._check(self.lib.gdiet_hip_post_batch(self._h, n, _ptr(qseq, C.c_uint8), _ptr(qoff, C.c_int64), _ptr(tseq, C.c_uint8), _ptr(toff, C.c_int64),
+                                                  _ptr(pool, C.c_uint32), _ptr(coff, C.c_int64), _ptr(nc, C.c_int32), _ptr(sc, C.c_int32), _ptr(mat, C.c_int8),
+                                                  int(q), int(e), int(log_gap), int(form), int(bool(exported)), _ptr(post, C.c_int32)))
+        return pool, nc, post[:n]
 
     def bgzf_deflate(self, data, eof=True):
         """gdiet_hip_bgzf_deflate: data cut into members of 65280 bytes, each compressed by one wavefront of the device into a complete

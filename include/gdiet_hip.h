@@ -302,6 +302,24 @@ int gdiet_hip_index_open_stats(const gdiet_index *idx, int64_t *counts6, double 
 int gdiet_hip_ref_block(gdiet_ctx *ctx, const char *text, size_t n, int state_in, uint8_t *nt4, size_t nt4_cap, size_t *n_bases,
                         uint32_t *rows, size_t row_cap, size_t *n_rows, size_t *claimed, int *state_out, uint32_t *run_nl);
 
+/* The kernel-level boundary of P1 (mm_fix_cigar + mm_update_extra, LR/align.c:93-172,259-318), for tests: the kernels the mapping path
+ * launches behind its backtrack, on n alignments given as raw arrays.
+ *   qseq / tseq   nt4 codes of all query / target windows; alignment b's begin at qoff[b] / toff[b] (n + 1 offsets each)
+ *   cigar         in/out: the CIGAR pool of coff[n] words; alignment b owns the slot [coff[b], coff[b + 1]) and its raw CIGAR starts the slot
+ *   n_cigar       in/out: operations per alignment
+ *   score         a slot whose score is -0x40000000, whose n_cigar is <= 0 or larger than its slot is dead: its GdPostOut is all zero
+ *                 and its slot and n_cigar are left alone
+ *   mat           the 5 x 5 scoring matrix mat[target * 5 + query]; q, e, log_gap as in mm_update_extra
+ *   form          0: one alignment per thread (map_post_kernel)   1: one alignment per wavefront (map_post_wave_kernel)
+ *   exported      1: the kernel itself stores score, n_cigar and the results to page-locked host memory (what the mapping path does when
+ *                 the results must not wait for a copy); the returned n_cigar and post are then those stores, and the score stored
+ *                 must equal the one given (GDIET_E_HIP otherwise)
+ *   post          n records of six int32: qshift, tshift, mlen, blen, dp_max, n_ambi
+ * The --eqx rewrite is not reachable from here. */
+int gdiet_hip_post_batch(gdiet_ctx *ctx, int n, const uint8_t *qseq, const int64_t *qoff, const uint8_t *tseq, const int64_t *toff,
+                         uint32_t *cigar, const int64_t *coff, int32_t *n_cigar, const int32_t *score, const int8_t *mat, int8_t q, int8_t e,
+                         int log_gap, int form, int exported, int32_t *post);
+
 /* the fields of mm_mapopt_t (LR/minimap.h:145-214) this path reads; fill them from the reference's struct */
 typedef struct {
 	int64_t flag;                 /* MM_F_* bits; only NO_PRINT_2ND, SR (selects the variant), FRAG_MODE, FOR_ONLY, REV_ONLY and, with SR, EQX are

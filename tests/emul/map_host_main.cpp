@@ -15,6 +15,31 @@
 #include <vector>
 #define __host__
 #define __device__
+// --dump-post=FILE: every input of P1 (gd_update_extra, map_host.h) in the format tests/emul/post_emul.cpp reads: the raw CIGAR as the
+// slot, the bases it consumes as the windows.  tests/test_post.py asks what the golden read sets feed to P1.
+#include <mutex>
+static FILE *g_post_dump = nullptr;
+static int32_t g_post_dumped = 0;
+static std::mutex g_post_mu;
+static void post_dump(const std::vector<uint32_t> &cg, const uint8_t *q, const uint8_t *t, const int8_t *mat, int8_t gq, int8_t ge, int log_gap)
+{
+	if (!g_post_dump) return;
+	int32_t ql = 0, tl = 0;
+	for (uint32_t c : cg) {
+		const uint32_t op = c & 0xf, len = c >> 4;
+		if (op == 0) ql += len, tl += len;
+		else if (op == 1) ql += len;
+		else if (op == 2 || op == 3) tl += len;
+	}
+	const int32_t h[8] = {(int32_t)cg.size(), (int32_t)cg.size(), ql, tl, 0, gq, ge, log_gap};
+	int8_t m[28] = {0};
+	memcpy(m, mat, 25);
+	std::lock_guard<std::mutex> lk(g_post_mu);
+	fwrite(h, 4, 8, g_post_dump), fwrite(m, 1, 28, g_post_dump);
+	fwrite(cg.data(), 4, cg.size(), g_post_dump), fwrite(q, 1, (size_t)ql, g_post_dump), fwrite(t, 1, (size_t)tl, g_post_dump);
+	++g_post_dumped;
+}
+#define GD_POST_DUMP_HOOK post_dump
 #include "map_index.h"
 #include "map_host.h"
 #include "map_stages.h"
@@ -131,6 +156,10 @@ int main(int argc, char **argv)
 			else if (a == "--print-seeds") { if (pass) trace = true; }   // the reference's stage trace (RS/SD/VT/AVT/BE/AL_SCORE lines, LR/map.c:1328-1338,1447-1459,1592-1602,1670-1675,1808-1810)
 			else if ((v = val("mmi"))) { if (pass) mmi_in = v; }           // use an .mmi written by the reference instead of building the index
 			else if ((v = val("dump-mmi"))) { if (pass) mmi_out = v; }    // write the index as an .mmi and exit
+			else if ((v = val("dump-post"))) { // (the record count is written over the first word at the end)
+				if (pass && !(g_post_dump = fopen(v, "wb"))) { perror(v); return 2; }
+				if (pass) fwrite(&g_post_dumped, 4, 1, g_post_dump);
+			}
 			else if (a == "-f") { // LR/main.c:440-448: a fraction selects mid_occ from the index, a number >= 1 is mid_occ itself
 				v = argv[++i];
 				if (pass) { const double x = strtod(v, 0); if (x < 1.0) mid_occ_frac = (float)x, O.mid_occ = 0; else O.mid_occ = (int)(x + .499); }
@@ -381,6 +410,11 @@ int main(int argc, char **argv)
 	for (size_t ri = 0; ri < qs.size(); ++ri) {
 		fputs(trace_of[ri].c_str(), stderr);
 		fputs(sam_of[ri].c_str(), stdout);
+	}
+	if (g_post_dump) {
+		rewind(g_post_dump);
+		fwrite(&g_post_dumped, 4, 1, g_post_dump);
+		if (fclose(g_post_dump)) return 2;
 	}
 	return 0;
 }
