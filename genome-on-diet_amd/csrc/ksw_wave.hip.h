@@ -59,10 +59,24 @@ __device__ __forceinline__ int64_t gdw_uniform_i64(int64_t v)
 	return (int64_t)((uint64_t)hi << 32 | lo);
 }
 
+// one lane of a vector register takes a wave-uniform value (v_writelane_b32: value and lane number are scalar operands)
+// (a front end that does not declare __builtin_amdgcn_writelane still has the intrinsic behind it: reached by its IR name)
+#if __has_builtin(__builtin_amdgcn_writelane)
+#define GDW_WRITELANE __builtin_amdgcn_writelane
+#else
+extern "C" __device__ int gdw_llvm_writelane_i32(int, int, int) __asm("llvm.amdgcn.writelane.i32");
+#define GDW_WRITELANE gdw_llvm_writelane_i32
+#endif
+__device__ __forceinline__ u32 gdw_writelane_u(u32 value_uniform, int lane_uniform, u32 old)
+{
+	return (u32)GDW_WRITELANE(__builtin_amdgcn_readfirstlane((int)value_uniform), __builtin_amdgcn_readfirstlane(lane_uniform), (int)old);
+}
+
 // ---- the narrow form of the 64-lane kernel: one HALF block per lane (ksw_wave_core.h, "the narrow form") ---------------------------
 // The DP rows of one alignment at band w <= GD_W_NARROW on a ring of 64 half blocks: the row loop of ksw_extd2_wave_kernel<64> -- general
 // rows at the corners of the matrix, paired steady rows in the middle -- with four packed registers per state array.  Backtrace rows
-// of 512 bytes from bt_rsrc's base.  Returns 8 x the score, wave-uniform.  tests/emul/narrow_emul.cpp mirrors it statement by statement.
+// of 512 bytes from bt_rsrc's base.  Returns 8 x the score, wave-uniform.  tests/emul/narrow_step_emul.cpp mirrors it statement by statement
+// (narrow_emul.cpp: the paired rows before the two-lane selector update, gdw_sel_step_half).
 __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *query_u /* wave-uniform copy */, const uint8_t *query, int qlen,
                                                const uint8_t *target, int tlen, int w, int lane, __amdgpu_buffer_rsrc_t bt_rsrc)
 {
@@ -119,6 +133,10 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 	};
 	const int nblkA = (w - 1 + 16) >> 4, nblkB = (w + 16) >> 4;
 	u32 m_lowest = 0; // 0 / ~0: this lane holds the first half of the lowest block of the window (of the row just done)
+	// first rows of a pair: every lane makes its selectors where m & step_mask == 0 -- a block is taken over, or any pair of a band whose
+	// two rows differ in `up` (w a multiple of 16) -- and on the first pair, m_full; elsewhere two lanes are patched (gdw_sel_step_half)
+	const int step_mask = nblkA == nblkB ? 15 : 0;
+	int m_full = 0;
 	auto pair_row = [&](const int r, const int m, auto a_tag) __attribute__((always_inline)) {
 		constexpr bool ROW_A = decltype(a_tag)::value;
 		WaveRow W;
@@ -126,7 +144,7 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 		W.st_ = m >> 4, W.en_ = W.en0 >> 4;
 		W.up = m + ((ROW_A ? nblkA : nblkB) << 4);
 		const int advanced = ROW_A && (m & 15) == 0;
-		const int pst_ = W.st_ - advanced; // st_ of the row before
+		const int pst_ = (m - (ROW_A ? 1 : 0)) >> 4; // st_ of the row before, st_ - advanced (as a shift: the flag as a number goes through a vector register)
 		W.use_array = advanced, W.v1key = K.key_open, W.set_tr = 0, W.ukey = 0;
 		const u32 pX = gdw_ror1<64>(H.X[3]), pV = gdw_ror1<64>(H.V[3]), pX2 = gdw_ror1<64>(H.X2[3]), pQ = gdw_ror1<64>(H.Qc[1]);
 		gdw_shift_query_half_m(H, pQ, m_lowest, gdw_seam_byte(query_u, qlen, r - (pst_ << 4))); // (the lane mask of the row before: its st_ is this row's pst_)
@@ -134,9 +152,16 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 			if (H.blk < W.st_) gdw_load_half(H, K, H.blk + 32, H.half, r, query, qlen, target, tlen);
 			any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
 		}
-		if (ROW_A || nblkA != nblkB) {
+		if (ROW_A ? (m & step_mask) == 0 || m == m_full : nblkA != nblkB) {
 			gdw_make_sel_half(H, W.st0, W.up);
 			m_lowest = (H.blk == W.st_ && H.half == 0) ? ~0u : 0u;
+		} else if (ROW_A) { // the window moved by one cell and no block was taken over: one selector dword changes in each of two lanes, m_lowest stays
+			// (both dwords of the lane are written, the other with what it holds: a register chosen by S.word[k] would be a branch per lane)
+			const GdwSelStep S = gdw_sel_step_half(m, w);
+#pragma unroll
+			for (int k = 0; k < 2; ++k)
+#pragma unroll
+				for (int g = 0; g < 2; ++g) H.SEL[g] = gdw_writelane_u(S.sel[k][g], S.lane[k], H.SEL[g]);
 		}
 		W.m_first_valid = 1, W.m_first_h = m_lowest;
 		gdw_update_scores_half(H, K, any_tn);
@@ -159,6 +184,7 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 		for (; r <= rend && r < rA; ++r) dp_row(r, std::false_type());
 		if (r == rA && rS > rA) {
 			int m = (rA - w + 1) >> 1;
+			m_full = m;
 			m_lowest = (H.blk == prev_st_ && H.half == 0) ? ~0u : 0u;
 			for (; r < rS; r += 2, ++m) {
 				pair_row(r, m, std::true_type());
@@ -179,7 +205,8 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 // The DP rows of one alignment at band w <= GD_W_QUARTER on a ring of 64 quarter blocks: gdw_narrow_rows with two packed registers per state
 // array and one dword each of scores, target, query and selectors -- half the recurrence instructions of the half-block rows and less of
 // the per-row overhead.  Backtrace rows of 256 bytes from bt_rsrc's base.  Returns 8 x the score, wave-uniform.
-// tests/emul/quarter_emul.cpp mirrors it statement by statement.
+// tests/emul/quarter_step_emul.cpp mirrors it statement by statement (quarter_emul.cpp: the paired rows before the two-lane selector
+// update, gdw_sel_step_quarter).
 __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *query_u /* wave-uniform copy */, const uint8_t *query, int qlen,
                                                const uint8_t *target, int tlen, int w, int lane, __amdgpu_buffer_rsrc_t bt_rsrc)
 {
@@ -234,6 +261,10 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 	};
 	const int nblkA = (w - 1 + 16) >> 4, nblkB = (w + 16) >> 4;
 	u32 m_lowest = 0; // 0 / ~0: this lane holds the first quarter of the lowest block of the window (of the row just done)
+	// first rows of a pair: every lane makes its selectors where m & step_mask == 0 -- a block is taken over, or any pair of a band whose
+	// two rows differ in `up` (w a multiple of 16) -- and on the first pair, m_full; elsewhere two lanes are patched (gdw_sel_step_quarter)
+	const int step_mask = nblkA == nblkB ? 15 : 0;
+	int m_full = 0;
 	auto pair_row = [&](const int r, const int m, auto a_tag) __attribute__((always_inline)) {
 		constexpr bool ROW_A = decltype(a_tag)::value;
 		WaveRow W;
@@ -241,7 +272,7 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 		W.st_ = m >> 4, W.en_ = W.en0 >> 4;
 		W.up = m + ((ROW_A ? nblkA : nblkB) << 4);
 		const int advanced = ROW_A && (m & 15) == 0;
-		const int pst_ = W.st_ - advanced; // st_ of the row before
+		const int pst_ = (m - (ROW_A ? 1 : 0)) >> 4; // st_ of the row before, st_ - advanced (as a shift: the flag as a number goes through a vector register)
 		W.use_array = advanced, W.v1key = K.key_open, W.set_tr = 0, W.ukey = 0;
 		const u32 pX = gdw_ror1<64>(H.X[1]), pV = gdw_ror1<64>(H.V[1]), pX2 = gdw_ror1<64>(H.X2[1]), pQ = gdw_ror1<64>(H.Qc);
 		gdw_shift_query_quarter_m(H, pQ, m_lowest, gdw_seam_byte(query_u, qlen, r - (pst_ << 4))); // (the lane mask of the row before: its st_ is this row's pst_)
@@ -249,9 +280,13 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 			if (H.blk < W.st_) gdw_load_quarter(H, K, H.blk + 16, H.quarter, r, query, qlen, target, tlen);
 			any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
 		}
-		if (ROW_A || nblkA != nblkB) {
+		if (ROW_A ? (m & step_mask) == 0 || m == m_full : nblkA != nblkB) {
 			gdw_make_sel_quarter(H, W.st0, W.up);
 			m_lowest = (H.blk == W.st_ && H.quarter == 0) ? ~0u : 0u;
+		} else if (ROW_A) { // the window moved by one cell and no block was taken over: two lanes' selectors change, m_lowest stays
+			const GdwSelStep S = gdw_sel_step_quarter(m, w);
+			H.SEL = gdw_writelane_u(S.sel[0][0], S.lane[0], H.SEL);
+			H.SEL = gdw_writelane_u(S.sel[1][0], S.lane[1], H.SEL);
 		}
 		W.m_first_valid = 1, W.m_first_h = m_lowest;
 		gdw_update_scores_quarter(H, K, any_tn);
@@ -274,6 +309,7 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 		for (; r <= rend && r < rA; ++r) dp_row(r, std::false_type());
 		if (r == rA && rS > rA) {
 			int m = (rA - w + 1) >> 1;
+			m_full = m;
 			m_lowest = (H.blk == prev_st_ && H.quarter == 0) ? ~0u : 0u;
 			for (; r < rS; r += 2, ++m) {
 				pair_row(r, m, std::true_type());

@@ -555,19 +555,49 @@ GDW_HD void gdw_load_half(WaveHalf &H, const WaveK &K, int m, int half, int r, c
 	H.R = 0;
 }
 
+// selector dword g of a half block of which cells [lo, hi) are rewritten, 0 <= lo, hi <= 8: per lane in gdw_make_sel_half, on the scalar
+// unit in gdw_sel_step_half -- one definition for both
+GDW_HD u32 gdw_sel_from_range_half(int lo, int hi, int g)
+{
+	const u32 bm = hi > lo ? (((1u << (hi - lo)) - 1u) << lo) : 0u;
+	const u32 n = (bm >> (4 * g)) & 15u;
+	const u32 spread = (n * 0x00204081u) & 0x01010101u;
+	return 0x03020100u + (spread << 2);
+}
 GDW_HD void gdw_make_sel_half(WaveHalf &H, int st0, int up)
 {
 	const int tb = (H.blk << 4) + (H.half << 3);
 	int lo = st0 - tb, hi = up - tb;
 	lo = lo < 0 ? 0 : lo > 8 ? 8 : lo;
 	hi = hi < 0 ? 0 : hi > 8 ? 8 : hi;
-	const u32 bm = hi > lo ? (((1u << (hi - lo)) - 1u) << lo) : 0u;
 #pragma unroll
-	for (int g = 0; g < 2; ++g) {
-		const u32 n = (bm >> (4 * g)) & 15u;
-		const u32 spread = (n * 0x00204081u) & 0x01010101u;
-		H.SEL[g] = 0x03020100u + (spread << 2);
-	}
+	for (int g = 0; g < 2; ++g) H.SEL[g] = gdw_sel_from_range_half(lo, hi, g);
+}
+
+// THE TWO-LANE UPDATE of the paired steady rows (gdw_narrow_rows, gdw_quarter_rows).  Where a pair's two rows share one window
+// [m, up), up = m + 16 nblk with nblk = (w + 15) >> 4 = (w + 16) >> 4 (w no multiple of 16), the pair with counter m rewrites the cells
+// of pair m - 1 less cell m - 1, plus cell up - 1: the selectors of exactly two lanes change, the one holding cell m - 1 and the one
+// holding cell up - 1 (2 nblk <= 62 half blocks, 4 nblk <= 60 quarter blocks apart on the ring of 64: never the same lane).  up - m is a
+// multiple of 16, so both cells sit at the same place c of their half / quarter block: the lower lane goes on rewriting its cells
+// [c + 1, 8), the upper lane now rewrites [0, c + 1) -- the limits gdw_make_sel_half clamps st0 - tb and up - tb to, as they come out for
+// these two lanes (tests/emul/sel_step_test.cpp holds every lane against gdw_make_sel_half outright).  Lanes and dwords are functions of
+// (m, w) alone: scalar unit, then v_writelane_b32.  Not for a pair that takes a block over (m & 15 == 0: the lanes of the retired block
+// reload) -- there and on the first pair every lane makes its selectors.
+struct GdwSelStep {
+	int lane[2];   // the lanes of cell m - 1 and of cell up - 1
+	int word[2];   // half form: which of SEL[0] / SEL[1] changes there (quarter form: 0)
+	u32 sel[2][2]; // the lane's selector dwords after the change (quarter form: [k][0] only); [k][1 - word[k]] is what the lane holds already,
+	               // so a caller may write both dwords of the lane instead of choosing a register by a wave-uniform branch
+};
+GDW_HD GdwSelStep gdw_sel_step_half(int m, int w)
+{
+	const int up = m + (((w + 15) >> 4) << 4), c = (m - 1) & 7;
+	GdwSelStep S;
+	S.lane[0] = ((m - 1) >> 3) & 63, S.lane[1] = ((up - 1) >> 3) & 63;
+	S.word[0] = S.word[1] = c >> 2;
+#pragma unroll
+	for (int g = 0; g < 2; ++g) S.sel[0][g] = gdw_sel_from_range_half(c + 1, 8, g), S.sel[1][g] = gdw_sel_from_range_half(0, c + 1, g);
+	return S;
 }
 
 // the same with the choice of the lowest block's lane as a 0 / ~0 lane mask (one v_bfi with the scalar seam byte as data)
@@ -879,15 +909,31 @@ GDW_HD void gdw_load_quarter(WaveQuarter &H, const WaveK &K, int m, int quarter,
 	H.R = 0;
 }
 
+// the selector dword of a quarter block of which cells [lo, hi) are rewritten, 0 <= lo, hi <= 4 (per lane, and in gdw_sel_step_quarter)
+GDW_HD u32 gdw_sel_from_range_quarter(int lo, int hi)
+{
+	const u32 n = hi > lo ? (((1u << (hi - lo)) - 1u) << lo) : 0u; // bit i: cell i is rewritten
+	const u32 spread = (n * 0x00204081u) & 0x01010101u;
+	return 0x03020100u + (spread << 2);
+}
 GDW_HD void gdw_make_sel_quarter(WaveQuarter &H, int st0, int up)
 {
 	const int tb = (H.blk << 4) + (H.quarter << 2);
 	int lo = st0 - tb, hi = up - tb;
 	lo = lo < 0 ? 0 : lo > 4 ? 4 : lo;
 	hi = hi < 0 ? 0 : hi > 4 ? 4 : hi;
-	const u32 n = hi > lo ? (((1u << (hi - lo)) - 1u) << lo) : 0u; // bit i: cell i is rewritten
-	const u32 spread = (n * 0x00204081u) & 0x01010101u;
-	H.SEL = 0x03020100u + (spread << 2);
+	H.SEL = gdw_sel_from_range_quarter(lo, hi);
+}
+// the two-lane update of a steady pair's selectors (see gdw_sel_step_half), for quarter blocks: cells [c + 1, 4) and [0, c + 1)
+GDW_HD GdwSelStep gdw_sel_step_quarter(int m, int w)
+{
+	const int up = m + (((w + 15) >> 4) << 4), c = (m - 1) & 3;
+	GdwSelStep S;
+	S.lane[0] = ((m - 1) >> 2) & 63, S.lane[1] = ((up - 1) >> 2) & 63;
+	S.word[0] = S.word[1] = 0;
+	S.sel[0][0] = gdw_sel_from_range_quarter(c + 1, 4), S.sel[1][0] = gdw_sel_from_range_quarter(0, c + 1);
+	S.sel[0][1] = S.sel[1][1] = 0;
+	return S;
 }
 
 // cell 0 takes the byte that cell 3 of the quarter below faced on the previous anti-diagonal: the top byte of the previous lane's Qc
