@@ -47,6 +47,14 @@ class BgzfWriter:
         self._open()
         mapper.bam_batch_raw(res, n, names, seqs, quals, lens, sink=self, comments=comments)
 
+    def write_sam(self, mapper, res, n, names, seqs, quals, lens, comments=None):
+        """The SAM lines of a mapped batch appended to the stream (``gdiet_hip_bgzf_out_write_sam``; the arguments of
+        ``Mapper.sam_batch_raw``, which this is with ``device=True`` and the writer as sink).  With a context the lines are written on the
+        device behind the writer's waiting tail and compressed there: the uncompressed text never reaches the host.  Write
+        ``mapper.sam_header()`` first, through ``write``."""
+        self._open()
+        mapper.sam_batch_raw(res, n, names, seqs, quals, lens, sink=self, comments=comments, device=True)
+
     def flush(self):
         self._open()
         self._check(self.lib.gdiet_hip_bgzf_out_flush(self._h))

@@ -35,6 +35,8 @@ BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           "_Z19bgzf_deflate_kernel": dict(vgprs=128, scratch=0),
           # BAM records encoded on the device (bam_encode.hip.h): batch i is encoded beside the DP of batch i + 1, like the difference strings
           "_Z17bam_encode_kernel": dict(vgprs=32, scratch=0),
+          # SAM lines formatted on the device (sam_encode.hip.h): the same place in the pipeline as the BAM encoder
+          "_Z17sam_encode_kernel": dict(vgprs=32, scratch=0),
           # BAM input unpacked on the device (bam_in.hip.h): block i + 1 is unpacked beside the DP of batch i, like the FASTQ passes
           "_Z17bam_unpack_kernel": dict(vgprs=32, scratch=0),
           # BAM records put into coordinate order (bam_sort.hip.h): a run is sorted, and a chunk of the merge gathered, beside the DP of the batches in flight

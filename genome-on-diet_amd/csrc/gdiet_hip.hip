@@ -181,7 +181,7 @@ struct gdiet_ctx {
 	//        thread parses the current one under fx.mu.  ev[0..3]: copy up | kernel | copy down
 	//   bzd  BGZF members written on the device (bgzf_driver.hip.h): a writer thread compresses the text of batch i while batch i + 1 maps
 	//        and the reader inflates.  ev[0..5]: copy up | deflate kernel || pack kernel | copy down; ms: copy up, the two kernels, copy down
-	//   bam  BAM records encoded on the device (bam_driver.hip.h): the same writer thread encodes batch i while batch i + 1 maps; it takes
+	//   bam  BAM records encoded, or SAM lines formatted (sam_driver.hip.h), on the device (bam_driver.hip.h): the same writer thread encodes batch i while batch i + 1 maps; it takes
 	//        bam.mu, then bzd.mu when the deflate kernel reads the records where they are.  ev[0..3]: copy up | encode kernel | copy down
 	//   bsort BAM records put into coordinate order on the device (bam_sort_driver.hip.h): apart from bam, so that a caller that sorts a buffer
 	//        never holds the encoder's mutex.  ev[0..2]: key, sort and scan | gather
@@ -191,6 +191,7 @@ struct gdiet_ctx {
 	std::vector<uint8_t> ds_enc;       // host copy of the reads a difference-string call without a resident batch encodes
 	DevBuf fx_scan;                    // the scan's scratch of the FASTQ parser (under fx.mu)
 	std::shared_ptr<void> bam_pool;    // GdbPool (bam_driver.hip.h): the flattened chunks of a batch and their merged table, kept from call to call (under bam.mu)
+	std::shared_ptr<void> sam_pool;    // GdsPool (sam_driver.hip.h): the same for SAM lines formatted on the device (under bam.mu)
 	std::string rg_line, rg_id;        // -R: the escaped @RG header line and its ID (gdiet_hip_set_read_group; read by the SAM formatters)
 };
 
@@ -1266,6 +1267,7 @@ extern "C" int gdiet_hip_debug_bgzf_seconds(const gdiet_fastx *fx, double *out6)
 }
 
 #include "bam_driver.hip.h" // BAM: the record encoder's driver, gdiet_hip_bam_header / _bam_batch_into / _bgzf_out_write_bam
+#include "sam_driver.hip.h" // SAM text on the device: the line formatter's driver, gdiet_hip_sam_batch_device_into / _bgzf_out_write_sam
 #include "bam_sort_driver.hip.h" // BAM records in coordinate order: the sort pass's driver, gdiet_hip_bam_sort_records
 
 extern "C" int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n, int64_t *roff, uint8_t *enc_host, uint8_t *enc_device)

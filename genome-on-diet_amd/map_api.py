@@ -125,6 +125,11 @@ def _bind(lib):
                                              C.POINTER(C.c_size_t)]
     lib.gdiet_hip_bam_batch_into.restype = C.c_int64
     lib.gdiet_hip_bgzf_out_write_bam.argtypes = [vp, vp, vp, C.c_int, cpp, cpp, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64]
+    lib.gdiet_hip_sam_batch_into.argtypes = lib.gdiet_hip_sam_batch.argtypes[:-1] + [C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lib.gdiet_hip_sam_batch_into.restype = C.c_size_t  # (bound here: the device route makes the kept buffer too, so its existence says nothing about this prototype)
+    lib.gdiet_hip_sam_batch_device_into.argtypes = lib.gdiet_hip_bam_batch_into.argtypes
+    lib.gdiet_hip_sam_batch_device_into.restype = C.c_int64
+    lib.gdiet_hip_bgzf_out_write_sam.argtypes = lib.gdiet_hip_bgzf_out_write_bam.argtypes
     lib._map_bound = True
 
 
@@ -391,11 +396,35 @@ class Mapper:
         self.ctx._check(self.lib.gdiet_hip_batch_export(self.ctx._h, h, None, None, host.ctypes.data_as(u8p), dev.ctypes.data_as(u8p)))
         return roff, host, dev
 
-    def sam_batch_raw(self, res, n, names, seqs, quals, lens, sink=None, comments=None):
+    def sam_batch_raw(self, res, n, names, seqs, quals, lens, sink=None, comments=None, device=False):
         """gdiet_hip_sam_batch on C arrays.  With sink (a binary file object) the text is formatted into a buffer kept by this mapper
         (gdiet_hip_sam_batch_into) and written from it without a copy, and its length returned; otherwise bytes are returned.
-        comments: the reader's array of comments, printed under F_COPY_COMMENT (gdiet_hip_sam_batch_comments_into)."""
+        comments: the reader's array of comments, printed under F_COPY_COMMENT (gdiet_hip_sam_batch_comments_into).
+        device=True: the same bytes, written by sam_encode_kernel (gdiet_hip_sam_batch_device_into).  With a BgzfWriter as sink the lines go
+        into its stream (gdiet_hip_bgzf_out_write_sam: on a writer with a context they are compressed where they were written and never
+        reach the host) and None is returned; with any other sink the text is written from the kept buffer, as without the keyword."""
         cpp = C.POINTER(C.c_char_p)
+        if device:
+            args = (self.ctx._h, self._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp), C.cast(comments, cpp), lens, res.n_regs, res.regs, self.opt.flag)
+            if sink is not None and hasattr(sink, "_h") and hasattr(sink, "write_sam"):
+                if self.lib.gdiet_hip_bgzf_out_write_sam(sink._h, *args):
+                    raise GdietError("gdiet_hip_bgzf_out_write_sam: %s" % self.lib.gdiet_hip_strerror(self.ctx._h).decode())
+                return None
+            if sink is not None and not hasattr(self, "_sam_buf"):
+                self._sam_buf, self._sam_cap = C.c_void_p(), C.c_size_t(0)
+            buf, cap = (self._sam_buf, self._sam_cap) if sink is not None else (C.c_void_p(), C.c_size_t(0))
+            try:
+                m = self.lib.gdiet_hip_sam_batch_device_into(*args, C.byref(buf), C.byref(cap))
+                if m < 0:
+                    raise GdietError("gdiet_hip_sam_batch_device_into: %s" % self.lib.gdiet_hip_strerror(self.ctx._h).decode())
+                if sink is None:
+                    return C.string_at(buf.value, m) if m else b""
+                if m:
+                    sink.write(memoryview((C.c_char * m).from_address(buf.value)))
+                return m
+            finally:
+                if sink is None and buf.value:
+                    C.CDLL(None).free(C.c_void_p(buf.value))
         if sink is not None or comments is not None:
             if sink is not None and not hasattr(self, "_sam_buf"):
                 self._sam_buf, self._sam_cap = C.c_void_p(), C.c_size_t(0)

@@ -726,6 +726,36 @@ int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, const gdiet_
                                  const char *const *seqs, const char *const *quals, const char *const *comments, const int32_t *lens,
                                  const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag);
 
+/* ---- SAM text on the device --------------------------------------------------------------------------------------------------------------
+ * The SAM lines of a batch written by the GPU, one wavefront per line (csrc/sam_encode.hip.h, the statements of csrc/sam_record.h), from
+ * a table the context's host threads flatten (csrc/sam_flatten.h).  The bytes are exactly those of gdiet_hip_sam_batch_comments_into
+ * for the same arguments and flags -- gd_write_sam's rules, not BAM's: a name of any length, a comment of any text, the CIGAR in a
+ * CG:B:I tag only under MM_F_LONG_CIGAR (behind the cs / MD tag), MM_F_NO_QUAL, MM_F_SOFTCLIP, MM_F_COPY_COMMENT, MM_F_SAM_HIT_ONLY and
+ * MM_F_NO_PRINT_2ND as in the host formatter, the cs / MD strings from the same pass on the GPU, the context's read group.  The host
+ * lays out what only it holds as ready text (RG:Z:, SA:Z:, the difference tag, the comment, the text of de:f:); every number, the CIGAR
+ * column, SEQ (reversed and complemented on the reverse strand) and QUAL are formatted on the device.  Line sizes are arithmetic on the
+ * rows, so one kernel writes every line at its final offset.  The route is opt-in: no other call changes.  The calls run on the BAM
+ * encoder's stream and lock.  Out of scope: PAF, gdiet_hip_sam_record, the header (gdiet_hip_sam_header), SEQ / QUAL taken from the
+ * device reader's resident block, difference strings kept resident between their pass and this kernel, paired-end fields. */
+
+/* The kernel-level boundary: the text comes down into a buffer the caller keeps (*buf / *cap as in gdiet_hip_sam_batch_comments_into;
+ * NUL-terminated).  Returns its length -- 0 for a batch that yields no line, which is no failure --, or a negative GDIET_E_* code:
+ * GDIET_E_PARAM for a record whose rid / qs / qe lie outside the index or the read, or with a clip of 2^28 bases or more (a clip travels
+ * as a CIGAR operation, so the limit is BAM's; gdiet_hip_strerror(ctx) names the read), or one the difference-string pass refuses, GDIET_E_NOMEM, GDIET_E_HIP if the device fails. */
+int64_t gdiet_hip_sam_batch_device_into(gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs,
+                                        const char *const *quals, const char *const *comments, const int32_t *lens, const int32_t *n_regs,
+                                        gdiet_reg_t *const *regs, int64_t opt_flag, char **buf, size_t *cap);
+/* The same lines appended to a BGZF stream writer (write the header with gdiet_hip_bgzf_out_write first).  On a writer opened with a
+ * context -- it must be ctx -- the route of gdiet_hip_bgzf_out_write_bam: the writer's waiting tail goes up in front of a resident
+ * buffer, the lines are written behind it, every whole member of 65280 bytes is compressed from that buffer, the members come down and
+ * are written, and what is left below a member comes down as the next tail; the uncompressed text never reaches the host.  On a writer
+ * without a context the text is formatted on ctx's device, comes down and goes through gdiet_hip_bgzf_out_write.  Either way the
+ * file's bytes are those of that second route.  Returns GDIET_OK or the codes of gdiet_hip_sam_batch_device_into and
+ * gdiet_hip_bgzf_out_write. */
+int gdiet_hip_bgzf_out_write_sam(gdiet_bgzf_out *h, gdiet_ctx *ctx, const gdiet_index *idx, int n_reads, const char *const *qnames,
+                                 const char *const *seqs, const char *const *quals, const char *const *comments, const int32_t *lens,
+                                 const int32_t *n_regs, gdiet_reg_t *const *regs, int64_t opt_flag);
+
 /* ---- Sorted BAM output ---------------------------------------------------------------------------------------------------------------
  * Coordinate order, and the BAI index of a file in that order.  Definitions (tests/bam_sort_ref.py restates them):
  *   ORDER   records are sorted by key = (uint32)refID << 32 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1), the low word computed in 32 bits.

@@ -4,7 +4,7 @@ No Python object is made per read: the C arrays of the reader go straight into t
 
     python tools/map_file.py --preset sr ref.fa[.gz] | ref.mmi reads.fq[.gz] | reads.bam -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
                              [-d out.mmi] [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
-                             [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--sort-mem BYTES] [--tmp-dir DIR]]]
+                             [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--sort-mem BYTES] [--tmp-dir DIR]]] [--sam-device]
 
 `ref` is a FASTA / FASTQ file (plain, gzip or BGZF) or an .mmi index file, known by its magic, not its name (Mapper.from_file:
 gdiet_hip_index_open -- FASTA blocks are parsed on the device); "synth:MBP" stands for bench.py's synthetic reference.  -d FILE dumps
@@ -24,6 +24,9 @@ the GPU, `host` with zlib at --bgzf-level on --bgzf-threads threads; the JSON li
 (gdiet_hip_bgzf_out_write_bam), in the BGZF container --bgzf picks (default `device`: the records are compressed where they were
 encoded and only compressed members come back; `host`: they come back and go through zlib).  Every output option keeps its meaning;
 a -y comment must be a list of SAM tags, or the run fails.  The JSON line gains bam_device_seconds.
+--sam-device formats the SAM lines on the device (gdiet_hip_sam_batch_device_into; the same bytes as without it): to a plain -o the text
+comes down and is written; with --bgzf device the lines are written behind the writer's tail and compressed where they are
+(gdiet_hip_bgzf_out_write_sam), so only compressed members reach the host.  It does not go with --bam.
 --bam --sort writes -o in coordinate order (BamSorter: every batch is encoded into a resident run buffer, a run of --sort-mem bytes is
 sorted on the device and spooled to an unnamed file in --tmp-dir, default the output's directory, and the runs are merged on the device
 at the end); the header then starts with @HD VN:1.6 SO:coordinate.  --index writes <out>.bai as well.  The JSON line gains bam_sort.
@@ -44,7 +47,7 @@ from __graft_entry__ import _load_pkg  # noqa: E402
 VERSION = "gdiet-hip-map_file"  # the VN: field of --header's @PG line
 
 
-def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False, bam=False, sorter=None):
+def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False, bam=False, sorter=None, sam_device=False):
     """returns (reads, seconds).  Three stages on three threads, as the reference's kt_pipeline runs its three steps (LR/map.c:2094-2170):
     read -> upload + submit -> wait + format + write; the C calls release the interpreter lock, so the stages overlap.
     A failure in any stage stops all three: `stop` is set, the writer keeps draining q_done (every open ticket is still waited for and
@@ -115,7 +118,8 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
                 if res is not None and not stop.is_set() and sorter is not None:
                     timed("sam+write", sorter.add, res, n, names, seqs, quals, lens, comments if with_comment else None)
                 elif res is not None and not stop.is_set():
-                    timed("sam+write", mapper.bam_batch_raw if bam else mapper.sam_batch_raw, res, n, names, seqs, quals, lens, out, comments if with_comment else None)
+                    timed("sam+write", mapper.bam_batch_raw if bam else mapper.sam_batch_raw, res, n, names, seqs, quals, lens, out, comments if with_comment else None,
+                          *([True] if sam_device and not bam else []))
             except Exception as e:  # noqa: BLE001
                 fail(e)
             try:
@@ -208,6 +212,7 @@ def main():
     ap.add_argument("--bgzf-level", type=int, default=-1, help="zlib level of --bgzf host (-1: zlib's default)")
     ap.add_argument("--bgzf-threads", type=int, default=4, help="host threads of --bgzf host")
     ap.add_argument("--bam", action="store_true", help="write -o as BAM (header always; records encoded on the device); --bgzf picks the compressor, default device")
+    ap.add_argument("--sam-device", action="store_true", help="format the SAM lines on the device (sam_encode_kernel); with --bgzf device they are compressed where they were written")
     ap.add_argument("--sort", action="store_true", help="with --bam: write the records in coordinate order (sorted and merged on the device; header with @HD SO:coordinate)")
     ap.add_argument("--index", action="store_true", help="with --bam --sort: write <out>.bai as well")
     ap.add_argument("--sort-mem", type=int, default=1 << 29, metavar="BYTES", help="bytes of records per sorted run (default 512 MiB)")
@@ -217,6 +222,8 @@ def main():
     a = ap.parse_args()
     if a.eqx and a.preset != "sr":
         ap.error("--eqx is interpreted for --preset sr only (the LongReads variant does not interpret MM_F_EQX)")
+    if a.sam_device and a.bam:
+        ap.error("--sam-device formats SAM text: it does not go with --bam")
     if a.bam and not a.bgzf:
         a.bgzf = "device"
     if (a.sort and not a.bam) or (a.index and not a.sort):
@@ -282,7 +289,7 @@ def main():
                 elif a.header:
                     out.write(m.sam_header(VERSION, sys.argv).encode())
                 n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment,
-                                 device_reader=a.device_reader, bam=a.bam)
+                                 device_reader=a.device_reader, bam=a.bam, sam_device=a.sam_device)
     except Exception as e:  # noqa: BLE001  (every ticket has been waited for by now: the context can be closed)
         print("map_file failed: %r" % (e,), file=sys.stderr)
         m.close()
@@ -293,7 +300,8 @@ def main():
                       **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats, "reads_format": map_file.last_format,
                       **({"bgzf_out": dict(bgzf_out.stats(), route=a.bgzf, device_seconds=[round(x, 4) for x in ctx.bgzf_deflate_seconds()])} if bgzf_out is not None else {}),
                       **({"bam_sort": sort_stats} if sort_stats is not None else {}),
-                      **({"bam": True, "bam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.bam else {})}))
+                      **({"bam": True, "bam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.bam else {}),
+                      **({"sam_device": True, "sam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.sam_device else {})}))
     m.close()
     ctx.close()
 
