@@ -57,6 +57,17 @@ class BamSorter:
         if rc:
             raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
 
+    def set_coverage(self, cov):
+        """Attach a ``Coverage`` (None: detach): every later ``add`` scatters into it from the records it has just encoded into the run
+        buffer, before they are sorted; the file's bytes do not change.  Keep ``cov`` open while attached."""
+        if not self._h:
+            raise ValueError("set_coverage on a closed BamSorter")
+        self.lib.gdiet_hip_bam_sort_set_coverage.argtypes = [C.c_void_p, C.c_void_p]
+        rc = self.lib.gdiet_hip_bam_sort_set_coverage(self._h, cov._h if cov is not None else None)
+        if rc:
+            raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
+        self._cov = cov
+
     def add_reads(self, res, reads):
         """add on Python objects: reads = [(qname, seq, qual or None[, comment or None]), ...]"""
         n = len(reads)

@@ -55,6 +55,14 @@ class BgzfWriter:
         self._open()
         mapper.sam_batch_raw(res, n, names, seqs, quals, lens, sink=self, comments=comments, device=True)
 
+    def set_coverage(self, cov):
+        """Attach a ``Coverage`` (None: detach): every later ``write_bam`` scatters into it from the records it has just encoded on the
+        device, before they are compressed; the file's bytes do not change.  The writer needs a context.  Keep ``cov`` open while attached."""
+        self._open()
+        self.lib.gdiet_hip_bgzf_out_set_coverage.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(self.lib.gdiet_hip_bgzf_out_set_coverage(self._h, cov._h if cov is not None else None))
+        self._cov = cov
+
     def flush(self):
         self._open()
         self._check(self.lib.gdiet_hip_bgzf_out_flush(self._h))

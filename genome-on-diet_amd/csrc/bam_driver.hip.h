@@ -12,6 +12,25 @@
 #include "bam_encode.hip.h"
 #include "bam_flatten.h"
 
+// An attached coverage accumulator's side of a call that encodes records (cov_driver.hip.h defines these): hold it for the call, enqueue
+// the scatter of the records just encoded on their stream, ask for the verdict once that stream has been synchronised.
+struct gdiet_coverage;
+static int gd_cov_hold(gdiet_coverage *c, std::string &why); // locks it; -1, unlocked again, with why if it takes no more records
+static void gd_cov_release(gdiet_coverage *c);
+static int gd_cov_enqueue_part(gdiet_coverage *c, hipStream_t s, const uint8_t *d_recs, const GdbPart &P, std::vector<uint64_t> &starts, std::string &why);
+static int gd_cov_verdict(gdiet_coverage *c, std::string &why);
+struct GdCovHold {
+	gdiet_coverage *c = nullptr;
+	std::vector<uint64_t> starts; // GdbRec::out of the call's records: alive until the stream has been synchronised
+	int take(gdiet_coverage *cov, std::string &why)
+	{
+		if (cov && gd_cov_hold(cov, why)) return -1;
+		c = cov;
+		return 0;
+	}
+	~GdCovHold() { if (c) gd_cov_release(c); }
+};
+
 // the chunks' pools and the merged table of a batch: the context's (gdiet_ctx::bam_pool), so that they keep their pages from mini-batch to
 // mini-batch -- a mini-batch is some 130 MB of table and text, and a fresh allocation of that size is paid for page by page every time
 struct GdbPool { std::vector<GdbPart> parts; GdbPart all; };
@@ -208,6 +227,8 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	std::lock_guard<std::mutex> lk(ctx->bam.mu);
 	GdbPart &P = gd_bam_pool(ctx).all;
 	std::string why;
+	GdCovHold cov; // (nothing without an attached accumulator)
+	if (cov.take(h->cov, why)) return gd_err_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_out_write_bam: " + why);
 	int rc = gd_bam_flatten(ctx, ix, n_reads, qnames, seqs, quals, comments, lens, n_regs, regs, opt_flag, P, why);
 	if (rc) return why.empty() ? rc : gd_err_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why);
 	if (P.bytes == 0) return GDIET_OK;
@@ -216,6 +237,7 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	std::vector<unsigned char> next_tail;
 	int wrc = 0;
 	rc = gd_bam_encode_device(ctx, P, w.tail.data(), w.tail.size(), why, [&](uint8_t *d_stream, size_t bytes, hipStream_t s) {
+		if (cov.c && gd_cov_enqueue_part(cov.c, s, d_stream + w.tail.size(), P, cov.starts, why)) return -1; // from the records where they are, before they are compressed
 		const size_t whole = bytes / GD_BGZF_MEMBER_IN * GD_BGZF_MEMBER_IN;
 		next_tail.resize(bytes - whole);
 		if (!next_tail.empty()) {
@@ -228,6 +250,7 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	if (rc) { w.dev_error = true, (void)w.fail(why); return gd_bzo_done(h, -1); }
 	if (wrc) return gd_bzo_done(h, wrc);
 	w.tail.swap(next_tail);
+	if (cov.c && (rc = gd_cov_verdict(cov.c, why)) != 0) return gd_err_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why);
 	return GDIET_OK;
 }
 

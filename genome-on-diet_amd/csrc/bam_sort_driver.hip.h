@@ -111,6 +111,7 @@ struct GdqDevice {
 	uint8_t *d_run = nullptr, *d_res = nullptr;
 	GdsRow *d_rows = nullptr;
 	size_t run_cap = 0, res_cap = 0, rows_cap = 0, front_len = 0;
+	gdiet_coverage *cov = nullptr; // gdiet_hip_bam_sort_set_coverage: every appended batch is scattered from the run buffer, on the encoder's lane
 
 	// p[0, cap) -> at least `need` bytes, the first `keep` bytes kept.  The caller holds bsort.mu and has made the stream.
 	template <class T> hipError_t grow(T **p, size_t *cap, size_t need, size_t keep)
@@ -143,6 +144,8 @@ struct GdqDevice {
 		std::lock_guard<std::mutex> lk(ctx->bam.mu);
 		GdLane &L = ctx->bam;
 		if (L.ready(ctx->device, 4, "device BAM encoder", why)) return -1;
+		GdCovHold held; // (nothing without an attached accumulator)
+		if (held.take(cov, why)) return -1;
 		hipStream_t s = L.stream;
 		hipError_t e = hipSuccess;
 		GdStreamMem mem(s);
@@ -168,7 +171,9 @@ struct GdqDevice {
 			if ((e = hipGetLastError()) != hipSuccess) return fail(e, "encode launch");
 		}
 		(void)hipEventRecord(L.ev[2], s);
+		if (held.c && n && gd_cov_enqueue_part(held.c, s, d_run + at, P, held.starts, why)) { mem.fail(); return -1; } // before the run is sorted or moved
 		if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "encode kernel");
+		if (held.c && gd_cov_verdict(held.c, why)) return -1;
 		for (int i = 0; i < 2; ++i) {
 			float ms = 0;
 			if (hipEventElapsedTime(&ms, L.ev[i], L.ev[i + 1]) == hipSuccess) L.ms[i] += ms;
@@ -352,6 +357,15 @@ extern "C" int gdiet_hip_bam_sort_add(gdiet_bam_sorter *h, const gdiet_index *ix
 	for (size_t k = 0; k < P.rec.size(); ++k) rec_out[k] = P.rec[k].out; // record starts: no walk
 	const int rc = h->q.add(&P, P.bytes, rec_out.data(), P.rec.size());
 	if (rc) return gd_bsq_fail(h, rc == -2 ? GDIET_E_PARAM : GDIET_E_HIP, "gdiet_hip_bam_sort_add");
+	return GDIET_OK;
+}
+
+extern "C" int gdiet_hip_bam_sort_set_coverage(gdiet_bam_sorter *h, gdiet_coverage *cov)
+{
+	if (!h) return GDIET_E_PARAM;
+	gd_err_clear();
+	if (cov && cov->ctx != h->ctx) return gd_err_fail(h->ctx, GDIET_E_PARAM, "gdiet_hip_bam_sort_set_coverage: the sorter and the accumulator need one context");
+	h->q.ex.cov = cov;
 	return GDIET_OK;
 }
 

@@ -216,7 +216,8 @@ struct GdBzdExecutor : GdBgzfDeflater {
 		return gd_bz_deflate_resident(ctx, (const uint8_t *)d_in, in_len, out, out_cap, out_len, why);
 	}
 };
-struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; };
+struct gdiet_coverage; // cov_driver.hip.h
+struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; gdiet_coverage *cov = nullptr; /* gdiet_hip_bgzf_out_set_coverage */ };
 
 extern "C" int gdiet_hip_bgzf_out_open(gdiet_ctx *ctx, const char *path, int level, int threads, gdiet_bgzf_out **out)
 {

@@ -830,6 +830,82 @@ int gdiet_hip_bam_sort_add(gdiet_bam_sorter *h, const gdiet_index *idx, int n_re
                            gdiet_reg_t *const *regs, int64_t opt_flag);
 int gdiet_hip_bam_sort_close(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *stats);
 
+/* ---- Coverage ------------------------------------------------------------------------------------------------------------------------
+ * Per-contig coverage and depth, a flag summary, mean depth per fixed window and the depth of any interval, accumulated on the device
+ * from uncompressed BAM alignment records (SAM specification 4.2) while they are resident there.  The reference prints SAM and stops:
+ * these rules are the definition (tests/cov_ref.py restates them).  The reference dictionary is the index's contigs
+ * (gdiet_hip_index_info): n_ref lengths.  Options: excl_flags (usual value 0x704: unmapped, secondary, QC-fail, duplicate; supplementary
+ * records count), min_mapq (0) and window (0: no window table).
+ *   THE REAL CIGAR  is the record's n_cigar_op words, unless they are the placeholder of specification 4.2.2 -- n_cigar_op == 2, word 0 ==
+ *           l_seq << 4 | S, word 1 an N --: then it is the array of the first CG tag met by walking the aux fields (types A c C s S i I f
+ *           Z H B), which must be CG:B:I.  The aux fields are walked for a placeholder only, and only up to that tag.
+ *   BAD     a record is bad if: refID >= n_ref; refID >= 0 and pos < 0; an operation code of the real CIGAR is above 8; refID >= 0 and
+ *           pos + (sum of the M D N = X lengths) lies past the contig; l_seq > 0 and the sum of the M I S = X lengths is above l_seq; it is
+ *           a placeholder without a well-formed CG:B:I tag; the aux walk leaves the record or meets an unknown type; or its fixed fields,
+ *           name, CIGAR, SEQ and QUAL do not fit its block_size (l_seq below 0 included).  A negative refID is never bad by itself.  A bad
+ *           record adds to no array and to no contig's counters; it is counted in `bad`, and its flag bits still count in the summary.
+ *           The add call that saw it returns GDIET_E_PARAM, the text names the call's first bad record (its index and the reason), and the
+ *           accumulator then refuses every add and finish: only close is left.
+ *   SUMMARY over every record seen: records; unmapped (0x4), secondary (0x100), supplementary (0x800); primary_mapped (none of the three);
+ *           reverse (0x10 on a record without 0x4); then exactly one of bad, excluded_by_flag ((flag & excl_flags) != 0),
+ *           excluded_by_mapq (mapq < min_mapq), counted (refID >= 0) -- tested in this order -- or none (an unplaced record that passes).
+ *   COUNTED a counted record adds 1 to its contig's n_reads and its mapq to sum_mapq, and walks its real CIGAR with a reference cursor
+ *           from pos and a query cursor from 0: M = X give every reference position of the run +1 depth, add the run's length to
+ *           sum_depth and, if the record has qualities (l_seq > 0 and qual[0] != 0xff), the stored quality bytes of the run's query bases
+ *           to sum_baseq and the run's length to n_baseq, and advance both cursors; D N advance the reference cursor, I S the query
+ *           cursor, H P neither.  A counted record without operations adds to n_reads and sum_mapq only.
+ *   RESULTS per contig n_reads, cov_bases (positions with depth > 0), sum_depth, sum_mapq, sum_baseq, n_baseq; with window > 0 per contig
+ *           ceil(len / window) windows (the last one short), each with cov_bases and sum_depth; depth is uint32 per position.  Input that
+ *           drives one position above 2^31 - 1 is out of contract.  Every result is an integer and a function of the multiset of input
+ *           records alone: no float is formed on the device, and nothing depends on the order of atomic arrivals, on how the records were
+ *           cut into calls, on the scan's chunk or on the route that delivered them.
+ * The device side (csrc/cov.hip.h, statements in csrc/cov.h): cov_scatter_kernel, one wavefront per record, validates, then adds +1 / -1
+ * per M = X run into an int32 difference array over the whole reference (total_len + 1 slots, contigs back to back, 64-bit offsets);
+ * finish turns it into the depth array by hipCUB's inclusive sum in chunks of at most 2^30 slots (the previous chunk's last depth is added
+ * to a chunk's first slot first) and cov_window_kernel, one wavefront per window, reduces it.  The array costs 4 bytes per reference
+ * base for as long as the handle lives: 12.4 GB for a GRCh38-sized reference of 3.1 Gbp.  Out of scope: per-base quality thresholds,
+ * the histograms of `samtools stats`, duplicate marking, references too large for 4 bytes per base, merging the accumulators of several
+ * GPUs. */
+typedef struct gdiet_coverage gdiet_coverage;
+typedef struct {
+	uint64_t records, unmapped, secondary, supplementary, primary_mapped, reverse, excluded_by_flag, excluded_by_mapq, counted, bad;
+} gdiet_cov_summary_t;
+typedef struct {
+	uint64_t n_reads, cov_bases, sum_depth, sum_mapq, sum_baseq, n_baseq;
+} gdiet_cov_contig_t;
+/* An accumulator over idx's contigs: allocates and clears the difference array (plain hipMalloc) and the counters.  GDIET_E_NOMEM, with
+ * the array's size in the text, if the device has too little memory; GDIET_E_PARAM for an index without contigs.  The array also goes
+ * when the context is destroyed: a handle that outlives its context takes nothing but close. */
+int gdiet_hip_cov_open(gdiet_ctx *ctx, const gdiet_index *idx, uint32_t excl_flags, uint32_t min_mapq, uint32_t window, gdiet_coverage **out);
+/* The kernel-level boundary for host records: recs[0, len) holds whole records, each with its block_size.  The host walks the
+ * block_size fields for the starts (a block_size below 32 or a range that ends inside a record: GDIET_E_PARAM, nothing was seen and the
+ * accumulator stays usable), the records go up and are scattered.  GDIET_E_PARAM for a bad record (above), GDIET_E_HIP for the device. */
+int gdiet_hip_cov_add_bam(gdiet_coverage *cov, const void *recs, size_t len);
+/* A mapped batch -- the batch arguments of gdiet_hip_bam_batch_into; opt_flag decides which records exist exactly as there --: flattened
+ * and encoded on the device by the BAM encoder, scattered from the resident records; nothing is copied down.  Errors as
+ * gdiet_hip_bam_batch_into, and GDIET_E_PARAM for a bad record. */
+int gdiet_hip_cov_add(gdiet_coverage *cov, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs, const char *const *quals,
+                      const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs, const char *const *comments, int64_t opt_flag);
+/* Attach an accumulator (NULL: detach) to a BGZF writer with a context or to a sorter: every later gdiet_hip_bgzf_out_write_bam /
+ * gdiet_hip_bam_sort_add scatters from the records it has just encoded, on the stream that holds them, before they are compressed or
+ * sorted; the bytes written do not change.  A poisoned or finished accumulator makes those calls fail before they encode.  A writer
+ * without a context is refused (GDIET_E_PARAM): its records are on the host.  One accumulator has one producer at a time (it carries a
+ * mutex of its own); the caller keeps it open for as long as it is attached. */
+int gdiet_hip_bgzf_out_set_coverage(gdiet_bgzf_out *writer, gdiet_coverage *cov);
+int gdiet_hip_bam_sort_set_coverage(gdiet_bam_sorter *sorter, gdiet_coverage *cov);
+/* The inclusive sum, the window reduction and the counters: contigs_out[0, n_ref) and *summary_out (either may be NULL).  After it the
+ * accumulator is read-only: add is refused, finish again returns the same figures.  _chunked: the scan's chunk in slots (0: the
+ * default, 2^28; at most 2^30) -- the results do not depend on it; it exists so that tests cross chunk borders on small references. */
+int gdiet_hip_cov_finish(gdiet_coverage *cov, gdiet_cov_contig_t *contigs_out, gdiet_cov_summary_t *summary_out);
+int gdiet_hip_cov_finish_chunked(gdiet_coverage *cov, uint64_t chunk, gdiet_cov_contig_t *contigs_out, gdiet_cov_summary_t *summary_out);
+/* After finish, on an accumulator opened with window > 0: the windows of contig rid.  Returns their number; with both outputs NULL that
+ * is all (the size first), else cap, the room of each output in windows, must hold them (GDIET_E_PARAM otherwise). */
+int64_t gdiet_hip_cov_windows(gdiet_coverage *cov, uint32_t rid, uint32_t *cov_bases_out, uint64_t *sum_depth_out, size_t cap);
+/* After finish: out[0, end - beg) takes the depth of positions [beg, end) of contig rid (0-based, end <= the contig's length). */
+int gdiet_hip_cov_depth(gdiet_coverage *cov, uint32_t rid, uint32_t beg, uint32_t end, uint32_t *out);
+/* Frees the arrays and the handle, whatever state it is in. */
+int gdiet_hip_cov_close(gdiet_coverage *cov);
+
 #ifdef __cplusplus
 }
 #endif

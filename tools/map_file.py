@@ -5,6 +5,7 @@ No Python object is made per read: the C arrays of the reader go straight into t
     python tools/map_file.py --preset sr ref.fa[.gz] | ref.mmi reads.fq[.gz] | reads.bam -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
                              [-d out.mmi] [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
                              [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--sort-mem BYTES] [--tmp-dir DIR]]] [--sam-device]
+                             [--coverage PREFIX [--cov-window N] [--cov-min-mapq Q] [--cov-excl-flags F]]
 
 `ref` is a FASTA / FASTQ file (plain, gzip or BGZF) or an .mmi index file, known by its magic, not its name (Mapper.from_file:
 gdiet_hip_index_open -- FASTA blocks are parsed on the device); "synth:MBP" stands for bench.py's synthetic reference.  -d FILE dumps
@@ -30,7 +31,12 @@ comes down and is written; with --bgzf device the lines are written behind the w
 --bam --sort writes -o in coordinate order (BamSorter: every batch is encoded into a resident run buffer, a run of --sort-mem bytes is
 sorted on the device and spooled to an unnamed file in --tmp-dir, default the output's directory, and the runs are merged on the device
 at the end); the header then starts with @HD VN:1.6 SO:coordinate.  --index writes <out>.bai as well.  The JSON line gains bam_sort.
-Without --sort nothing changes."""
+Without --sort nothing changes.
+--coverage PREFIX accumulates per-contig coverage and depth on the device (Coverage: 4 bytes of device memory per reference base) and
+writes PREFIX.coverage.tsv, and PREFIX.regions.bed with --cov-window N.  With --bam --sort, or --bam --bgzf device, the accumulator is
+attached to the sorter or the writer and reads the records they have just encoded; otherwise (SAM output, or unsorted --bgzf host) the writer thread
+calls Coverage.add on every batch, which encodes the batch's BAM records on the device for the accumulator alone.  The output file does
+not change.  The JSON line gains coverage.  Without --coverage nothing changes."""
 import argparse
 import json
 import os
@@ -47,7 +53,8 @@ from __graft_entry__ import _load_pkg  # noqa: E402
 VERSION = "gdiet-hip-map_file"  # the VN: field of --header's @PG line
 
 
-def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False, bam=False, sorter=None, sam_device=False):
+def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False, bam=False, sorter=None, sam_device=False,
+             cov_add=None):
     """returns (reads, seconds).  Three stages on three threads, as the reference's kt_pipeline runs its three steps (LR/map.c:2094-2170):
     read -> upload + submit -> wait + format + write; the C calls release the interpreter lock, so the stages overlap.
     A failure in any stage stops all three: `stop` is set, the writer keeps draining q_done (every open ticket is still waited for and
@@ -57,7 +64,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
     import threading
     fx = pkg.FastxReader(reads_path, threads=reader_threads, ctx=mapper.ctx if device_reader else None)
     mapper.set_inflight(inflight)
-    T = {"read": 0.0, "upload": 0.0, "submit": 0.0, "wait": 0.0, "sam+write": 0.0, "free": 0.0}
+    T = {"read": 0.0, "upload": 0.0, "submit": 0.0, "wait": 0.0, "sam+write": 0.0, "free": 0.0, **({"coverage": 0.0} if cov_add is not None else {})}
     q_read, q_done = queue.Queue(maxsize=2), queue.Queue()
     open_tickets = threading.Semaphore(inflight)  # the library takes at most `inflight` tickets: one permit per open ticket
     errors, stop = [], threading.Event()
@@ -120,6 +127,8 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
                 elif res is not None and not stop.is_set():
                     timed("sam+write", mapper.bam_batch_raw if bam else mapper.sam_batch_raw, res, n, names, seqs, quals, lens, out, comments if with_comment else None,
                           *([True] if sam_device and not bam else []))
+                if res is not None and not stop.is_set() and cov_add is not None:  # (an accumulator that is not attached to the writer or the sorter)
+                    timed("coverage", cov_add.add, res, n, names, seqs, quals, lens, comments if with_comment else None)
             except Exception as e:  # noqa: BLE001
                 fail(e)
             try:
@@ -217,6 +226,10 @@ def main():
     ap.add_argument("--index", action="store_true", help="with --bam --sort: write <out>.bai as well")
     ap.add_argument("--sort-mem", type=int, default=1 << 29, metavar="BYTES", help="bytes of records per sorted run (default 512 MiB)")
     ap.add_argument("--tmp-dir", metavar="DIR", help="where the runs are spooled (unnamed files; default: the directory of -o)")
+    ap.add_argument("--coverage", metavar="PREFIX", help="accumulate coverage and depth on the device; writes PREFIX.coverage.tsv (and PREFIX.regions.bed with --cov-window)")
+    ap.add_argument("--cov-window", type=int, default=0, metavar="N", help="with --coverage: mean depth per window of N bases")
+    ap.add_argument("--cov-min-mapq", type=int, default=0, metavar="Q", help="with --coverage: records with a lower MAPQ are not counted")
+    ap.add_argument("--cov-excl-flags", type=lambda x: int(x, 0), default=0x704, metavar="F", help="with --coverage: records with one of these FLAG bits are not counted (default 0x704)")
     ap.add_argument("-d", dest="dump", metavar="FILE", help="dump the index to FILE (.mmi, as the reference's -d) after the build; FILE can be given as ref later")
     ap.add_argument("--device-reader", action="store_true", help="parse and encode four-line FASTQ on the device (gdiet_hip_fastx_attach); the reader hands out resident batches")
     a = ap.parse_args()
@@ -264,13 +277,19 @@ def main():
     t_idx = time.perf_counter() - t0
     chunk = a.K or (39321600 if a.preset == "sr" else 80_000_000)
     sort_stats = None
+    cov, cov_report = None, None
     try:
         bgzf_out = None
+        if a.coverage:
+            cov = pkg.Coverage(m, excl_flags=a.cov_excl_flags, min_mapq=a.cov_min_mapq, window=a.cov_window)
+        attach = cov is not None and a.bam and (a.sort or a.bgzf == "device")  # the records are resident in the sorter's or the writer's hands
         if a.sort:
             sorter = pkg.BamSorter(a.out, m, bgzf=a.bgzf, level=a.bgzf_level, threads=a.bgzf_threads, run_bytes=a.sort_mem, tmp_dir=a.tmp_dir, index=a.index, version=VERSION, argv=sys.argv)
+            if attach:
+                sorter.set_coverage(cov)
             try:
                 n, dt = map_file(pkg, m, a.reads, None, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment, device_reader=a.device_reader,
-                                 bam=True, sorter=sorter)
+                                 bam=True, sorter=sorter, cov_add=None if attach else cov)
                 t_close = time.perf_counter()
                 sort_stats = dict(sorter.close(), route=a.bgzf)
                 sort_stats["close_seconds"] = round(time.perf_counter() - t_close, 3)
@@ -284,14 +303,24 @@ def main():
         else:
             with (pkg.BgzfWriter(a.out, ctx=ctx if a.bgzf == "device" else None, level=a.bgzf_level, threads=a.bgzf_threads) if a.bgzf else open(a.out, "wb")) as out:
                 bgzf_out = out if a.bgzf else None
+                if attach:
+                    out.set_coverage(cov)
                 if a.bam:
                     out.write(m.bam_header(VERSION, sys.argv))
                 elif a.header:
                     out.write(m.sam_header(VERSION, sys.argv).encode())
                 n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment,
-                                 device_reader=a.device_reader, bam=a.bam, sam_device=a.sam_device)
+                                 device_reader=a.device_reader, bam=a.bam, sam_device=a.sam_device, cov_add=None if attach else cov)
+        if cov is not None:
+            t_cov = time.perf_counter()
+            _, summary = cov.finish()
+            cov.write(a.coverage)
+            cov_report = dict(summary, prefix=a.coverage, window=a.cov_window, attached=attach, finish_write_seconds=round(time.perf_counter() - t_cov, 3))
+            cov.close()
     except Exception as e:  # noqa: BLE001  (every ticket has been waited for by now: the context can be closed)
         print("map_file failed: %r" % (e,), file=sys.stderr)
+        if cov is not None:
+            cov.close()
         m.close()
         ctx.close()
         sys.exit(1)
@@ -300,6 +329,7 @@ def main():
                       **({"reader_stats": map_file.last_reader_stats} if a.device_reader else {}), "bgzf_stats": map_file.last_bgzf_stats, "reads_format": map_file.last_format,
                       **({"bgzf_out": dict(bgzf_out.stats(), route=a.bgzf, device_seconds=[round(x, 4) for x in ctx.bgzf_deflate_seconds()])} if bgzf_out is not None else {}),
                       **({"bam_sort": sort_stats} if sort_stats is not None else {}),
+                      **({"coverage": cov_report} if cov_report is not None else {}),
                       **({"bam": True, "bam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.bam else {}),
                       **({"sam_device": True, "sam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.sam_device else {})}))
     m.close()
