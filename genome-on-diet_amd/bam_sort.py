@@ -68,6 +68,16 @@ class BamSorter:
             raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
         self._cov = cov
 
+    def set_pileup(self, pile):
+        """Attach a ``Pileup`` (None: detach), beside ``set_coverage`` and under its rules; both may be attached at once."""
+        if not self._h:
+            raise ValueError("set_pileup on a closed BamSorter")
+        self.lib.gdiet_hip_bam_sort_set_pileup.argtypes = [C.c_void_p, C.c_void_p]
+        rc = self.lib.gdiet_hip_bam_sort_set_pileup(self._h, pile._h if pile is not None else None)
+        if rc:
+            raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
+        self._pile = pile
+
     def add_reads(self, res, reads):
         """add on Python objects: reads = [(qname, seq, qual or None[, comment or None]), ...]"""
         n = len(reads)

@@ -63,6 +63,13 @@ class BgzfWriter:
         self._check(self.lib.gdiet_hip_bgzf_out_set_coverage(self._h, cov._h if cov is not None else None))
         self._cov = cov
 
+    def set_pileup(self, pile):
+        """Attach a ``Pileup`` (None: detach), beside ``set_coverage`` and under its rules; both may be attached at once."""
+        self._open()
+        self.lib.gdiet_hip_bgzf_out_set_pileup.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(self.lib.gdiet_hip_bgzf_out_set_pileup(self._h, pile._h if pile is not None else None))
+        self._pile = pile
+
     def flush(self):
         self._open()
         self._check(self.lib.gdiet_hip_bgzf_out_flush(self._h))

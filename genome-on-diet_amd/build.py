@@ -44,7 +44,11 @@ BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           "_Z17bam_gather_kernel": dict(vgprs=32, scratch=0),
           # coverage accumulated from the resident BAM records (cov.hip.h): batch i is scattered beside the DP of batch i + 1, like the encoders
           "_Z18cov_scatter_kernel": dict(vgprs=32, scratch=0),
-          "_Z17cov_window_kernel": dict(vgprs=32, scratch=0)}
+          "_Z17cov_window_kernel": dict(vgprs=32, scratch=0),
+          # base counts per position piled up from the resident BAM records, and the calls after finish (pile.hip.h)
+          "_Z19pile_scatter_kernel": dict(vgprs=32, scratch=0),
+          "_Z16pile_call_kernel": dict(vgprs=32, scratch=0),
+          "_Z16pile_site_kernel": dict(vgprs=32, scratch=0)}
 
 
 def _newest_source():

@@ -30,6 +30,23 @@ struct GdCovHold {
 	}
 	~GdCovHold() { if (c) gd_cov_release(c); }
 };
+// an attached pileup accumulator's side, likewise (pile_driver.hip.h); where both are attached the coverage accumulator is taken first
+struct gdiet_pileup;
+static int gd_pile_hold(gdiet_pileup *p, std::string &why);
+static void gd_pile_release(gdiet_pileup *p);
+static int gd_pile_enqueue_part(gdiet_pileup *p, hipStream_t s, const uint8_t *d_recs, const GdbPart &P, std::vector<uint64_t> &starts, std::string &why);
+static int gd_pile_verdict(gdiet_pileup *p, std::string &why);
+struct GdPileHold {
+	gdiet_pileup *c = nullptr;
+	std::vector<uint64_t> starts;
+	int take(gdiet_pileup *pile, std::string &why)
+	{
+		if (pile && gd_pile_hold(pile, why)) return -1;
+		c = pile;
+		return 0;
+	}
+	~GdPileHold() { if (c) gd_pile_release(c); }
+};
 
 // the chunks' pools and the merged table of a batch: the context's (gdiet_ctx::bam_pool), so that they keep their pages from mini-batch to
 // mini-batch -- a mini-batch is some 130 MB of table and text, and a fresh allocation of that size is paid for page by page every time
@@ -229,6 +246,8 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	std::string why;
 	GdCovHold cov; // (nothing without an attached accumulator)
 	if (cov.take(h->cov, why)) return gd_err_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_out_write_bam: " + why);
+	GdPileHold pile;
+	if (pile.take(h->pile, why)) return gd_err_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_out_write_bam: " + why);
 	int rc = gd_bam_flatten(ctx, ix, n_reads, qnames, seqs, quals, comments, lens, n_regs, regs, opt_flag, P, why);
 	if (rc) return why.empty() ? rc : gd_err_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why);
 	if (P.bytes == 0) return GDIET_OK;
@@ -238,6 +257,7 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	int wrc = 0;
 	rc = gd_bam_encode_device(ctx, P, w.tail.data(), w.tail.size(), why, [&](uint8_t *d_stream, size_t bytes, hipStream_t s) {
 		if (cov.c && gd_cov_enqueue_part(cov.c, s, d_stream + w.tail.size(), P, cov.starts, why)) return -1; // from the records where they are, before they are compressed
+		if (pile.c && gd_pile_enqueue_part(pile.c, s, d_stream + w.tail.size(), P, pile.starts, why)) return -1;
 		const size_t whole = bytes / GD_BGZF_MEMBER_IN * GD_BGZF_MEMBER_IN;
 		next_tail.resize(bytes - whole);
 		if (!next_tail.empty()) {
@@ -250,7 +270,10 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	if (rc) { w.dev_error = true, (void)w.fail(why); return gd_bzo_done(h, -1); }
 	if (wrc) return gd_bzo_done(h, wrc);
 	w.tail.swap(next_tail);
+	std::string why_pile;
+	const int rc_pile = pile.c ? gd_pile_verdict(pile.c, why_pile) : 0; // (both are asked before either returns: a bad record poisons both)
 	if (cov.c && (rc = gd_cov_verdict(cov.c, why)) != 0) return gd_err_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why);
+	if (rc_pile) return gd_err_fail(ctx, rc_pile, "gdiet_hip_bgzf_out_write_bam: " + why_pile);
 	return GDIET_OK;
 }
 

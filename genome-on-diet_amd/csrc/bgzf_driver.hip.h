@@ -217,7 +217,8 @@ struct GdBzdExecutor : GdBgzfDeflater {
 	}
 };
 struct gdiet_coverage; // cov_driver.hip.h
-struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; gdiet_coverage *cov = nullptr; /* gdiet_hip_bgzf_out_set_coverage */ };
+struct gdiet_pileup;   // pile_driver.hip.h
+struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; gdiet_coverage *cov = nullptr; /* gdiet_hip_bgzf_out_set_coverage */ gdiet_pileup *pile = nullptr; /* _set_pileup */ };
 
 extern "C" int gdiet_hip_bgzf_out_open(gdiet_ctx *ctx, const char *path, int level, int threads, gdiet_bgzf_out **out)
 {

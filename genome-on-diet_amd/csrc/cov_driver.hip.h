@@ -50,6 +50,27 @@ static int gd_cov_usable(gdiet_coverage *h, std::string &why)
 	return 0;
 }
 
+// The starts of the host records recs[0, len) of an add_bam call (coverage's and the pileup's): nothing but block_size is looked at here,
+// the kernel validates the rest.  0, or -1 with why: nothing was seen
+static int gd_record_starts(const void *recs, size_t len, std::vector<uint64_t> &start, std::string &why)
+{
+	const uint8_t *b = (const uint8_t *)recs;
+	size_t pos = 0;
+	while (len - pos >= 4) {
+		const int32_t bs = (int32_t)gds_le32(b + pos);
+		if (bs < 32) {
+			why = "BAM record " + std::to_string(start.size()) + " at offset " + std::to_string(pos) + ": a block_size of " + std::to_string(bs) + ", below the 32 fixed bytes";
+			return -1;
+		}
+		if (len - pos - 4 < (size_t)bs) break;
+		start.push_back(pos);
+		pos += 4 + (size_t)bs;
+	}
+	if (pos != len) { why = "offset " + std::to_string(pos) + ": the range ends inside a record"; return -1; }
+	if (start.size() > 0x7fffffffull) { why = "2^31 records or more in one call"; return -1; }
+	return 0;
+}
+
 // The scatter of the n records at d_recs[0, bytes) whose starts are h_start[0, n), enqueued on s with the allocations of mem; the caller
 // holds h->mu, keeps h_start alive until it has synchronised s, and then asks gd_cov_verdict.  0, or -1 with why (the device failed).
 static int gd_cov_enqueue(gdiet_coverage *h, hipStream_t s, GdStreamMem &mem, const uint8_t *d_recs, uint64_t bytes, const uint64_t *h_start, uint64_t n, std::string &why)
@@ -197,20 +218,9 @@ extern "C" int gdiet_hip_cov_add_bam(gdiet_coverage *h, const void *recs, size_t
 	std::lock_guard<std::mutex> hk(h->mu);
 	std::string why;
 	if (gd_cov_usable(h, why)) return gd_cov_fail(h, GDIET_E_PARAM, who, why);
-	// the starts: nothing but block_size is looked at here, the kernel validates the rest
-	const uint8_t *b = (const uint8_t *)recs;
 	std::vector<uint64_t> start;
-	size_t pos = 0;
-	while (len - pos >= 4) {
-		const int32_t bs = (int32_t)gds_le32(b + pos);
-		if (bs < 32) return gd_cov_fail(h, GDIET_E_PARAM, who, "BAM record " + std::to_string(start.size()) + " at offset " + std::to_string(pos) + ": a block_size of " + std::to_string(bs) + ", below the 32 fixed bytes");
-		if (len - pos - 4 < (size_t)bs) break;
-		start.push_back(pos);
-		pos += 4 + (size_t)bs;
-	}
-	if (pos != len) return gd_cov_fail(h, GDIET_E_PARAM, who, "offset " + std::to_string(pos) + ": the range ends inside a record");
+	if (gd_record_starts(recs, len, start, why)) return gd_cov_fail(h, GDIET_E_PARAM, who, why);
 	if (start.empty()) return GDIET_OK;
-	if (start.size() > 0x7fffffffull) return gd_cov_fail(h, GDIET_E_PARAM, who, "2^31 records or more in one call");
 	gdiet_ctx *ctx = h->ctx;
 	GdLane &L = ctx->cov;
 	std::lock_guard<std::mutex> lk(L.mu);

@@ -190,6 +190,7 @@ struct gdiet_ctx {
 	GdLane ds, fx, bz, bzd, bam, bsort, cov;
 	template <class F> void each_lane(F f) { f(ds), f(fx), f(bz), f(bzd), f(bam), f(bsort), f(cov); }
 	std::vector<void *> cov_open;      // gdiet_coverage* opened on this context and not yet closed: their arrays go with it (under cov_reg_mu)
+	std::vector<void *> pile_open;     // gdiet_pileup* likewise (pile_driver.hip.h; under cov_reg_mu)
 	std::mutex cov_reg_mu;
 	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff; // (under ds.mu)
 	std::vector<uint8_t> ds_enc;       // host copy of the reads a difference-string call without a resident batch encodes
@@ -333,6 +334,7 @@ static void gd_pool_free(void *pool); // map_pipeline.hip.h
 template <class F> static void gd_parallel_for(gdiet_ctx *ctx, int n_threads, int n, F f); // map_pipeline.hip.h
 static void gd_join_open_tickets(gdiet_ctx *ctx);
 static void gd_cov_orphan_all(gdiet_ctx *ctx); // cov_driver.hip.h
+static void gd_pile_orphan_all(gdiet_ctx *ctx); // pile_driver.hip.h
 
 extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 {
@@ -346,6 +348,7 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
 	gd_cov_orphan_all(ctx); // the arrays of coverage accumulators that are still open
+	gd_pile_orphan_all(ctx); // and of pileup accumulators
 	std::vector<hipEvent_t> events(ctx->ev, ctx->ev + 4);
 	events.insert(events.end(), {ctx->arena_ev, ctx->wait_ev, ctx->gather_ev});
 	std::vector<hipStream_t> streams{ctx->stream_dp, ctx->stream};
@@ -1275,6 +1278,7 @@ extern "C" int gdiet_hip_debug_bgzf_seconds(const gdiet_fastx *fx, double *out6)
 #include "bam_driver.hip.h" // BAM: the record encoder's driver, gdiet_hip_bam_header / _bam_batch_into / _bgzf_out_write_bam
 #include "sam_driver.hip.h" // SAM text on the device: the line formatter's driver, gdiet_hip_sam_batch_device_into / _bgzf_out_write_sam
 #include "cov_driver.hip.h" // coverage and depth accumulated from the resident records: gdiet_hip_cov_*
+#include "pile_driver.hip.h" // base counts per position and variant sites from the resident records: gdiet_hip_pile_*
 #include "bam_sort_driver.hip.h" // BAM records in coordinate order: the sort pass's driver, gdiet_hip_bam_sort_records
 
 extern "C" int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n, int64_t *roff, uint8_t *enc_host, uint8_t *enc_device)

@@ -906,6 +906,86 @@ int gdiet_hip_cov_depth(gdiet_coverage *cov, uint32_t rid, uint32_t beg, uint32_
 /* Frees the arrays and the handle, whatever state it is in. */
 int gdiet_hip_cov_close(gdiet_coverage *cov);
 
+/* ---- Pileup --------------------------------------------------------------------------------------------------------------------------
+ * What the reads show at every position of a list of regions: eight counters per position, accumulated on the device from uncompressed
+ * BAM alignment records while they are resident there, and, after finish, a consensus byte per position and the variant sites, formed
+ * on the device in integers.  The reference prints SAM and stops: these rules are the definition (tests/pile_ref.py restates them).
+ *   REGIONS  (rid, beg, end), 0-based and half-open, given at open.  Refused with GDIET_E_PARAM, the text naming the first offending
+ *           region: an empty region (beg >= end), a region past its contig (rid >= n_ref or end > the contig's length), a list that is
+ *           not sorted by (rid, beg), overlapping regions.  Abutting regions are allowed.  An empty list means every contig whole.
+ *           The positions are numbered region after region with 64-bit offsets; T is their total.
+ *   COUNTERS eight uint32 per position in the order A C G T N DEL INS REV: 32 bytes per position, 32 * T bytes of plain hipMalloc for as
+ *           long as the handle lives (GDIET_E_NOMEM carries the size in its text): 99 GB for a whole GRCh38 of 3.1 Gbp, 32 MB per Mbp
+ *           of panel.  A counter driven above 2^32 - 1, or a depth above it, is out of contract.
+ *   WHICH RECORDS COUNT  the real CIGAR, the bad-record reasons and the filter chain are those of "Coverage": bad, then excl_flags, then
+ *           min_mapq.  One category is added in front of `counted`: no_seq, a placed record that passes the filters but has l_seq == 0.
+ *           The summary is coverage's ten counters, then no_seq, then skipped_baseq.
+ *   WALK    of a counted record, with a reference cursor r from pos and a query cursor q from 0:
+ *           M = X   for every base b of the run whose position r + b lies in a region: if the record has qualities (qual[0] != 0xff)
+ *                   and qual[q + b] < min_baseq, the base adds 1 to skipped_baseq and to no counter; otherwise the SEQ nibble at q + b
+ *                   selects the counter -- 1 A, 2 C, 4 G, 8 T, any other code ('=' included) N -- and a record with flag 0x10 also adds
+ *                   1 to REV.  Both cursors advance.
+ *           D       DEL += 1 at every position of the run that lies in a region; no quality test.  Only r advances.
+ *           N       only r advances.
+ *           I       if r > pos (an operation before it has consumed reference) and position r - 1 lies in a region, INS += 1 there:
+ *                   one count per insertion, whatever its length.  Otherwise it is not counted.  Only q advances.
+ *           S       only q advances.   H P   neither cursor advances.
+ *           A position outside every region is skipped silently; a run may cross several regions and the gaps between them.
+ *   BAD     a bad record touches nothing, fails its call with GDIET_E_PARAM naming the call's first bad record and its reason, and
+ *           poisons the handle, exactly as in "Coverage".
+ *   CALLS   after finish, with min_depth, min_alt and a fraction num / den (den > 0); no float is formed on the device.
+ *           depth = A + C + G + T + N + DEL.  The reference base is that of the index's packed reference S: 0..3, 4 for N.
+ *           The consensus byte of a position is 'N' if depth < min_depth or all of A C G T DEL are 0, else the largest of A C G T DEL,
+ *           ties going to the earlier in that order, written A C G T *.
+ *           A position is a site if depth >= min_depth and (some allele k of A C G T DEL other than the reference base has cnt[k] >=
+ *           min_alt and (uint64)cnt[k] * den >= (uint64)num * depth, or INS >= min_alt and (uint64)INS * den >= (uint64)num * depth).
+ *           At a reference N every one of A C G T DEL is "other".  Sites come out in position order, region after region, as rows
+ *           {rid, pos, ref, alt, depth, cnt[8]}: ref 0..4; alt 0..3 for A C G T, 4 for DEL, 5 for INS -- the largest qualifying allele
+ *           of A C G T DEL with the same tie order, 5 only when none of them qualifies.
+ *   Every result is a function of the multiset of input records, the regions and the options alone: it does not depend on how the
+ *   records were cut into calls, on the route, on the scan's chunk or on the order of atomic arrivals.
+ * The device side (csrc/pile.hip.h, statements in csrc/pile.h, which reuses those of csrc/cov.h): pile_scatter_kernel, one wavefront
+ * per record, validates as coverage does, then takes the runs of every round of 64 operations one after another, the positions of a run
+ * dealt over the 64 lanes, each lane reading its own SEQ nibble and QUAL byte and adding with a plain integer atomic.
+ * pile_call_kernel, one thread per position, writes the consensus byte and a 0 / 1 site flag; hipCUB's exclusive sum over the flags,
+ * in chunks of at most 2^30 positions with a carry, gives the sites' offsets and pile_site_kernel writes the rows.  Out of scope:
+ * per-strand counters per allele, the inserted sequences, genotype likelihoods, VCF, merging the accumulators of several GPUs,
+ * regions given after open. */
+typedef struct gdiet_pileup gdiet_pileup;
+typedef struct { uint32_t rid, beg, end; } gdiet_pile_region_t;
+typedef struct {
+	uint64_t records, unmapped, secondary, supplementary, primary_mapped, reverse, excluded_by_flag, excluded_by_mapq, counted, bad, no_seq, skipped_baseq;
+} gdiet_pile_summary_t;
+typedef struct { uint32_t rid, pos, ref, alt, depth, cnt[8]; } gdiet_pile_site_t;
+/* An accumulator over regions[0, n_regions) of idx's contigs (n_regions == 0: every contig whole): allocates and clears the counters.
+ * idx must stay alive for as long as the handle is used: the calls read its packed reference.  The counters also go when the context is
+ * destroyed: a handle that outlives its context takes nothing but close. */
+int gdiet_hip_pile_open(gdiet_ctx *ctx, const gdiet_index *idx, const gdiet_pile_region_t *regions, size_t n_regions, uint32_t excl_flags, uint32_t min_mapq, uint32_t min_baseq,
+                        gdiet_pileup **out);
+/* Host records and a mapped batch: as gdiet_hip_cov_add_bam and gdiet_hip_cov_add (opt_flag decides which records exist). */
+int gdiet_hip_pile_add_bam(gdiet_pileup *pile, const void *recs, size_t len);
+int gdiet_hip_pile_add(gdiet_pileup *pile, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs, const char *const *quals,
+                       const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs, const char *const *comments, int64_t opt_flag);
+/* Attach (NULL: detach) to a BGZF writer with a context or to a sorter, beside gdiet_hip_bgzf_out_set_coverage /
+ * gdiet_hip_bam_sort_set_coverage and under their rules; a coverage and a pileup accumulator may be attached at once.  The bytes
+ * written do not change.  Lock order: the encoder's mutex, the coverage accumulator's, the pileup accumulator's, the context's lane. */
+int gdiet_hip_bgzf_out_set_pileup(gdiet_bgzf_out *writer, gdiet_pileup *pile);
+int gdiet_hip_bam_sort_set_pileup(gdiet_bam_sorter *sorter, gdiet_pileup *pile);
+/* The summary (may be NULL).  After it the accumulator is read-only: add is refused, finish again returns the same figures.  _chunked:
+ * the chunk, in positions, of the exclusive sum that _sites runs (0: the default, 2^24; at most 2^30) -- no result depends on it; it
+ * exists so that tests cross chunk borders on small inputs. */
+int gdiet_hip_pile_finish(gdiet_pileup *pile, gdiet_pile_summary_t *summary_out);
+int gdiet_hip_pile_finish_chunked(gdiet_pileup *pile, uint64_t chunk, gdiet_pile_summary_t *summary_out);
+/* After finish: out[0, 8 * (end - beg)) takes the counters of positions [beg, end) of contig rid, which must lie inside one region. */
+int gdiet_hip_pile_counts(gdiet_pileup *pile, uint32_t rid, uint32_t beg, uint32_t end, uint32_t *out);
+/* After finish: out takes one consensus byte per position of region `region` (its number in the list; a contig's with an empty list). */
+int gdiet_hip_pile_consensus(gdiet_pileup *pile, size_t region, uint32_t min_depth, uint8_t *out);
+/* After finish: the sites.  Returns their number; with out == NULL that is all (the size first), else cap, the room of out in rows,
+ * must hold them (GDIET_E_PARAM otherwise, the text says how many there are). */
+int64_t gdiet_hip_pile_sites(gdiet_pileup *pile, uint32_t min_depth, uint32_t min_alt, uint32_t num, uint32_t den, gdiet_pile_site_t *out, size_t cap);
+/* Frees the counters and the handle, whatever state it is in. */
+int gdiet_hip_pile_close(gdiet_pileup *pile);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ No Python object is made per read: the C arrays of the reader go straight into t
                              [-d out.mmi] [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
                              [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--sort-mem BYTES] [--tmp-dir DIR]]] [--sam-device]
                              [--coverage PREFIX [--cov-window N] [--cov-min-mapq Q] [--cov-excl-flags F]]
+                             [--pileup PREFIX [--pile-regions BED] [--pile-min-baseq Q] [--pile-min-mapq Q] [--pile-excl-flags F] [--pile-min-depth N] [--pile-min-alt N] [--pile-frac NUM/DEN]]
 
 `ref` is a FASTA / FASTQ file (plain, gzip or BGZF) or an .mmi index file, known by its magic, not its name (Mapper.from_file:
 gdiet_hip_index_open -- FASTA blocks are parsed on the device); "synth:MBP" stands for bench.py's synthetic reference.  -d FILE dumps
@@ -36,7 +37,11 @@ Without --sort nothing changes.
 writes PREFIX.coverage.tsv, and PREFIX.regions.bed with --cov-window N.  With --bam --sort, or --bam --bgzf device, the accumulator is
 attached to the sorter or the writer and reads the records they have just encoded; otherwise (SAM output, or unsorted --bgzf host) the writer thread
 calls Coverage.add on every batch, which encodes the batch's BAM records on the device for the accumulator alone.  The output file does
-not change.  The JSON line gains coverage.  Without --coverage nothing changes."""
+not change.  The JSON line gains coverage.  Without --coverage nothing changes.
+--pileup PREFIX piles up base counts per position on the device (Pileup: 32 bytes of device memory per position) over the regions of
+--pile-regions BED (contig, 0-based start, end; sorted as the contigs are and disjoint; default: every contig whole) and writes
+PREFIX.pileup.tsv, the variant sites under --pile-min-depth / --pile-min-alt / --pile-frac, and PREFIX.consensus.fa.  It attaches exactly as
+--coverage does and may be combined with it.  The JSON line gains pileup.  Without --pileup nothing changes."""
 import argparse
 import json
 import os
@@ -54,7 +59,7 @@ VERSION = "gdiet-hip-map_file"  # the VN: field of --header's @PG line
 
 
 def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False, bam=False, sorter=None, sam_device=False,
-             cov_add=None):
+             cov_add=None, pile_add=None):
     """returns (reads, seconds).  Three stages on three threads, as the reference's kt_pipeline runs its three steps (LR/map.c:2094-2170):
     read -> upload + submit -> wait + format + write; the C calls release the interpreter lock, so the stages overlap.
     A failure in any stage stops all three: `stop` is set, the writer keeps draining q_done (every open ticket is still waited for and
@@ -64,7 +69,7 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
     import threading
     fx = pkg.FastxReader(reads_path, threads=reader_threads, ctx=mapper.ctx if device_reader else None)
     mapper.set_inflight(inflight)
-    T = {"read": 0.0, "upload": 0.0, "submit": 0.0, "wait": 0.0, "sam+write": 0.0, "free": 0.0, **({"coverage": 0.0} if cov_add is not None else {})}
+    T = {"read": 0.0, "upload": 0.0, "submit": 0.0, "wait": 0.0, "sam+write": 0.0, "free": 0.0, **({"coverage": 0.0} if cov_add is not None else {}), **({"pileup": 0.0} if pile_add is not None else {})}
     q_read, q_done = queue.Queue(maxsize=2), queue.Queue()
     open_tickets = threading.Semaphore(inflight)  # the library takes at most `inflight` tickets: one permit per open ticket
     errors, stop = [], threading.Event()
@@ -129,6 +134,8 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
                           *([True] if sam_device and not bam else []))
                 if res is not None and not stop.is_set() and cov_add is not None:  # (an accumulator that is not attached to the writer or the sorter)
                     timed("coverage", cov_add.add, res, n, names, seqs, quals, lens, comments if with_comment else None)
+                if res is not None and not stop.is_set() and pile_add is not None:
+                    timed("pileup", pile_add.add, res, n, names, seqs, quals, lens, comments if with_comment else None)
             except Exception as e:  # noqa: BLE001
                 fail(e)
             try:
@@ -230,6 +237,14 @@ def main():
     ap.add_argument("--cov-window", type=int, default=0, metavar="N", help="with --coverage: mean depth per window of N bases")
     ap.add_argument("--cov-min-mapq", type=int, default=0, metavar="Q", help="with --coverage: records with a lower MAPQ are not counted")
     ap.add_argument("--cov-excl-flags", type=lambda x: int(x, 0), default=0x704, metavar="F", help="with --coverage: records with one of these FLAG bits are not counted (default 0x704)")
+    ap.add_argument("--pileup", metavar="PREFIX", help="pile up base counts per position on the device; writes PREFIX.pileup.tsv (the variant sites) and PREFIX.consensus.fa")
+    ap.add_argument("--pile-regions", metavar="BED", help="with --pileup: the regions (contig, 0-based start, end), sorted and disjoint; default: every contig whole")
+    ap.add_argument("--pile-min-baseq", type=int, default=0, metavar="Q", help="with --pileup: bases with a lower quality are not counted")
+    ap.add_argument("--pile-min-mapq", type=int, default=0, metavar="Q", help="with --pileup: records with a lower MAPQ are not counted")
+    ap.add_argument("--pile-excl-flags", type=lambda x: int(x, 0), default=0x704, metavar="F", help="with --pileup: records with one of these FLAG bits are not counted (default 0x704)")
+    ap.add_argument("--pile-min-depth", type=int, default=8, metavar="N", help="with --pileup: a site and a consensus base need this depth (default 8)")
+    ap.add_argument("--pile-min-alt", type=int, default=2, metavar="N", help="with --pileup: a site's allele needs this count (default 2)")
+    ap.add_argument("--pile-frac", default="1/5", metavar="NUM/DEN", help="with --pileup: and this fraction of the depth (default 1/5)")
     ap.add_argument("-d", dest="dump", metavar="FILE", help="dump the index to FILE (.mmi, as the reference's -d) after the build; FILE can be given as ref later")
     ap.add_argument("--device-reader", action="store_true", help="parse and encode four-line FASTQ on the device (gdiet_hip_fastx_attach); the reader hands out resident batches")
     a = ap.parse_args()
@@ -278,18 +293,29 @@ def main():
     chunk = a.K or (39321600 if a.preset == "sr" else 80_000_000)
     sort_stats = None
     cov, cov_report = None, None
+    pile, pile_report = None, None
     try:
         bgzf_out = None
         if a.coverage:
             cov = pkg.Coverage(m, excl_flags=a.cov_excl_flags, min_mapq=a.cov_min_mapq, window=a.cov_window)
-        attach = cov is not None and a.bam and (a.sort or a.bgzf == "device")  # the records are resident in the sorter's or the writer's hands
+        if a.pileup:
+            regions = None
+            if a.pile_regions:
+                with open(a.pile_regions) as f:
+                    regions = [(m.names.index(x[0]), int(x[1]), int(x[2])) for x in (l.split() for l in f if l.strip() and not l.startswith(("#", "track", "browser")))]
+            num, den = (int(x) for x in a.pile_frac.split("/"))
+            pile = pkg.Pileup(m, regions=regions, excl_flags=a.pile_excl_flags, min_mapq=a.pile_min_mapq, min_baseq=a.pile_min_baseq)
+        resident = a.bam and (a.sort or a.bgzf == "device")  # the records are resident in the sorter's or the writer's hands
+        attach, attach_pile = cov is not None and resident, pile is not None and resident
         if a.sort:
             sorter = pkg.BamSorter(a.out, m, bgzf=a.bgzf, level=a.bgzf_level, threads=a.bgzf_threads, run_bytes=a.sort_mem, tmp_dir=a.tmp_dir, index=a.index, version=VERSION, argv=sys.argv)
             if attach:
                 sorter.set_coverage(cov)
+            if attach_pile:
+                sorter.set_pileup(pile)
             try:
                 n, dt = map_file(pkg, m, a.reads, None, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment, device_reader=a.device_reader,
-                                 bam=True, sorter=sorter, cov_add=None if attach else cov)
+                                 bam=True, sorter=sorter, cov_add=None if attach else cov, pile_add=None if attach_pile else pile)
                 t_close = time.perf_counter()
                 sort_stats = dict(sorter.close(), route=a.bgzf)
                 sort_stats["close_seconds"] = round(time.perf_counter() - t_close, 3)
@@ -305,22 +331,32 @@ def main():
                 bgzf_out = out if a.bgzf else None
                 if attach:
                     out.set_coverage(cov)
+                if attach_pile:
+                    out.set_pileup(pile)
                 if a.bam:
                     out.write(m.bam_header(VERSION, sys.argv))
                 elif a.header:
                     out.write(m.sam_header(VERSION, sys.argv).encode())
                 n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment,
-                                 device_reader=a.device_reader, bam=a.bam, sam_device=a.sam_device, cov_add=None if attach else cov)
+                                 device_reader=a.device_reader, bam=a.bam, sam_device=a.sam_device, cov_add=None if attach else cov, pile_add=None if attach_pile else pile)
         if cov is not None:
             t_cov = time.perf_counter()
             _, summary = cov.finish()
             cov.write(a.coverage)
             cov_report = dict(summary, prefix=a.coverage, window=a.cov_window, attached=attach, finish_write_seconds=round(time.perf_counter() - t_cov, 3))
             cov.close()
+        if pile is not None:
+            t_pile = time.perf_counter()
+            summary = pile.finish()
+            pile.write(a.pileup, min_depth=a.pile_min_depth, min_alt=a.pile_min_alt, frac=(num, den))
+            pile_report = dict(summary, prefix=a.pileup, regions=len(pile.regions), attached=attach_pile, finish_write_seconds=round(time.perf_counter() - t_pile, 3))
+            pile.close()
     except Exception as e:  # noqa: BLE001  (every ticket has been waited for by now: the context can be closed)
         print("map_file failed: %r" % (e,), file=sys.stderr)
         if cov is not None:
             cov.close()
+        if pile is not None:
+            pile.close()
         m.close()
         ctx.close()
         sys.exit(1)
@@ -330,6 +366,7 @@ def main():
                       **({"bgzf_out": dict(bgzf_out.stats(), route=a.bgzf, device_seconds=[round(x, 4) for x in ctx.bgzf_deflate_seconds()])} if bgzf_out is not None else {}),
                       **({"bam_sort": sort_stats} if sort_stats is not None else {}),
                       **({"coverage": cov_report} if cov_report is not None else {}),
+                      **({"pileup": pile_report} if pile_report is not None else {}),
                       **({"bam": True, "bam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.bam else {}),
                       **({"sam_device": True, "sam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.sam_device else {})}))
     m.close()
