@@ -57,26 +57,24 @@ class BamSorter:
         if rc:
             raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
 
+    def _attach(self, kind, obj):
+        if not self._h:
+            raise ValueError("set_%s on a closed BamSorter" % kind)
+        fn = getattr(self.lib, "gdiet_hip_bam_sort_set_" + kind)
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        rc = fn(self._h, obj._h if obj is not None else None)
+        if rc:
+            raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
+        setattr(self, "_" + kind, obj)  # (kept alive while attached)
+
     def set_coverage(self, cov):
         """Attach a ``Coverage`` (None: detach): every later ``add`` scatters into it from the records it has just encoded into the run
         buffer, before they are sorted; the file's bytes do not change.  Keep ``cov`` open while attached."""
-        if not self._h:
-            raise ValueError("set_coverage on a closed BamSorter")
-        self.lib.gdiet_hip_bam_sort_set_coverage.argtypes = [C.c_void_p, C.c_void_p]
-        rc = self.lib.gdiet_hip_bam_sort_set_coverage(self._h, cov._h if cov is not None else None)
-        if rc:
-            raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
-        self._cov = cov
+        self._attach("coverage", cov)
 
     def set_pileup(self, pile):
         """Attach a ``Pileup`` (None: detach), beside ``set_coverage`` and under its rules; both may be attached at once."""
-        if not self._h:
-            raise ValueError("set_pileup on a closed BamSorter")
-        self.lib.gdiet_hip_bam_sort_set_pileup.argtypes = [C.c_void_p, C.c_void_p]
-        rc = self.lib.gdiet_hip_bam_sort_set_pileup(self._h, pile._h if pile is not None else None)
-        if rc:
-            raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
-        self._pile = pile
+        self._attach("pileup", pile)
 
     def add_reads(self, res, reads):
         """add on Python objects: reads = [(qname, seq, qual or None[, comment or None]), ...]"""

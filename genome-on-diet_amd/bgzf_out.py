@@ -55,20 +55,21 @@ class BgzfWriter:
         self._open()
         mapper.sam_batch_raw(res, n, names, seqs, quals, lens, sink=self, comments=comments, device=True)
 
+    def _attach(self, kind, obj):
+        self._open()
+        fn = getattr(self.lib, "gdiet_hip_bgzf_out_set_" + kind)
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, obj._h if obj is not None else None))
+        setattr(self, "_" + kind, obj)  # (kept alive while attached)
+
     def set_coverage(self, cov):
         """Attach a ``Coverage`` (None: detach): every later ``write_bam`` scatters into it from the records it has just encoded on the
         device, before they are compressed; the file's bytes do not change.  The writer needs a context.  Keep ``cov`` open while attached."""
-        self._open()
-        self.lib.gdiet_hip_bgzf_out_set_coverage.argtypes = [C.c_void_p, C.c_void_p]
-        self._check(self.lib.gdiet_hip_bgzf_out_set_coverage(self._h, cov._h if cov is not None else None))
-        self._cov = cov
+        self._attach("coverage", cov)
 
     def set_pileup(self, pile):
         """Attach a ``Pileup`` (None: detach), beside ``set_coverage`` and under its rules; both may be attached at once."""
-        self._open()
-        self.lib.gdiet_hip_bgzf_out_set_pileup.argtypes = [C.c_void_p, C.c_void_p]
-        self._check(self.lib.gdiet_hip_bgzf_out_set_pileup(self._h, pile._h if pile is not None else None))
-        self._pile = pile
+        self._attach("pileup", pile)
 
     def flush(self):
         self._open()

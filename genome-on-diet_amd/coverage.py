@@ -1,12 +1,14 @@
 """Per-contig coverage and depth accumulated on the device: ``Coverage`` over the library's accumulator (``gdiet_hip_cov_*``,
-csrc/cov_driver.hip.h).  The records of every batch are walked where they are resident (csrc/cov.hip.h: one wavefront per record
-scatters +1 / -1 into a difference array over the whole reference); ``finish`` sums the array and reduces it per window.  The rules are
-the section "Coverage" of include/gdiet_hip.h.  The array costs 4 bytes per reference base while the object lives."""
+csrc/cov_driver.hip.h; what it shares with ``Pileup`` is in accum.py).  The records of every batch are walked where they are resident
+(csrc/cov.hip.h: one wavefront per record scatters +1 / -1 into a difference array over the whole reference); ``finish`` sums the array
+and reduces it per window.  The rules are the section "Coverage" of include/gdiet_hip.h.  The array costs 4 bytes per reference base
+while the object lives."""
 import ctypes as C
 
 import numpy as np
 
-from .hip_abi import GdietError, load_library
+from .accum import Accumulator
+from .hip_abi import load_library
 from .map_api import Reg
 
 SUMMARY = ("records", "unmapped", "secondary", "supplementary", "primary_mapped", "reverse", "excluded_by_flag", "excluded_by_mapq", "counted", "bad")
@@ -30,12 +32,13 @@ def _bind(lib):
     lib._cov_bound = True
 
 
-class Coverage:
+class Coverage(Accumulator):
     """``Coverage(mapper, excl_flags=0x704, min_mapq=0, window=0)``.  Records come in through ``add`` (a mapped batch: the arguments of
     ``Mapper.bam_batch_raw``; encoded and scattered on the device, nothing comes down), ``add_bam`` (bytes of uncompressed BAM records) or
     an attached ``BgzfWriter`` / ``BamSorter`` (``set_coverage``).  ``finish()`` returns (per-contig numpy records, summary dict); then
     ``windows(rid)``, ``depth(rid, beg, end)`` and ``write(prefix)`` read the result.  A bad record raises ``GdietError`` and leaves the
     object refusing everything but ``close``."""
+    _prefix, _name = "cov", "Coverage"
 
     def __init__(self, mapper, excl_flags=0x704, min_mapq=0, window=0):
         self.lib = load_library()
@@ -46,38 +49,6 @@ class Coverage:
         self._h = C.c_void_p()
         self._result = None
         self._check(self.lib.gdiet_hip_cov_open(mapper.ctx._h, mapper._idx, int(excl_flags), int(min_mapq), self.window, C.byref(self._h)))
-
-    def _check(self, rc):
-        if rc < 0:
-            t = self.lib.gdiet_hip_strerror(self.mapper.ctx._h)
-            raise GdietError("gdiet_hip error %d: %s" % (rc, t.decode() if t else ""))
-        return rc
-
-    def _open(self):
-        if not self._h:
-            raise ValueError("a closed Coverage")
-
-    def add(self, res, n, names, seqs, quals, lens, comments=None):
-        self._open()
-        cpp = C.POINTER(C.c_char_p)
-        self._check(self.lib.gdiet_hip_cov_add(self._h, self.mapper._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp), lens, res.n_regs, res.regs,
-                                               C.cast(comments, cpp), self.mapper.opt.flag))
-
-    def add_reads(self, res, reads):
-        """add on Python objects: reads = [(qname, seq, qual or None[, comment or None]), ...]"""
-        n = len(reads)
-        enc = lambda x: x if isinstance(x, bytes) else x.encode()
-        qn = (C.c_char_p * n)(*[enc(r[0]) for r in reads])
-        sq = (C.c_char_p * n)(*[enc(r[1]) for r in reads])
-        ql = (C.c_char_p * n)(*[None if len(r) < 3 or r[2] is None else enc(r[2]) for r in reads])
-        cm = (C.c_char_p * n)(*[None if len(r) < 4 or r[3] is None else enc(r[3]) for r in reads])
-        lens = np.array([len(r[1]) for r in reads], np.int32)
-        self.add(res, n, qn, sq, ql, lens.ctypes.data_as(C.POINTER(C.c_int32)), comments=cm)
-
-    def add_bam(self, data):
-        self._open()
-        data = bytes(data)
-        self._check(self.lib.gdiet_hip_cov_add_bam(self._h, data, len(data)))
 
     def finish(self, chunk=0):
         """(contigs, summary): numpy records n_reads cov_bases sum_depth sum_mapq sum_baseq n_baseq, one per contig, and the dict of the
@@ -121,20 +92,3 @@ class Coverage:
                     for k, s in enumerate(sums):
                         beg, end = k * self.window, min(n, (k + 1) * self.window)
                         f.write("%s\t%d\t%d\t%.2f\n" % (name, beg, end, int(s) / (end - beg)))
-
-    def close(self):
-        if self._h:
-            h, self._h = self._h, C.c_void_p()
-            self.lib.gdiet_hip_cov_close(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -12,42 +12,6 @@
 #include "bam_encode.hip.h"
 #include "bam_flatten.h"
 
-// An attached coverage accumulator's side of a call that encodes records (cov_driver.hip.h defines these): hold it for the call, enqueue
-// the scatter of the records just encoded on their stream, ask for the verdict once that stream has been synchronised.
-struct gdiet_coverage;
-static int gd_cov_hold(gdiet_coverage *c, std::string &why); // locks it; -1, unlocked again, with why if it takes no more records
-static void gd_cov_release(gdiet_coverage *c);
-static int gd_cov_enqueue_part(gdiet_coverage *c, hipStream_t s, const uint8_t *d_recs, const GdbPart &P, std::vector<uint64_t> &starts, std::string &why);
-static int gd_cov_verdict(gdiet_coverage *c, std::string &why);
-struct GdCovHold {
-	gdiet_coverage *c = nullptr;
-	std::vector<uint64_t> starts; // GdbRec::out of the call's records: alive until the stream has been synchronised
-	int take(gdiet_coverage *cov, std::string &why)
-	{
-		if (cov && gd_cov_hold(cov, why)) return -1;
-		c = cov;
-		return 0;
-	}
-	~GdCovHold() { if (c) gd_cov_release(c); }
-};
-// an attached pileup accumulator's side, likewise (pile_driver.hip.h); where both are attached the coverage accumulator is taken first
-struct gdiet_pileup;
-static int gd_pile_hold(gdiet_pileup *p, std::string &why);
-static void gd_pile_release(gdiet_pileup *p);
-static int gd_pile_enqueue_part(gdiet_pileup *p, hipStream_t s, const uint8_t *d_recs, const GdbPart &P, std::vector<uint64_t> &starts, std::string &why);
-static int gd_pile_verdict(gdiet_pileup *p, std::string &why);
-struct GdPileHold {
-	gdiet_pileup *c = nullptr;
-	std::vector<uint64_t> starts;
-	int take(gdiet_pileup *pile, std::string &why)
-	{
-		if (pile && gd_pile_hold(pile, why)) return -1;
-		c = pile;
-		return 0;
-	}
-	~GdPileHold() { if (c) gd_pile_release(c); }
-};
-
 // the chunks' pools and the merged table of a batch: the context's (gdiet_ctx::bam_pool), so that they keep their pages from mini-batch to
 // mini-batch -- a mini-batch is some 130 MB of table and text, and a fresh allocation of that size is paid for page by page every time
 struct GdbPool { std::vector<GdbPart> parts; GdbPart all; };
@@ -159,6 +123,14 @@ static int gd_bam_encode_device(gdiet_ctx *ctx, const GdbPart &P, const unsigned
 	return 0;
 }
 
+static int gd_bam_args_ok(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs, const int32_t *lens, const int32_t *n_regs,
+                          gdiet_reg_t *const *regs)
+{
+	return ctx && ix && n_reads >= 0 && (n_reads == 0 || (qnames && seqs && lens && n_regs && regs));
+}
+
+#include "accum_driver.hip.h" // the accumulators over the records encoded above: their add routes use the encoder, gdiet_hip_bgzf_out_write_bam below feeds the attached ones
+
 // magic, the text gdiet_hip_sam_header returns (no NUL), the reference dictionary
 extern "C" size_t gdiet_hip_bam_header(gdiet_ctx *ctx, const gdiet_index *ix, const char *version, int argc, const char *const *argv, char **out)
 {
@@ -187,12 +159,6 @@ extern "C" size_t gdiet_hip_bam_header_so(gdiet_ctx *ctx, const gdiet_index *ix,
 	memcpy(buf, s.data(), s.size()), buf[s.size()] = 0;
 	*out = buf;
 	return s.size();
-}
-
-static int gd_bam_args_ok(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs, const int32_t *lens, const int32_t *n_regs,
-                          gdiet_reg_t *const *regs)
-{
-	return ctx && ix && n_reads >= 0 && (n_reads == 0 || (qnames && seqs && lens && n_regs && regs));
 }
 
 extern "C" int64_t gdiet_hip_bam_batch_into(gdiet_ctx *ctx, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs, const char *const *quals,
@@ -244,10 +210,8 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	std::lock_guard<std::mutex> lk(ctx->bam.mu);
 	GdbPart &P = gd_bam_pool(ctx).all;
 	std::string why;
-	GdCovHold cov; // (nothing without an attached accumulator)
-	if (cov.take(h->cov, why)) return gd_err_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_out_write_bam: " + why);
-	GdPileHold pile;
-	if (pile.take(h->pile, why)) return gd_err_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_out_write_bam: " + why);
+	GdAccumHold held; // (nothing without an attached accumulator)
+	if (held.take(h->acc, why)) return gd_err_fail(ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_out_write_bam: " + why);
 	int rc = gd_bam_flatten(ctx, ix, n_reads, qnames, seqs, quals, comments, lens, n_regs, regs, opt_flag, P, why);
 	if (rc) return why.empty() ? rc : gd_err_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why);
 	if (P.bytes == 0) return GDIET_OK;
@@ -256,8 +220,7 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	std::vector<unsigned char> next_tail;
 	int wrc = 0;
 	rc = gd_bam_encode_device(ctx, P, w.tail.data(), w.tail.size(), why, [&](uint8_t *d_stream, size_t bytes, hipStream_t s) {
-		if (cov.c && gd_cov_enqueue_part(cov.c, s, d_stream + w.tail.size(), P, cov.starts, why)) return -1; // from the records where they are, before they are compressed
-		if (pile.c && gd_pile_enqueue_part(pile.c, s, d_stream + w.tail.size(), P, pile.starts, why)) return -1;
+		if (gd_accum_enqueue_all(held, s, d_stream + w.tail.size(), P, why)) return -1; // from the records where they are, before they are compressed
 		const size_t whole = bytes / GD_BGZF_MEMBER_IN * GD_BGZF_MEMBER_IN;
 		next_tail.resize(bytes - whole);
 		if (!next_tail.empty()) {
@@ -270,11 +233,8 @@ extern "C" int gdiet_hip_bgzf_out_write_bam(gdiet_bgzf_out *h, gdiet_ctx *ctx, c
 	if (rc) { w.dev_error = true, (void)w.fail(why); return gd_bzo_done(h, -1); }
 	if (wrc) return gd_bzo_done(h, wrc);
 	w.tail.swap(next_tail);
-	std::string why_pile;
-	const int rc_pile = pile.c ? gd_pile_verdict(pile.c, why_pile) : 0; // (both are asked before either returns: a bad record poisons both)
-	if (cov.c && (rc = gd_cov_verdict(cov.c, why)) != 0) return gd_err_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why);
-	if (rc_pile) return gd_err_fail(ctx, rc_pile, "gdiet_hip_bgzf_out_write_bam: " + why_pile);
-	return GDIET_OK;
+	rc = gd_accum_verdict_all(held, why);
+	return rc ? gd_err_fail(ctx, rc, "gdiet_hip_bgzf_out_write_bam: " + why) : GDIET_OK;
 }
 
 // measurement only (tools/map_file.py; not declared in include/gdiet_hip.h): the device's side of encoding BAM records since the context

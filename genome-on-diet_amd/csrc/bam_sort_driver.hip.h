@@ -111,8 +111,7 @@ struct GdqDevice {
 	uint8_t *d_run = nullptr, *d_res = nullptr;
 	GdsRow *d_rows = nullptr;
 	size_t run_cap = 0, res_cap = 0, rows_cap = 0, front_len = 0;
-	gdiet_coverage *cov = nullptr; // gdiet_hip_bam_sort_set_coverage: every appended batch is scattered from the run buffer, on the encoder's lane
-	gdiet_pileup *pile = nullptr;  // gdiet_hip_bam_sort_set_pileup: likewise
+	GdAccumSet acc; // gdiet_hip_bam_sort_set_coverage / _set_pileup: every appended batch is scattered from the run buffer, on the encoder's lane
 
 	// p[0, cap) -> at least `need` bytes, the first `keep` bytes kept.  The caller holds bsort.mu and has made the stream.
 	template <class T> hipError_t grow(T **p, size_t *cap, size_t need, size_t keep)
@@ -145,10 +144,8 @@ struct GdqDevice {
 		std::lock_guard<std::mutex> lk(ctx->bam.mu);
 		GdLane &L = ctx->bam;
 		if (L.ready(ctx->device, 4, "device BAM encoder", why)) return -1;
-		GdCovHold held; // (nothing without an attached accumulator)
-		if (held.take(cov, why)) return -1;
-		GdPileHold held_pile;
-		if (held_pile.take(pile, why)) return -1;
+		GdAccumHold held; // (nothing without an attached accumulator)
+		if (held.take(acc, why)) return -1;
 		hipStream_t s = L.stream;
 		hipError_t e = hipSuccess;
 		GdStreamMem mem(s);
@@ -174,13 +171,9 @@ struct GdqDevice {
 			if ((e = hipGetLastError()) != hipSuccess) return fail(e, "encode launch");
 		}
 		(void)hipEventRecord(L.ev[2], s);
-		if (held.c && n && gd_cov_enqueue_part(held.c, s, d_run + at, P, held.starts, why)) { mem.fail(); return -1; } // before the run is sorted or moved
-		if (held_pile.c && n && gd_pile_enqueue_part(held_pile.c, s, d_run + at, P, held_pile.starts, why)) { mem.fail(); return -1; }
+		if (gd_accum_enqueue_all(held, s, d_run + at, P, why)) { mem.fail(); return -1; } // before the run is sorted or moved
 		if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "encode kernel");
-		std::string why_pile;
-		const int rc_pile = held_pile.c ? gd_pile_verdict(held_pile.c, why_pile) : 0; // (both are asked before either returns: a bad record poisons both)
-		if (held.c && gd_cov_verdict(held.c, why)) return -1;
-		if (rc_pile) { why = why_pile; return -1; }
+		if (gd_accum_verdict_all(held, why)) return -1;
 		for (int i = 0; i < 2; ++i) {
 			float ms = 0;
 			if (hipEventElapsedTime(&ms, L.ev[i], L.ev[i + 1]) == hipSuccess) L.ms[i] += ms;
@@ -369,20 +362,11 @@ extern "C" int gdiet_hip_bam_sort_add(gdiet_bam_sorter *h, const gdiet_index *ix
 
 extern "C" int gdiet_hip_bam_sort_set_coverage(gdiet_bam_sorter *h, gdiet_coverage *cov)
 {
-	if (!h) return GDIET_E_PARAM;
-	gd_err_clear();
-	if (cov && cov->ctx != h->ctx) return gd_err_fail(h->ctx, GDIET_E_PARAM, "gdiet_hip_bam_sort_set_coverage: the sorter and the accumulator need one context");
-	h->q.ex.cov = cov;
-	return GDIET_OK;
+	return h ? gd_accum_attach(h->ctx, h->q.ex.acc, GD_ACC_COV, cov, "gdiet_hip_bam_sort_set_coverage", "sorter") : GDIET_E_PARAM;
 }
-
 extern "C" int gdiet_hip_bam_sort_set_pileup(gdiet_bam_sorter *h, gdiet_pileup *pile)
 {
-	if (!h) return GDIET_E_PARAM;
-	gd_err_clear();
-	if (pile && pile->ctx != h->ctx) return gd_err_fail(h->ctx, GDIET_E_PARAM, "gdiet_hip_bam_sort_set_pileup: the sorter and the accumulator need one context");
-	h->q.ex.pile = pile;
-	return GDIET_OK;
+	return h ? gd_accum_attach(h->ctx, h->q.ex.acc, GD_ACC_PILE, pile, "gdiet_hip_bam_sort_set_pileup", "sorter") : GDIET_E_PARAM;
 }
 
 extern "C" int gdiet_hip_bam_sort_close(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *stats)

@@ -216,9 +216,12 @@ struct GdBzdExecutor : GdBgzfDeflater {
 		return gd_bz_deflate_resident(ctx, (const uint8_t *)d_in, in_len, out, out_cap, out_len, why);
 	}
 };
-struct gdiet_coverage; // cov_driver.hip.h
-struct gdiet_pileup;   // pile_driver.hip.h
-struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; gdiet_coverage *cov = nullptr; /* gdiet_hip_bgzf_out_set_coverage */ gdiet_pileup *pile = nullptr; /* _set_pileup */ };
+// The accumulators attached to a writer or a sorter (accum_driver.hip.h): fixed slots, and the slot order is the order in which a call
+// locks them.  An empty slot costs nothing.
+struct GdAccum;
+enum { GD_ACC_COV = 0, GD_ACC_PILE, GD_ACC_SLOTS };
+struct GdAccumSet { GdAccum *slot[GD_ACC_SLOTS] = {}; };
+struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; GdAccumSet acc; /* gdiet_hip_bgzf_out_set_coverage / _set_pileup */ };
 
 extern "C" int gdiet_hip_bgzf_out_open(gdiet_ctx *ctx, const char *path, int level, int threads, gdiet_bgzf_out **out)
 {

@@ -1,27 +1,17 @@
-// Driver of the coverage accumulator (cov.hip.h) and its entry points gdiet_hip_cov_*.  Included by gdiet_hip.hip behind bam_driver.hip.h
-// (needs gdiet_ctx, gdiet_index, GdLane, GdStreamMem, err_mark.h, the BAM flattening and the encoder's driver).
+// Driver of the coverage accumulator (cov.hip.h) and its entry points gdiet_hip_cov_*.  Included by gdiet_hip.hip behind bam_driver.hip.h,
+// which brings accum_driver.hip.h: the routes on which records arrive, the lock order and everything the accumulators share are there.
 //
-// The accumulator owns the difference array (plain hipMalloc: it lives as long as the handle, 4 bytes per reference base) and one small
-// table: the contigs' bases and lengths, the counters, the cell of the first bad record.  Records reach it on three routes, which end
-// in the same kernel on whatever stream holds the records:
-//   gdiet_hip_cov_add_bam   host records: a walk for the starts, upload, scatter; on the lane gdiet_ctx::cov
-//   gdiet_hip_cov_add       a mapped batch: flattened and encoded by the BAM encoder's driver, scattered from the resident records on the
-//                           encoder's lane; nothing comes down
-//   attached                gdiet_hip_bgzf_out_write_bam and the sorter's append call gd_cov_enqueue on the records they have just
-//                           encoded, on the encoder's lane, before the records are compressed or sorted; the starts are GdbRec::out
-// Every route synchronises its stream before it returns, so finish (on the lane cov) needs no event.  One producer at a time:
-// gdiet_coverage::mu is held from the enqueue to the verdict.  Lock order: bam.mu, then the accumulator's, then cov.mu of the context.
+// Coverage's own: the difference array (4 bytes per reference base) and one small table -- the contigs' bases and lengths, the counters,
+// the cell of the first bad record; the scan and the window reduction of finish; the readers.
 #pragma once
 #include <hipcub/hipcub.hpp>
 #include "cov.hip.h"
-#include "bam_flatten.h"
 
-enum { GDC_DEFAULT_WINDOW = 65536, GDC_MAX_BLOCKS = 8192 };
+enum { GDC_DEFAULT_WINDOW = 65536 };
 static const uint64_t GDC_DEFAULT_CHUNK = 1ull << 28, GDC_MAX_CHUNK = 1ull << 30;
 
-struct gdiet_coverage {
-	std::mutex mu;
-	gdiet_ctx *ctx = nullptr; // NULL once the context has been destroyed: the arrays went with it
+struct gdiet_coverage : GdAccum {
+	gdiet_coverage() : GdAccum("coverage") {}
 	uint32_t n_ref = 0, window = 0, win_eff = GDC_DEFAULT_WINDOW;
 	uint64_t total = 0, n_win = 0;
 	std::vector<uint32_t> clen;
@@ -29,125 +19,23 @@ struct gdiet_coverage {
 	int32_t *d_diff = nullptr;
 	uint64_t *d_tab = nullptr; // base | contig counters | summary | first bad | wbase | lengths
 	GdcDev D;
-	uint64_t h_first_bad = ~(uint64_t)0;
-	bool poisoned = false, finished = false;
 	std::vector<gdiet_cov_contig_t> contigs;
 	gdiet_cov_summary_t summary;
 	std::vector<uint32_t> win_cov;
 	std::vector<uint64_t> win_sum;
 	const uint64_t *d_wbase() const { return d_tab + (n_ref + 1) + (uint64_t)GDC_N_CONTIG * n_ref + GDC_N_SUMMARY + 1; }
+	void launch(hipStream_t s, const uint8_t *d_recs, uint64_t bytes, const uint64_t *d_start, uint64_t n, unsigned blocks) override
+	{
+		hipLaunchKernelGGL(cov_scatter_kernel, dim3(blocks), dim3(256), 0, s, d_recs, bytes, d_start, n, D);
+	}
+	void free_arrays() override
+	{
+		if (d_diff) (void)hipFree(d_diff);
+		if (d_tab) (void)hipFree(d_tab);
+		d_diff = nullptr, d_tab = nullptr;
+	}
 };
 static_assert(sizeof(gdiet_cov_contig_t) == 8 * GDC_N_CONTIG && sizeof(gdiet_cov_summary_t) == 8 * GDC_N_SUMMARY, "the counters are the structs of the header");
-
-static int gd_cov_fail(gdiet_coverage *h, int rc, const char *who, const std::string &what) { return gd_err_fail(h ? h->ctx : nullptr, rc, std::string(who) + ": " + what); }
-
-// 0, or -1 with why: the accumulator takes no more records
-static int gd_cov_usable(gdiet_coverage *h, std::string &why)
-{
-	if (!h->ctx || !h->d_diff) { why = "coverage: the context has been destroyed"; return -1; }
-	if (h->poisoned) { why = "coverage: used after a bad record"; return -1; }
-	if (h->finished) { why = "coverage: finished, the accumulator is read-only"; return -1; }
-	return 0;
-}
-
-// The starts of the host records recs[0, len) of an add_bam call (coverage's and the pileup's): nothing but block_size is looked at here,
-// the kernel validates the rest.  0, or -1 with why: nothing was seen
-static int gd_record_starts(const void *recs, size_t len, std::vector<uint64_t> &start, std::string &why)
-{
-	const uint8_t *b = (const uint8_t *)recs;
-	size_t pos = 0;
-	while (len - pos >= 4) {
-		const int32_t bs = (int32_t)gds_le32(b + pos);
-		if (bs < 32) {
-			why = "BAM record " + std::to_string(start.size()) + " at offset " + std::to_string(pos) + ": a block_size of " + std::to_string(bs) + ", below the 32 fixed bytes";
-			return -1;
-		}
-		if (len - pos - 4 < (size_t)bs) break;
-		start.push_back(pos);
-		pos += 4 + (size_t)bs;
-	}
-	if (pos != len) { why = "offset " + std::to_string(pos) + ": the range ends inside a record"; return -1; }
-	if (start.size() > 0x7fffffffull) { why = "2^31 records or more in one call"; return -1; }
-	return 0;
-}
-
-// The scatter of the n records at d_recs[0, bytes) whose starts are h_start[0, n), enqueued on s with the allocations of mem; the caller
-// holds h->mu, keeps h_start alive until it has synchronised s, and then asks gd_cov_verdict.  0, or -1 with why (the device failed).
-static int gd_cov_enqueue(gdiet_coverage *h, hipStream_t s, GdStreamMem &mem, const uint8_t *d_recs, uint64_t bytes, const uint64_t *h_start, uint64_t n, std::string &why)
-{
-	hipError_t e = hipSuccess;
-	auto fail = [&](hipError_t err, const char *what) {
-		why = std::string("coverage: ") + what + ": " + hipGetErrorString(err);
-		return -1;
-	};
-	h->h_first_bad = ~(uint64_t)0;
-	if (n == 0) return 0;
-	uint64_t *d_start;
-	if ((e = mem.alloc(&d_start, 8 * (size_t)n + 16)) != hipSuccess) return fail(e, "starts");
-	if ((e = hipMemcpyAsync(d_start, h_start, 8 * (size_t)n, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "starts copy");
-	if ((e = hipMemsetAsync(h->D.first_bad, 0xff, 8, s)) != hipSuccess) return fail(e, "cell");
-	const uint64_t blocks = std::min<uint64_t>((n + 3) / 4, GDC_MAX_BLOCKS);
-	hipLaunchKernelGGL(cov_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_recs, bytes, (const uint64_t *)d_start, n, h->D);
-	if ((e = hipGetLastError()) != hipSuccess) return fail(e, "scatter launch");
-	if ((e = hipMemcpyAsync(&h->h_first_bad, h->D.first_bad, 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "cell copy down");
-	return 0;
-}
-// after the stream has been synchronised: 0, or GDIET_E_PARAM with why naming the call's first bad record (the accumulator is poisoned)
-static int gd_cov_verdict(gdiet_coverage *h, std::string &why)
-{
-	if (h->h_first_bad == ~(uint64_t)0) return 0;
-	h->poisoned = true;
-	why = "coverage: record " + std::to_string(h->h_first_bad >> 8) + " of the call: " + gdc_reason_text((uint32_t)(h->h_first_bad & 0xff));
-	h->h_first_bad = ~(uint64_t)0;
-	return GDIET_E_PARAM;
-}
-
-// ---- the attached routes (declared in bam_driver.hip.h) -------------------------------------------------------------------------------
-static int gd_cov_hold(gdiet_coverage *h, std::string &why)
-{
-	h->mu.lock();
-	if (gd_cov_usable(h, why)) { h->mu.unlock(); return -1; }
-	return 0;
-}
-static void gd_cov_release(gdiet_coverage *h) { h->mu.unlock(); }
-// the records of P, encoded at d_recs[0, P.bytes): their starts are GdbRec::out, so nothing is walked
-static int gd_cov_enqueue_part(gdiet_coverage *h, hipStream_t s, const uint8_t *d_recs, const GdbPart &P, std::vector<uint64_t> &starts, std::string &why)
-{
-	starts.resize(P.rec.size());
-	for (size_t k = 0; k < P.rec.size(); ++k) starts[k] = P.rec[k].out;
-	GdStreamMem mem(s); // (the table is freed behind the kernel, in stream order)
-	return gd_cov_enqueue(h, s, mem, d_recs, P.bytes, starts.data(), starts.size(), why);
-}
-extern "C" int gdiet_hip_bgzf_out_set_coverage(gdiet_bgzf_out *w, gdiet_coverage *cov)
-{
-	if (!w) return GDIET_E_PARAM;
-	gd_err_clear();
-	if (cov && (!w->ctx || cov->ctx != w->ctx)) return gd_err_fail(w->ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_out_set_coverage: the writer and the accumulator need one context");
-	w->cov = cov;
-	return GDIET_OK;
-}
-
-static void gd_cov_free_arrays(gdiet_coverage *h) // the caller holds h->mu
-{
-	if (h->d_diff) (void)hipFree(h->d_diff);
-	if (h->d_tab) (void)hipFree(h->d_tab);
-	h->d_diff = nullptr, h->d_tab = nullptr;
-}
-// gdiet_hip_destroy: the arrays of the accumulators still open go with the context; their handles take nothing but close from then on
-static void gd_cov_orphan_all(gdiet_ctx *ctx)
-{
-	std::vector<void *> open;
-	{
-		std::lock_guard<std::mutex> lk(ctx->cov_reg_mu);
-		open.swap(ctx->cov_open);
-	}
-	for (void *p : open) {
-		gdiet_coverage *h = (gdiet_coverage *)p;
-		std::lock_guard<std::mutex> lk(h->mu);
-		gd_cov_free_arrays(h);
-		h->ctx = nullptr;
-	}
-}
 
 extern "C" int gdiet_hip_cov_open(gdiet_ctx *ctx, const gdiet_index *ix, uint32_t excl_flags, uint32_t min_mapq, uint32_t window, gdiet_coverage **out)
 {
@@ -166,8 +54,8 @@ extern "C" int gdiet_hip_cov_open(gdiet_ctx *ctx, const gdiet_index *ix, uint32_
 	}
 	h->total = h->base[n_ref], h->n_win = h->wbase[n_ref];
 	auto refuse = [&](int rc, const std::string &what) {
-		gd_cov_free_arrays(h);
-		const int code = gd_cov_fail(h, rc, who, what);
+		gd_accum_free(h);
+		const int code = gd_accum_fail(h, rc, who, what);
 		delete h;
 		return code;
 	};
@@ -202,73 +90,22 @@ extern "C" int gdiet_hip_cov_open(gdiet_ctx *ctx, const gdiet_index *ix, uint32_
 		(void)hipStreamSynchronize(s);
 		return refuse(GDIET_E_HIP, std::string("coverage: clearing the arrays: ") + hipGetErrorString(e));
 	}
-	{
-		std::lock_guard<std::mutex> rk(ctx->cov_reg_mu);
-		ctx->cov_open.push_back(h);
-	}
+	h->d_first_bad = D.first_bad;
+	gd_accum_register(ctx, h);
 	*out = h;
 	return GDIET_OK;
 }
 
-extern "C" int gdiet_hip_cov_add_bam(gdiet_coverage *h, const void *recs, size_t len)
-{
-	if (!h || (!recs && len)) return GDIET_E_PARAM;
-	gd_err_clear();
-	const char *who = "gdiet_hip_cov_add_bam";
-	std::lock_guard<std::mutex> hk(h->mu);
-	std::string why;
-	if (gd_cov_usable(h, why)) return gd_cov_fail(h, GDIET_E_PARAM, who, why);
-	std::vector<uint64_t> start;
-	if (gd_record_starts(recs, len, start, why)) return gd_cov_fail(h, GDIET_E_PARAM, who, why);
-	if (start.empty()) return GDIET_OK;
-	gdiet_ctx *ctx = h->ctx;
-	GdLane &L = ctx->cov;
-	std::lock_guard<std::mutex> lk(L.mu);
-	if (L.ready(ctx->device, 0, "coverage", why)) return gd_cov_fail(h, GDIET_E_HIP, who, why);
-	hipStream_t s = L.stream;
-	GdStreamMem mem(s);
-	uint8_t *d_in;
-	hipError_t e = hipSuccess;
-	auto hip_fail = [&](hipError_t err, const char *what) {
-		mem.fail();
-		return gd_cov_fail(h, GDIET_E_HIP, who, std::string("coverage: ") + what + ": " + hipGetErrorString(err));
-	};
-	if ((e = mem.alloc(&d_in, len + 16)) != hipSuccess) return hip_fail(e, "records");
-	if ((e = hipMemcpyAsync(d_in, recs, len, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e, "records copy");
-	if (gd_cov_enqueue(h, s, mem, d_in, len, start.data(), start.size(), why)) { mem.fail(); return gd_cov_fail(h, GDIET_E_HIP, who, why); }
-	if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "scatter kernel");
-	const int rc = gd_cov_verdict(h, why);
-	return rc ? gd_cov_fail(h, rc, who, why) : GDIET_OK;
-}
-
+extern "C" int gdiet_hip_cov_add_bam(gdiet_coverage *h, const void *recs, size_t len) { return gd_accum_add_bam(h, "gdiet_hip_cov_add_bam", recs, len); }
 extern "C" int gdiet_hip_cov_add(gdiet_coverage *h, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs, const char *const *quals,
                                  const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs, const char *const *comments, int64_t opt_flag)
 {
-	if (!h) return GDIET_E_PARAM;
-	gd_err_clear();
-	const char *who = "gdiet_hip_cov_add";
-	gdiet_ctx *ctx;
-	{
-		std::lock_guard<std::mutex> hk(h->mu);
-		ctx = h->ctx;
-	}
-	if (!ctx) return gd_cov_fail(h, GDIET_E_PARAM, who, "coverage: the context has been destroyed");
-	if (!gd_bam_args_ok(ctx, ix, n_reads, qnames, seqs, lens, n_regs, regs)) return GDIET_E_PARAM;
-	std::lock_guard<std::mutex> lk(ctx->bam.mu);
-	std::lock_guard<std::mutex> hk(h->mu);
-	std::string why;
-	if (gd_cov_usable(h, why)) return gd_cov_fail(h, GDIET_E_PARAM, who, why);
-	GdbPart &P = gd_bam_pool(ctx).all;
-	int rc = gd_bam_flatten(ctx, ix, n_reads, qnames, seqs, quals, comments, lens, n_regs, regs, opt_flag, P, why);
-	if (rc) return why.empty() ? rc : gd_cov_fail(h, rc, who, why);
-	if (P.bytes == 0) return GDIET_OK;
-	std::vector<uint64_t> starts;
-	rc = gd_bam_encode_device(ctx, P, nullptr, 0, why, [&](uint8_t *d_stream, size_t, hipStream_t s) { // (the stream is synchronised when this has returned)
-		return gd_cov_enqueue_part(h, s, d_stream, P, starts, why);
-	});
-	if (rc) return gd_cov_fail(h, GDIET_E_HIP, who, why);
-	rc = gd_cov_verdict(h, why);
-	return rc ? gd_cov_fail(h, rc, who, why) : GDIET_OK;
+	return gd_accum_add(h, "gdiet_hip_cov_add", ix, n_reads, qnames, seqs, quals, lens, n_regs, regs, comments, opt_flag);
+}
+extern "C" int gdiet_hip_cov_close(gdiet_coverage *h) { return gd_accum_close(h); }
+extern "C" int gdiet_hip_bgzf_out_set_coverage(gdiet_bgzf_out *w, gdiet_coverage *cov)
+{
+	return w ? gd_accum_attach(w->ctx, w->acc, GD_ACC_COV, cov, "gdiet_hip_bgzf_out_set_coverage", "writer") : GDIET_E_PARAM;
 }
 
 // the inclusive sum in chunks, the window reduction, the counters: once; the caller holds h->mu.  0 or a GDIET_E_* code with why
@@ -335,9 +172,9 @@ extern "C" int gdiet_hip_cov_finish_chunked(gdiet_coverage *h, uint64_t chunk, g
 	std::lock_guard<std::mutex> hk(h->mu);
 	std::string why;
 	if (!h->finished) {
-		if (gd_cov_usable(h, why)) return gd_cov_fail(h, GDIET_E_PARAM, who, why);
+		if (gd_accum_usable(h, why)) return gd_accum_fail(h, GDIET_E_PARAM, who, why);
 		const int rc = gd_cov_finish_device(h, chunk, why);
-		if (rc) { h->poisoned = true; return gd_cov_fail(h, rc, who, why); }
+		if (rc) { h->poisoned = true; return gd_accum_fail(h, rc, who, why); }
 	}
 	if (contigs_out) memcpy(contigs_out, h->contigs.data(), sizeof(gdiet_cov_contig_t) * h->n_ref);
 	if (summary_out) *summary_out = h->summary;
@@ -354,12 +191,12 @@ extern "C" int64_t gdiet_hip_cov_windows(gdiet_coverage *h, uint32_t rid, uint32
 	gd_err_clear();
 	const char *who = "gdiet_hip_cov_windows";
 	std::lock_guard<std::mutex> hk(h->mu);
-	if (!h->finished) return gd_cov_fail(h, GDIET_E_PARAM, who, "coverage: not finished");
-	if (!h->window) return gd_cov_fail(h, GDIET_E_PARAM, who, "coverage: opened without a window");
-	if (rid >= h->n_ref) return gd_cov_fail(h, GDIET_E_PARAM, who, "coverage: rid " + std::to_string(rid) + " of " + std::to_string(h->n_ref) + " contigs");
+	if (!h->finished) return gd_accum_fail(h, GDIET_E_PARAM, who, "coverage: not finished");
+	if (!h->window) return gd_accum_fail(h, GDIET_E_PARAM, who, "coverage: opened without a window");
+	if (rid >= h->n_ref) return gd_accum_fail(h, GDIET_E_PARAM, who, "coverage: rid " + std::to_string(rid) + " of " + std::to_string(h->n_ref) + " contigs");
 	const uint64_t w0 = h->wbase[rid], n = h->wbase[rid + 1] - w0;
 	if (!cov_bases_out && !sum_depth_out) return (int64_t)n; // the size first
-	if (cap < n) return gd_cov_fail(h, GDIET_E_PARAM, who, "coverage: " + std::to_string(n) + " windows, room for " + std::to_string(cap));
+	if (cap < n) return gd_accum_fail(h, GDIET_E_PARAM, who, "coverage: " + std::to_string(n) + " windows, room for " + std::to_string(cap));
 	if (cov_bases_out && n) memcpy(cov_bases_out, h->win_cov.data() + w0, 4 * (size_t)n);
 	if (sum_depth_out && n) memcpy(sum_depth_out, h->win_sum.data() + w0, 8 * (size_t)n);
 	return (int64_t)n;
@@ -371,34 +208,16 @@ extern "C" int gdiet_hip_cov_depth(gdiet_coverage *h, uint32_t rid, uint32_t beg
 	gd_err_clear();
 	const char *who = "gdiet_hip_cov_depth";
 	std::lock_guard<std::mutex> hk(h->mu);
-	if (!h->finished) return gd_cov_fail(h, GDIET_E_PARAM, who, "coverage: not finished");
-	if (!h->ctx || !h->d_diff) return gd_cov_fail(h, GDIET_E_PARAM, who, "coverage: the context has been destroyed");
-	if (rid >= h->n_ref || beg > end || end > h->clen[rid]) return gd_cov_fail(h, GDIET_E_PARAM, who, "coverage: the interval lies outside the contig");
+	if (!h->finished) return gd_accum_fail(h, GDIET_E_PARAM, who, "coverage: not finished");
+	if (!h->ctx || !h->d_diff) return gd_accum_fail(h, GDIET_E_PARAM, who, "coverage: the context has been destroyed");
+	if (rid >= h->n_ref || beg > end || end > h->clen[rid]) return gd_accum_fail(h, GDIET_E_PARAM, who, "coverage: the interval lies outside the contig");
 	if (beg == end) return GDIET_OK;
 	if (!out) return GDIET_E_PARAM;
 	GdLane &L = h->ctx->cov;
 	std::lock_guard<std::mutex> lk(L.mu);
 	std::string why;
-	if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_cov_fail(h, GDIET_E_HIP, who, why);
+	if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_accum_fail(h, GDIET_E_HIP, who, why);
 	hipError_t e = hipMemcpyAsync(out, h->d_diff + h->base[rid] + beg, 4 * (size_t)(end - beg), hipMemcpyDeviceToHost, L.stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(L.stream);
-	return e == hipSuccess ? GDIET_OK : gd_cov_fail(h, GDIET_E_HIP, who, std::string("coverage: depth copy down: ") + hipGetErrorString(e));
-}
-
-extern "C" int gdiet_hip_cov_close(gdiet_coverage *h)
-{
-	if (!h) return GDIET_E_PARAM;
-	gd_err_clear();
-	{
-		std::lock_guard<std::mutex> hk(h->mu);
-		if (h->ctx) {
-			(void)hipSetDevice(h->ctx->device);
-			std::lock_guard<std::mutex> rk(h->ctx->cov_reg_mu);
-			auto &v = h->ctx->cov_open;
-			v.erase(std::remove(v.begin(), v.end(), (void *)h), v.end());
-		}
-		gd_cov_free_arrays(h);
-	}
-	delete h;
-	return GDIET_OK;
+	return e == hipSuccess ? GDIET_OK : gd_accum_fail(h, GDIET_E_HIP, who, std::string("coverage: depth copy down: ") + hipGetErrorString(e));
 }

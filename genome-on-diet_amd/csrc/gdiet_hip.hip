@@ -100,6 +100,7 @@ struct GdStreamMem {
 };
 
 #define GD_MAX_INFLIGHT 8 // batches in flight per context (gdiet_hip_set_inflight)
+struct GdAccum; // accum_driver.hip.h
 struct gdiet_ctx {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -185,12 +186,12 @@ struct gdiet_ctx {
 	//        bam.mu, then bzd.mu when the deflate kernel reads the records where they are.  ev[0..3]: copy up | encode kernel | copy down
 	//   bsort BAM records put into coordinate order on the device (bam_sort_driver.hip.h): apart from bam, so that a caller that sorts a buffer
 	//        never holds the encoder's mutex.  ev[0..2]: key, sort and scan | gather
-	//   cov  coverage accumulated from host records, its scan and its window reduction (cov_driver.hip.h): apart from bam, so that a caller
-	//        that finishes one accumulator never holds the encoder's mutex.  No events
+	//   cov  the accumulators' own lane (accum_driver.hip.h): coverage or a pileup accumulated from host records, coverage's scan and window
+	//        reduction, the pileup's calls (cov_driver.hip.h, pile_driver.hip.h): apart from bam, so that a caller that finishes or reads one
+	//        accumulator never holds the encoder's mutex.  No events
 	GdLane ds, fx, bz, bzd, bam, bsort, cov;
 	template <class F> void each_lane(F f) { f(ds), f(fx), f(bz), f(bzd), f(bam), f(bsort), f(cov); }
-	std::vector<void *> cov_open;      // gdiet_coverage* opened on this context and not yet closed: their arrays go with it (under cov_reg_mu)
-	std::vector<void *> pile_open;     // gdiet_pileup* likewise (pile_driver.hip.h; under cov_reg_mu)
+	std::vector<GdAccum *> accum_open; // the coverage and pileup accumulators opened on this context and not yet closed: their arrays go with it (accum_driver.hip.h; under cov_reg_mu)
 	std::mutex cov_reg_mu;
 	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff; // (under ds.mu)
 	std::vector<uint8_t> ds_enc;       // host copy of the reads a difference-string call without a resident batch encodes
@@ -333,8 +334,7 @@ extern "C" int gdiet_hip_init(gdiet_ctx **out, int device)
 static void gd_pool_free(void *pool); // map_pipeline.hip.h
 template <class F> static void gd_parallel_for(gdiet_ctx *ctx, int n_threads, int n, F f); // map_pipeline.hip.h
 static void gd_join_open_tickets(gdiet_ctx *ctx);
-static void gd_cov_orphan_all(gdiet_ctx *ctx); // cov_driver.hip.h
-static void gd_pile_orphan_all(gdiet_ctx *ctx); // pile_driver.hip.h
+static void gd_accum_orphan_all(gdiet_ctx *ctx); // accum_driver.hip.h
 
 extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 {
@@ -347,8 +347,7 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 		if (ctx->async_lane[i]) gdiet_hip_destroy(ctx->async_lane[i]), ctx->async_lane[i] = nullptr;
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-	gd_cov_orphan_all(ctx); // the arrays of coverage accumulators that are still open
-	gd_pile_orphan_all(ctx); // and of pileup accumulators
+	gd_accum_orphan_all(ctx); // the arrays of the coverage and pileup accumulators that are still open
 	std::vector<hipEvent_t> events(ctx->ev, ctx->ev + 4);
 	events.insert(events.end(), {ctx->arena_ev, ctx->wait_ev, ctx->gather_ev});
 	std::vector<hipStream_t> streams{ctx->stream_dp, ctx->stream};
@@ -1275,7 +1274,7 @@ extern "C" int gdiet_hip_debug_bgzf_seconds(const gdiet_fastx *fx, double *out6)
 	return GDIET_OK;
 }
 
-#include "bam_driver.hip.h" // BAM: the record encoder's driver, gdiet_hip_bam_header / _bam_batch_into / _bgzf_out_write_bam
+#include "bam_driver.hip.h" // BAM: the record encoder's driver, gdiet_hip_bam_header / _bam_batch_into / _bgzf_out_write_bam; brings accum_driver.hip.h, what the two accumulators share
 #include "sam_driver.hip.h" // SAM text on the device: the line formatter's driver, gdiet_hip_sam_batch_device_into / _bgzf_out_write_sam
 #include "cov_driver.hip.h" // coverage and depth accumulated from the resident records: gdiet_hip_cov_*
 #include "pile_driver.hip.h" // base counts per position and variant sites from the resident records: gdiet_hip_pile_*

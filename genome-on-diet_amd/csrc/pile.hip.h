@@ -38,31 +38,9 @@ __global__ __launch_bounds__(256) void pile_scatter_kernel(const uint8_t *__rest
 	GdpWave W;
 	uint32_t acc = 0; // (a call holds fewer than 2^31 records) lane i < GDP_S_SKIPPED_BASEQ: counter i of the summary over this wavefront's records
 	for (uint64_t j = (uint64_t)blockIdx.x * 4 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); j < n_rec; j += stride) {
-		const uint64_t at = start[j];
 		GdcHead H;
-		const uint8_t *rec = buf + at;
-		uint32_t head = GDC_BAD_FIELDS;
-		if (at <= len && len - at >= GDS_FIXED) { // lane i loads word i of the fixed bytes; the fields are scalars from there on
-			const uint32_t mine = lane < GDS_FIXED / 4 ? gdc_ld32(rec + 4 * lane) : 0u;
-			uint32_t w[GDS_FIXED / 4];
-#pragma unroll
-			for (int i = 0; i < GDS_FIXED / 4; ++i) w[i] = (uint32_t)__builtin_amdgcn_readlane((int)mine, i);
-			head = gdc_uni(gdc_head_words(rec, len - at, w, &H));
-			H.ops_at = gdc_uni(H.ops_at), H.n_ops = gdc_uni(H.n_ops), H.has_qual = gdc_uni(H.has_qual);
-		} else H.n = 0, H.ops_at = H.qual_at = 0, H.refID = H.pos = -1, H.n_ops = H.mapq = H.flag = H.l_seq = H.has_qual = 0;
-		// PASS 1
-		uint64_t ref = 0, qry = 0;
-		uint32_t bad_op = 0;
-		if (!head)
-#pragma unroll 1
-			for (uint32_t k = lane; k < H.n_ops; k += 64) {
-				uint32_t L, rl, ql;
-				(void)gdc_op(rec, H, k, &L, &rl, &ql, &bad_op);
-				ref += rl, qry += ql;
-			}
-		ref = gdc_wave_sum64(ref), qry = gdc_wave_sum64(qry);
-		bad_op = __any((int)bad_op) ? 1u : 0u;
-		const uint32_t reason = gdc_decide(H, head, D.n_ref, D.clen, ref, qry, bad_op);
+		const uint8_t *rec;
+		const uint32_t reason = gdc_record_pass1(buf, len, start[j], lane, D.n_ref, D.clen, &H, &rec);
 		uint32_t counted;
 		const uint32_t bits = gdp_summary_bits(H, reason, D.excl_flags, D.min_mapq, &counted);
 		if (lane < GDP_S_SKIPPED_BASEQ) acc += bits >> lane & 1u;

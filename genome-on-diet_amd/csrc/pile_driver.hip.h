@@ -1,22 +1,16 @@
 // Driver of the pileup accumulator (pile.hip.h) and its entry points gdiet_hip_pile_*.  Included by gdiet_hip.hip behind
-// cov_driver.hip.h, whose shape it has.
+// cov_driver.hip.h; the routes on which records arrive, the lock order and everything the accumulators share are in accum_driver.hip.h.
 //
-// The accumulator owns the counters (plain hipMalloc: 32 bytes per position of the regions, for as long as the handle lives) and one
-// small table: the regions, the contigs' lengths, the summary, the cell of the first bad record.  Records reach it on coverage's three
-// routes (gdiet_hip_pile_add_bam on the lane gdiet_ctx::cov; gdiet_hip_pile_add and the attached writer / sorter on the encoder's lane),
-// which end in pile_scatter_kernel on whatever stream holds the records.  Every route synchronises its stream before it returns, so
-// finish and the calls (on the lane cov) need no event.  One producer at a time: gdiet_pileup::mu is held from the enqueue to the
-// verdict.  Lock order: bam.mu, then the coverage accumulator's, then the pileup accumulator's, then cov.mu of the context.
+// The pileup's own: the counters (32 bytes per position of the regions) and one small table -- the regions, the contigs' lengths, the
+// summary, the cell of the first bad record; finish; the readers and the calls after it, on the lane gdiet_ctx::cov.
 #pragma once
 #include <hipcub/hipcub.hpp>
 #include "pile.hip.h"
-#include "bam_flatten.h"
 
 static const uint64_t GDP_DEFAULT_CHUNK = 1ull << 24, GDP_MAX_CHUNK = 1ull << 30;
 
-struct gdiet_pileup {
-	std::mutex mu;
-	gdiet_ctx *ctx = nullptr; // NULL once the context has been destroyed: the arrays went with it
+struct gdiet_pileup : GdAccum {
+	gdiet_pileup() : GdAccum("pileup") {}
 	const gdiet_index *ix = nullptr;
 	uint32_t n_ref = 0;
 	uint64_t total = 0, chunk = GDP_DEFAULT_CHUNK;
@@ -25,97 +19,19 @@ struct gdiet_pileup {
 	uint32_t *d_cnt = nullptr;
 	uint64_t *d_tab = nullptr; // summary | first bad | regions | lengths
 	GdpDev D;
-	uint64_t h_first_bad = ~(uint64_t)0;
-	bool poisoned = false, finished = false;
 	gdiet_pile_summary_t summary;
+	void launch(hipStream_t s, const uint8_t *d_recs, uint64_t bytes, const uint64_t *d_start, uint64_t n, unsigned blocks) override
+	{
+		hipLaunchKernelGGL(pile_scatter_kernel, dim3(blocks), dim3(256), 0, s, d_recs, bytes, d_start, n, D);
+	}
+	void free_arrays() override
+	{
+		if (d_cnt) (void)hipFree(d_cnt);
+		if (d_tab) (void)hipFree(d_tab);
+		d_cnt = nullptr, d_tab = nullptr;
+	}
 };
 static_assert(sizeof(gdiet_pile_summary_t) == 8 * GDP_N_SUMMARY && sizeof(gdiet_pile_site_t) == 4 * (5 + GDP_N_CNT) && sizeof(GdpRegion) == 24, "the structs of the header");
-
-static int gd_pile_fail(gdiet_pileup *h, int rc, const char *who, const std::string &what) { return gd_err_fail(h ? h->ctx : nullptr, rc, std::string(who) + ": " + what); }
-
-// 0, or -1 with why: the accumulator takes no more records
-static int gd_pile_usable(gdiet_pileup *h, std::string &why)
-{
-	if (!h->ctx || !h->d_cnt) { why = "pileup: the context has been destroyed"; return -1; }
-	if (h->poisoned) { why = "pileup: used after a bad record"; return -1; }
-	if (h->finished) { why = "pileup: finished, the accumulator is read-only"; return -1; }
-	return 0;
-}
-
-// as gd_cov_enqueue: the caller holds h->mu, keeps h_start alive until it has synchronised s, and then asks gd_pile_verdict
-static int gd_pile_enqueue(gdiet_pileup *h, hipStream_t s, GdStreamMem &mem, const uint8_t *d_recs, uint64_t bytes, const uint64_t *h_start, uint64_t n, std::string &why)
-{
-	hipError_t e = hipSuccess;
-	auto fail = [&](hipError_t err, const char *what) {
-		why = std::string("pileup: ") + what + ": " + hipGetErrorString(err);
-		return -1;
-	};
-	h->h_first_bad = ~(uint64_t)0;
-	if (n == 0) return 0;
-	uint64_t *d_start;
-	if ((e = mem.alloc(&d_start, 8 * (size_t)n + 16)) != hipSuccess) return fail(e, "starts");
-	if ((e = hipMemcpyAsync(d_start, h_start, 8 * (size_t)n, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "starts copy");
-	if ((e = hipMemsetAsync(h->D.first_bad, 0xff, 8, s)) != hipSuccess) return fail(e, "cell");
-	const uint64_t blocks = std::min<uint64_t>((n + 3) / 4, GDC_MAX_BLOCKS);
-	hipLaunchKernelGGL(pile_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_recs, bytes, (const uint64_t *)d_start, n, h->D);
-	if ((e = hipGetLastError()) != hipSuccess) return fail(e, "scatter launch");
-	if ((e = hipMemcpyAsync(&h->h_first_bad, h->D.first_bad, 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "cell copy down");
-	return 0;
-}
-static int gd_pile_verdict(gdiet_pileup *h, std::string &why)
-{
-	if (h->h_first_bad == ~(uint64_t)0) return 0;
-	h->poisoned = true;
-	why = "pileup: record " + std::to_string(h->h_first_bad >> 8) + " of the call: " + gdc_reason_text((uint32_t)(h->h_first_bad & 0xff));
-	h->h_first_bad = ~(uint64_t)0;
-	return GDIET_E_PARAM;
-}
-
-// ---- the attached routes (declared in bam_driver.hip.h) -------------------------------------------------------------------------------
-static int gd_pile_hold(gdiet_pileup *h, std::string &why)
-{
-	h->mu.lock();
-	if (gd_pile_usable(h, why)) { h->mu.unlock(); return -1; }
-	return 0;
-}
-static void gd_pile_release(gdiet_pileup *h) { h->mu.unlock(); }
-static int gd_pile_enqueue_part(gdiet_pileup *h, hipStream_t s, const uint8_t *d_recs, const GdbPart &P, std::vector<uint64_t> &starts, std::string &why)
-{
-	starts.resize(P.rec.size());
-	for (size_t k = 0; k < P.rec.size(); ++k) starts[k] = P.rec[k].out;
-	GdStreamMem mem(s); // (the table is freed behind the kernel, in stream order)
-	return gd_pile_enqueue(h, s, mem, d_recs, P.bytes, starts.data(), starts.size(), why);
-}
-extern "C" int gdiet_hip_bgzf_out_set_pileup(gdiet_bgzf_out *w, gdiet_pileup *pile)
-{
-	if (!w) return GDIET_E_PARAM;
-	gd_err_clear();
-	if (pile && (!w->ctx || pile->ctx != w->ctx)) return gd_err_fail(w->ctx, GDIET_E_PARAM, "gdiet_hip_bgzf_out_set_pileup: the writer and the accumulator need one context");
-	w->pile = pile;
-	return GDIET_OK;
-}
-
-static void gd_pile_free_arrays(gdiet_pileup *h) // the caller holds h->mu
-{
-	if (h->d_cnt) (void)hipFree(h->d_cnt);
-	if (h->d_tab) (void)hipFree(h->d_tab);
-	h->d_cnt = nullptr, h->d_tab = nullptr;
-}
-// gdiet_hip_destroy: the arrays of the accumulators still open go with the context; their handles take nothing but close from then on
-static void gd_pile_orphan_all(gdiet_ctx *ctx)
-{
-	std::vector<void *> open;
-	{
-		std::lock_guard<std::mutex> lk(ctx->cov_reg_mu);
-		open.swap(ctx->pile_open);
-	}
-	for (void *p : open) {
-		gdiet_pileup *h = (gdiet_pileup *)p;
-		std::lock_guard<std::mutex> lk(h->mu);
-		gd_pile_free_arrays(h);
-		h->ctx = nullptr;
-	}
-}
 
 extern "C" int gdiet_hip_pile_open(gdiet_ctx *ctx, const gdiet_index *ix, const gdiet_pile_region_t *regions, size_t n_regions, uint32_t excl_flags, uint32_t min_mapq,
                                    uint32_t min_baseq, gdiet_pileup **out)
@@ -131,8 +47,8 @@ extern "C" int gdiet_hip_pile_open(gdiet_ctx *ctx, const gdiet_index *ix, const 
 	h->clen.resize(n_ref);
 	for (size_t i = 0; i < n_ref; ++i) h->clen[i] = ix->h.seq[i].len;
 	auto refuse = [&](int rc, const std::string &what) {
-		gd_pile_free_arrays(h);
-		const int code = gd_pile_fail(h, rc, who, what);
+		gd_accum_free(h);
+		const int code = gd_accum_fail(h, rc, who, what);
 		delete h;
 		return code;
 	};
@@ -185,73 +101,22 @@ extern "C" int gdiet_hip_pile_open(gdiet_ctx *ctx, const gdiet_index *ix, const 
 		(void)hipStreamSynchronize(s);
 		return refuse(GDIET_E_HIP, std::string("pileup: clearing the arrays: ") + hipGetErrorString(e));
 	}
-	{
-		std::lock_guard<std::mutex> rk(ctx->cov_reg_mu);
-		ctx->pile_open.push_back(h);
-	}
+	h->d_first_bad = D.first_bad;
+	gd_accum_register(ctx, h);
 	*out = h;
 	return GDIET_OK;
 }
 
-extern "C" int gdiet_hip_pile_add_bam(gdiet_pileup *h, const void *recs, size_t len)
-{
-	if (!h || (!recs && len)) return GDIET_E_PARAM;
-	gd_err_clear();
-	const char *who = "gdiet_hip_pile_add_bam";
-	std::lock_guard<std::mutex> hk(h->mu);
-	std::string why;
-	if (gd_pile_usable(h, why)) return gd_pile_fail(h, GDIET_E_PARAM, who, why);
-	std::vector<uint64_t> start;
-	if (gd_record_starts(recs, len, start, why)) return gd_pile_fail(h, GDIET_E_PARAM, who, why); // (cov_driver.hip.h)
-	if (start.empty()) return GDIET_OK;
-	gdiet_ctx *ctx = h->ctx;
-	GdLane &L = ctx->cov;
-	std::lock_guard<std::mutex> lk(L.mu);
-	if (L.ready(ctx->device, 0, "coverage", why)) return gd_pile_fail(h, GDIET_E_HIP, who, why);
-	hipStream_t s = L.stream;
-	GdStreamMem mem(s);
-	uint8_t *d_in;
-	hipError_t e = hipSuccess;
-	auto hip_fail = [&](hipError_t err, const char *what) {
-		mem.fail();
-		return gd_pile_fail(h, GDIET_E_HIP, who, std::string("pileup: ") + what + ": " + hipGetErrorString(err));
-	};
-	if ((e = mem.alloc(&d_in, len + 16)) != hipSuccess) return hip_fail(e, "records");
-	if ((e = hipMemcpyAsync(d_in, recs, len, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e, "records copy");
-	if (gd_pile_enqueue(h, s, mem, d_in, len, start.data(), start.size(), why)) { mem.fail(); return gd_pile_fail(h, GDIET_E_HIP, who, why); }
-	if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "scatter kernel");
-	const int rc = gd_pile_verdict(h, why);
-	return rc ? gd_pile_fail(h, rc, who, why) : GDIET_OK;
-}
-
+extern "C" int gdiet_hip_pile_add_bam(gdiet_pileup *h, const void *recs, size_t len) { return gd_accum_add_bam(h, "gdiet_hip_pile_add_bam", recs, len); }
 extern "C" int gdiet_hip_pile_add(gdiet_pileup *h, const gdiet_index *ix, int n_reads, const char *const *qnames, const char *const *seqs, const char *const *quals,
                                   const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs, const char *const *comments, int64_t opt_flag)
 {
-	if (!h) return GDIET_E_PARAM;
-	gd_err_clear();
-	const char *who = "gdiet_hip_pile_add";
-	gdiet_ctx *ctx;
-	{
-		std::lock_guard<std::mutex> hk(h->mu);
-		ctx = h->ctx;
-	}
-	if (!ctx) return gd_pile_fail(h, GDIET_E_PARAM, who, "pileup: the context has been destroyed");
-	if (!gd_bam_args_ok(ctx, ix, n_reads, qnames, seqs, lens, n_regs, regs)) return GDIET_E_PARAM;
-	std::lock_guard<std::mutex> lk(ctx->bam.mu);
-	std::lock_guard<std::mutex> hk(h->mu);
-	std::string why;
-	if (gd_pile_usable(h, why)) return gd_pile_fail(h, GDIET_E_PARAM, who, why);
-	GdbPart &P = gd_bam_pool(ctx).all;
-	int rc = gd_bam_flatten(ctx, ix, n_reads, qnames, seqs, quals, comments, lens, n_regs, regs, opt_flag, P, why);
-	if (rc) return why.empty() ? rc : gd_pile_fail(h, rc, who, why);
-	if (P.bytes == 0) return GDIET_OK;
-	std::vector<uint64_t> starts;
-	rc = gd_bam_encode_device(ctx, P, nullptr, 0, why, [&](uint8_t *d_stream, size_t, hipStream_t s) { // (the stream is synchronised when this has returned)
-		return gd_pile_enqueue_part(h, s, d_stream, P, starts, why);
-	});
-	if (rc) return gd_pile_fail(h, GDIET_E_HIP, who, why);
-	rc = gd_pile_verdict(h, why);
-	return rc ? gd_pile_fail(h, rc, who, why) : GDIET_OK;
+	return gd_accum_add(h, "gdiet_hip_pile_add", ix, n_reads, qnames, seqs, quals, lens, n_regs, regs, comments, opt_flag);
+}
+extern "C" int gdiet_hip_pile_close(gdiet_pileup *h) { return gd_accum_close(h); }
+extern "C" int gdiet_hip_bgzf_out_set_pileup(gdiet_bgzf_out *w, gdiet_pileup *pile)
+{
+	return w ? gd_accum_attach(w->ctx, w->acc, GD_ACC_PILE, pile, "gdiet_hip_bgzf_out_set_pileup", "writer") : GDIET_E_PARAM;
 }
 
 extern "C" int gdiet_hip_pile_finish_chunked(gdiet_pileup *h, uint64_t chunk, gdiet_pile_summary_t *summary_out)
@@ -262,13 +127,13 @@ extern "C" int gdiet_hip_pile_finish_chunked(gdiet_pileup *h, uint64_t chunk, gd
 	std::lock_guard<std::mutex> hk(h->mu);
 	std::string why;
 	if (!h->finished) {
-		if (gd_pile_usable(h, why)) return gd_pile_fail(h, GDIET_E_PARAM, who, why);
+		if (gd_accum_usable(h, why)) return gd_accum_fail(h, GDIET_E_PARAM, who, why);
 		GdLane &L = h->ctx->cov;
 		std::lock_guard<std::mutex> lk(L.mu);
-		if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_pile_fail(h, GDIET_E_HIP, who, why);
+		if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_accum_fail(h, GDIET_E_HIP, who, why);
 		hipError_t e = hipMemcpyAsync(&h->summary, h->D.summary, sizeof(h->summary), hipMemcpyDeviceToHost, L.stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(L.stream);
-		if (e != hipSuccess) { h->poisoned = true; return gd_pile_fail(h, GDIET_E_HIP, who, std::string("pileup: summary copy down: ") + hipGetErrorString(e)); }
+		if (e != hipSuccess) { h->poisoned = true; return gd_accum_fail(h, GDIET_E_HIP, who, std::string("pileup: summary copy down: ") + hipGetErrorString(e)); }
 		h->chunk = std::min<uint64_t>(chunk ? chunk : GDP_DEFAULT_CHUNK, GDP_MAX_CHUNK);
 		h->finished = true;
 	}
@@ -292,19 +157,19 @@ extern "C" int gdiet_hip_pile_counts(gdiet_pileup *h, uint32_t rid, uint32_t beg
 	const char *who = "gdiet_hip_pile_counts";
 	std::lock_guard<std::mutex> hk(h->mu);
 	std::string why;
-	if (gd_pile_readable(h, why)) return gd_pile_fail(h, GDIET_E_PARAM, who, why);
+	if (gd_pile_readable(h, why)) return gd_accum_fail(h, GDIET_E_PARAM, who, why);
 	const GdpRegion *R = nullptr;
 	for (const GdpRegion &g : h->regs)
 		if (g.rid == rid && g.beg <= beg && beg <= end && end <= g.end) { R = &g; break; }
-	if (!R) return gd_pile_fail(h, GDIET_E_PARAM, who, "pileup: the interval does not lie inside one region");
+	if (!R) return gd_accum_fail(h, GDIET_E_PARAM, who, "pileup: the interval does not lie inside one region");
 	if (beg == end) return GDIET_OK;
 	if (!out) return GDIET_E_PARAM;
 	GdLane &L = h->ctx->cov;
 	std::lock_guard<std::mutex> lk(L.mu);
-	if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_pile_fail(h, GDIET_E_HIP, who, why);
+	if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_accum_fail(h, GDIET_E_HIP, who, why);
 	hipError_t e = hipMemcpyAsync(out, h->d_cnt + (R->off + (beg - R->beg)) * GDP_N_CNT, 4 * (size_t)GDP_N_CNT * (end - beg), hipMemcpyDeviceToHost, L.stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(L.stream);
-	return e == hipSuccess ? GDIET_OK : gd_pile_fail(h, GDIET_E_HIP, who, std::string("pileup: counters copy down: ") + hipGetErrorString(e));
+	return e == hipSuccess ? GDIET_OK : gd_accum_fail(h, GDIET_E_HIP, who, std::string("pileup: counters copy down: ") + hipGetErrorString(e));
 }
 
 static GdpCallIn gd_pile_call_in(const gdiet_pileup *h, uint64_t t0, uint64_t m, const GdpCallOpt &opt)
@@ -321,20 +186,20 @@ extern "C" int gdiet_hip_pile_consensus(gdiet_pileup *h, size_t region, uint32_t
 	const char *who = "gdiet_hip_pile_consensus";
 	std::lock_guard<std::mutex> hk(h->mu);
 	std::string why;
-	if (gd_pile_readable(h, why)) return gd_pile_fail(h, GDIET_E_PARAM, who, why);
-	if (region >= h->regs.size()) return gd_pile_fail(h, GDIET_E_PARAM, who, "pileup: region " + std::to_string(region) + " of " + std::to_string(h->regs.size()));
+	if (gd_pile_readable(h, why)) return gd_accum_fail(h, GDIET_E_PARAM, who, why);
+	if (region >= h->regs.size()) return gd_accum_fail(h, GDIET_E_PARAM, who, "pileup: region " + std::to_string(region) + " of " + std::to_string(h->regs.size()));
 	if (!out) return GDIET_E_PARAM;
 	const GdpRegion &R = h->regs[region];
 	const uint64_t n = R.end - R.beg;
 	GdLane &L = h->ctx->cov;
 	std::lock_guard<std::mutex> lk(L.mu);
-	if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_pile_fail(h, GDIET_E_HIP, who, why);
+	if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_accum_fail(h, GDIET_E_HIP, who, why);
 	hipStream_t s = L.stream;
 	GdStreamMem mem(s);
 	hipError_t e = hipSuccess;
 	auto hip_fail = [&](hipError_t err, const char *what) {
 		mem.fail();
-		return gd_pile_fail(h, GDIET_E_HIP, who, std::string("pileup: ") + what + ": " + hipGetErrorString(err));
+		return gd_accum_fail(h, GDIET_E_HIP, who, std::string("pileup: ") + what + ": " + hipGetErrorString(err));
 	};
 	uint8_t *d_cons;
 	if ((e = mem.alloc(&d_cons, (size_t)n + 16)) != hipSuccess) return hip_fail(e, "consensus bytes");
@@ -353,17 +218,17 @@ extern "C" int64_t gdiet_hip_pile_sites(gdiet_pileup *h, uint32_t min_depth, uin
 	const char *who = "gdiet_hip_pile_sites";
 	std::lock_guard<std::mutex> hk(h->mu);
 	std::string why;
-	if (gd_pile_readable(h, why)) return gd_pile_fail(h, GDIET_E_PARAM, who, why);
-	if (den == 0) return gd_pile_fail(h, GDIET_E_PARAM, who, "pileup: a fraction with den == 0");
+	if (gd_pile_readable(h, why)) return gd_accum_fail(h, GDIET_E_PARAM, who, why);
+	if (den == 0) return gd_accum_fail(h, GDIET_E_PARAM, who, "pileup: a fraction with den == 0");
 	GdLane &L = h->ctx->cov;
 	std::lock_guard<std::mutex> lk(L.mu);
-	if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_pile_fail(h, GDIET_E_HIP, who, why);
+	if (L.ready(h->ctx->device, 0, "coverage", why)) return gd_accum_fail(h, GDIET_E_HIP, who, why);
 	hipStream_t s = L.stream;
 	GdStreamMem mem(s);
 	hipError_t e = hipSuccess;
 	auto hip_fail = [&](hipError_t err, const char *what) {
 		mem.fail();
-		return (int64_t)gd_pile_fail(h, GDIET_E_HIP, who, std::string("pileup: ") + what + ": " + hipGetErrorString(err));
+		return (int64_t)gd_accum_fail(h, GDIET_E_HIP, who, std::string("pileup: ") + what + ": " + hipGetErrorString(err));
 	};
 	// per chunk of positions: flags, their exclusive sum, the chunk's count comes down (the carry), the rows are written and come down
 	const uint64_t chunk = std::min<uint64_t>(h->chunk, h->total);
@@ -401,24 +266,6 @@ extern "C" int64_t gdiet_hip_pile_sites(gdiet_pileup *h, uint32_t min_depth, uin
 		}
 		n_sites += n_c;
 	}
-	if (out && n_sites > cap) return gd_pile_fail(h, GDIET_E_PARAM, who, "pileup: " + std::to_string(n_sites) + " sites, room for " + std::to_string(cap));
+	if (out && n_sites > cap) return gd_accum_fail(h, GDIET_E_PARAM, who, "pileup: " + std::to_string(n_sites) + " sites, room for " + std::to_string(cap));
 	return (int64_t)n_sites;
-}
-
-extern "C" int gdiet_hip_pile_close(gdiet_pileup *h)
-{
-	if (!h) return GDIET_E_PARAM;
-	gd_err_clear();
-	{
-		std::lock_guard<std::mutex> hk(h->mu);
-		if (h->ctx) {
-			(void)hipSetDevice(h->ctx->device);
-			std::lock_guard<std::mutex> rk(h->ctx->cov_reg_mu);
-			auto &v = h->ctx->pile_open;
-			v.erase(std::remove(v.begin(), v.end(), (void *)h), v.end());
-		}
-		gd_pile_free_arrays(h);
-	}
-	delete h;
-	return GDIET_OK;
 }

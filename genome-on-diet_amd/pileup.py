@@ -1,13 +1,14 @@
 """Base counts per position and variant sites accumulated on the device: ``Pileup`` over the library's accumulator (``gdiet_hip_pile_*``,
-csrc/pile_driver.hip.h).  The records of every batch are walked where they are resident (csrc/pile.hip.h: one wavefront per record adds
-every base, deletion and insertion anchor to the eight counters of its position); after ``finish`` the consensus and the sites are
-formed on the device in integers.  The rules are the section "Pileup" of include/gdiet_hip.h.  The counters cost 32 bytes per position of
-the regions while the object lives."""
+csrc/pile_driver.hip.h; what it shares with ``Coverage`` is in accum.py).  The records of every batch are walked where they are
+resident (csrc/pile.hip.h: one wavefront per record adds every base, deletion and insertion anchor to the eight counters of its
+position); after ``finish`` the consensus and the sites are formed on the device in integers.  The rules are the section "Pileup" of
+include/gdiet_hip.h.  The counters cost 32 bytes per position of the regions while the object lives."""
 import ctypes as C
 
 import numpy as np
 
-from .hip_abi import GdietError, load_library
+from .accum import Accumulator
+from .hip_abi import load_library
 from .map_api import Reg
 
 SUMMARY = ("records", "unmapped", "secondary", "supplementary", "primary_mapped", "reverse", "excluded_by_flag", "excluded_by_mapq", "counted", "bad", "no_seq", "skipped_baseq")
@@ -35,13 +36,14 @@ def _bind(lib):
     lib._pile_bound = True
 
 
-class Pileup:
+class Pileup(Accumulator):
     """``Pileup(mapper, regions=None, excl_flags=0x704, min_mapq=0, min_baseq=0)``; ``regions`` is a list of (rid, beg, end), 0-based and
     half-open, sorted and disjoint (None: every contig whole).  Records come in through ``add`` (a mapped batch: the arguments of
     ``Mapper.bam_batch_raw``; encoded and scattered on the device, nothing comes down), ``add_bam`` (bytes of uncompressed BAM records) or
     an attached ``BgzfWriter`` / ``BamSorter`` (``set_pileup``).  ``finish()`` returns the summary dict; then ``counts``, ``consensus``,
     ``sites`` and ``write`` read the result.  A bad record raises ``GdietError`` and leaves the object refusing everything but ``close``.
     Keep the mapper open while the object is used."""
+    _prefix, _name = "pile", "Pileup"
 
     def __init__(self, mapper, regions=None, excl_flags=0x704, min_mapq=0, min_baseq=0):
         self.lib = load_library()
@@ -55,27 +57,6 @@ class Pileup:
         self._summary = None
         self._check(self.lib.gdiet_hip_pile_open(mapper.ctx._h, mapper._idx, given.ctypes.data if len(given) else None, len(given), int(excl_flags), int(min_mapq), int(min_baseq),
                                                  C.byref(self._h)))
-
-    def _check(self, rc):
-        if rc < 0:
-            t = self.lib.gdiet_hip_strerror(self.mapper.ctx._h)
-            raise GdietError("gdiet_hip error %d: %s" % (rc, t.decode() if t else ""))
-        return rc
-
-    def _open(self):
-        if not self._h:
-            raise ValueError("a closed Pileup")
-
-    def add(self, res, n, names, seqs, quals, lens, comments=None):
-        self._open()
-        cpp = C.POINTER(C.c_char_p)
-        self._check(self.lib.gdiet_hip_pile_add(self._h, self.mapper._idx, n, C.cast(names, cpp), C.cast(seqs, cpp), C.cast(quals, cpp), lens, res.n_regs, res.regs,
-                                                C.cast(comments, cpp), self.mapper.opt.flag))
-
-    def add_bam(self, data):
-        self._open()
-        data = bytes(data)
-        self._check(self.lib.gdiet_hip_pile_add_bam(self._h, data, len(data)))
 
     def finish(self, chunk=0):
         """the dict of the twelve summary counters.  ``chunk`` is the chunk, in positions, of the scan ``sites`` runs (0: the default); no
@@ -131,20 +112,3 @@ class Pileup:
                     f.write(np.concatenate([s[:whole].reshape(-1, 60), np.full((whole // 60, 1), 10, np.uint8)], axis=1).tobytes())
                 if whole < len(s):
                     f.write(s[whole:].tobytes() + b"\n")
-
-    def close(self):
-        if self._h:
-            h, self._h = self._h, C.c_void_p()
-            self.lib.gdiet_hip_pile_close(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -10,15 +10,9 @@
 //         WIN <rid> <n> <cov_bases sum_depth> x n                                     per contig, if window > 0
 //         DEPTH <rid> <depth of every position>                                       per contig
 // Exit status 0; 2 usage / file errors; 3 the input ends inside a record; 7 the two lane orders differ or the array's last slot is not 0.
-#include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <fstream>
 #include <memory>
-#include <sstream>
-#include <string>
-#include <vector>
-#include "cov.h"
+#include "record_emul.h"
 
 struct Tables {
 	uint32_t n_ref = 0, excl = 0, min_mapq = 0, window = 0, win_eff = 65536;
@@ -42,24 +36,12 @@ struct PlainAdd {
 static void record(const uint8_t *buf, uint64_t len, uint64_t at, uint64_t j, const Tables &T, Result &R, bool down)
 {
 	GdcHead H;
-	const uint32_t head = gdc_head(buf, len, at, &H);
+	const uint32_t reason = record_pass1(buf, len, at, T.n_ref, T.clen.get(), down, &H);
 	const uint8_t *rec = buf + at;
-	uint64_t ref = 0, qry = 0;
-	uint32_t bad_op = 0;
-	if (!head)
-		for (uint32_t i = 0; i < 64; ++i) {
-			const uint32_t lane = down ? 63 - i : i;
-			for (uint32_t k = lane; k < H.n_ops; k += 64) {
-				uint32_t L, rl, ql;
-				(void)gdc_op(rec, H, k, &L, &rl, &ql, &bad_op);
-				ref += rl, qry += ql;
-			}
-		}
-	const uint32_t reason = gdc_decide(H, head, T.n_ref, T.clen.get(), ref, qry, bad_op);
 	uint32_t counted;
 	const uint32_t bits = gdc_summary_bits(H, reason, T.excl, T.min_mapq, &counted);
 	for (uint32_t l = 0; l < GDC_N_SUMMARY; ++l) R.summary[l] += bits >> l & 1u;
-	if (reason && (j << 8 | reason) < R.first_bad) R.first_bad = j << 8 | reason;
+	note_bad(&R.first_bad, j, reason);
 	if (!counted) return;
 	const uint64_t base = T.base[H.refID];
 	const uint32_t clen = T.clen[H.refID];
@@ -119,11 +101,8 @@ int main(int argc, char **argv)
 		fprintf(stderr, "usage: cov_emul <in.records> <excl_flags> <min_mapq> <window> <chunk> <n_ref> <len> ...\n");
 		return 2;
 	}
-	std::ifstream f(argv[1], std::ios::binary);
-	if (!f) { perror(argv[1]); return 2; }
-	std::stringstream ss;
-	ss << f.rdbuf();
-	const std::string data = ss.str();
+	std::string data;
+	if (!slurp(argv[1], data)) return 2;
 	Tables T;
 	T.excl = (uint32_t)strtoul(argv[2], nullptr, 0), T.min_mapq = (uint32_t)strtoul(argv[3], nullptr, 0), T.window = (uint32_t)strtoul(argv[4], nullptr, 0);
 	T.chunk = strtoull(argv[5], nullptr, 0), T.n_ref = (uint32_t)strtoul(argv[6], nullptr, 0);
@@ -133,22 +112,15 @@ int main(int argc, char **argv)
 		T.clen[r] = (uint32_t)strtoul(argv[7 + r], nullptr, 0);
 		T.base[r + 1] = T.base[r] + T.clen[r], T.wbase[r + 1] = T.wbase[r] + ((uint64_t)T.clen[r] + T.win_eff - 1) / T.win_eff;
 	}
-	std::vector<uint64_t> start; // the driver's walk: block_size alone
-	size_t pos = 0;
-	while (data.size() - pos >= 4) {
-		const int32_t bs = (int32_t)gds_le32((const uint8_t *)data.data() + pos);
-		if (bs < 32 || data.size() - pos - 4 < (size_t)bs) break;
-		start.push_back(pos), pos += 4 + (size_t)bs;
-	}
-	if (pos != data.size()) { fprintf(stderr, "offset %zu: the range ends inside a record\n", pos); return 3; }
+	std::vector<uint64_t> start;
+	if (record_starts(data, start)) return 3;
 	Result up, dn;
 	if (run(data, start, T, false, up) || run(data, start, T, true, dn)) return 7;
 	const uint64_t total = T.base[T.n_ref];
 	if (memcmp(up.diff.get(), dn.diff.get(), 4 * (total + 1)) || memcmp(up.contig.get(), dn.contig.get(), 8 * (size_t)GDC_N_CONTIG * T.n_ref) ||
 	    memcmp(up.summary.get(), dn.summary.get(), 8 * GDC_N_SUMMARY) || up.first_bad != dn.first_bad || up.win_cov != dn.win_cov || up.win_sum != dn.win_sum)
 		return 7;
-	if (up.first_bad != ~(uint64_t)0)
-		printf("BAD %llu %u %s\n", (unsigned long long)(up.first_bad >> 8), (unsigned)(up.first_bad & 0xff), gdc_reason_text((uint32_t)(up.first_bad & 0xff)));
+	print_bad(up.first_bad);
 	printf("SUMMARY");
 	for (int i = 0; i < GDC_N_SUMMARY; ++i) printf(" %llu", (unsigned long long)up.summary[i]);
 	printf("\n");

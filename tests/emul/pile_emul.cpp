@@ -13,14 +13,9 @@
 //         CONS <region> <consensus bytes>                                             per region
 //         SITE <rid pos ref alt depth> <eight counters>                               per site, in order
 // Exit status 0; 2 usage / file errors; 3 the input ends inside a record; 7 the two lane orders differ.
-#include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <fstream>
 #include <memory>
-#include <sstream>
-#include <string>
-#include <vector>
+#include "record_emul.h"
 #include "pile.h"
 
 struct Tables {
@@ -50,24 +45,12 @@ static void record(const uint8_t *buf, uint64_t len, uint64_t at, uint64_t j, co
 {
 	Host W;
 	GdcHead H;
-	const uint32_t head = gdc_head(buf, len, at, &H);
+	const uint32_t reason = record_pass1(buf, len, at, T.n_ref, T.clen.get(), down, &H);
 	const uint8_t *rec = buf + at;
-	uint64_t ref = 0, qry = 0;
-	uint32_t bad_op = 0;
-	if (!head)
-		for (uint32_t i = 0; i < 64; ++i) {
-			const uint32_t lane = down ? 63 - i : i;
-			for (uint32_t k = lane; k < H.n_ops; k += 64) {
-				uint32_t L, rl, ql;
-				(void)gdc_op(rec, H, k, &L, &rl, &ql, &bad_op);
-				ref += rl, qry += ql;
-			}
-		}
-	const uint32_t reason = gdc_decide(H, head, T.n_ref, T.clen.get(), ref, qry, bad_op);
 	uint32_t counted;
 	const uint32_t bits = gdp_summary_bits(H, reason, T.excl, T.min_mapq, &counted);
 	for (uint32_t l = 0; l < GDP_S_SKIPPED_BASEQ; ++l) R.summary[l] += bits >> l & 1u;
-	if (reason && (j << 8 | reason) < R.first_bad) R.first_bad = j << 8 | reason;
+	note_bad(&R.first_bad, j, reason);
 	if (!counted) return;
 	uint32_t carry_r = (uint32_t)H.pos, carry_q = 0;
 	for (uint32_t b0 = 0; b0 < H.n_ops; b0 += 64) {
@@ -136,14 +119,6 @@ int main(int argc, char **argv)
 		fprintf(stderr, "usage: pile_emul <in.records> <ref.codes> <excl_flags> <min_mapq> <min_baseq> <chunk> <min_depth> <min_alt> <num> <den> <n_ref> <len> ... <n_reg> <rid beg end> ...\n");
 		return 2;
 	}
-	auto slurp = [](const char *path, std::string &out) {
-		std::ifstream f(path, std::ios::binary);
-		if (!f) { perror(path); return false; }
-		std::stringstream ss;
-		ss << f.rdbuf();
-		out = ss.str();
-		return true;
-	};
 	std::string data, codes;
 	if (!slurp(argv[1], data) || !slurp(argv[2], codes)) return 2;
 	Tables T;
@@ -169,21 +144,14 @@ int main(int argc, char **argv)
 		if (G.rid >= T.n_ref || G.beg >= G.end || G.end > T.clen[G.rid]) return 2;
 		T.total += G.end - G.beg;
 	}
-	std::vector<uint64_t> start; // the driver's walk: block_size alone
-	size_t pos = 0;
-	while (data.size() - pos >= 4) {
-		const int32_t bs = (int32_t)gds_le32((const uint8_t *)data.data() + pos);
-		if (bs < 32 || data.size() - pos - 4 < (size_t)bs) break;
-		start.push_back(pos), pos += 4 + (size_t)bs;
-	}
-	if (pos != data.size()) { fprintf(stderr, "offset %zu: the range ends inside a record\n", pos); return 3; }
+	std::vector<uint64_t> start;
+	if (record_starts(data, start)) return 3;
 	Result up, dn;
 	run(data, start, T, false, up), run(data, start, T, true, dn);
 	if (memcmp(up.cnt.get(), dn.cnt.get(), 4 * (size_t)GDP_N_CNT * T.total) || memcmp(up.summary.get(), dn.summary.get(), 8 * GDP_N_SUMMARY) || up.first_bad != dn.first_bad ||
 	    up.cons != dn.cons || up.rows != dn.rows)
 		return 7;
-	if (up.first_bad != ~(uint64_t)0)
-		printf("BAD %llu %u %s\n", (unsigned long long)(up.first_bad >> 8), (unsigned)(up.first_bad & 0xff), gdc_reason_text((uint32_t)(up.first_bad & 0xff)));
+	print_bad(up.first_bad);
 	printf("SUMMARY");
 	for (int i = 0; i < GDP_N_SUMMARY; ++i) printf(" %llu", (unsigned long long)up.summary[i]);
 	printf("\n");
