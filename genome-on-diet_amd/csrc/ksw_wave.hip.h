@@ -77,6 +77,10 @@ __device__ __forceinline__ u32 gdw_writelane_u(u32 value_uniform, int lane_unifo
 // rows at the corners of the matrix, paired steady rows in the middle -- with four packed registers per state array.  Backtrace rows
 // of 512 bytes from bt_rsrc's base.  Returns 8 x the score, wave-uniform.  tests/emul/narrow_step_emul.cpp mirrors it statement by statement
 // (narrow_emul.cpp: the paired rows before the two-lane selector update, gdw_sel_step_half).
+// The paired rows take their fresh query byte from the seam stream (GdwSeam, ksw_wave_core.h: a window of 8 query bytes in scalar
+// registers, the next one loaded a window ahead, no bounds test and no wait on a row) and skip the target-N term of the scores on the
+// scalar unit unless a lane's target bytes hold an N.  tests/emul/narrow_seam_emul.cpp mirrors them as they are now; the general rows
+// (dp_row) read the byte with gdw_seam_byte as before.
 __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *query_u /* wave-uniform copy */, const uint8_t *query, int qlen,
                                                const uint8_t *target, int tlen, int w, int lane, __amdgpu_buffer_rsrc_t bt_rsrc)
 {
@@ -137,6 +141,10 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 	// two rows differ in `up` (w a multiple of 16) -- and on the first pair, m_full; elsewhere two lanes are patched (gdw_sel_step_half)
 	const int step_mask = nblkA == nblkB ? 15 : 0;
 	int m_full = 0;
+	GdwSeam SQ = {0, 0}; // the paired rows' query bytes (set before the first pair)
+	u32 lut_lo_v = K.lut_lo; // (a copy in a vector register for the paired rows: v_perm_b32 takes one scalar operand, and the second was copied on every row)
+	GDW_KEEP_BRANCH(lut_lo_v);
+	u32 any_tn_u = 0; // any_tn as a number in a scalar register, for the paired rows' branch round the target-N term (set with the stream)
 	auto pair_row = [&](const int r, const int m, auto a_tag) __attribute__((always_inline)) {
 		constexpr bool ROW_A = decltype(a_tag)::value;
 		WaveRow W;
@@ -144,13 +152,16 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 		W.st_ = m >> 4, W.en_ = W.en0 >> 4;
 		W.up = m + ((ROW_A ? nblkA : nblkB) << 4);
 		const int advanced = ROW_A && (m & 15) == 0;
-		const int pst_ = (m - (ROW_A ? 1 : 0)) >> 4; // st_ of the row before, st_ - advanced (as a shift: the flag as a number goes through a vector register)
 		W.use_array = advanced, W.v1key = K.key_open, W.set_tr = 0, W.ukey = 0;
 		const u32 pX = gdw_ror1<64>(H.X[3]), pV = gdw_ror1<64>(H.V[3]), pX2 = gdw_ror1<64>(H.X2[3]), pQ = gdw_ror1<64>(H.Qc[1]);
-		gdw_shift_query_half_m(H, pQ, m_lowest, gdw_seam_byte(query_u, qlen, r - (pst_ << 4))); // (the lane mask of the row before: its st_ is this row's pst_)
+		// the row's fresh query byte query[r - 16 pst_] from the stream (ksw_wave_core.h, "the seam stream"); pst_ = (m - ROW_A) >> 4 is the
+		// st_ of the row before, st_ - advanced, and the lane mask is that row's too
+		if (!ROW_A && (m & 15) == 0) gdw_seam_init(SQ, query_u, qlen, r, m); // (the row before took a block over: the byte's index steps back by 15)
+		gdw_shift_query_half_m(H, pQ, m_lowest, gdw_seam_next(SQ, query_u, qlen, r, m - (ROW_A ? 1 : 0)));
 		if (advanced) {
 			if (H.blk < W.st_) gdw_load_half(H, K, H.blk + 32, H.half, r, query, qlen, target, tlen);
-			any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
+			const uint64_t bn = __builtin_amdgcn_ballot_w64(H.tn != 0);
+			any_tn = bn != 0, any_tn_u = (u32)bn | (u32)(bn >> 32);
 		}
 		if (ROW_A ? (m & step_mask) == 0 || m == m_full : nblkA != nblkB) {
 			gdw_make_sel_half(H, W.st0, W.up);
@@ -164,7 +175,7 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 				for (int g = 0; g < 2; ++g) H.SEL[g] = gdw_writelane_u(S.sel[k][g], S.lane[k], H.SEL[g]);
 		}
 		W.m_first_valid = 1, W.m_first_h = m_lowest;
-		gdw_update_scores_half(H, K, any_tn);
+		gdw_update_scores_half_n(H, K, any_tn_u, lut_lo_v);
 		if (H.blk <= W.en_) {
 			u32 out[2];
 			gdw_compute_half<true>(H, K, W, pX, pV, pX2, out);
@@ -186,6 +197,8 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 			int m = (rA - w + 1) >> 1;
 			m_full = m;
 			m_lowest = (H.blk == prev_st_ && H.half == 0) ? ~0u : 0u;
+			gdw_seam_init(SQ, query_u, qlen, r, m - 1);
+			any_tn_u = any_tn ? 1u : 0u;
 			for (; r < rS; r += 2, ++m) {
 				pair_row(r, m, std::true_type());
 				pair_row(r + 1, m, std::false_type());
@@ -206,7 +219,8 @@ __device__ __forceinline__ int gdw_narrow_rows(const WaveK &K, const uint8_t *qu
 // array and one dword each of scores, target, query and selectors -- half the recurrence instructions of the half-block rows and less of
 // the per-row overhead.  Backtrace rows of 256 bytes from bt_rsrc's base.  Returns 8 x the score, wave-uniform.
 // tests/emul/quarter_step_emul.cpp mirrors it statement by statement (quarter_emul.cpp: the paired rows before the two-lane selector
-// update, gdw_sel_step_quarter).
+// update, gdw_sel_step_quarter).  Seam stream and target-N branch as in gdw_narrow_rows
+// (tests/emul/quarter_seam_emul.cpp).
 __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *query_u /* wave-uniform copy */, const uint8_t *query, int qlen,
                                                const uint8_t *target, int tlen, int w, int lane, __amdgpu_buffer_rsrc_t bt_rsrc)
 {
@@ -265,6 +279,10 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 	// two rows differ in `up` (w a multiple of 16) -- and on the first pair, m_full; elsewhere two lanes are patched (gdw_sel_step_quarter)
 	const int step_mask = nblkA == nblkB ? 15 : 0;
 	int m_full = 0;
+	GdwSeam SQ = {0, 0}; // the paired rows' query bytes (set before the first pair)
+	u32 lut_lo_v = K.lut_lo; // (a copy in a vector register for the paired rows: v_perm_b32 takes one scalar operand, and the second was copied on every row)
+	GDW_KEEP_BRANCH(lut_lo_v);
+	u32 any_tn_u = 0; // any_tn as a number in a scalar register, for the paired rows' branch round the target-N term (set with the stream)
 	auto pair_row = [&](const int r, const int m, auto a_tag) __attribute__((always_inline)) {
 		constexpr bool ROW_A = decltype(a_tag)::value;
 		WaveRow W;
@@ -272,13 +290,16 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 		W.st_ = m >> 4, W.en_ = W.en0 >> 4;
 		W.up = m + ((ROW_A ? nblkA : nblkB) << 4);
 		const int advanced = ROW_A && (m & 15) == 0;
-		const int pst_ = (m - (ROW_A ? 1 : 0)) >> 4; // st_ of the row before, st_ - advanced (as a shift: the flag as a number goes through a vector register)
 		W.use_array = advanced, W.v1key = K.key_open, W.set_tr = 0, W.ukey = 0;
 		const u32 pX = gdw_ror1<64>(H.X[1]), pV = gdw_ror1<64>(H.V[1]), pX2 = gdw_ror1<64>(H.X2[1]), pQ = gdw_ror1<64>(H.Qc);
-		gdw_shift_query_quarter_m(H, pQ, m_lowest, gdw_seam_byte(query_u, qlen, r - (pst_ << 4))); // (the lane mask of the row before: its st_ is this row's pst_)
+		// the row's fresh query byte query[r - 16 pst_] from the stream (ksw_wave_core.h, "the seam stream"); pst_ = (m - ROW_A) >> 4 is the
+		// st_ of the row before, st_ - advanced, and the lane mask is that row's too
+		if (!ROW_A && (m & 15) == 0) gdw_seam_init(SQ, query_u, qlen, r, m); // (the row before took a block over: the byte's index steps back by 15)
+		gdw_shift_query_quarter_m(H, pQ, m_lowest, gdw_seam_next(SQ, query_u, qlen, r, m - (ROW_A ? 1 : 0)));
 		if (advanced) {
 			if (H.blk < W.st_) gdw_load_quarter(H, K, H.blk + 16, H.quarter, r, query, qlen, target, tlen);
-			any_tn = __builtin_amdgcn_ballot_w64(H.tn != 0) != 0;
+			const uint64_t bn = __builtin_amdgcn_ballot_w64(H.tn != 0);
+			any_tn = bn != 0, any_tn_u = (u32)bn | (u32)(bn >> 32);
 		}
 		if (ROW_A ? (m & step_mask) == 0 || m == m_full : nblkA != nblkB) {
 			gdw_make_sel_quarter(H, W.st0, W.up);
@@ -289,7 +310,7 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 			H.SEL = gdw_writelane_u(S.sel[1][0], S.lane[1], H.SEL);
 		}
 		W.m_first_valid = 1, W.m_first_h = m_lowest;
-		gdw_update_scores_quarter(H, K, any_tn);
+		gdw_update_scores_quarter_n(H, K, any_tn_u, lut_lo_v);
 		if (H.blk <= W.en_) {
 			u32 out;
 			gdw_compute_quarter(H, K, W, pX, pV, pX2, out);
@@ -311,6 +332,8 @@ __device__ __forceinline__ int gdw_quarter_rows(const WaveK &K, const uint8_t *q
 			int m = (rA - w + 1) >> 1;
 			m_full = m;
 			m_lowest = (H.blk == prev_st_ && H.quarter == 0) ? ~0u : 0u;
+			gdw_seam_init(SQ, query_u, qlen, r, m - 1);
+			any_tn_u = any_tn ? 1u : 0u;
 			for (; r < rS; r += 2, ++m) {
 				pair_row(r, m, std::true_type());
 				pair_row(r + 1, m, std::false_type());

@@ -96,6 +96,15 @@ GDW_HD u32 gdw_bfi_u(u32 mask, u32 a, u32 b)
 #else
 GDW_HD u32 gdw_bfi_u(u32 mask, u32 a, u32 b) { return gdw_bfi(mask, a, b); }
 #endif
+// inside a wave-uniform `if`: the value passes through an empty asm statement, which the compiler neither removes nor executes
+// speculatively, so the `if` stays a branch (host: nothing)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GDW_KEEP_BRANCH(v) asm volatile("" : "+v"(v))
+#define GDW_RARE_S(s) asm volatile("" : "+s"(s)) // a wave-uniform value the compiler knows nothing about from here on
+#else
+#define GDW_KEEP_BRANCH(v) ((void)0)
+#define GDW_RARE_S(s) ((void)0)
+#endif
 GDW_HD u32 gdw_pack2(int v) { return ((u32)v & 0xffffu) | ((u32)v << 16); }
 GDW_HD int gdw_lo(u32 a) { return (int)(int16_t)(a & 0xffffu); }
 GDW_HD int gdw_hi(u32 a) { return (int)(int16_t)(a >> 16); }
@@ -160,6 +169,93 @@ struct WaveLane {
 
 // query byte facing cell t on anti-diagonal r; outside [0,qlen) the reference reads zeroed memory
 GDW_HD u32 gdw_qbyte(const uint8_t *query, int qlen, int j) { return (j >= 0 && j < qlen) ? query[j] : 0u; }
+
+// ---- the seam stream of the paired steady rows (gdw_quarter_rows, gdw_narrow_rows) ---------------------------------------------------
+// The fresh query byte of a row is query[j], j = r - 16 pst_ (0 outside [0, qlen): gdw_seam_byte, ksw_wave.hip.h).  Over the paired rows j
+// rises by one a row and steps back by 15 on the second row of a pair that took a block over: a sequential stream.  The stream keeps the
+// aligned 8 bytes that hold query[j] (win, bytes outside the query zero) and the 8 after them (nxt), so a row takes its byte with a shift
+// and no bounds test.  The row that enters a new window (byte 0 of it) moves nxt to win and loads the window after -- eight rows
+// before its first byte is used, so no row waits for a load it has just issued.  16 pst_ is a multiple of 8: the byte's place in its
+// window is (address of query + r) & 7 whatever pst_ is.  All of it is wave-uniform: scalar registers, and on the device one aligned dword
+// load per four query bytes through the constant address space.  As in gdw_seam_byte, every dword loaded holds at least one byte of the
+// query -- `query` may start at any byte alignment and its arena may end with its last dword.
+// (tests/emul/seam_stream_test.cpp holds every paired row against gdw_qbyte and every load against that rule.)
+#if defined(__HIP_DEVICE_COMPILE__)
+GDW_HD u32 gdw_seam_load(const uint8_t *p /* 4-aligned, wave-uniform */)
+{
+	typedef const __attribute__((address_space(4))) u32 *gdw_const_u32p;
+	return *(gdw_const_u32p)(uintptr_t)p;
+}
+GDW_HD uint64_t gdw_seam_load2(const uint8_t *p /* 8-aligned, wave-uniform */)
+{
+	typedef const __attribute__((address_space(4))) uint64_t *gdw_const_u64p;
+	return *(gdw_const_u64p)(uintptr_t)p;
+}
+// what is before stays before: a window is taken out of nxt before the loads that overwrite nxt are issued, so they can land in its registers
+#define GDW_SEAM_ORDER(w) asm volatile("" : "+s"(w) : : "memory")
+#else
+#ifndef GDW_SEAM_LOAD_HOOK
+#define GDW_SEAM_LOAD_HOOK(p) ((void)0) // (a host test may look at every address the stream loads from)
+#endif
+GDW_HD u32 gdw_seam_load(const uint8_t *p)
+{
+	GDW_SEAM_LOAD_HOOK(p);
+	return (u32)p[0] | (u32)p[1] << 8 | (u32)p[2] << 16 | (u32)p[3] << 24;
+}
+GDW_HD uint64_t gdw_seam_load2(const uint8_t *p) { return (uint64_t)gdw_seam_load(p + 4) << 32 | gdw_seam_load(p); }
+#define GDW_SEAM_ORDER(w) ((void)0)
+#endif
+struct GdwSeam {
+	uint64_t win; // the window of the row just served: byte k = query[jb + k], 0 at and beyond the query's end
+	uint64_t nxt; // the 8 bytes after it as they were loaded; a dword that holds no byte of the query was not loaded and keeps what it held.
+	              // Bytes beyond the query's end are cleared when the window moves to win, a window's worth of rows later: a refill only
+	              // issues loads and uses nothing of them
+};
+// the two dwords of query[jb .. jb + 7], 0 <= jb, query + jb 8-aligned, into nxt; a dword without a byte of the query is not read
+GDW_HD void gdw_seam_fetch(GdwSeam &S, const uint8_t *query, int qlen, int jb)
+{
+	if (jb + 4 < qlen) S.nxt = gdw_seam_load2(query + jb);
+	else if (jb < qlen) S.nxt = gdw_seam_load(query + jb);
+}
+// ... and which of a window's bytes are below the query's end
+GDW_HD uint64_t gdw_seam_inside(int qlen, int jb)
+{
+	int n = qlen - jb;
+	n = n < 0 ? 0 : n > 8 ? 8 : n;
+	return ~((~0ull << (4 * n)) << (4 * n)); // the low n bytes (in two steps: 8 n can be 64)
+}
+// The rows name their byte by (r, mb): j = r - 16 (mb >> 4), mb = m - 1 on the first row of a pair and m on the second (pst_ = mb >> 4).
+// Whatever a refill works out from them stays inside its branch (GDW_RARE_S: the compiler would otherwise carry the window's address and
+// index through every row as induction registers of their own); the steady row reads r only.
+GDW_HD int gdw_seam_pos(const uint8_t *query, int r) { return (int)(((u32)(uintptr_t)query + (u32)r) & 7u); } // (16 (mb >> 4) is a multiple of 8)
+// before the row (r, mb): the first paired row, and the second row of a pair that took a block over (the step back by 15).  The paired
+// rows have r - 16 (mb >> 4) >= 17 (st0 >= 16 and a band of at least one cell), so no window starts below the query's first byte.
+GDW_HD void gdw_seam_init(GdwSeam &S, const uint8_t *query, int qlen, int r, int mb)
+{
+	GDW_RARE_S(r);
+	GDW_RARE_S(mb);
+	const int pos = gdw_seam_pos(query, r);
+	const int jb = r - ((mb >> 4) << 4) - pos - (pos == 0 ? 8 : 0); // (a row at byte 0 of a window moves nxt to win first)
+	S.nxt = 0;
+	gdw_seam_fetch(S, query, qlen, jb);
+	S.win = S.nxt & gdw_seam_inside(qlen, jb);
+	gdw_seam_fetch(S, query, qlen, jb + 8);
+}
+// the byte of row (r, mb), gdw_seam_byte(query, qlen, j); j is one more than on the call before, or what gdw_seam_init was called for
+GDW_HD u32 gdw_seam_next(GdwSeam &S, const uint8_t *query, int qlen, int r, int mb)
+{
+	const int pos = gdw_seam_pos(query, r);
+	if (pos == 0) {
+		GDW_RARE_S(r);
+		GDW_RARE_S(mb);
+		const int j = r - ((mb >> 4) << 4);
+		uint64_t w = S.nxt & gdw_seam_inside(qlen, j);
+		GDW_SEAM_ORDER(w);
+		S.win = w;
+		gdw_seam_fetch(S, query, qlen, j + 8);
+	}
+	return (u32)(S.win >> (8 * pos)) & 0xffu;
+}
 
 // (re)load a lane for block m at anti-diagonal r: reference's initial fill (SR/ksw2_extd2_sse.c:107,111-116)
 GDW_HD void gdw_load_block(WaveLane &L, const WaveK &K, int m, int r, const uint8_t *query, int qlen,
@@ -595,8 +691,12 @@ GDW_HD GdwSelStep gdw_sel_step_half(int m, int w)
 	GdwSelStep S;
 	S.lane[0] = ((m - 1) >> 3) & 63, S.lane[1] = ((up - 1) >> 3) & 63;
 	S.word[0] = S.word[1] = c >> 2;
+	// gdw_sel_from_range_half(c + 1, 8, g) and (0, c + 1, g) without the masks and the multiplies: byte i of selector dword g is i + 4
+	// where cell 4 g + i is rewritten, so over the lane's two dwords the lower lane adds 4 to the bytes above c -- eight bytes of 4 shifted
+	// up by c + 1 bytes (in two steps: c + 1 can be 8) -- and the upper lane to the other bytes
+	const uint64_t t = (0x0404040404040404ull << (8 * c)) << 8;
 #pragma unroll
-	for (int g = 0; g < 2; ++g) S.sel[0][g] = gdw_sel_from_range_half(c + 1, 8, g), S.sel[1][g] = gdw_sel_from_range_half(0, c + 1, g);
+	for (int g = 0; g < 2; ++g) S.sel[0][g] = 0x03020100u + (u32)(t >> (32 * g)), S.sel[1][g] = 0x07060504u - (u32)(t >> (32 * g));
 	return S;
 }
 
@@ -632,6 +732,19 @@ GDW_HD void gdw_update_scores_half(WaveHalf &H, const WaveK &K, bool any_tn)
 		if (any_tn) x |= H.Tb[g] & ~(H.Qc[g] << 1) & 0x04040404u;
 		H.Sb[g] = gdw_perm(gdw_perm(K.lut_hi, K.lut_lo, x), H.Sb[g], H.SEL[g]);
 	}
+}
+
+// the same for the paired steady rows, the target-N term under a branch the device keeps (see gdw_update_scores_quarter_n)
+GDW_HD void gdw_update_scores_half_n(WaveHalf &H, const WaveK &K, u32 any_tn /* wave-uniform, a number: 0 = no lane's target bytes hold an N */, u32 lut_lo /* K.lut_lo, wherever the caller keeps it */)
+{
+	u32 x[2] = {H.Tb[0] ^ H.Qc[0], H.Tb[1] ^ H.Qc[1]};
+	if (any_tn != 0) {
+		u32 n0 = H.Tb[0] & ~(H.Qc[0] << 1) & 0x04040404u, n1 = H.Tb[1] & ~(H.Qc[1] << 1) & 0x04040404u;
+		GDW_KEEP_BRANCH(n0);
+		x[0] |= n0, x[1] |= n1;
+	}
+#pragma unroll
+	for (int g = 0; g < 2; ++g) H.Sb[g] = gdw_perm(gdw_perm(K.lut_hi, lut_lo, x[g]), H.Sb[g], H.SEL[g]);
 }
 
 GDW_HD void gdw_reset_tr_half(WaveHalf &H, const WaveK &K, const WaveRow &W)
@@ -931,7 +1044,11 @@ GDW_HD GdwSelStep gdw_sel_step_quarter(int m, int w)
 	GdwSelStep S;
 	S.lane[0] = ((m - 1) >> 2) & 63, S.lane[1] = ((up - 1) >> 2) & 63;
 	S.word[0] = S.word[1] = 0;
-	S.sel[0][0] = gdw_sel_from_range_quarter(c + 1, 4), S.sel[1][0] = gdw_sel_from_range_quarter(0, c + 1);
+	// gdw_sel_from_range_quarter(c + 1, 4) and (0, c + 1) without the mask, the multiply and a branch for c == 3: byte i of a selector is
+	// i + 4 where cell i is rewritten, so the lower lane adds 4 to the bytes above c -- 0x04040404 shifted up by c + 1 bytes, what leaves
+	// the dword dropped -- and the upper lane to the other bytes
+	const u32 t = (u32)(0x0404040400ull << (8 * c));
+	S.sel[0][0] = 0x03020100u + t, S.sel[1][0] = 0x07060504u - t;
 	S.sel[0][1] = S.sel[1][1] = 0;
 	return S;
 }
@@ -953,6 +1070,19 @@ GDW_HD void gdw_update_scores_quarter(WaveQuarter &H, const WaveK &K, bool any_t
 	u32 x = H.Tb ^ H.Qc;
 	if (any_tn) x |= H.Tb & ~(H.Qc << 1) & 0x04040404u;
 	H.Sb = gdw_perm(gdw_perm(K.lut_hi, K.lut_lo, x), H.Sb, H.SEL);
+}
+
+// the same for the paired steady rows: the target-N term under a branch the device keeps (an empty asm statement in it: the compiler may not
+// turn the branch into a select and compute the term on every row; targets without N -- nearly all -- then skip it on the scalar unit)
+GDW_HD void gdw_update_scores_quarter_n(WaveQuarter &H, const WaveK &K, u32 any_tn /* wave-uniform, a number: 0 = no lane's target bytes hold an N */, u32 lut_lo /* K.lut_lo, wherever the caller keeps it */)
+{
+	u32 x = H.Tb ^ H.Qc;
+	if (any_tn != 0) {
+		u32 n = H.tn & ~(H.Qc << 1); // (H.tn = H.Tb & 0x04040404)
+		GDW_KEEP_BRANCH(n);
+		x |= n;
+	}
+	H.Sb = gdw_perm(gdw_perm(K.lut_hi, lut_lo, x), H.Sb, H.SEL);
 }
 
 GDW_HD void gdw_reset_tr_quarter(WaveQuarter &H, const WaveK &K, const WaveRow &W)
