@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from .hip_abi import GdietError, load_library
+from .hip_abi import DupStats, GdietError, load_library
 from .map_api import Reg
 
 
@@ -17,13 +17,15 @@ class SortStats(C.Structure):
 
 class BamSorter:
     """``BamSorter(path, mapper, bgzf="device", level=-1, threads=4, run_bytes=1 << 29, chunk_bytes=1 << 28, tmp_dir=None, index=True,
-    version=None, argv=())``: writes the header ``mapper.bam_header(version, argv, sort_order="coordinate")`` at once.  ``add`` takes a
+    version=None, argv=(), markdup=False)``: writes the header ``mapper.bam_header(version, argv, sort_order="coordinate")`` at once.  ``add`` takes a
     mapped batch (the arguments of ``Mapper.bam_batch_raw``); ``close`` returns the stats: records, runs, spooled_bytes, chunks, members,
     n_no_coor and the sorter's seconds (device: key_sort, gather; wall: spool_write, spool_read, compress).  ``bgzf="host"``: zlib at
     ``level`` on ``threads`` host threads compresses.  The spools live in ``tmp_dir`` (default: the output's directory) without a
-    name: nothing is left behind."""
+    name: nothing is left behind.  ``markdup=True``: bit 0x400 of the file's records is decided on the device under the rule "Duplicate
+    marking" of include/gdiet_hip.h (one decision over the whole file, before its first chunk is streamed), and ``close`` returns one
+    more entry, ``"dup"``: examined, eligible, duplicates, max_group."""
 
-    def __init__(self, path, mapper, bgzf="device", level=-1, threads=4, run_bytes=1 << 29, chunk_bytes=1 << 28, tmp_dir=None, index=True, version=None, argv=()):
+    def __init__(self, path, mapper, bgzf="device", level=-1, threads=4, run_bytes=1 << 29, chunk_bytes=1 << 28, tmp_dir=None, index=True, version=None, argv=(), markdup=False):
         if bgzf not in ("device", "host"):
             raise ValueError("bgzf is 'device' or 'host'")
         self.lib = load_library()
@@ -31,6 +33,9 @@ class BamSorter:
         self.lib.gdiet_hip_bam_sort_open.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int, C.POINTER(vp)]
         self.lib.gdiet_hip_bam_sort_add.argtypes = [vp, vp, C.c_int, cpp, cpp, cpp, cpp, i32p, i32p, C.POINTER(C.POINTER(Reg)), C.c_int64]
         self.lib.gdiet_hip_bam_sort_close.argtypes = [vp, C.POINTER(SortStats)]
+        self.lib.gdiet_hip_bam_sort_close_dup.argtypes = [vp, C.POINTER(SortStats), C.POINTER(DupStats)]
+        self.lib.gdiet_hip_bam_sort_set_markdup.argtypes = [vp, C.c_int]
+        self.markdup = False
         self.mapper, self.path = mapper, str(path)
         self._h = C.c_void_p()
         self.stats = None
@@ -43,6 +48,17 @@ class BamSorter:
             if h:
                 self.lib.gdiet_hip_bam_sort_close(h, None)
             raise GdietError("gdiet_hip error %d: %s" % (rc, text))
+        if markdup:
+            self.set_markdup(True)
+
+    def set_markdup(self, on):
+        """gdiet_hip_bam_sort_set_markdup: chosen before the first ``add``; afterwards it is refused (GdietError)"""
+        if not self._h:
+            raise ValueError("set_markdup on a closed BamSorter")
+        rc = self.lib.gdiet_hip_bam_sort_set_markdup(self._h, int(bool(on)))
+        if rc:
+            raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
+        self.markdup = bool(on)
 
     def _text(self):
         t = self.lib.gdiet_hip_strerror(self.mapper.ctx._h)
@@ -69,11 +85,15 @@ class BamSorter:
 
     def set_coverage(self, cov):
         """Attach a ``Coverage`` (None: detach): every later ``add`` scatters into it from the records it has just encoded into the run
-        buffer, before they are sorted; the file's bytes do not change.  Keep ``cov`` open while attached."""
+        buffer, before they are sorted; the file's bytes do not change.  Keep ``cov`` open while attached.  With ``markdup`` the scatter
+        still happens at ``add``, before any duplicate flag exists, so duplicates are counted: to leave them out, feed the finished
+        file's records to a ``Coverage`` through ``add_bam``."""
         self._attach("coverage", cov)
 
     def set_pileup(self, pile):
-        """Attach a ``Pileup`` (None: detach), beside ``set_coverage`` and under its rules; both may be attached at once."""
+        """Attach a ``Pileup`` (None: detach), beside ``set_coverage`` and under its rules; both may be attached at once.  Like an
+        attached ``Coverage`` it sees the records before ``markdup`` has flagged any: duplicates are piled up too (``add_bam`` of the
+        finished records leaves them out)."""
         self._attach("pileup", pile)
 
     def add_reads(self, res, reads):
@@ -91,11 +111,13 @@ class BamSorter:
         """ends the file, writes the index, frees the spools; returns the stats (also after a failure: the handle is freed either way)"""
         if not self._h:
             return self.stats
-        st = SortStats()
+        st, dup = SortStats(), DupStats()
         h, self._h = self._h, C.c_void_p()
-        rc = self.lib.gdiet_hip_bam_sort_close(h, C.byref(st))
+        rc = self.lib.gdiet_hip_bam_sort_close_dup(h, C.byref(st), C.byref(dup))
         self.stats = dict(records=st.records, runs=st.runs, spooled_bytes=st.spooled_bytes, chunks=st.chunks, members=st.members, n_no_coor=st.n_no_coor,
                           seconds=dict(zip(("key_sort", "gather", "spool_write", "spool_read", "compress"), (round(x, 6) for x in st.seconds))))
+        if self.markdup:
+            self.stats["dup"] = dup.as_dict()
         if rc:
             raise GdietError("gdiet_hip error %d: %s" % (rc, self._text()))
         return self.stats

@@ -42,6 +42,10 @@ BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           # BAM records put into coordinate order (bam_sort.hip.h): a run is sorted, and a chunk of the merge gathered, beside the DP of the batches in flight
           "_Z14bam_key_kernel": dict(vgprs=32, scratch=0),
           "_Z17bam_gather_kernel": dict(vgprs=32, scratch=0),
+          # duplicates marked in the sorter's resident runs and chunks (bam_markdup.hip.h): beside the DP wavefronts, like the rest of the sort
+          "_Z14dup_key_kernel": dict(vgprs=32, scratch=0),
+          "_Z17dup_decide_kernel": dict(vgprs=32, scratch=0),
+          "_Z16dup_apply_kernel": dict(vgprs=32, scratch=0),
           # coverage accumulated from the resident BAM records (cov.hip.h): batch i is scattered beside the DP of batch i + 1, like the encoders
           "_Z18cov_scatter_kernel": dict(vgprs=32, scratch=0),
           "_Z17cov_window_kernel": dict(vgprs=32, scratch=0),

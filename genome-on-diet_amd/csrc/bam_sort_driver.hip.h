@@ -10,6 +10,7 @@
 #include "bam_sort.hip.h"
 #include "bam_index.h"
 #include "bam_sorter.h"
+#include "bam_markdup_driver.hip.h"
 
 // The pass, enqueued on s: d_in[0, len) and d_start[0, n) are resident; d_out[0, len) takes the sorted records and d_rows[0, n) their
 // index rows.  The caller holds bsort.mu, owns mem and synchronises.  0, or -1 with why.
@@ -111,6 +112,7 @@ struct GdqDevice {
 	uint8_t *d_run = nullptr, *d_res = nullptr;
 	GdsRow *d_rows = nullptr;
 	size_t run_cap = 0, res_cap = 0, rows_cap = 0, front_len = 0;
+	uint64_t res_bytes = 0; // of the records of the resident result, behind front_len
 	GdAccumSet acc; // gdiet_hip_bam_sort_set_coverage / _set_pileup: every appended batch is scattered from the run buffer, on the encoder's lane
 
 	// p[0, cap) -> at least `need` bytes, the first `keep` bytes kept.  The caller holds bsort.mu and has made the stream.
@@ -187,7 +189,7 @@ struct GdqDevice {
 		if ((e = grow(&d_res, &res_cap, fl + (size_t)bytes + 16, 0)) != hipSuccess) return bad(why, "result buffer", e);
 		if ((e = grow(&d_rows, &rows_cap, sizeof(GdsRow) * (size_t)n + 16, 0)) != hipSuccess) return bad(why, "rows", e);
 		if (fl && (e = hipMemcpyAsync(d_res, front, fl, hipMemcpyHostToDevice, ctx->bsort.stream)) != hipSuccess) return bad(why, "tail copy", e);
-		front_len = fl;
+		front_len = fl, res_bytes = bytes;
 		return 0;
 	}
 	void time_pass()
@@ -276,6 +278,89 @@ struct GdqDevice {
 		if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "gather");
 		float ms = 0;
 		if (hipEventElapsedTime(&ms, L.ev[1], L.ev[2]) == hipSuccess) L.ms[1] += ms;
+		return 0;
+	}
+	// ---- duplicate marking (bam_markdup_driver.hip.h) over the resident result of n records -------------------------------------------
+	// the entries {key, score} of its records, in its order, down to the host
+	int dup_keys(uint64_t n, uint64_t *key, uint32_t *score, std::string &why)
+	{
+		if (n == 0) return 0;
+		GdLane &L = ctx->bsort;
+		std::lock_guard<std::mutex> lk(L.mu);
+		if (L.ready(ctx->device, 3, "BAM sorter", why)) return -1;
+		hipStream_t s = L.stream;
+		GdStreamMem mem(s);
+		hipError_t e = hipSuccess;
+		auto fail = [&](hipError_t err, const char *what) { mem.fail(); return bad(why, what, err); };
+		uint64_t *d_key;
+		uint32_t *d_score;
+		if ((e = mem.alloc(&d_key, 8 * (size_t)n)) != hipSuccess || (e = mem.alloc(&d_score, 4 * (size_t)n)) != hipSuccess) return fail(e, "duplicate entries");
+		if (gd_dup_keys_dev(ctx, mem, d_res + front_len, res_bytes, nullptr, d_rows, n, d_key, d_score, nullptr, why)) { mem.fail(); return -1; }
+		if ((e = hipMemcpyAsync(key, d_key, 8 * (size_t)n, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "duplicate entries copy down");
+		if ((e = hipMemcpyAsync(score, d_score, 4 * (size_t)n, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "duplicate entries copy down");
+		if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "duplicate entries copy down");
+		return 0;
+	}
+	// the entries of the whole file in output order -> the bitmap by place ((n + 31) / 32 words) and the counts
+	int dup_decide(const uint64_t *key, const uint32_t *score, uint64_t n, uint32_t *bitmap, GdmStats *st, std::string &why)
+	{
+		*st = GdmStats();
+		if (n == 0) return 0;
+		GdLane &L = ctx->bsort;
+		std::lock_guard<std::mutex> lk(L.mu);
+		if (L.ready(ctx->device, 3, "BAM sorter", why)) return -1;
+		hipStream_t s = L.stream;
+		GdStreamMem mem(s);
+		hipError_t e = hipSuccess;
+		auto fail = [&](hipError_t err, const char *what) { mem.fail(); return bad(why, what, err); };
+		uint64_t *d_key;
+		uint32_t *d_score, *d_idx, *d_bitmap, *d_st, h_st[4] = {0, 0, 0, 0};
+		const size_t words = (size_t)((n + 31) / 32);
+		std::vector<uint32_t> iota((size_t)n);
+		for (uint64_t k = 0; k < n; ++k) iota[(size_t)k] = (uint32_t)k;
+		if ((e = mem.alloc(&d_key, 8 * (size_t)n)) != hipSuccess || (e = mem.alloc(&d_score, 4 * (size_t)n)) != hipSuccess || (e = mem.alloc(&d_idx, 4 * (size_t)n)) != hipSuccess)
+			return fail(e, "duplicate entries");
+		if ((e = mem.alloc(&d_bitmap, 4 * words + 16)) != hipSuccess) return fail(e, "duplicate bitmap");
+		if ((e = hipMemcpyAsync(d_key, key, 8 * (size_t)n, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "duplicate entries copy");
+		if ((e = hipMemcpyAsync(d_score, score, 4 * (size_t)n, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "duplicate entries copy");
+		if ((e = hipMemcpyAsync(d_idx, iota.data(), 4 * (size_t)n, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "duplicate entries copy");
+		if (gd_dup_decide_dev(ctx, mem, d_key, d_score, d_idx, n, d_bitmap, &d_st, why)) { mem.fail(); return -1; }
+		if ((e = hipMemcpyAsync(bitmap, d_bitmap, 4 * words, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "duplicate bitmap copy down");
+		if ((e = hipMemcpyAsync(h_st, d_st, 16, hipMemcpyDeviceToHost, s)) != hipSuccess) return fail(e, "duplicate counters copy down");
+		if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "duplicate decision");
+		gd_dup_stats(h_st, n, st);
+		return 0;
+	}
+	// record k of the resident result takes bit bit0 + k of bitmap (bit0 below 32)
+	int dup_apply(const uint32_t *bitmap, uint32_t bit0, uint64_t n, std::string &why)
+	{
+		if (n == 0) return 0;
+		GdLane &L = ctx->bsort;
+		std::lock_guard<std::mutex> lk(L.mu);
+		if (L.ready(ctx->device, 3, "BAM sorter", why)) return -1;
+		hipStream_t s = L.stream;
+		GdStreamMem mem(s);
+		hipError_t e = hipSuccess;
+		auto fail = [&](hipError_t err, const char *what) { mem.fail(); return bad(why, what, err); };
+		const size_t words = (size_t)((bit0 + n + 31) / 32);
+		uint32_t *d_bitmap;
+		if ((e = mem.alloc(&d_bitmap, 4 * words + 16)) != hipSuccess) return fail(e, "duplicate bitmap");
+		if ((e = hipMemcpyAsync(d_bitmap, bitmap, 4 * words, hipMemcpyHostToDevice, s)) != hipSuccess) return fail(e, "duplicate bitmap copy");
+		hipLaunchKernelGGL(dup_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_res + front_len, res_bytes, (const uint64_t *)nullptr, d_rows, n, (const uint32_t *)d_bitmap, bit0);
+		if ((e = hipGetLastError()) != hipSuccess) return fail(e, "duplicate apply launch");
+		if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "duplicate apply");
+		return 0;
+	}
+	// one run that is the whole file: key pass, decision and rewrite where the records are
+	int dup_mark_resident(uint64_t n, GdmStats *st, std::string &why)
+	{
+		*st = GdmStats();
+		if (n == 0) return 0;
+		GdLane &L = ctx->bsort;
+		std::lock_guard<std::mutex> lk(L.mu);
+		if (L.ready(ctx->device, 3, "BAM sorter", why)) return -1;
+		GdStreamMem mem(L.stream);
+		if (gd_dup_mark_dev(ctx, mem, d_res + front_len, res_bytes, nullptr, d_rows, n, st, why)) { mem.fail(); return -1; }
 		return 0;
 	}
 	int down(void *dst, const void *d_src, size_t n, const char *what, std::string &why)
@@ -369,7 +454,16 @@ extern "C" int gdiet_hip_bam_sort_set_pileup(gdiet_bam_sorter *h, gdiet_pileup *
 	return h ? gd_accum_attach(h->ctx, h->q.ex.acc, GD_ACC_PILE, pile, "gdiet_hip_bam_sort_set_pileup", "sorter") : GDIET_E_PARAM;
 }
 
-extern "C" int gdiet_hip_bam_sort_close(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *stats)
+extern "C" int gdiet_hip_bam_sort_set_markdup(gdiet_bam_sorter *h, int on)
+{
+	if (!h) return GDIET_E_PARAM;
+	gd_err_clear();
+	if (h->q.failed) return gd_bsq_fail(h, GDIET_E_PARAM, "gdiet_hip_bam_sort_set_markdup");
+	if (h->q.set_markdup(on != 0)) return gd_err_fail(h->ctx, GDIET_E_PARAM, "gdiet_hip_bam_sort_set_markdup: the sorter has taken records: duplicate marking is chosen before the first add");
+	return GDIET_OK;
+}
+
+extern "C" int gdiet_hip_bam_sort_close_dup(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *stats, gdiet_dup_stats_t *dup_stats)
 {
 	if (!h) return GDIET_E_PARAM;
 	gd_err_clear();
@@ -379,8 +473,10 @@ extern "C" int gdiet_hip_bam_sort_close(gdiet_bam_sorter *h, gdiet_bam_sort_stat
 		stats->records = s.records, stats->runs = s.runs, stats->spooled_bytes = s.spooled_bytes, stats->chunks = s.chunks, stats->members = s.members, stats->n_no_coor = s.n_no_coor;
 		for (int i = 0; i < 5; ++i) stats->seconds[i] = s.seconds[i];
 	}
+	gd_dup_stats_out(h->q.dup, dup_stats);
 	const int code = rc ? gd_bsq_fail(h, h->q.w.dev_error ? GDIET_E_HIP : GDIET_E_PARAM, "gdiet_hip_bam_sort_close") : GDIET_OK;
 	h->q.ex.free_all();
 	delete h;
 	return code;
 }
+extern "C" int gdiet_hip_bam_sort_close(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *stats) { return gdiet_hip_bam_sort_close_dup(h, stats, nullptr); }

@@ -15,6 +15,10 @@
 //   seal    the device pass over the run (Ex::sort_run), the sorted run down to the host and into a spool file of its own in tmp_dir,
 //           created and unlinked at once, written sequentially, uncompressed.  The run's sorted keys and record sizes stay: 12 bytes
 //           per record.
+//   markdup (off by default; bam_markdup.h): a spooled run's entries {key, score} are taken from the resident sorted run at its seal and
+//           stay on the host, 12 more bytes per record.  At close one run is marked where it is; several runs: the entries are laid out
+//           in output order behind Ex::order, ONE decision covers the whole file (groups span runs and chunks) and gives a bitmap by
+//           place, and every chunk is rewritten with its slice of the bitmap between its gather and its emit.
 //   close   one run that was never spooled: its sorted buffer is the output stream as it is.  Several runs: one stable device sort of the
 //           concatenated keys (Ex::order), the plan, and per chunk the ranges read from the spools, laid side by side, gathered
 //           (Ex::gather).  The stream -- header, then records -- goes through the BGZF writer core (GdBgzfOut), from the resident buffer
@@ -31,8 +35,10 @@
 #include <algorithm>
 #include <chrono>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "bam_index.h"
+#include "bam_markdup.h"
 #include "bgzf_out.h"
 
 struct GdqRange { uint64_t lo = 0, hi = 0, byte_lo = 0, byte_hi = 0; }; // records [lo, hi) of a run: bytes [byte_lo, byte_hi) of its spool
@@ -110,6 +116,17 @@ static inline bool gdq_header_refs(const uint8_t *h, size_t n, std::vector<std::
 //   int fetch(uint64_t from, uint64_t n_bytes, uint8_t *dst, std::string &why)         bytes [from, from + n_bytes) of the resident result
 //   const void *resident()                                              the device address of the resident result
 //   void seconds(double *key_sort, double *gather)                      the device's time so far
+// An executor that marks duplicates (bam_markdup.h) has four more; GdqSorter reaches them only where GdqHasDup finds them, so an executor
+// without them sorts as before and refuses set_markdup:
+//   int dup_keys(uint64_t n, uint64_t *key, uint32_t *score, std::string &why)     the entries of the resident result's n records, in its order
+//   int dup_decide(const uint64_t *key, const uint32_t *score, uint64_t n, uint32_t *bitmap, GdmStats *st, std::string &why)
+//                                                                       entries in output order -> bit j: the record at place j is a duplicate
+//   int dup_apply(const uint32_t *bitmap, uint32_t bit0, uint64_t n, std::string &why)  record k of the resident result takes bit bit0 + k
+//   int dup_mark_resident(uint64_t n, GdmStats *st, std::string &why)   all three over the resident result alone
+// A bad record (bam_markdup.h) fails dup_keys / dup_mark_resident with its text.
+template <class Ex, class = void> struct GdqHasDup : std::false_type {};
+template <class Ex> struct GdqHasDup<Ex, std::void_t<decltype(&Ex::dup_keys), decltype(&Ex::dup_decide), decltype(&Ex::dup_apply), decltype(&Ex::dup_mark_resident)>> : std::true_type {};
+
 template <class Ex>
 struct GdqSorter {
 	Ex ex;
@@ -133,6 +150,11 @@ struct GdqSorter {
 	std::vector<std::pair<uint64_t, uint64_t>> log;
 	std::vector<uint8_t> host;    // a run or a chunk on its way
 	GdqStats st;
+	// duplicate marking (off: nothing below is touched and the executor is asked for nothing more)
+	bool markdup = false, added = false;
+	std::vector<uint64_t> dup_key;   // {key, score} of all sealed runs, in run order: 12 more bytes per record
+	std::vector<uint32_t> dup_score;
+	GdmStats dup;
 
 	int fail(const std::string &what) { if (!failed) failed = true, msg = what; return -1; }
 	static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -156,6 +178,14 @@ struct GdqSorter {
 		header_len = n_header;
 		opened = true;
 		if (w.write(header, n_header)) return fail("output: " + w.msg);
+		return 0;
+	}
+
+	// 0; -1: records have been added, or the executor cannot mark
+	int set_markdup(bool on)
+	{
+		if (added || (on && !GdqHasDup<Ex>::value)) return -1;
+		markdup = on;
 		return 0;
 	}
 
@@ -230,6 +260,14 @@ struct GdqSorter {
 		if (ex.sort_run(start.data(), n, bytes, f, fl, why)) return fail(why);
 		++st.runs;
 		start.clear(), fill = 0;
+		if constexpr (GdqHasDup<Ex>::value) {
+			if (markdup && direct && ex.dup_mark_resident(n, &dup, why)) return fail(why);
+			if (markdup && !direct) {
+				const size_t d0 = dup_key.size();
+				dup_key.resize(d0 + (size_t)n), dup_score.resize(d0 + (size_t)n);
+				if (ex.dup_keys(n, dup_key.data() + d0, dup_score.data() + d0, why)) return fail(why);
+			}
+		}
 		if (direct) return emit(n, bytes, fl);
 		std::vector<GdsRow> rr((size_t)n);
 		host.resize((size_t)bytes);
@@ -252,6 +290,7 @@ struct GdqSorter {
 	int add(const void *batch, uint64_t bytes, const uint64_t *rec_out, uint64_t n)
 	{
 		if (failed) return -1;
+		added = true;
 		if (n == 0) return 0;
 		if ((uint64_t)st.records + n >= ((uint64_t)1 << 31)) { fail("2^31 records or more in one file"); return -2; } // (the merge's one sort counts them in an int)
 		if (fill && fill + bytes > run_bytes && seal(false)) return -1;
@@ -272,6 +311,15 @@ struct GdqSorter {
 		for (const Run &r : runs) run_n.push_back(r.n), base.push_back(base.back() + r.n);
 		std::vector<GdqChunk> plan;
 		if (!gdq_plan_chunks(order.data(), sizes.data(), n, run_n, chunk_bytes, plan, why)) return fail(why);
+		std::vector<uint32_t> bitmap; // by place: the one decision over the whole file, taken before the first chunk is streamed
+		if constexpr (GdqHasDup<Ex>::value)
+			if (markdup) {
+				std::vector<uint64_t> ek((size_t)n);
+				std::vector<uint32_t> es((size_t)n);
+				for (uint64_t j = 0; j < n; ++j) ek[(size_t)j] = dup_key[order[(size_t)j]], es[(size_t)j] = dup_score[order[(size_t)j]];
+				bitmap.assign((size_t)((n + 31) / 32) + 1, 0u);
+				if (ex.dup_decide(ek.data(), es.data(), n, bitmap.data(), &dup, why)) return fail(why);
+			}
 		std::vector<uint64_t> src, psize, dst, side_at(runs.size());
 		std::vector<std::vector<uint64_t>> at(runs.size()); // per run: where the records of the chunk's range start in the side-by-side buffer
 		for (const GdqChunk &c : plan) {
@@ -299,6 +347,8 @@ struct GdqSorter {
 			size_t fl = 0;
 			const uint8_t *f = front(&fl);
 			if (ex.gather(host.data(), c.bytes, src.data(), psize.data(), dst.data(), m, c.bytes, f, fl, why)) return fail(why);
+			if constexpr (GdqHasDup<Ex>::value)
+				if (markdup && ex.dup_apply(bitmap.data() + (c.j0 >> 5), (uint32_t)(c.j0 & 31u), m, why)) return fail(why);
 			if (emit(m, c.bytes, fl)) return -1;
 			++st.chunks;
 		}

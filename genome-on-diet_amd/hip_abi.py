@@ -81,6 +81,8 @@ def load_library():
     lib.gdiet_hip_bam_in_unpack.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), i64p, i32p, i32p]
     lib.gdiet_hip_bam_sort_records.argtypes = [vp, C.c_char_p, C.c_size_t, vp, vp, C.c_size_t, i64p]
     lib.gdiet_hip_bam_sort_records.restype = C.c_int64
+    lib.gdiet_hip_bam_markdup_records.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.POINTER(DupStats)]
+    lib.gdiet_hip_bam_markdup_records.restype = C.c_int64
     lib.gdiet_hip_fastx_format.argtypes = [vp]
     lib.gdiet_hip_bgzf_deflate.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     lib.gdiet_hip_bgzf_out_open.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
@@ -94,6 +96,14 @@ def load_library():
     lib.gdiet_hip_post_batch.argtypes = [vp, C.c_int, u8p, i64p, u8p, i64p, u32p, i64p, i32p, i32p, C.POINTER(C.c_int8), C.c_int8, C.c_int8, C.c_int, C.c_int, C.c_int, i32p]
     _lib = lib
     return lib
+
+
+class DupStats(C.Structure):
+    """gdiet_dup_stats_t"""
+    _fields_ = [("examined", C.c_int64), ("eligible", C.c_int64), ("duplicates", C.c_int64), ("max_group", C.c_int64)]
+
+    def as_dict(self):
+        return dict(examined=self.examined, eligible=self.eligible, duplicates=self.duplicates, max_group=self.max_group)
 
 
 def _ptr(a, ty):
@@ -170,6 +180,18 @@ class Context:
         if rc < 0:
             self._check(int(rc))
         return out.raw[:len(records)], rows[:n.value]
+
+    def bam_markdup_records(self, records):
+        """gdiet_hip_bam_markdup_records: whole uncompressed BAM records, in any order, with bit 0x400 rewritten by the device under the
+        rule "Duplicate marking" of include/gdiet_hip.h, the buffer's order breaking ties: (bytes, dict(examined, eligible, duplicates,
+        max_group)).  A bad record raises GdietError and nothing is returned"""
+        records = bytes(records)
+        st = DupStats()
+        out = C.create_string_buffer(max(1, len(records)))
+        rc = self.lib.gdiet_hip_bam_markdup_records(self._h, records, len(records), C.cast(out, C.c_void_p), C.byref(st))
+        if rc < 0:
+            self._check(int(rc))
+        return out.raw[:len(records)], st.as_dict()
 
     REF_LS, REF_HD, REF_SQ = 0, 1, 2  # the parser's state at byte 0 of a block: at a line start, inside a header line, inside a sequence line
 

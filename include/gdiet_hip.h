@@ -830,6 +830,54 @@ int gdiet_hip_bam_sort_add(gdiet_bam_sorter *h, const gdiet_index *idx, int n_re
                            gdiet_reg_t *const *regs, int64_t opt_flag);
 int gdiet_hip_bam_sort_close(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *stats);
 
+/* ---- Duplicate marking ---------------------------------------------------------------------------------------------------------------
+ * Bit 0x400 of BAM alignment records, decided on the device: the step between sort and index of a post-mapping toolchain (samtools
+ * markdup, Picard MarkDuplicates).  The reference writes no duplicate flags: these rules are the definition (tests/markdup_ref.py
+ * restates them).  Single-end only.
+ *   ELIGIBLE  a record with (flag & 0xB04) == 0 (not unmapped, secondary, QC-fail or supplementary), refID >= 0 and pos >= 0.  An
+ *             ineligible record is written exactly as it came; a 0x400 it carries stays.
+ *   THE REAL CIGAR  as for Coverage: the record's n_cigar_op words, or the CG:B:I array of a placeholder record.
+ *   U         the unclipped 5' coordinate, from the real CIGAR, the sums taken in 64 bits:
+ *             forward strand:          u = pos - (sum of the S and H lengths in front of the first other operation)
+ *             reverse strand (0x10):   u = pos + (sum of the M D N = X lengths) - 1 + (sum of the S and H lengths behind the last other
+ *                                      operation)
+ *             A CIGAR of S and H alone (or none) has all of its lengths in both clip sums.
+ *   GROUP     the eligible records with equal (refID, u, strand).  The group key is refID << 34 | (u + 2^32) << 1 | strand; the all-ones
+ *             word marks an ineligible record, so -2^32 <= u <= 2^32 - 2 and refID < 2^30 are required: on these the key is injective.
+ *   SCORE     the sum, as uint32, of the QUAL bytes q with 15 <= q and q != 0xFF (Picard's sum of base qualities): missing qualities
+ *             score 0.
+ *   WINNER    the highest score of the group; among equal scores the record that comes first in the output order (the file's order for
+ *             the sorter, the buffer's for gdiet_hip_bam_markdup_records).  Bit 0x400 of every eligible record is cleared and then set
+ *             on every member of a group but its winner.  Nothing else of a record changes: not its size, its bin or its place -- the
+ *             sort key does not read the bit --, so the marked file, like the sorted one, is a function of the input records alone.
+ *   BAD       a record is bad if its fixed fields, name, CIGAR, SEQ and QUAL do not fit its block_size, it is a placeholder without a
+ *             well-formed CG:B:I tag or the aux walk to that tag leaves the record (every record: the reasons of Coverage's record
+ *             head); or, eligible, an operation code of its real CIGAR is above 8, or u or refID leave the range of the key.  A bad
+ *             record fails the call with GDIET_E_PARAM, the text names the first one and its reason, and nothing is written; the
+ *             sorter then takes nothing but its close.
+ *   STATS     examined (records seen), eligible, duplicates (bits set), max_group (members of the largest group; 0 without an eligible
+ *             record).
+ * The device passes (csrc/bam_markdup.hip.h): dup_key_kernel (one wavefront per record: u and the score, one entry {key, score} per
+ * record), two stable hipCUB radix sorts of the entries -- by descending score, then by key --, dup_decide_kernel (one thread per sorted
+ * entry: an entry whose key equals its predecessor's sets the bit of its place) and dup_apply_kernel (one thread per record: the bit
+ * rewritten where the record is resident).  In the sorter the entries of a spooled run stay on the host (12 bytes per record), and one
+ * decision covers the whole file before its first chunk is streamed: groups span runs and chunks.  A Coverage or Pileup attached to
+ * the sorter scatters at add, before any flag exists, and so still counts duplicates: feed it the finished records (add_bam) to
+ * leave them out.  Out of scope: removing duplicates, optical duplicates, UMI / barcode-aware grouping, marking the secondary and
+ * supplementary records of a duplicate, paired-end rules, a library-size estimate, an @PG line, unsorted BAM output. */
+typedef struct {
+	int64_t examined, eligible, duplicates, max_group;
+} gdiet_dup_stats_t;
+/* The kernel-level boundary: recs[0, len) holds whole uncompressed BAM records in any order (under 2 GiB); out[0, len) takes them with
+ * bit 0x400 rewritten under the rule, the buffer's order breaking ties.  Returns len, or a negative code: GDIET_E_PARAM for a range that
+ * ends inside a record or a bad record (out is then not written), GDIET_E_HIP if the device fails. */
+int64_t gdiet_hip_bam_markdup_records(gdiet_ctx *ctx, const void *recs, size_t len, void *out, gdiet_dup_stats_t *dup_stats);
+/* Duplicate marking of a sorter's file, off by default: chosen before the first gdiet_hip_bam_sort_add (GDIET_E_PARAM afterwards).  With
+ * it off the sorter launches exactly what it launches without this call. */
+int gdiet_hip_bam_sort_set_markdup(gdiet_bam_sorter *h, int on);
+/* gdiet_hip_bam_sort_close that also hands out the duplicate counts (all 0 with marking off); either pointer may be NULL. */
+int gdiet_hip_bam_sort_close_dup(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *stats, gdiet_dup_stats_t *dup_stats);
+
 /* ---- Coverage ------------------------------------------------------------------------------------------------------------------------
  * Per-contig coverage and depth, a flag summary, mean depth per fixed window and the depth of any interval, accumulated on the device
  * from uncompressed BAM alignment records (SAM specification 4.2) while they are resident there.  The reference prints SAM and stops:

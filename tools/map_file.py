@@ -4,7 +4,7 @@ No Python object is made per read: the C arrays of the reader go straight into t
 
     python tools/map_file.py --preset sr ref.fa[.gz] | ref.mmi reads.fq[.gz] | reads.bam -o out.sam [-K 39321600] [--inflight 3] [--reader-threads 4] [--MD | --cs[=short|long]]
                              [-d out.mmi] [--header] [-R '@RG\tID:x\tSM:y'] [-Y] [-L] [-y] [-Q] [--sam-hit-only] [--device-reader]
-                             [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--sort-mem BYTES] [--tmp-dir DIR]]] [--sam-device]
+                             [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--markdup] [--sort-mem BYTES] [--tmp-dir DIR]]] [--sam-device]
                              [--coverage PREFIX [--cov-window N] [--cov-min-mapq Q] [--cov-excl-flags F]]
                              [--pileup PREFIX [--pile-regions BED] [--pile-min-baseq Q] [--pile-min-mapq Q] [--pile-excl-flags F] [--pile-min-depth N] [--pile-min-alt N] [--pile-frac NUM/DEN]]
 
@@ -32,7 +32,9 @@ comes down and is written; with --bgzf device the lines are written behind the w
 --bam --sort writes -o in coordinate order (BamSorter: every batch is encoded into a resident run buffer, a run of --sort-mem bytes is
 sorted on the device and spooled to an unnamed file in --tmp-dir, default the output's directory, and the runs are merged on the device
 at the end); the header then starts with @HD VN:1.6 SO:coordinate.  --index writes <out>.bai as well.  The JSON line gains bam_sort.
-Without --sort nothing changes.
+--markdup (with --bam --sort) marks duplicate reads in the sorted file: bit 0x400, decided on the device over the whole file before its
+first chunk is written (include/gdiet_hip.h, "Duplicate marking"); bam_sort gains "dup".  An accumulator attached to the sorter (--coverage,
+--pileup) reads the records before they are flagged and so still counts duplicates.  Without --sort nothing changes.
 --coverage PREFIX accumulates per-contig coverage and depth on the device (Coverage: 4 bytes of device memory per reference base) and
 writes PREFIX.coverage.tsv, and PREFIX.regions.bed with --cov-window N.  With --bam --sort, or --bam --bgzf device, the accumulator is
 attached to the sorter or the writer and reads the records they have just encoded; otherwise (SAM output, or unsorted --bgzf host) the writer thread
@@ -231,6 +233,7 @@ def main():
     ap.add_argument("--sam-device", action="store_true", help="format the SAM lines on the device (sam_encode_kernel); with --bgzf device they are compressed where they were written")
     ap.add_argument("--sort", action="store_true", help="with --bam: write the records in coordinate order (sorted and merged on the device; header with @HD SO:coordinate)")
     ap.add_argument("--index", action="store_true", help="with --bam --sort: write <out>.bai as well")
+    ap.add_argument("--markdup", action="store_true", help="with --bam --sort: mark duplicate reads (bit 0x400), decided on the device over the whole sorted file")
     ap.add_argument("--sort-mem", type=int, default=1 << 29, metavar="BYTES", help="bytes of records per sorted run (default 512 MiB)")
     ap.add_argument("--tmp-dir", metavar="DIR", help="where the runs are spooled (unnamed files; default: the directory of -o)")
     ap.add_argument("--coverage", metavar="PREFIX", help="accumulate coverage and depth on the device; writes PREFIX.coverage.tsv (and PREFIX.regions.bed with --cov-window)")
@@ -256,6 +259,8 @@ def main():
         a.bgzf = "device"
     if (a.sort and not a.bam) or (a.index and not a.sort):
         ap.error("--sort goes with --bam, --index with --sort")
+    if a.markdup and not (a.bam and a.sort):
+        ap.error("--markdup needs --bam --sort: duplicates are decided over the whole sorted file, which only the sorter holds")
     pkg = _load_pkg()
     ctx = pkg.Context(0)
     tag_bits = (0x1000000 if a.MD else 0) | (0x40 if a.cs else 0) | (0x800 if a.cs == "long" else 0)
@@ -308,7 +313,8 @@ def main():
         resident = a.bam and (a.sort or a.bgzf == "device")  # the records are resident in the sorter's or the writer's hands
         attach, attach_pile = cov is not None and resident, pile is not None and resident
         if a.sort:
-            sorter = pkg.BamSorter(a.out, m, bgzf=a.bgzf, level=a.bgzf_level, threads=a.bgzf_threads, run_bytes=a.sort_mem, tmp_dir=a.tmp_dir, index=a.index, version=VERSION, argv=sys.argv)
+            sorter = pkg.BamSorter(a.out, m, bgzf=a.bgzf, level=a.bgzf_level, threads=a.bgzf_threads, run_bytes=a.sort_mem, tmp_dir=a.tmp_dir, index=a.index, version=VERSION, argv=sys.argv,
+                                   markdup=a.markdup)
             if attach:
                 sorter.set_coverage(cov)
             if attach_pile:
