@@ -18,6 +18,10 @@ BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           "_Z21ksw_extd2_pipe_kernelILb1E": dict(vgprs=128, scratch=320),  # four wavefronts per SIMD; the spills sit in the once-per-alignment staging code, none in the steps
           "_Z20map_post_wave_kernel": dict(vgprs=32, scratch=0),
           "_Z21map_pack_cigar_kernel": dict(vgprs=32, scratch=0),
+          # the wave seed kernel on the tile sketch (map_tile_sketch.h): 64 registers = two of its wavefronts in the room one retiring DP
+          # wavefront leaves (96 + the 32 a full house leaves free); not the 32 that would start beside a full house.  Its scratch is
+          # mm_seed_select's heap on lane 0 (1 KB) and a few spills outside the tile loop.
+          "_Z20map_seed_wave_kernel": dict(vgprs=64, scratch=1152),
           # the rest of a HiFi batch's tail: with two batches in flight every kernel between a batch's main DP launch and its results runs
           # beside the other batch's DP launch (profiles/r13_batch_tail.md)
           "_Z25ksw_backtrack_wave_kernel": dict(vgprs=32, scratch=0),

@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "map_stages.h"
+#include "map_tile_sketch.h"
 #include "map_post.h"
 
 struct MapDevOpt { // uniform per batch
@@ -555,9 +556,9 @@ __global__ __launch_bounds__(64) void map_post_wave_kernel(int nb, const MapBox 
 }
 
 // ---- wave-parallel form of map_seed_kernel: one 64-lane wavefront per read -------------------------------------------
-// The winnowing automaton is sequential, but exact slices of it can be produced independently (gd_sketch_slice), so the 64
-// lanes sketch 64 slices of the read, compact their minimizers in read order with a wavefront prefix sum, probe the index
-// in parallel, and leave only the short sequential parts (query-occurrence filter, high-occurrence seed selection) to lane 0.
+// The sketches run in position-parallel form (map_tile_sketch.h: 64 positions of the read per step of the wavefront, one per lane,
+// the emissions compacted in read order straight into the minimizer list), the index probes in parallel, and only the short
+// sequential parts (query-occurrence filter, high-occurrence seed selection) are left to lane 0.
 
 #ifdef GD_SEED_PROF
 __device__ unsigned long long gd_seed_prof[8];
@@ -565,71 +566,15 @@ __device__ unsigned long long gd_seed_prof[8];
 #else
 #define GD_PROF_T(i) do { } while (0)
 #endif
-struct GdEmitLane { // per-lane emission list in scratch
-	GdMini *out;
-	unsigned n, cap;
-	__device__ bool operator()(const GdMini &m)
-	{
-		if (n < cap) out[n] = m;
-		++n;
-		return false;
-	}
+
+struct MapSeedLds {
+	GdTileLds tile;
+	uint32_t shift_n[64]; // minimizers per pattern phase (S1 -> S3)
 };
+// dynamic LDS bytes of a wave seed kernel launch: the sketch's record, later the sort buffer of `cap` hashes
+static inline size_t gd_seed_wave_lds_bytes(int cap) { return sizeof(MapSeedLds) > (size_t)cap * sizeof(uint64_t) ? sizeof(MapSeedLds) : (size_t)cap * sizeof(uint64_t); }
 
-// parallel sketch of `dl` sparsified bases; the first min(total, cap) minimizers in read order go to dst[0..).
-// Returns (uniform) the count, or ~0u when a scratch list or dst overflowed.
-// the steps [a, b) of a sketch over dl sparsified bases, 64 exact slices; their minimizers are appended in read order to dst[have..)
-// as long as the list stays below `cap` (0: no cap).  Returns (uniform) the new length, or ~0u when a scratch list or dst overflowed.
-__device__ __forceinline__ unsigned map_par_sketch_range(const uint8_t *str, unsigned dl, unsigned a, unsigned b, int w, int k, unsigned shift, const GdPattern &P,
-                                                         GdMini *tmp, unsigned R, GdMini *dst, unsigned dst_cap, uint32_t cap, unsigned have, GdMini *win)
-{
-	const unsigned lane = threadIdx.x & 63;
-	const unsigned chunk = (b - a + 63) / 64;
-	const unsigned i0 = a + lane * chunk, i1 = i0 + chunk < b ? i0 + chunk : b;
-	GdEmitLane e = {tmp + (size_t)lane * R, 0, R};
-#ifdef GD_SEED_PROF
-	unsigned long long prof_t = wall_clock64();
-#endif
-	if (chunk && i0 < b) gd_sketch_slice<GdEmitLane, true>(str, dl, i0, i1, w, k, 0, shift, P, true, e, win + lane, 64);
-	GD_PROF_T(6);
-	unsigned incl = e.n;
-	for (int d = 1; d < 64; d <<= 1) {
-		const unsigned v = __shfl_up(incl, d);
-		if ((int)lane >= d) incl += v;
-	}
-	const unsigned total = have + __shfl(incl, 63), off = have + incl - e.n;
-	const unsigned eff = (cap > 0 && total >= cap) ? cap : total;
-	bool bad = e.n > R;
-	for (unsigned j = 0; j < e.n && !bad; ++j) {
-		const unsigned p = off + j;
-		if (p >= eff) break;
-		if (p < dst_cap) dst[p] = e.out[j];
-		else bad = true;
-	}
-	GD_PROF_T(7);
-	return __any(bad) ? ~0u : eff;
-}
-
-// parallel sketch of `dl` sparsified bases; the first min(total, cap) minimizers in read order go to dst[0..).
-// Returns (uniform) the count, or ~0u on overflow.  With a cap the sequential reference stops at the cap-th minimizer; slices
-// cannot stop each other, so a prefix that should hold it (the expected 2 / (w + 1) minimizers per base, 25 % margin) is sketched
-// first and the rest of the read only if the prefix fell short -- the slices being exact, the first `cap` minimizers are the same
-// either way.  (Phase >= 1 of mm_sketch2 is capped at phase 0's count, found in the first 20 % of a HiFi read: without this the
-// capped pass cost as much as an uncapped one.)
-__device__ __forceinline__ unsigned map_par_sketch(const uint8_t *str, unsigned dl, int w, int k, unsigned shift, const GdPattern &P, GdMini *tmp,
-                                                   unsigned R, GdMini *dst, unsigned dst_cap, uint32_t cap, GdMini *win /* LDS: w x 64 entries, lane-interleaved */)
-{
-	if (cap == 0) return map_par_sketch_range(str, dl, 0, dl, w, k, shift, P, tmp, R, dst, dst_cap, 0, 0, win);
-	uint64_t l1 = (uint64_t)cap * (uint64_t)(w + 1) / 2;
-	l1 += l1 / 4 + (unsigned)(w + k);
-	if (l1 >= dl) return map_par_sketch_range(str, dl, 0, dl, w, k, shift, P, tmp, R, dst, dst_cap, cap, 0, win);
-	const unsigned n1 = map_par_sketch_range(str, dl, 0, (unsigned)l1, w, k, shift, P, tmp, R, dst, dst_cap, cap, 0, win);
-	if (n1 == ~0u || n1 >= cap) return n1;
-	__syncthreads(); // (the lanes' scratch lists and LDS windows are reused)
-	return map_par_sketch_range(str, dl, (unsigned)l1, dl, w, k, shift, P, tmp, R, dst, dst_cap, cap, n1, win);
-}
-
-__global__ __launch_bounds__(64) void map_seed_wave_kernel(int n_reads, const uint8_t *__restrict__ reads, const int64_t *__restrict__ roff,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void map_seed_wave_kernel(int n_reads, const uint8_t *__restrict__ reads, const int64_t *__restrict__ roff,
                                                            GdIdxView I, MapDevOpt O, const MapReadScratch *__restrict__ sc, GdMini *__restrict__ mv_arena,
                                                            uint64_t *__restrict__ u64_arena, GdSeed *__restrict__ seed_arena, MapSeedOut *__restrict__ out,
                                                            const int32_t *__restrict__ ids /* the reads of this launch (null: 0 .. n_reads - 1) */)
@@ -645,64 +590,64 @@ __global__ __launch_bounds__(64) void map_seed_wave_kernel(int n_reads, const ui
 	if (len <= 0) { if (lane == 0) out[rid] = o; return; }
 	const MapReadScratch S = sc[rid];
 	GdMini *mv = mv_arena + S.mv_off;
-	GdMini *tmp = (GdMini *)(u64_arena + S.u64_off); // 2*mv_cap uint64 = mv_cap GdMini
 	GdSeed *seeds = seed_arena + S.seed_off;
-	const unsigned R = S.mv_cap / 64;
-	// dynamic LDS: the winnowing windows of the 64 lanes (w x 64 entries, lane-interleaved), reused by the hash sort of S4
+	// dynamic LDS: the tile sketch's exchange record and the phase counts of S1, reused by the hash sort of S4 and the seeds of S5
 	extern __shared__ __attribute__((aligned(16))) uint8_t seed_lds[];
-	GdMini *win = reinterpret_cast<GdMini *>(seed_lds);
+	MapSeedLds *SL = reinterpret_cast<MapSeedLds *>(seed_lds);
 #ifdef GD_SEED_PROF
 	unsigned long long prof_t = wall_clock64();
 #endif
-	// S1: mm_sketch2 -- every phase, phase 0 on the cropped read, later phases capped at phase 0's count (LR/sketch.c:2174-2223)
-	unsigned len_crop, total = 0;
+	// S1: mm_sketch2 -- every phase, phase 0 on the cropped read, later phases capped at phase 0's count (LR/sketch.c:2174-2223); then
+	// S3: mm_get_shift and S2: mm_sketch3 at the chosen phase.  The passes are one loop around one inlined copy of the tile sketch
+	// (pass W is S2's), which keeps the kernel's code and its register count down.
+	unsigned len_crop, total = 0, n_mv = 0;
 	uint32_t cap;
 	if (O.max_seeds < 1) len_crop = (unsigned)((float)O.max_seeds * len), cap = UINT32_MAX;
 	else len_crop = (unsigned)len, cap = (uint32_t)O.max_seeds;
-	uint32_t shift_n[64];
-	bool bad = false;
-	for (int shift = 0; shift < O.pat.W; ++shift) {
-		const unsigned dl = gd_diet_len(O.pat, len_crop, (unsigned)shift);
-		const unsigned n = map_par_sketch(str, dl, O.w, O.k, (unsigned)shift, O.pat, tmp, R, mv + total, S.mv_cap - total, cap == UINT32_MAX ? 0u : cap, win);
-		__syncthreads();
-		if (n == ~0u) { bad = true; break; }
-		shift_n[shift] = n, total += n;
-		if (cap == UINT32_MAX) len_crop = (unsigned)len, cap = n;
-	}
-	if (bad) { o.n_seeds = -1; if (lane == 0) out[rid] = o; return; }
-	GD_PROF_T(0);
-	// S3: mm_get_shift -- probes in parallel, one sum per phase
-	{
-		unsigned best = 0, base = 0;
-		for (int i = 0; i < O.pat.W; ++i) {
-			unsigned cur = 0;
-			for (unsigned j = lane; j < shift_n[i]; j += 64) {
-				uint64_t st;
-				cur += gd_idx_get(I, mv[base + j].x >> 8, &st);
+	const int W = O.pat.W;
+#pragma unroll 1
+	for (int pass = 0; pass <= W; ++pass) {
+		int shift = pass;
+		if (pass == W) {
+			GD_PROF_T(0);
+			// S3: mm_get_shift -- probes in parallel, one sum per phase
+			unsigned best = 0, base = 0;
+#pragma unroll 1
+			for (int i = 0; i < W; ++i) {
+				unsigned cur = 0;
+				const unsigned n_i = SL->shift_n[i];
+#pragma unroll 1
+				for (unsigned j = lane; j < n_i; j += 64) {
+					uint64_t st;
+					cur += gd_idx_get(I, mv[base + j].x >> 8, &st);
+				}
+				for (int d = 32; d > 0; d >>= 1) cur += __shfl_xor(cur, d);
+				if (cur > best) o.shift = i, best = cur;
+				base += n_i;
 			}
-			for (int d = 32; d > 0; d >>= 1) cur += __shfl_xor(cur, d);
-			if (cur > best) o.shift = i, best = cur;
-			base += shift_n[i];
+			__syncthreads();
+			GD_PROF_T(1);
+			shift = o.shift, len_crop = (unsigned)len, total = 0, cap = O.max_nb_seeds;
+		}
+		const unsigned dl = gd_diet_len(O.pat, len_crop, (unsigned)shift);
+		const unsigned n = gd_tile_sketch(str, dl, O.w, O.k, 0, (unsigned)shift, O.pat, true, mv + total, S.mv_cap - total, cap == UINT32_MAX ? 0u : cap, &SL->tile);
+		__syncthreads();
+		if (n == ~0u) { o.n_seeds = -1; if (lane == 0) out[rid] = o; return; }
+		if (pass == W) n_mv = n;
+		else {
+			SL->shift_n[pass] = n, total += n;
+			if (cap == UINT32_MAX) len_crop = (unsigned)len, cap = n;
 		}
 	}
 	__syncthreads();
-	GD_PROF_T(1);
-	// S2: mm_sketch3 at the chosen phase
-	unsigned n_mv;
-	{
-		const unsigned dl = gd_diet_len(O.pat, (unsigned)len, (unsigned)o.shift);
-		n_mv = map_par_sketch(str, dl, O.w, O.k, (unsigned)o.shift, O.pat, tmp, R, mv, S.mv_cap, O.max_nb_seeds == UINT32_MAX ? 0u : O.max_nb_seeds, win);
-		__syncthreads();
-		if (n_mv == ~0u) { o.n_seeds = -1; if (lane == 0) out[rid] = o; return; }
-		if (O.max_nb_seeds != UINT32_MAX && O.max_nb_seeds > 0 && n_mv == O.max_nb_seeds) o.tel = (uint32_t)(mv[n_mv - 1].y >> 1); // :2010-2012
-	}
+	if (O.max_nb_seeds != UINT32_MAX && O.max_nb_seeds > 0 && n_mv == O.max_nb_seeds) o.tel = (uint32_t)(mv[n_mv - 1].y >> 1); // :2010-2012
 	GD_PROF_T(2);
 	// S4: mm_seed_mz_flt.  It only ever drops something when one hash occurs more than mid_occ times in the read, which a
 	// wavefront bitonic sort of the hashes in LDS decides in a few microseconds (a run longer than mid_occ <=> s[i] == s[i + mid_occ]
 	// for some i); only then -- practically never -- does lane 0 run the sequential filter.  Lists too long for the LDS buffer
 	// (O.sort_cap, sized by the host for the longest read of the batch, at most MAP_SORT_CAP_MAX) take the sequential path directly.
 	if (O.q_occ_frac > 0.0f && (int64_t)n_mv > (int64_t)O.mid_occ && O.mid_occ > 0) {
-		uint64_t *srt = reinterpret_cast<uint64_t *>(seed_lds); // the window storage is idle now
+		uint64_t *srt = reinterpret_cast<uint64_t *>(seed_lds); // the sketch's record is idle now
 		bool need = true;
 		{ // cheap exact pre-check: count the hashes in buckets (LDS atomics); no bucket above mid_occ => no hash above mid_occ => nothing to drop
 			const unsigned nb = (unsigned)(O.seed_lds / sizeof(uint32_t)) >= 8192u ? 8192u : 4096u; // (the launch provides at least 16 KB)

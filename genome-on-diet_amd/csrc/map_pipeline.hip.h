@@ -518,7 +518,7 @@ static int gd_stage_seed(GdMapCall &c)
 	int rc;
 	if ((rc = gd_host_grow(ctx, ctx->h_seedout, sizeof(MapSeedOut) * (size_t)n))) return rc;
 	MapSeedOut *so = c.so = (MapSeedOut *)ctx->h_seedout.p;
-	const size_t seed_lds = gd_seed_lds_bytes(O.w, D.sort_cap);
+	const size_t seed_lds = gd_seed_wave_lds_bytes(D.sort_cap);
 	D.seed_lds = (uint32_t)seed_lds;
 	if (seed_lds > 64 * 1024) GD_HIP(hipFuncSetAttribute((const void *)map_seed_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)seed_lds));
 	for (int attempt = 0; attempt < 2; ++attempt) {
@@ -534,13 +534,13 @@ static int gd_stage_seed(GdMapCall &c)
 			for (const auto &cls : c.cls.classes) {
 				MapDevOpt Dc = D;
 				Dc.sort_cap = cls.first;
-				const size_t lds_c = gd_seed_lds_bytes(O.w, cls.first);
+				const size_t lds_c = gd_seed_wave_lds_bytes(cls.first);
 				Dc.seed_lds = (uint32_t)lds_c;
 				hipLaunchKernelGGL(map_seed_wave_kernel, dim3(cls.second), dim3(64), lds_c, s, cls.second, B.d_reads, B.d_roff, ix->dview, Dc, (const MapReadScratch *)ctx->m_sc.p,
 				                   (GdMini *)ctx->m_mv.p, (uint64_t *)ctx->m_u64.p, (GdSeed *)ctx->m_seed.p, (MapSeedOut *)ctx->m_seedout.p, (const int32_t *)ctx->m_seedids.p + at);
 				at += cls.second;
 			}
-		} else // one read per wavefront: 64 exact slices of the winnowing automaton + parallel index probes
+		} else // one read per wavefront: the tile sketch (64 positions per step) + parallel index probes
 			hipLaunchKernelGGL(map_seed_wave_kernel, dim3(n), dim3(64), seed_lds, s, n, B.d_reads, B.d_roff, ix->dview, D, (const MapReadScratch *)ctx->m_sc.p,
 			                   (GdMini *)ctx->m_mv.p, (uint64_t *)ctx->m_u64.p, (GdSeed *)ctx->m_seed.p, (MapSeedOut *)ctx->m_seedout.p, (const int32_t *)nullptr);
 		GD_HIP(hipGetLastError()); // a refused launch (LDS size, grid) must not pass for stale seed records

@@ -26,7 +26,8 @@ static inline int gd_seed_cap(const GdPattern &pat, int w, int64_t len, int *cls
 	return cap;
 }
 
-// dynamic LDS bytes of a seed kernel launch: the winnowing windows of 64 lanes, later the sort buffer
+// dynamic LDS bytes of a seed kernel that keeps the winnowing windows of 64 reads in LDS (w x 64 entries) and sorts in the same buffer.
+// (The wave seed kernel holds no windows any more: its launches are sized by gd_seed_wave_lds_bytes, map_kernels.hip.h.)
 static inline size_t gd_seed_lds_bytes(int w, int cap) { return std::max<size_t>((size_t)w * 64 * sizeof(GdMini), (size_t)cap * sizeof(uint64_t)); }
 
 // Reads of very different lengths (ONT: log-normal up to 150 kbp): one launch per capacity class, each read in the class its own
@@ -78,8 +79,8 @@ static inline uint64_t gd_scratch_layout(int n, const int64_t *roff, int w, cons
 	uint64_t tot = 0;
 	for (int i = 0; i < n; ++i) {
 		const uint32_t len = (uint32_t)(roff[i + 1] - roff[i]);
-		// hard bound: one minimizer per base (mm_sketch3) or the list of mm_sketch2, whichever is longer, plus the per-lane staging lists of
-		// the wavefront sketch (64 lists of ceil(len/64) + w + 2)
+		// hard bound: one minimizer per base (mm_sketch3) or the list of mm_sketch2, whichever is longer, plus a margin of
+		// 64 * (w + 4) entries (once the staging lists of the sliced wavefront sketch; the tile sketch writes the list directly)
 		const uint32_t hard = (uint32_t)std::max<uint64_t>(len, gd_sketch2_bound(pat, max_seeds, len));
 		sc[i].mv_cap = full ? hard + 64 * (uint32_t)(w + 4) : len / 3 + 512, sc[i].mv_off = tot, sc[i].u64_off = 2 * tot, sc[i].seed_off = tot, sc[i].pad = 0;
 		tot += sc[i].mv_cap;

@@ -66,13 +66,14 @@ GDM_HD unsigned gd_diet_len(const GdPattern &P, unsigned len, unsigned shift)
 // `emit(m)` is called for every minimizer the reference pushes, in the same order; it returns true to stop
 // (the two capped variants return from inside the loop).  final_ge: the final flush uses l >= w+k-1 (sketch2/3 and the
 // AVX-512 mm_sketch, :607) instead of l > w+k-1 (scalar mm_sketch, :1760).
-// Chunked execution (used by the wave-parallel kernels, where each lane sketches one slice of the read): the automaton's
+// Chunked execution (the device index builder sketches slices of a contig; the wave seed kernel has its own position-parallel form,
+// map_tile_sketch.h): the automaton's
 // state after >= k-1+w steps is a pure function of the last w k-mers and of l (the run length of non-N bases, which only
 // matters below w+k), so a slice [i_emit, i_end) can be produced exactly by starting w+k steps earlier with the true l
 // and suppressing every emission before i_emit.  i_begin/l_init describe that warm-up start; do_final = the slice is the
 // last one and performs the end-of-sequence flush.
-// win / wstride: storage of the w-entry window (entry j at win[j * wstride]); nullptr = a local array.  The wave-parallel device
-// kernels pass lane-interleaved LDS (a dynamically indexed local array lives in scratch memory there, an order of magnitude slower).
+// win / wstride: storage of the w-entry window (entry j at win[j * wstride]); nullptr = a local array.  The per-thread seed
+// kernel passes thread-interleaved LDS (a dynamically indexed local array lives in scratch memory there, an order of magnitude slower).
 // EXT_WIN (a compile-time choice, and the whole chain force-inlined on the device): with a run-time choice between the caller's
 // LDS window and a local array the window pointer is a generic one -- every access a flat_load / flat_store through the vector
 // memory path (~500 cycles) instead of a ds_read / ds_write (~64), and the local array costs 1 KB of scratch per lane even if unused.
