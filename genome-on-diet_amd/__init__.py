@@ -14,4 +14,5 @@ from .bgzf_out import BgzfWriter  # noqa: F401,E402
 from .bam_sort import BamSorter  # noqa: F401,E402
 from .coverage import Coverage  # noqa: F401,E402
 from .pileup import Pileup  # noqa: F401,E402
+from .stats import Stats  # noqa: F401,E402
 from .shard import JobClock, effective_cpus, rank_seed, read_range, read_ranges_by_cost  # noqa: F401,E402

@@ -1,4 +1,4 @@
-"""What ``Coverage`` and ``Pileup`` share: the handle of an accumulator over BAM records (csrc/accum_driver.hip.h) and the calls that
+"""What ``Coverage``, ``Pileup`` and ``Stats`` share: the handle of an accumulator over BAM records (csrc/accum_driver.hip.h) and the calls that
 bring records in.  A subclass names the prefix of its entry points (``gdiet_hip_<prefix>_*``) and itself, binds them, opens ``self._h`` in its
 constructor and adds ``finish`` and its readers."""
 import ctypes as C
@@ -9,7 +9,7 @@ from .hip_abi import GdietError
 
 
 class Accumulator:
-    _prefix = None  # "cov" / "pile"
+    _prefix = None  # "cov" / "pile" / "stats"
     _name = None  # the class's name in the message of a closed object
 
     def _fn(self, name):

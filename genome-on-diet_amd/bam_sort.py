@@ -96,6 +96,12 @@ class BamSorter:
         finished records leaves them out)."""
         self._attach("pileup", pile)
 
+    def set_stats(self, stats):
+        """Attach a ``Stats`` (None: detach), beside ``set_coverage`` and ``set_pileup`` and under their rules; all three may be attached at
+        once.  Like them it sees the records before ``markdup`` has flagged any: marked duplicates are counted like any other record
+        (``add_bam`` of the finished records leaves them out)."""
+        self._attach("stats", stats)
+
     def add_reads(self, res, reads):
         """add on Python objects: reads = [(qname, seq, qual or None[, comment or None]), ...]"""
         n = len(reads)

@@ -71,6 +71,10 @@ class BgzfWriter:
         """Attach a ``Pileup`` (None: detach), beside ``set_coverage`` and under its rules; both may be attached at once."""
         self._attach("pileup", pile)
 
+    def set_stats(self, stats):
+        """Attach a ``Stats`` (None: detach), beside ``set_coverage`` and ``set_pileup`` and under their rules; all three may be attached at once."""
+        self._attach("stats", stats)
+
     def flush(self):
         self._open()
         self._check(self.lib.gdiet_hip_bgzf_out_flush(self._h))

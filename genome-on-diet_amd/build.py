@@ -56,7 +56,9 @@ BUDGET = {"_Z21ksw_extd2_wave_kernelILi64ELi0ELb1E": dict(vgprs=96, scratch=0),
           # base counts per position piled up from the resident BAM records, and the calls after finish (pile.hip.h)
           "_Z19pile_scatter_kernel": dict(vgprs=32, scratch=0),
           "_Z16pile_call_kernel": dict(vgprs=32, scratch=0),
-          "_Z16pile_site_kernel": dict(vgprs=32, scratch=0)}
+          "_Z16pile_site_kernel": dict(vgprs=32, scratch=0),
+          # read and alignment statistics from the resident BAM records (stats.hip.h): the compiler's own figure
+          "_Z20stats_scatter_kernel": dict(vgprs=64, scratch=0)}
 
 
 def _newest_source():

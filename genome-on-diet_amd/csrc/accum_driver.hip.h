@@ -1,5 +1,5 @@
-// What the accumulators over BAM records have in common: the coverage accumulator (cov_driver.hip.h) and the pileup accumulator
-// (pile_driver.hip.h) derive from GdAccum and keep only their own tables, their open, their finish and their readers.  Included by
+// What the accumulators over BAM records have in common: the coverage accumulator (cov_driver.hip.h), the pileup accumulator
+// (pile_driver.hip.h) and the statistics accumulator (stats_driver.hip.h) derive from GdAccum and keep only their own tables, their open, their finish and their readers.  Included by
 // bam_driver.hip.h behind the record encoder's driver and in front of the writer that feeds the attached accumulators (needs gdiet_ctx,
 // GdLane, GdStreamMem, err_mark.h, GdAccumSet of bgzf_driver.hip.h, the BAM flattening and gd_bam_encode_device).
 //
@@ -15,8 +15,8 @@
 // On the last two routes the starts are GdbRec::out: nothing is walked, and one table of them serves every accumulator of the call.
 // Every route synchronises its stream before it returns, so finish and the readers (on the lane cov) need no event.  One producer at a
 // time: GdAccum::mu is held from the enqueue to the verdict.
-// LOCK ORDER: bam.mu, then the coverage accumulator's mu, then the pileup accumulator's (the slots of a GdAccumSet in order), then
-// cov.mu of the context; cov_reg_mu is taken last and alone.
+// LOCK ORDER: bam.mu, then the coverage accumulator's mu, then the pileup accumulator's, then the statistics accumulator's (the slots of
+// a GdAccumSet in order: GD_ACC_COV, GD_ACC_PILE, GD_ACC_STATS), then cov.mu of the context; cov_reg_mu is taken last and alone.
 #pragma once
 #include "cov.h"
 #include "bam_starts.h"
@@ -30,10 +30,11 @@ struct GdAccum {
 	uint64_t *d_first_bad = nullptr; // the cell in the accumulator's table: min over a call's bad records of (index << 8 | reason).  NULL: no arrays
 	uint64_t h_first_bad = ~(uint64_t)0;
 	bool poisoned = false, finished = false;
-	const char *const label; // "coverage" / "pileup": the accumulator's name in every message
+	const char *const label; // "coverage" / "pileup" / "stats": the accumulator's name in every message
 	explicit GdAccum(const char *name) : label(name) {}
 	virtual ~GdAccum() {}
-	// the scatter kernel over the n records at d_recs[0, bytes) whose starts are d_start[0, n), on s
+	// the scatter kernel over the n records at d_recs[0, bytes) whose starts are d_start[0, n), on s; blocks: one per four records, at most
+	// GDC_MAX_BLOCKS (an accumulator whose kernel pays per block may launch fewer)
 	virtual void launch(hipStream_t s, const uint8_t *d_recs, uint64_t bytes, const uint64_t *d_start, uint64_t n, unsigned blocks) = 0;
 	virtual void free_arrays() = 0; // hipFree of what open allocated; the caller holds mu
 };

@@ -113,7 +113,7 @@ struct GdqDevice {
 	GdsRow *d_rows = nullptr;
 	size_t run_cap = 0, res_cap = 0, rows_cap = 0, front_len = 0;
 	uint64_t res_bytes = 0; // of the records of the resident result, behind front_len
-	GdAccumSet acc; // gdiet_hip_bam_sort_set_coverage / _set_pileup: every appended batch is scattered from the run buffer, on the encoder's lane
+	GdAccumSet acc; // gdiet_hip_bam_sort_set_coverage / _set_pileup / _set_stats: every appended batch is scattered from the run buffer, on the encoder's lane
 
 	// p[0, cap) -> at least `need` bytes, the first `keep` bytes kept.  The caller holds bsort.mu and has made the stream.
 	template <class T> hipError_t grow(T **p, size_t *cap, size_t need, size_t keep)
@@ -452,6 +452,11 @@ extern "C" int gdiet_hip_bam_sort_set_coverage(gdiet_bam_sorter *h, gdiet_covera
 extern "C" int gdiet_hip_bam_sort_set_pileup(gdiet_bam_sorter *h, gdiet_pileup *pile)
 {
 	return h ? gd_accum_attach(h->ctx, h->q.ex.acc, GD_ACC_PILE, pile, "gdiet_hip_bam_sort_set_pileup", "sorter") : GDIET_E_PARAM;
+}
+
+extern "C" int gdiet_hip_bam_sort_set_stats(gdiet_bam_sorter *h, gdiet_stats *stats)
+{
+	return h ? gd_accum_attach(h->ctx, h->q.ex.acc, GD_ACC_STATS, stats, "gdiet_hip_bam_sort_set_stats", "sorter") : GDIET_E_PARAM;
 }
 
 extern "C" int gdiet_hip_bam_sort_set_markdup(gdiet_bam_sorter *h, int on)

@@ -219,9 +219,9 @@ struct GdBzdExecutor : GdBgzfDeflater {
 // The accumulators attached to a writer or a sorter (accum_driver.hip.h): fixed slots, and the slot order is the order in which a call
 // locks them.  An empty slot costs nothing.
 struct GdAccum;
-enum { GD_ACC_COV = 0, GD_ACC_PILE, GD_ACC_SLOTS };
+enum { GD_ACC_COV = 0, GD_ACC_PILE, GD_ACC_STATS, GD_ACC_SLOTS };
 struct GdAccumSet { GdAccum *slot[GD_ACC_SLOTS] = {}; };
-struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; GdAccumSet acc; /* gdiet_hip_bgzf_out_set_coverage / _set_pileup */ };
+struct gdiet_bgzf_out { GdBgzfOut w; gdiet_ctx *ctx = nullptr; GdAccumSet acc; /* gdiet_hip_bgzf_out_set_coverage / _set_pileup / _set_stats */ };
 
 extern "C" int gdiet_hip_bgzf_out_open(gdiet_ctx *ctx, const char *path, int level, int threads, gdiet_bgzf_out **out)
 {

@@ -191,7 +191,7 @@ struct gdiet_ctx {
 	//        accumulator never holds the encoder's mutex.  No events
 	GdLane ds, fx, bz, bzd, bam, bsort, cov;
 	template <class F> void each_lane(F f) { f(ds), f(fx), f(bz), f(bzd), f(bam), f(bsort), f(cov); }
-	std::vector<GdAccum *> accum_open; // the coverage and pileup accumulators opened on this context and not yet closed: their arrays go with it (accum_driver.hip.h; under cov_reg_mu)
+	std::vector<GdAccum *> accum_open; // the coverage, pileup and statistics accumulators opened on this context and not yet closed: their arrays go with it (accum_driver.hip.h; under cov_reg_mu)
 	std::mutex cov_reg_mu;
 	DevBuf ds_rec, ds_cig, ds_len, ds_off, ds_scan, ds_text, ds_reads, ds_roff; // (under ds.mu)
 	std::vector<uint8_t> ds_enc;       // host copy of the reads a difference-string call without a resident batch encodes
@@ -347,7 +347,7 @@ extern "C" void gdiet_hip_destroy(gdiet_ctx *ctx)
 		if (ctx->async_lane[i]) gdiet_hip_destroy(ctx->async_lane[i]), ctx->async_lane[i] = nullptr;
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-	gd_accum_orphan_all(ctx); // the arrays of the coverage and pileup accumulators that are still open
+	gd_accum_orphan_all(ctx); // the arrays of the coverage, pileup and statistics accumulators that are still open
 	std::vector<hipEvent_t> events(ctx->ev, ctx->ev + 4);
 	events.insert(events.end(), {ctx->arena_ev, ctx->wait_ev, ctx->gather_ev});
 	std::vector<hipStream_t> streams{ctx->stream_dp, ctx->stream};
@@ -1278,6 +1278,7 @@ extern "C" int gdiet_hip_debug_bgzf_seconds(const gdiet_fastx *fx, double *out6)
 #include "sam_driver.hip.h" // SAM text on the device: the line formatter's driver, gdiet_hip_sam_batch_device_into / _bgzf_out_write_sam
 #include "cov_driver.hip.h" // coverage and depth accumulated from the resident records: gdiet_hip_cov_*
 #include "pile_driver.hip.h" // base counts per position and variant sites from the resident records: gdiet_hip_pile_*
+#include "stats_driver.hip.h" // read and alignment statistics from the resident records: gdiet_hip_stats_*
 #include "bam_sort_driver.hip.h" // BAM records in coordinate order: the sort pass's driver, gdiet_hip_bam_sort_records
 
 extern "C" int gdiet_hip_batch_export(gdiet_ctx *ctx, const gdiet_read_batch *b, int32_t *n, int64_t *roff, uint8_t *enc_host, uint8_t *enc_device)

@@ -98,6 +98,24 @@ def load_library():
     return lib
 
 
+def bind_stats(lib):
+    """the entry points of the statistics accumulator (include/gdiet_hip.h, "Alignment statistics"); stats.py calls this once"""
+    if getattr(lib, "_stats_bound", False):
+        return
+    vp, cpp, i32p, u32, u64 = C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_uint32, C.c_uint64
+    lib.gdiet_hip_stats_open.argtypes = [vp, vp, u32, u32, u32, u32, u32, C.POINTER(vp)]
+    lib.gdiet_hip_stats_open_bounded.argtypes = [vp, vp, u32, u32, u32, u32, u32, u64, C.POINTER(vp)]
+    lib.gdiet_hip_stats_add_bam.argtypes = [vp, C.c_char_p, C.c_size_t]
+    lib.gdiet_hip_stats_add.argtypes = [vp, vp, C.c_int, cpp, cpp, cpp, i32p, i32p, vp, cpp, C.c_int64]  # (regs: gdiet_reg_t *const *, map_api.Reg)
+    lib.gdiet_hip_stats_finish.argtypes = [vp, vp]
+    lib.gdiet_hip_stats_table.argtypes = [vp, C.c_int, vp, C.c_size_t]
+    lib.gdiet_hip_stats_table.restype = C.c_int64
+    lib.gdiet_hip_stats_close.argtypes = [vp]
+    lib.gdiet_hip_bgzf_out_set_stats.argtypes = [vp, vp]
+    lib.gdiet_hip_bam_sort_set_stats.argtypes = [vp, vp]
+    lib._stats_bound = True
+
+
 class DupStats(C.Structure):
     """gdiet_dup_stats_t"""
     _fields_ = [("examined", C.c_int64), ("eligible", C.c_int64), ("duplicates", C.c_int64), ("max_group", C.c_int64)]

@@ -912,7 +912,7 @@ int gdiet_hip_bam_sort_close_dup(gdiet_bam_sorter *h, gdiet_bam_sort_stats_t *st
  * finish turns it into the depth array by hipCUB's inclusive sum in chunks of at most 2^30 slots (the previous chunk's last depth is added
  * to a chunk's first slot first) and cov_window_kernel, one wavefront per window, reduces it.  The array costs 4 bytes per reference
  * base for as long as the handle lives: 12.4 GB for a GRCh38-sized reference of 3.1 Gbp.  Out of scope: per-base quality thresholds,
- * the histograms of `samtools stats`, duplicate marking, references too large for 4 bytes per base, merging the accumulators of several
+ * the histograms of `samtools stats` (they are "Alignment statistics" below), duplicate marking, references too large for 4 bytes per base, merging the accumulators of several
  * GPUs. */
 typedef struct gdiet_coverage gdiet_coverage;
 typedef struct {
@@ -1033,6 +1033,105 @@ int gdiet_hip_pile_consensus(gdiet_pileup *pile, size_t region, uint32_t min_dep
 int64_t gdiet_hip_pile_sites(gdiet_pileup *pile, uint32_t min_depth, uint32_t min_alt, uint32_t num, uint32_t den, gdiet_pile_site_t *out, size_t cap);
 /* Frees the counters and the handle, whatever state it is in. */
 int gdiet_hip_pile_close(gdiet_pileup *pile);
+
+/* ---- Alignment statistics ---------------------------------------------------------------------------------------------------------------
+ * What `samtools flagstat` and `samtools stats` report after a run, accumulated on the device from uncompressed BAM alignment records
+ * while they are resident there: a summary and eleven histograms.  The reference prints SAM and stops: these rules are the definition
+ * (tests/stats_ref.py restates them).  Every counter is an unsigned 64-bit integer and every add is an integer add, so every result is a
+ * function of the multiset of input records and the options alone: it does not depend on how the records were cut into calls, on the
+ * route or on the order of atomic arrivals.  The tables of disjoint sets of records simply add.
+ * Options: excl_flags (usual value 0x700: secondary, QC-fail, duplicate), min_mapq (0), cycles (512; 1 .. 1024), max_len (65536;
+ * 1 .. 2^20), max_indel (64; 1 .. 4096).  A value out of range is GDIET_E_PARAM with a message.
+ *   VALIDATION  the real CIGAR, the bad-record reasons, the poisoning and the naming of the call's first bad record are those of
+ *           "Coverage".  A bad record adds to `records`, to `bad` and to the flag counters of coverage's summary, and to nothing else.
+ *   TWO POPULATIONS  with f the flag of a good record:
+ *           it is a READ if (f & (excl_flags | 0x900)) == 0: unmapped reads are reads, MAPQ is not looked at;
+ *           it is an ALIGNMENT if coverage's `counted` holds with the flags excl_flags | 0x4: not excluded, mapq >= min_mapq, refID >= 0.
+ *           A supplementary record is an alignment but not a read.  A record may be both, or neither.
+ *   BASE CODE  of a SEQ nibble: 1 2 4 8 give A C G T (0 .. 3); every other nibble, '=' included, gives 4 ("other").
+ *   CYCLE   of query index qi, in the read's original orientation: lead + qi on the forward strand, trail + (l_seq - 1 - qi) on the
+ *           reverse strand (f & 0x10), where lead / trail is the length of a hard clip (operation code 5) that is the first / the last
+ *           operation of the real CIGAR, else 0.  A per-cycle table has cycles + 1 rows; row `cycles` takes every cycle >= cycles.
+ *   OVER READS
+ *           read_len[min(l_seq, max_len)]                      max_len + 1 bins
+ *           gc[101]            if l_seq > 0: with a the number of A C G T bases and g the number of C G bases, if a > 0 the bin
+ *                              (200 g + a) / (2 a) in integer division (100 g / a rounded, halves up)
+ *           base_cycle[cycles + 1][5]   every base by its cycle and its code; on a reverse read the code is complemented (A <-> T,
+ *                              C <-> G, other stays other)
+ *           with qualities present (l_seq > 0 and the first QUAL byte is not 0xff):
+ *           qual_cycle[cycles + 1][2]   per cycle the number of quality bytes and their sum
+ *           base_qual[96]      every quality byte q at min(q, 95)
+ *   OVER ALIGNMENTS  walking the real CIGAR as "Coverage" does, reference cursor from pos, query cursor from 0:
+ *           mapq[256]
+ *           ins_len[max_indel + 1]   every I run of length L > 0 at min(L, max_indel);  del_len likewise for D runs.  N is no deletion.
+ *           soft- and hard-clipped bases (codes 4 and 5) go into the summary.
+ *           for every base of an M = X run, if l_seq > 0, with rc the code of the base as stored and fc the code of the reference base
+ *           of its position in the index's packed reference (0 .. 3, 4 for N):
+ *             subst[5][5]      cell [fc][rc]: reference orientation
+ *             the base is COMPARABLE if rc < 4 and fc < 4, a MATCH if comparable and rc == fc, a MISMATCH if comparable and rc != fc
+ *             cmp_cycle[cycles + 1][2]   per cycle of the base the comparable bases and the mismatches
+ *           per alignment, with m matches, x mismatches, i and d the numbers of I and D runs of length above 0 and den = m + x + i + d:
+ *             identity[101]    if den > 0 the bin 100 m / den (64-bit integer division); else no_identity += 1
+ *           an alignment with l_seq == 0 adds to mapq, the indel tables, the clips, no_seq and no_identity.
+ *   SUMMARY coverage's ten counters under the flags excl_flags | 0x4 (so `counted` is the number of alignments, and an unmapped record
+ *           is excluded_by_flag); duplicate and qcfail (flag bits 0x400 and 0x200, over good records); reads, read_bases (l_seq over
+ *           reads); aligned_bases (the bases that entered subst), matches, mismatches, other_bases (not comparable); ins_events,
+ *           ins_bases, del_events, del_bases (runs of length above 0); soft_clipped, hard_clipped; no_seq, no_identity.
+ *   DUPLICATES  an accumulator attached to a sorter with duplicate marking scatters when the batch is added, before any record carries
+ *           0x400: marked duplicates are counted like any other record.  To leave them out feed the finished file's records through
+ *           gdiet_hip_stats_add_bam.
+ * The device side (csrc/stats.hip.h, statements in csrc/stats.h, which reuses those of csrc/cov.h and csrc/pile.h):
+ * stats_scatter_kernel, one wavefront per record, four records to a block.  Every table but read_len is kept per block in local memory
+ * as uint32 (about 21 KB with the default options), added to with local-memory atomics and flushed once per block with 64-bit global
+ * atomics; adds that many lanes would make to one cell are reduced across the wavefront first; a block flushes before a cell could
+ * pass 2^32.  The whole state is n_all * 8 bytes, 43 KB plus 8 bytes per read-length bin.  finish runs no kernel.  Out of scope:
+ * insert sizes and other paired-end statistics, per-contig breakdowns, coverage distribution and GC-depth (derivable from "Coverage"),
+ * indels per cycle, mismatch counts from NM / MD, merging the tables of several GPUs (add them), plots. */
+typedef struct gdiet_stats gdiet_stats;
+typedef struct {
+	uint64_t records, unmapped, secondary, supplementary, primary_mapped, reverse, excluded_by_flag, excluded_by_mapq, counted, bad;
+	uint64_t duplicate, qcfail, reads, read_bases, aligned_bases, matches, mismatches, other_bases;
+	uint64_t ins_events, ins_bases, del_events, del_bases, soft_clipped, hard_clipped, no_seq, no_identity;
+} gdiet_stats_summary_t;
+/* the tables gdiet_hip_stats_table reads, with their sizes in counters */
+enum {
+	GDIET_STATS_GC = 0,     /* 101 */
+	GDIET_STATS_BASE_CYCLE, /* (cycles + 1) * 5, row-major */
+	GDIET_STATS_QUAL_CYCLE, /* (cycles + 1) * 2: count, sum */
+	GDIET_STATS_BASE_QUAL,  /* 96 */
+	GDIET_STATS_MAPQ,       /* 256 */
+	GDIET_STATS_INS_LEN,    /* max_indel + 1 */
+	GDIET_STATS_DEL_LEN,    /* max_indel + 1 */
+	GDIET_STATS_SUBST,      /* 25: [reference code][read code] */
+	GDIET_STATS_CMP_CYCLE,  /* (cycles + 1) * 2: comparable, mismatches */
+	GDIET_STATS_IDENTITY,   /* 101 */
+	GDIET_STATS_READ_LEN    /* max_len + 1 */
+};
+/* An accumulator over idx's contigs: allocates and clears the tables.  idx must stay alive for as long as the handle takes records: the
+ * kernel reads its packed reference.  The tables also go when the context is destroyed: a handle that outlives its context takes
+ * nothing but close.  _bounded: the weight, in bases, a block may hold in local memory between two flushes (0: the default, 2^24, which
+ * is also the most) -- no result depends on it; it exists so that tests reach the flush and the path of a record too heavy for local
+ * memory on small inputs. */
+int gdiet_hip_stats_open(gdiet_ctx *ctx, const gdiet_index *idx, uint32_t excl_flags, uint32_t min_mapq, uint32_t cycles, uint32_t max_len, uint32_t max_indel, gdiet_stats **out);
+int gdiet_hip_stats_open_bounded(gdiet_ctx *ctx, const gdiet_index *idx, uint32_t excl_flags, uint32_t min_mapq, uint32_t cycles, uint32_t max_len, uint32_t max_indel, uint64_t bound,
+                                 gdiet_stats **out);
+/* Host records and a mapped batch: as gdiet_hip_cov_add_bam and gdiet_hip_cov_add (opt_flag decides which records exist). */
+int gdiet_hip_stats_add_bam(gdiet_stats *stats, const void *recs, size_t len);
+int gdiet_hip_stats_add(gdiet_stats *stats, const gdiet_index *idx, int n_reads, const char *const *qnames, const char *const *seqs, const char *const *quals,
+                        const int32_t *lens, const int32_t *n_regs, gdiet_reg_t *const *regs, const char *const *comments, int64_t opt_flag);
+/* Attach (NULL: detach) to a BGZF writer with a context or to a sorter, beside the coverage and the pileup accumulator and under their
+ * rules; all three may be attached at once, and one table of record starts serves them.  The bytes written do not change.  Lock order:
+ * the encoder's mutex, the coverage accumulator's, the pileup accumulator's, the statistics accumulator's, the context's lane. */
+int gdiet_hip_bgzf_out_set_stats(gdiet_bgzf_out *writer, gdiet_stats *stats);
+int gdiet_hip_bam_sort_set_stats(gdiet_bam_sorter *sorter, gdiet_stats *stats);
+/* The tables come down (no kernel runs) and *summary_out (may be NULL) is filled.  After it the accumulator is read-only: add is
+ * refused, finish again returns the same figures. */
+int gdiet_hip_stats_finish(gdiet_stats *stats, gdiet_stats_summary_t *summary_out);
+/* After finish: table `which` (GDIET_STATS_*).  Returns its size in counters; with out == NULL that is all, else cap, the room of out in
+ * counters, must hold them (GDIET_E_PARAM otherwise). */
+int64_t gdiet_hip_stats_table(gdiet_stats *stats, int which, uint64_t *out, size_t cap);
+/* Frees the tables and the handle, whatever state it is in. */
+int gdiet_hip_stats_close(gdiet_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ No Python object is made per read: the C arrays of the reader go straight into t
                              [--bgzf {host,device}] [--bgzf-level N] [--bgzf-threads N] [--bam [--sort [--index] [--markdup] [--sort-mem BYTES] [--tmp-dir DIR]]] [--sam-device]
                              [--coverage PREFIX [--cov-window N] [--cov-min-mapq Q] [--cov-excl-flags F]]
                              [--pileup PREFIX [--pile-regions BED] [--pile-min-baseq Q] [--pile-min-mapq Q] [--pile-excl-flags F] [--pile-min-depth N] [--pile-min-alt N] [--pile-frac NUM/DEN]]
+                             [--stats PREFIX [--stats-cycles N] [--stats-max-len N] [--stats-max-indel N] [--stats-min-mapq Q] [--stats-excl-flags F]]
 
 `ref` is a FASTA / FASTQ file (plain, gzip or BGZF) or an .mmi index file, known by its magic, not its name (Mapper.from_file:
 gdiet_hip_index_open -- FASTA blocks are parsed on the device); "synth:MBP" stands for bench.py's synthetic reference.  -d FILE dumps
@@ -43,7 +44,12 @@ not change.  The JSON line gains coverage.  Without --coverage nothing changes.
 --pileup PREFIX piles up base counts per position on the device (Pileup: 32 bytes of device memory per position) over the regions of
 --pile-regions BED (contig, 0-based start, end; sorted as the contigs are and disjoint; default: every contig whole) and writes
 PREFIX.pileup.tsv, the variant sites under --pile-min-depth / --pile-min-alt / --pile-frac, and PREFIX.consensus.fa.  It attaches exactly as
---coverage does and may be combined with it.  The JSON line gains pileup.  Without --pileup nothing changes."""
+--coverage does and may be combined with it.  The JSON line gains pileup.  Without --pileup nothing changes.
+--stats PREFIX collects read and alignment statistics on the device (Stats: a few tens of kilobytes of device memory, whatever the
+reference) and writes PREFIX.stats.tsv, the summary and histograms of `samtools flagstat` / `samtools stats` in tagged sections (SN RL
+GCF GCC QC BQ MQ IL DL SUB MPC IDN), with --stats-cycles rows per per-cycle table, read lengths up to --stats-max-len and indel lengths
+up to --stats-max-indel.  It attaches exactly as --coverage does and may be combined with it and with --pileup; with --markdup it still
+counts the duplicates (it reads the records before they are flagged).  The JSON line gains stats.  Without --stats nothing changes."""
 import argparse
 import json
 import os
@@ -61,7 +67,7 @@ VERSION = "gdiet-hip-map_file"  # the VN: field of --header's @PG line
 
 
 def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with_qual=True, with_comment=False, device_reader=False, bam=False, sorter=None, sam_device=False,
-             cov_add=None, pile_add=None):
+             cov_add=None, pile_add=None, stats_add=None):
     """returns (reads, seconds).  Three stages on three threads, as the reference's kt_pipeline runs its three steps (LR/map.c:2094-2170):
     read -> upload + submit -> wait + format + write; the C calls release the interpreter lock, so the stages overlap.
     A failure in any stage stops all three: `stop` is set, the writer keeps draining q_done (every open ticket is still waited for and
@@ -71,7 +77,8 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
     import threading
     fx = pkg.FastxReader(reads_path, threads=reader_threads, ctx=mapper.ctx if device_reader else None)
     mapper.set_inflight(inflight)
-    T = {"read": 0.0, "upload": 0.0, "submit": 0.0, "wait": 0.0, "sam+write": 0.0, "free": 0.0, **({"coverage": 0.0} if cov_add is not None else {}), **({"pileup": 0.0} if pile_add is not None else {})}
+    T = {"read": 0.0, "upload": 0.0, "submit": 0.0, "wait": 0.0, "sam+write": 0.0, "free": 0.0, **({"coverage": 0.0} if cov_add is not None else {}), **({"pileup": 0.0} if pile_add is not None else {}),
+         **({"stats": 0.0} if stats_add is not None else {})}
     q_read, q_done = queue.Queue(maxsize=2), queue.Queue()
     open_tickets = threading.Semaphore(inflight)  # the library takes at most `inflight` tickets: one permit per open ticket
     errors, stop = [], threading.Event()
@@ -138,6 +145,8 @@ def map_file(pkg, mapper, reads_path, out, chunk, inflight, reader_threads, with
                     timed("coverage", cov_add.add, res, n, names, seqs, quals, lens, comments if with_comment else None)
                 if res is not None and not stop.is_set() and pile_add is not None:
                     timed("pileup", pile_add.add, res, n, names, seqs, quals, lens, comments if with_comment else None)
+                if res is not None and not stop.is_set() and stats_add is not None:
+                    timed("stats", stats_add.add, res, n, names, seqs, quals, lens, comments if with_comment else None)
             except Exception as e:  # noqa: BLE001
                 fail(e)
             try:
@@ -248,6 +257,12 @@ def main():
     ap.add_argument("--pile-min-depth", type=int, default=8, metavar="N", help="with --pileup: a site and a consensus base need this depth (default 8)")
     ap.add_argument("--pile-min-alt", type=int, default=2, metavar="N", help="with --pileup: a site's allele needs this count (default 2)")
     ap.add_argument("--pile-frac", default="1/5", metavar="NUM/DEN", help="with --pileup: and this fraction of the depth (default 1/5)")
+    ap.add_argument("--stats", metavar="PREFIX", help="collect read and alignment statistics on the device; writes PREFIX.stats.tsv")
+    ap.add_argument("--stats-cycles", type=int, default=512, metavar="N", help="with --stats: rows of the per-cycle tables; later cycles share the last row (default 512, at most 1024)")
+    ap.add_argument("--stats-max-len", type=int, default=65536, metavar="N", help="with --stats: the last read-length bin (default 65536)")
+    ap.add_argument("--stats-max-indel", type=int, default=64, metavar="N", help="with --stats: the last indel-length bin (default 64)")
+    ap.add_argument("--stats-min-mapq", type=int, default=0, metavar="Q", help="with --stats: records with a lower MAPQ are no alignments")
+    ap.add_argument("--stats-excl-flags", type=lambda x: int(x, 0), default=0x700, metavar="F", help="with --stats: records with one of these FLAG bits are left out (default 0x700)")
     ap.add_argument("-d", dest="dump", metavar="FILE", help="dump the index to FILE (.mmi, as the reference's -d) after the build; FILE can be given as ref later")
     ap.add_argument("--device-reader", action="store_true", help="parse and encode four-line FASTQ on the device (gdiet_hip_fastx_attach); the reader hands out resident batches")
     a = ap.parse_args()
@@ -299,6 +314,7 @@ def main():
     sort_stats = None
     cov, cov_report = None, None
     pile, pile_report = None, None
+    stats, stats_report = None, None
     try:
         bgzf_out = None
         if a.coverage:
@@ -310,8 +326,10 @@ def main():
                     regions = [(m.names.index(x[0]), int(x[1]), int(x[2])) for x in (l.split() for l in f if l.strip() and not l.startswith(("#", "track", "browser")))]
             num, den = (int(x) for x in a.pile_frac.split("/"))
             pile = pkg.Pileup(m, regions=regions, excl_flags=a.pile_excl_flags, min_mapq=a.pile_min_mapq, min_baseq=a.pile_min_baseq)
+        if a.stats:
+            stats = pkg.Stats(m, excl_flags=a.stats_excl_flags, min_mapq=a.stats_min_mapq, cycles=a.stats_cycles, max_len=a.stats_max_len, max_indel=a.stats_max_indel)
         resident = a.bam and (a.sort or a.bgzf == "device")  # the records are resident in the sorter's or the writer's hands
-        attach, attach_pile = cov is not None and resident, pile is not None and resident
+        attach, attach_pile, attach_stats = cov is not None and resident, pile is not None and resident, stats is not None and resident
         if a.sort:
             sorter = pkg.BamSorter(a.out, m, bgzf=a.bgzf, level=a.bgzf_level, threads=a.bgzf_threads, run_bytes=a.sort_mem, tmp_dir=a.tmp_dir, index=a.index, version=VERSION, argv=sys.argv,
                                    markdup=a.markdup)
@@ -319,9 +337,11 @@ def main():
                 sorter.set_coverage(cov)
             if attach_pile:
                 sorter.set_pileup(pile)
+            if attach_stats:
+                sorter.set_stats(stats)
             try:
                 n, dt = map_file(pkg, m, a.reads, None, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment, device_reader=a.device_reader,
-                                 bam=True, sorter=sorter, cov_add=None if attach else cov, pile_add=None if attach_pile else pile)
+                                 bam=True, sorter=sorter, cov_add=None if attach else cov, pile_add=None if attach_pile else pile, stats_add=None if attach_stats else stats)
                 t_close = time.perf_counter()
                 sort_stats = dict(sorter.close(), route=a.bgzf)
                 sort_stats["close_seconds"] = round(time.perf_counter() - t_close, 3)
@@ -339,12 +359,15 @@ def main():
                     out.set_coverage(cov)
                 if attach_pile:
                     out.set_pileup(pile)
+                if attach_stats:
+                    out.set_stats(stats)
                 if a.bam:
                     out.write(m.bam_header(VERSION, sys.argv))
                 elif a.header:
                     out.write(m.sam_header(VERSION, sys.argv).encode())
                 n, dt = map_file(pkg, m, a.reads, out, chunk, a.inflight, a.reader_threads, with_qual=not a.no_qual, with_comment=a.copy_comment,
-                                 device_reader=a.device_reader, bam=a.bam, sam_device=a.sam_device, cov_add=None if attach else cov, pile_add=None if attach_pile else pile)
+                                 device_reader=a.device_reader, bam=a.bam, sam_device=a.sam_device, cov_add=None if attach else cov, pile_add=None if attach_pile else pile,
+                                 stats_add=None if attach_stats else stats)
         if cov is not None:
             t_cov = time.perf_counter()
             _, summary = cov.finish()
@@ -357,12 +380,20 @@ def main():
             pile.write(a.pileup, min_depth=a.pile_min_depth, min_alt=a.pile_min_alt, frac=(num, den))
             pile_report = dict(summary, prefix=a.pileup, regions=len(pile.regions), attached=attach_pile, finish_write_seconds=round(time.perf_counter() - t_pile, 3))
             pile.close()
+        if stats is not None:
+            t_stats = time.perf_counter()
+            summary, _ = stats.finish()
+            stats.write(a.stats)
+            stats_report = dict(summary, prefix=a.stats, attached=attach_stats, finish_write_seconds=round(time.perf_counter() - t_stats, 3))
+            stats.close()
     except Exception as e:  # noqa: BLE001  (every ticket has been waited for by now: the context can be closed)
         print("map_file failed: %r" % (e,), file=sys.stderr)
         if cov is not None:
             cov.close()
         if pile is not None:
             pile.close()
+        if stats is not None:
+            stats.close()
         m.close()
         ctx.close()
         sys.exit(1)
@@ -373,6 +404,7 @@ def main():
                       **({"bam_sort": sort_stats} if sort_stats is not None else {}),
                       **({"coverage": cov_report} if cov_report is not None else {}),
                       **({"pileup": pile_report} if pile_report is not None else {}),
+                      **({"stats": stats_report} if stats_report is not None else {}),
                       **({"bam": True, "bam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.bam else {}),
                       **({"sam_device": True, "sam_device_seconds": [round(x, 4) for x in m.bam_device_seconds()]} if a.sam_device else {})}))
     m.close()
